@@ -13,7 +13,16 @@ Secondary lines (same JSON object, "secondary"): configs[1] (SE150 1 GB, md5 vs 
 N > 1: ONE configs[3]-shaped PE150 input of N x (2 x 8 GB) encoded chunk-parallel by the N GPUs: see run_multi() (static resident shares + a plan step);
 --queue: the same input through a host work queue - rank-agnostic batches pulled from a shared counter - see run_queue() (also with --gpus 1: the whole input on one GPU).
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+N = 1 without --full (the plain run) does what the headline needs and nothing else: it makes the input, warms up, times --steps steps and prints the line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, the stage times and block rates of those steps).  --full adds, as before: the parity check of
+the measured workload against the reference's golden (before the timed steps), the decode with the chunk index handed over, the device clocks, the
+roofline with its two rocprofv3 --pmc passes, the CPU baselines, the secondary configs[1] / configs[4] lines and the host-work-queue line.
+
+--dump-outputs DIR (N = 1): after the timed steps, what the last step computed - the .rfq image and the decoded mates - goes to DIR/<name>.npy as float32 /
+float64 arrays (sizes, chunk offsets, per-chunk / per-block crc32, the header bytes and a fixed, seeded sample of bytes; < 64 MB in all): see dump_outputs().
+The input is seeded, so two builds run with the same arguments can be compared array for array.
+
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -159,17 +168,23 @@ def golden_md5(key, units, seed, k):
     return None
 
 
+def workload_input(key, units, seed):
+    """The synthetic FASTQ of a workload as host arrays (a1, a2): the generator is seeded, so the same arguments give the same bytes."""
+    import _oracle as O
+    _, prof, dunits, dseed, kw = WORKLOADS[key]
+    return O.gen_np(prof, units or dunits, seed=(dseed if seed is None else seed), **kw)
+
+
 class Workload:
     """One synthetic input resident in HBM + the encode/decode step over it."""
 
-    def __init__(self, codec, dev, key, units, seed, chunk_kb, decode=True):
+    def __init__(self, codec, dev, key, units, seed, chunk_kb, decode=True, arrays=None):
         import torch
-        import _oracle as O
         from repaq_amd import SE, PE_TWO_FILES
         label, prof, dunits, dseed, kw = WORKLOADS[key]
         self.key, self.units, self.seed, self.k = key, units or dunits, (dseed if seed is None else seed), chunk_kb
         self.paired = prof in (1, 3)
-        self.a1, self.a2 = O.gen_np(prof, self.units, seed=self.seed, **kw)
+        self.a1, self.a2 = arrays if arrays is not None else workload_input(key, units, seed)
         self.n1, self.n2 = int(self.a1.size), int(self.a2.size) if self.paired else 0
         self.n = self.n1 + self.n2
         self.label = label % ((self.n / (2e9 if self.paired else 1e9)), self.units, self.seed, chunk_kb)
@@ -426,6 +441,54 @@ def line_of(w, steps, dt, total_bytes, parity):
             "chunks": w.chunks, "rfq_over_fastq": round(w.rfq_len / w.n, 4),
             "encode_MBps": round(w.n * steps / w.enc_s / 1e6, 1) if w.enc_s else None, "decode_MBps": round(w.n * steps / w.dec_s / 1e6, 1) if w.dec_s else None,
             "parity": parity, "stage_ms": {k: round(v, 3) for k, v in stage.items()}}, stage, enc_ms, dec_ms
+
+
+DUMP_SAMPLE = 1 << 22        # bytes sampled from each output (float32: 16 MB per array)
+DUMP_BLOCK = 1 << 20         # the decoded text is fingerprinted in blocks of 1 MiB (one crc32 each)
+DUMP_LIMIT = 64_000_000      # bytes, all arrays together
+
+
+def dump_outputs(w, out_dir):
+    """What the last timed step handed its caller, as DIR/<name>.npy (float64 for sizes and checksums, float32 for bytes): the .rfq image (encode) and the
+    decoded mates (decode) in full would be GBs, so each is given as its sizes, exact checksums over all of it (crc32 per .rfq chunk, per MiB of text),
+    and the bytes at DUMP_SAMPLE positions drawn by a fixed seed from its length.  The header's bytes are given whole."""
+    import zlib
+    import numpy as np
+    import torch
+    r = w.r
+    arrays = {}
+
+    def sample(n, seed):
+        return np.sort(np.random.default_rng(seed).integers(0, n, size=min(n, DUMP_SAMPLE), dtype=np.int64)) if n else np.zeros(0, np.int64)
+
+    img = w.codec.dev_get(r.d_rfq, r.rfq_len)
+    offs = [int(r.h_chunk_off[i]) for i in range(r.n_chunks + 1)] if r.n_chunks else [r.rfq_len]
+    view = memoryview(img)
+    arrays["rfq_sizes"] = np.array([r.rfq_len, r.n_chunks, r.n_reads, r.n_bases], dtype=np.float64)
+    arrays["rfq_chunk_offsets"] = np.array(offs, dtype=np.float64)
+    arrays["rfq_chunk_crc32"] = np.array([zlib.crc32(view[offs[i]:offs[i + 1]]) for i in range(len(offs) - 1)], dtype=np.float64)
+    arrays["rfq_header"] = np.frombuffer(img, dtype=np.uint8, count=offs[0]).astype(np.float32)
+    arrays["rfq_sample"] = np.frombuffer(img, dtype=np.uint8)[sample(r.rfq_len, 1)].astype(np.float32)
+    del view, img
+    if w.do_decode:
+        d = w.d
+        arrays["decoded_sizes"] = np.array([d.n1, d.n2, d.n_chunks, d.n_reads, d.n_bases], dtype=np.float64)
+        for mate, t, n, seed in ((1, w.o1, d.n1, 2), (2, w.o2, d.n2, 3)):
+            if t is None:
+                continue
+            crc = []
+            for s in range(0, n, 256 * DUMP_BLOCK):
+                h = memoryview(t[s:min(n, s + 256 * DUMP_BLOCK)].cpu().numpy())
+                crc += [zlib.crc32(h[b:b + DUMP_BLOCK]) for b in range(0, len(h), DUMP_BLOCK)]
+            arrays["fastq%d_block_crc32" % mate] = np.array(crc, dtype=np.float64)
+            idx = torch.from_numpy(sample(n, seed)).to(t.device)
+            arrays["fastq%d_sample" % mate] = t.index_select(0, idx).cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 SEG_PAIRS, SEG_SEED0, SEGS_PER_GPU, HEAD_PAIRS = 2_800_000, 4000, 8, 4000
@@ -873,7 +936,23 @@ def main():
     ap.add_argument("--queue-chunks", type=int, default=1024, help="--queue: chunks per batch (profiles/r06_d_queue_sweep_workers.txt: 256 / 512 / 1024 chunks x 1 / 2 / 3 worker contexts)")
     ap.add_argument("--queue-workers", type=int, default=2, help="--queue: worker contexts (host threads) per GPU")
     ap.add_argument("--strong", action="store_true", help="N>1: strong scaling - the input is --segs-per-gpu segments IN ALL (default 8 = 2 x 8 GB), split over the N GPUs")
+    ap.add_argument("--full", action="store_true", help="N=1: also the parity check, the indexed decode, clocks, roofline (+ PMC passes), CPU baselines, secondary and queue lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="N=1: write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.queue):
+        ap.error("--dump-outputs is for the one-GPU run without --queue")
+
+    pre = None
+    if args.gpus == 1 and not args.queue:
+        # the input is made on a helper thread (the generator is C code that drops the GIL) while torch and the codec start up
+        from concurrent.futures import ThreadPoolExecutor
+        import numpy  # noqa: F401
+        import _oracle  # noqa: F401
+        ex = ThreadPoolExecutor(1)
+        pre = ex.submit(workload_input, args.workload, args.units, args.seed)
+        ex.shutdown(wait=False)
 
     import torch
     from repaq_amd import dist as D
@@ -896,14 +975,14 @@ def main():
     codec = RfqCodec(device=local)     # raises loudly without the HIP library / a GPU: there is no fallback
 
     sync = torch.cuda.synchronize
-    w = Workload(codec, dev, args.workload, args.units, args.seed, args.chunk_kb, decode=not args.encode_only)
-    parity = "unchecked" if args.no_verify else w.check()
+    w = Workload(codec, dev, args.workload, args.units, args.seed, args.chunk_kb, decode=not args.encode_only, arrays=pre.result())
+    parity = "unchecked" if args.no_verify else (w.check() if args.full else "unchecked (checked with --full)")
     dt = w.run(args.steps, args.warmup, sync, lambda: None)
     head, stage, enc_ms, dec_ms = line_of(w, args.steps, dt, w.n, parity)
+    if args.dump_outputs:
+        dump_outputs(w, args.dump_outputs)
     if args.pmc_child:
         print(json.dumps({"pmc_child": True, "value": head["value_MBps"]})); codec.close(); return
-    indexed = w.decode_indexed(args.steps, sync) if w.do_decode else None
-    live, live_note = (None, "--no-pmc") if args.no_pmc else pmc_traffic_live(args.workload, args.chunk_kb, args.units, args.seed)
     out = {
         "metric": "raw FASTQ MB/s encode+decode" if w.do_decode else "raw FASTQ MB/s encode",
         "value": head["value_MBps"], "unit": "MB/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -911,14 +990,21 @@ def main():
         "dtype": "u8", "data": "synthetic",
         "config": {"workload": w.label, "chunks_per_gpu": w.chunks, "rfq_over_fastq": head["rfq_over_fastq"],
                    "encode_MBps_per_gpu": head["encode_MBps"], "decode_MBps_per_gpu": head["decode_MBps"],
-                   # the headline decode finds the chunk starts itself (a .rfq file has no index); the same decode handed the encoder's chunk offsets:
-                   "decode_MBps_indexed": indexed[0] if indexed else None, "walk_ms_indexed": indexed[1] if indexed else None,
-                   "value_MBps_indexed": round(2 * w.n / (w.n / (head["encode_MBps"] * 1e6) + w.n / (indexed[0] * 1e6)) / 1e6, 1) if indexed and head["encode_MBps"] else None,
-                   # the K timed steps again as blocks (every step ends with the host holding its result, so a step's wall time is its own): median block rate, spread, device clocks
-                   "blocks": blocks_of(w.step_s, w.n * (2 if w.do_decode else 1)), "clocks": smi_clocks(local),
+                   # the K timed steps again as blocks (every step ends with the host holding its result, so a step's wall time is its own): median block rate, spread
+                   "blocks": blocks_of(w.step_s, w.n * (2 if w.do_decode else 1)),
                    "parity": parity, "stage_ms": head["stage_ms"]},
-        "roofline": roofline_of(w, stage, enc_ms, dec_ms, args.workload, live, live_note),
     }
+    if not args.full:
+        print(json.dumps(out))
+        codec.close()
+        return
+    indexed = w.decode_indexed(args.steps, sync) if w.do_decode else None
+    live, live_note = (None, "--no-pmc") if args.no_pmc else pmc_traffic_live(args.workload, args.chunk_kb, args.units, args.seed)
+    # the headline decode finds the chunk starts itself (a .rfq file has no index); the same decode handed the encoder's chunk offsets, and the device clocks:
+    out["config"].update({"decode_MBps_indexed": indexed[0] if indexed else None, "walk_ms_indexed": indexed[1] if indexed else None,
+                          "value_MBps_indexed": round(2 * w.n / (w.n / (head["encode_MBps"] * 1e6) + w.n / (indexed[0] * 1e6)) / 1e6, 1) if indexed and head["encode_MBps"] else None,
+                          "clocks": smi_clocks(local)})
+    out["roofline"] = roofline_of(w, stage, enc_ms, dec_ms, args.workload, live, live_note)
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w.a1, w.a2, w.paired, w.units, args.cpu_sample)
         allc = cpu_baseline_all_cores(w.a1, w.a2, w.paired, w.units, max(1, args.cpu_sample // 8))

@@ -5,7 +5,7 @@
 set -u
 TAG=${1:-round}; QUICK=${2:-}; ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd $ROOT
-timeout 900 python bench.py > $OUT/bench.json.log 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.json.log 2> $OUT/bench.err
 cd /tmp; export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o cfg2 -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-pmc > $OUT/bench_under_rocprof.json.log 2>&1
 if [ -z "$QUICK" ] || [ "$QUICK" = kernels ]; then
