@@ -165,7 +165,37 @@ typedef struct {
  * BIT_ENCODE_QUAL_BY_COL (legacy run-length quality coding, src/rfqcodec.cpp:919-955; v0.5.1 never writes one) decode too. */
 RFQ_API int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* args, rfq_decode_result* res);
 
-/* stage timings of the last batch call, in milliseconds, measured with HIP events on the context's stream.
+/* The same image decoded into per-read ARRAYS instead of FASTQ text: row i of each output is the i-th record rfq_decode_batch (split_pe = 0) would
+ * write - Repaq::decompress order; for a PE file row 2k is R1 of pair k and row 2k+1 its R2, in its original orientation.  A base row holds exactly
+ * the bytes of the record's sequence line (implied N included) or their codes, a quality row the bytes of its quality line minus qual_offset
+ * (mod 256); both are padded to row_len.  Names and strand lines are not produced; the NO_LINE_BREAK bits change nothing (rows have no newlines).
+ * All three output pointers NULL = a size query: n_rows, n_chunks, max_len and consumed are returned and nothing is decoded.  RFQ_E_NOSPACE (nothing
+ * written; the message says what is needed) when row_len < max_len, a row buffer holds fewer than n_rows * row_len bytes or d_lens fewer than
+ * n_rows entries.  An image rfq_decode_batch refuses is refused with the same code.  Synchronous: the rows are in place when the call returns.
+ * Row buffers with row_len % 16 == 0 and 16-byte alignment are written in whole 16-byte groups; anything else byte by byte. */
+#define RFQ_ROWS_ASCII 0        /* base rows hold the FASTQ bytes (A C G T N)          */
+#define RFQ_ROWS_CODE  1        /* base rows hold codes: A 0, C 1, G 2, T 3, N 4        */
+typedef struct {
+    const uint8_t* d_rfq; size_t n;       /* as rfq_decode_args                                                        */
+    int32_t  has_header, final;           /* as rfq_decode_args (streaming: consumed = whole chunks)                    */
+    const uint64_t* h_chunk_off; uint32_t n_chunk_off;   /* optional chunk index, verified exactly as in rfq_decode_batch */
+    uint32_t row_len;                     /* row stride in bytes (>= 1; >= max_len)                                     */
+    int32_t  base_mode;                   /* RFQ_ROWS_ASCII / RFQ_ROWS_CODE                                             */
+    uint8_t  qual_offset;                 /* quality row byte = quality char - qual_offset (mod 256); 0 = the raw char  */
+    uint8_t  pad_base, pad_qual;          /* written at positions >= the read's length                                  */
+    uint8_t  reserved;
+    uint8_t* d_bases; size_t bases_cap;   /* [n_rows][row_len] device buffer; NULL = no base rows                       */
+    uint8_t* d_quals; size_t quals_cap;   /* [n_rows][row_len]; NULL = no quality rows                                  */
+    int32_t* d_lens;  size_t lens_cap;    /* [n_rows] read lengths in bytes (4-byte aligned); cap in entries; NULL = not wanted */
+} rfq_decode_rows_args;
+typedef struct {
+    uint64_t n_rows, n_bases;             /* reads (PE: both mates) and the sum of their lengths                         */
+    uint32_t n_chunks, max_len;           /* chunks decoded; the longest read                                            */
+    size_t   consumed;                    /* bytes of the image covered by whole chunks                                  */
+} rfq_decode_rows_result;
+RFQ_API int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* args, rfq_decode_rows_result* res);
+
+/* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
 

@@ -53,6 +53,21 @@ class DecodeResult(C.Structure):
                 ("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("consumed", C.c_size_t)]
 
 
+ROWS_ASCII, ROWS_CODE = 0, 1
+
+
+class DecodeRowsArgs(C.Structure):
+    _fields_ = [("d_rfq", C.c_void_p), ("n", C.c_size_t), ("has_header", C.c_int32), ("final", C.c_int32),
+                ("h_chunk_off", C.POINTER(C.c_uint64)), ("n_chunk_off", C.c_uint32), ("row_len", C.c_uint32), ("base_mode", C.c_int32),
+                ("qual_offset", C.c_uint8), ("pad_base", C.c_uint8), ("pad_qual", C.c_uint8), ("reserved", C.c_uint8),
+                ("d_bases", C.c_void_p), ("bases_cap", C.c_size_t), ("d_quals", C.c_void_p), ("quals_cap", C.c_size_t),
+                ("d_lens", C.c_void_p), ("lens_cap", C.c_size_t)]
+
+
+class DecodeRowsResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_bases", C.c_uint64), ("n_chunks", C.c_uint32), ("max_len", C.c_uint32), ("consumed", C.c_size_t)]
+
+
 _libs = {}
 
 
@@ -81,6 +96,7 @@ def load(path=None):
     L.rfq_clear_header.argtypes = [C.c_void_p]; L.rfq_clear_header.restype = None
     L.rfq_encode_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(EncodeResult)]
     L.rfq_decode_batch.argtypes = [C.c_void_p, C.POINTER(DecodeArgs), C.POINTER(DecodeResult)]
+    L.rfq_decode_rows.argtypes = [C.c_void_p, C.POINTER(DecodeRowsArgs), C.POINTER(DecodeRowsResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -104,6 +120,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

@@ -126,6 +126,48 @@ class RfqCodec:
         self._check(self._L.rfq_decode_batch(self._h, C.byref(a), C.byref(r)))
         return r
 
+    # --- the reads of an image as fixed-stride rows (rfq_decode_rows)
+    def decode_rows(self, d_rfq, n, row_len=0, codes=False, qual_offset=33, pad_base=255, pad_qual=255, d_bases=None, bases_cap=0, d_quals=None, quals_cap=0,
+                    d_lens=None, lens_cap=0, has_header=True, final=True, chunk_off=None, n_chunks=0):
+        """rfq_decode_rows: row i of d_bases / d_quals (device buffers of n_rows * row_len bytes) = read i of decode(split_pe=False), padded to row_len;
+        d_lens: n_rows int32 read lengths.  No output buffer given (row_len=0 and no pointers) = a size query: n_rows, n_chunks, max_len, consumed.
+        codes: bases as A0 C1 G2 T3 N4; quality bytes are the characters minus qual_offset.  Returns DecodeRowsResult."""
+        if chunk_off is not None and not isinstance(chunk_off, C.POINTER(C.c_uint64)):
+            n_chunks = len(chunk_off) - 1
+            chunk_off = C.cast((C.c_uint64 * len(chunk_off))(*chunk_off), C.POINTER(C.c_uint64))
+        a = A.DecodeRowsArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off if (chunk_off is not None and n_chunks) else None,
+                             n_chunks if chunk_off is not None else 0, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII, qual_offset, pad_base, pad_qual, 0,
+                             d_bases, bases_cap, d_quals, quals_cap, d_lens, lens_cap)
+        r = A.DecodeRowsResult()
+        self._check(self._L.rfq_decode_rows(self._h, C.byref(a), C.byref(r)))
+        return r
+
+    def decode_rows_bytes(self, rfq: bytes, row_len=None, codes=False, qual_offset=33, pad_base=255, pad_qual=255, bases=True, quals=True, lens=True, **kw):
+        """host bytes in, numpy arrays out: (n_rows, max_len, bases [n, L] uint8, quals [n, L] uint8, lens [n] int32) - None for an output not asked
+        for.  row_len=None: the image's longest read (a size query first)."""
+        import numpy as np
+        d = self.dev_put(rfq); bufs = []
+        try:
+            q = self.decode_rows(d, len(rfq), **kw)
+            L = max(q.max_len, 1) if row_len is None else int(row_len)
+            n = q.n_rows; nb = max(n * L, 1)
+            ob = self.dev_put(b"\0" * nb) if bases else None
+            oq = self.dev_put(b"\0" * nb) if quals else None
+            ol = self.dev_put(b"\0" * max(4 * n, 4)) if lens else None
+            bufs = [x for x in (ob, oq, ol) if x is not None]
+            r = self.decode_rows(d, len(rfq), row_len=L, codes=codes, qual_offset=qual_offset, pad_base=pad_base, pad_qual=pad_qual,
+                                 d_bases=ob, bases_cap=n * L, d_quals=oq, quals_cap=n * L, d_lens=ol, lens_cap=n, **kw)
+            n = r.n_rows
+
+            def rows(p):
+                return np.frombuffer(self.dev_get(p, n * L), dtype=np.uint8).reshape(n, L) if p is not None else None
+            lv = np.frombuffer(self.dev_get(ol, 4 * n), dtype=np.int32) if ol is not None else None
+            return n, r.max_len, rows(ob), rows(oq), lv
+        finally:
+            self.dev_free(d)
+            for p in bufs:
+                self.dev_free(p)
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

@@ -30,6 +30,93 @@ static void launch_pos_list(rfq_ctx* ctx, const rfq_decode_args* a, const DChunk
 // bases: sum of the range's read lengths (the walk's 64-bit total)
 struct DecRange { const DChunk* CH; uint32_t n_chunks, n_reads, max_reads, max_stream, max_npos, max_len, max_bases, max_nrec, max_one, pieces, piece_avg, piece_n1;
         uint64_t bases; };
+// ---- the expanded stage of a range (the text path's fallback emitter and rfq_decode_rows read what it leaves in HBM)
+// read table: per-read values (k_dec_readtab), the quality / stored-base prefixes (two scans), their totals read back.  text: the text bookkeeping
+// (tin / tp, filled by k_dec_textlen) is allocated too.  R.len / R.ov / R.mid are the caller's.
+static int dec_table_expanded(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, DReadTab& R, bool text, uint32_t* total_bases, U4* pv_tot) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>(); DecStatus* dst = B[DB_STATUS].as<DecStatus>();
+    const uint32_t n_chunks = g.n_chunks, n_reads = g.n_reads, max_reads = std::max(g.max_reads, 1u);
+    const size_t nr = (size_t)n_reads + 2, nc = (size_t)n_chunks + 2;
+    HIPCHK(ctx, B[DB_CHUNKID].ensure(nr * 4));
+    HIPCHK(ctx, B[DB_PVIN].ensure(nr * 16)); HIPCHK(ctx, B[DB_PV].ensure(nr * 16)); HIPCHK(ctx, B[DB_PQ].ensure(nr * 4));
+    if (text) { HIPCHK(ctx, B[DB_TIN].ensure(nr * 16)); HIPCHK(ctx, B[DB_TP].ensure(nr * 16)); }
+    HIPCHK(ctx, B[DB_QBASE].ensure(nc * 8)); HIPCHK(ctx, B[DB_SBASE].ensure(nc * 8));
+    HIPCHK(ctx, B[DB_SCAN].ensure((nr / SCAN_TILE + 2) * 16 + 1024));
+    R.chunk = B[DB_CHUNKID].as<uint32_t>();
+    R.pvin = B[DB_PVIN].as<U4>(); R.pv = B[DB_PV].as<U4>(); R.pq = B[DB_PQ].as<uint32_t>();
+    R.tin = text ? B[DB_TIN].as<U4>() : nullptr; R.tp = text ? B[DB_TP].as<U4>() : nullptr;
+    hipLaunchKernelGGL(k_dec_readtab, dim3((max_reads + 255) / 256, n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, D, R, dst);
+    KCHK(ctx, "k_dec_readtab");
+    scan_exclusive<uint32_t>(S, R.len, R.pq, n_reads, B[DB_SCAN].as<uint32_t>(), 1);
+    scan_exclusive<U4>(S, R.pvin, R.pv, n_reads, B[DB_SCAN].as<U4>(), 1);
+    HIPCHK(ctx, ctx->fetch(total_bases, R.pq + n_reads, 4, S));
+    HIPCHK(ctx, ctx->fetch(pv_tot, R.pv + n_reads, 16, S));
+    DecStatus h2; HIPCHK(ctx, ctx->fetch(&h2, dst, sizeof h2, S)); HIPCHK(ctx, ctx->fetch_sync(S));
+    ctx->timer.end(S);
+    if (h2.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt overlap buffer");
+    return RFQ_OK;
+}
+// qualities and stored bases expanded into qdec / sdec (k_dec_bases, fill, unpack, position streams, exception records, RLE), timer stage "streams".
+// coords: the coordinate decoder rides along on the main stream (the text path's name lines need it; rows do not)
+struct DecExpanded { uint64_t* qbase; uint64_t* sbase; uint8_t* qdec; uint8_t* sdec; size_t qbytes, sbytes; };
+static int dec_streams_expanded(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const DReadTab& R, uint32_t total_bases, const U4& pv_tot, bool coords,
+                                DecExpanded* E) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader& HH = ctx->h_hdr; const DevHeader* D = ctx->d_hdr.as<DevHeader>();
+    DecStatus* dst = B[DB_STATUS].as<DecStatus>(); const DChunk* CH = g.CH; const uint32_t n_chunks = g.n_chunks; const size_t nc = (size_t)n_chunks + 2;
+    const bool rle_h = !(HH.flags & (H_DONT_QUAL | H_QUAL_BY_COL));
+    ctx->timer.begin("streams", S);
+    const size_t qbytes = (size_t)total_bases + 64 * nc + 256, sbytes = (size_t)pv_tot.d + 64 * nc + 256;
+    HIPCHK(ctx, B[DB_QDEC].ensure(qbytes)); HIPCHK(ctx, B[DB_SDEC].ensure(sbytes));
+    uint64_t* const qbase = B[DB_QBASE].as<uint64_t>(); uint64_t* const sbase = B[DB_SBASE].as<uint64_t>();
+    uint8_t* const qdec = B[DB_QDEC].as<uint8_t>(); uint8_t* const sdec = B[DB_SDEC].as<uint8_t>();
+    hipLaunchKernelGGL(k_dec_bases, dim3((n_chunks + 255) / 256), dim3(256), 0, S, CH, R, qbase, sbase, n_chunks);
+    // Two chains run side by side (rfq_ctx::aux, fork / join by events):
+    //   main  prefill of qdec, coordinate decoder, [summaries linked] quality position streams scattered into qdec, exception records
+    //   aux   position-stream summaries + link, 2-bit unpack into sdec, N positions scattered into sdec
+    const bool forked = ctx->aux_ready();
+    hipStream_t A = forked ? ctx->aux : S;
+    if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, S)); HIPCHK(ctx, hipStreamWaitEvent(A, ctx->ev_fork, 0)); }
+    const uint32_t bpc = std::max(1u, std::min(64u, 4096u / n_chunks));
+    // the prefill is pure bandwidth, the coordinate decoder and the stream summaries are pure latency: third chain
+    hipStream_t F = forked ? ctx->aux2 : S;
+    if (forked) HIPCHK(ctx, hipStreamWaitEvent(F, ctx->ev_fork, 0));
+    // (many short blocks: slots keep turning over for the two other chains)
+    hipLaunchKernelGGL(k_dec_fill, dim3((uint32_t)std::min<size_t>(8192, (qbytes / 16 + 255) / 256 + 1)), dim3(256), 0, F, qdec, (uint64_t)qbytes, D);
+    if (forked) HIPCHK(ctx, hipEventRecord(ctx->ev_f, F));
+    if (coords) hipLaunchKernelGGL(k_dec_coords, dim3(2, n_chunks), dim3(64), 0, S, a->d_rfq, CH, D, B[DB_XV].as<uint32_t>(), B[DB_YV].as<uint32_t>());
+    if ((HH.flags & H_N_POS) || ((HH.flags & H_QUAL_BY_COL) && !(HH.flags & H_DONT_QUAL))) {
+        // position streams in POS_SEG-byte segments: summary -> link -> emit (see rfq_decode_kernels.h)
+        // (grid sizes from the largest quality / N-position section: a file with raw qualities has no quality streams to walk)
+        const bool bycol = (HH.flags & H_QUAL_BY_COL) && !(HH.flags & H_DONT_QUAL), hasn = (HH.flags & H_N_POS) != 0;
+        const uint32_t nn = bycol ? std::min<uint32_t>(HH.n_normal, NPOS_SLOT) : 0u, nstr = HH.n_normal + 1;
+        const uint32_t mq = nn ? g.max_stream / POS_SEG + 1 : 0u, mn = hasn ? g.max_npos / POS_SEG + 1 : 0u, maxseg = std::max(1u, std::max(mq, mn));
+        const size_t nseg = (size_t)n_chunks * nstr * maxseg;
+        HIPCHK(ctx, B[DB_SEGF].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGA].ensure(nseg * 16 + 16)); HIPCHK(ctx, B[DB_SEGN].ensure((size_t)n_chunks * nstr * 4 + 16));
+        HIPCHK(ctx, B[DB_SEGS].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGP].ensure(nseg * 4 + 16));
+        HIPCHK(ctx, hipMemsetAsync(B[DB_SEGN].p, 0, (size_t)n_chunks * nstr * 4, A));
+#define RFQ_SUM_ARGS a->d_rfq, CH, D, R, (const uint64_t*)qbase, (const uint64_t*)sbase, qdec, sdec, B[DB_SEGF].as<uint8_t>(), B[DB_SEGA].as<int>(), B[DB_SEGN].as<uint32_t>(), maxseg, dst, (uint64_t)a->n
+        if (nn) hipLaunchKernelGGL(k_dec_pos_sum, dim3(mq, nn, n_chunks), dim3(64), 0, A, RFQ_SUM_ARGS, 0u, nstr);
+        if (hasn) hipLaunchKernelGGL(k_dec_pos_sum, dim3(mn, 1, n_chunks), dim3(64), 0, A, RFQ_SUM_ARGS, HH.n_normal, nstr);
+#undef RFQ_SUM_ARGS
+        hipLaunchKernelGGL(k_dec_pos_link, dim3((n_chunks * nstr + 255) / 256), dim3(256), 0, A, (const uint8_t*)B[DB_SEGF].as<uint8_t>(),
+                (const int*)B[DB_SEGA].as<int>(),
+                           (const uint32_t*)B[DB_SEGN].as<uint32_t>(), B[DB_SEGS].as<uint8_t>(), B[DB_SEGP].as<int>(), maxseg, n_chunks * nstr);
+        if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_mid, A)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_mid, 0)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_f, 0)); }
+        hipLaunchKernelGGL(k_dec_unpack, dim3(bpc, n_chunks), dim3(256), 0, A, a->d_rfq, CH, R, (const uint64_t*)sbase, sdec, (uint64_t)a->n);
+        if (nn) hipLaunchKernelGGL(k_dec_pos_emit, dim3(mq, nn, n_chunks), dim3(64), 0, S, a->d_rfq, CH, D, R, (const uint64_t*)qbase, (const uint64_t*)sbase, qdec, sdec,
+                                   (const uint8_t*)B[DB_SEGS].as<uint8_t>(), (const int*)B[DB_SEGP].as<int>(), maxseg, (uint64_t)a->n, 0u, nstr);
+        if (hasn) hipLaunchKernelGGL(k_dec_pos_emit, dim3(mn, 1, n_chunks), dim3(64), 0, A, a->d_rfq, CH, D, R, (const uint64_t*)qbase, (const uint64_t*)sbase, qdec,
+                sdec,
+                                     (const uint8_t*)B[DB_SEGS].as<uint8_t>(), (const int*)B[DB_SEGP].as<int>(), maxseg, (uint64_t)a->n, HH.n_normal, nstr);
+    } else hipLaunchKernelGGL(k_dec_unpack, dim3(bpc, n_chunks), dim3(256), 0, A, a->d_rfq, CH, R, (const uint64_t*)sbase, sdec, (uint64_t)a->n);
+    if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_join, A)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_join, 0)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_f, 0)); }
+    if (rle_h) hipLaunchKernelGGL(k_dec_rle, dim3(1, n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R, (const uint64_t*)qbase, qdec);
+    hipLaunchKernelGGL(k_dec_except, dim3(bpc, n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R, (const uint64_t*)qbase, qdec);
+    KCHK(ctx, "k_dec_streams");
+    ctx->timer.end(S);
+    E->qbase = qbase; E->sbase = sbase; E->qdec = qdec; E->sdec = sdec; E->qbytes = qbytes; E->sbytes = sbytes;
+    return RFQ_OK;
+}
 // RfqCodec::decodeChunk + Read::toString for the chunks of one range (reads, bases and text of a range are placed by 32-bit prefix sums).
 // out1 / out2: caller buffers (16-byte aligned) or null = the context's own result buffers; *p1 / *p2 = where the text went.
 // force_expanded: the retry of a range whose fused emit raised DE_E3_RETRY - straight to the expanded path, whatever made the tile test fail (the retry
@@ -135,22 +222,8 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
         ctx->timer.end(S);
         *nbases = g.bases;
     } else {
-        HIPCHK(ctx, B[DB_CHUNKID].ensure(nr * 4));
-        HIPCHK(ctx, B[DB_PVIN].ensure(nr * 16)); HIPCHK(ctx, B[DB_PV].ensure(nr * 16)); HIPCHK(ctx, B[DB_PQ].ensure(nr * 4));
-        HIPCHK(ctx, B[DB_TIN].ensure(nr * 16)); HIPCHK(ctx, B[DB_TP].ensure(nr * 16));
-        HIPCHK(ctx, B[DB_QBASE].ensure(nc * 8)); HIPCHK(ctx, B[DB_SBASE].ensure(nc * 8));
-        HIPCHK(ctx, B[DB_SCAN].ensure((nr / SCAN_TILE + 2) * 16 + 1024));
-        R.chunk = B[DB_CHUNKID].as<uint32_t>();
-        R.pvin = B[DB_PVIN].as<U4>(); R.pv = B[DB_PV].as<U4>(); R.pq = B[DB_PQ].as<uint32_t>(); R.tin = B[DB_TIN].as<U4>(); R.tp = B[DB_TP].as<U4>();
-        hipLaunchKernelGGL(k_dec_readtab, dim3((max_reads + 255) / 256, n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R, dst);
-        KCHK(ctx, "k_dec_readtab");
-        scan_exclusive<uint32_t>(S, R.len, R.pq, n_reads, B[DB_SCAN].as<uint32_t>(), 1);
-        scan_exclusive<U4>(S, R.pvin, R.pv, n_reads, B[DB_SCAN].as<U4>(), 1);
-        HIPCHK(ctx, ctx->fetch(&total_bases, R.pq + n_reads, 4, S));
-        HIPCHK(ctx, ctx->fetch(&pv_tot, R.pv + n_reads, 16, S));
-        { DecStatus h2; HIPCHK(ctx, ctx->fetch(&h2, dst, sizeof h2, S)); HIPCHK(ctx, ctx->fetch_sync(S)); hs.err = h2.err; }
-        ctx->timer.end(S);
-        if (hs.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt overlap buffer");
+        const int rc = dec_table_expanded(ctx, a, g, R, true, &total_bases, &pv_tot);
+        if (rc) return rc;
         *nbases = total_bases;
     }
 
@@ -162,57 +235,9 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
     }
     uint64_t* qbase = nullptr; uint64_t* sbase = nullptr; uint8_t* qdec = nullptr; uint8_t* sdec = nullptr; size_t qbytes = 0, sbytes = 0;
     if (!fused) {
-    ctx->timer.begin("streams", S);
-    qbytes = (size_t)total_bases + 64 * nc + 256; sbytes = (size_t)pv_tot.d + 64 * nc + 256;
-    HIPCHK(ctx, B[DB_QDEC].ensure(qbytes)); HIPCHK(ctx, B[DB_SDEC].ensure(sbytes));
-    qbase = B[DB_QBASE].as<uint64_t>(); sbase = B[DB_SBASE].as<uint64_t>();
-    qdec = B[DB_QDEC].as<uint8_t>(); sdec = B[DB_SDEC].as<uint8_t>();
-    hipLaunchKernelGGL(k_dec_bases, dim3((n_chunks + 255) / 256), dim3(256), 0, S, CH, R, qbase, sbase, n_chunks);
-    // Two chains run side by side (rfq_ctx::aux, fork / join by events):
-    //   main  prefill of qdec, coordinate decoder, [summaries linked] quality position streams scattered into qdec, exception records
-    //   aux   position-stream summaries + link, 2-bit unpack into sdec, N positions scattered into sdec
-    const bool forked = ctx->aux_ready();
-    hipStream_t A = forked ? ctx->aux : S;
-    if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, S)); HIPCHK(ctx, hipStreamWaitEvent(A, ctx->ev_fork, 0)); }
-    const uint32_t bpc = std::max(1u, std::min(64u, 4096u / n_chunks));
-    // the prefill is pure bandwidth, the coordinate decoder and the stream summaries are pure latency: third chain
-    hipStream_t F = forked ? ctx->aux2 : S;
-    if (forked) HIPCHK(ctx, hipStreamWaitEvent(F, ctx->ev_fork, 0));
-    // (many short blocks: slots keep turning over for the two other chains)
-    hipLaunchKernelGGL(k_dec_fill, dim3((uint32_t)std::min<size_t>(8192, (qbytes / 16 + 255) / 256 + 1)), dim3(256), 0, F, qdec, (uint64_t)qbytes, D);
-    if (forked) HIPCHK(ctx, hipEventRecord(ctx->ev_f, F));
-    hipLaunchKernelGGL(k_dec_coords, dim3(2, n_chunks), dim3(64), 0, S, a->d_rfq, CH, D, B[DB_XV].as<uint32_t>(), B[DB_YV].as<uint32_t>());
-    if ((HH.flags & H_N_POS) || ((HH.flags & H_QUAL_BY_COL) && !(HH.flags & H_DONT_QUAL))) {
-        // position streams in POS_SEG-byte segments: summary -> link -> emit (see rfq_decode_kernels.h)
-        // (grid sizes from the largest quality / N-position section: a file with raw qualities has no quality streams to walk)
-        const bool bycol = (HH.flags & H_QUAL_BY_COL) && !(HH.flags & H_DONT_QUAL), hasn = (HH.flags & H_N_POS) != 0;
-        const uint32_t nn = bycol ? std::min<uint32_t>(HH.n_normal, NPOS_SLOT) : 0u, nstr = HH.n_normal + 1;
-        const uint32_t mq = nn ? hs.max_stream / POS_SEG + 1 : 0u, mn = hasn ? hs.max_npos / POS_SEG + 1 : 0u, maxseg = std::max(1u, std::max(mq, mn));
-        const size_t nseg = (size_t)n_chunks * nstr * maxseg;
-        HIPCHK(ctx, B[DB_SEGF].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGA].ensure(nseg * 16 + 16)); HIPCHK(ctx, B[DB_SEGN].ensure((size_t)n_chunks * nstr * 4 + 16));
-        HIPCHK(ctx, B[DB_SEGS].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGP].ensure(nseg * 4 + 16));
-        HIPCHK(ctx, hipMemsetAsync(B[DB_SEGN].p, 0, (size_t)n_chunks * nstr * 4, A));
-#define RFQ_SUM_ARGS a->d_rfq, CH, D, R, (const uint64_t*)qbase, (const uint64_t*)sbase, qdec, sdec, B[DB_SEGF].as<uint8_t>(), B[DB_SEGA].as<int>(), B[DB_SEGN].as<uint32_t>(), maxseg, dst, (uint64_t)a->n
-        if (nn) hipLaunchKernelGGL(k_dec_pos_sum, dim3(mq, nn, n_chunks), dim3(64), 0, A, RFQ_SUM_ARGS, 0u, nstr);
-        if (hasn) hipLaunchKernelGGL(k_dec_pos_sum, dim3(mn, 1, n_chunks), dim3(64), 0, A, RFQ_SUM_ARGS, HH.n_normal, nstr);
-#undef RFQ_SUM_ARGS
-        hipLaunchKernelGGL(k_dec_pos_link, dim3((n_chunks * nstr + 255) / 256), dim3(256), 0, A, (const uint8_t*)B[DB_SEGF].as<uint8_t>(),
-                (const int*)B[DB_SEGA].as<int>(),
-                           (const uint32_t*)B[DB_SEGN].as<uint32_t>(), B[DB_SEGS].as<uint8_t>(), B[DB_SEGP].as<int>(), maxseg, n_chunks * nstr);
-        if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_mid, A)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_mid, 0)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_f, 0)); }
-        hipLaunchKernelGGL(k_dec_unpack, dim3(bpc, n_chunks), dim3(256), 0, A, a->d_rfq, CH, R, (const uint64_t*)sbase, sdec, (uint64_t)a->n);
-        if (nn) hipLaunchKernelGGL(k_dec_pos_emit, dim3(mq, nn, n_chunks), dim3(64), 0, S, a->d_rfq, CH, D, R, (const uint64_t*)qbase, (const uint64_t*)sbase, qdec, sdec,
-                                   (const uint8_t*)B[DB_SEGS].as<uint8_t>(), (const int*)B[DB_SEGP].as<int>(), maxseg, (uint64_t)a->n, 0u, nstr);
-        if (hasn) hipLaunchKernelGGL(k_dec_pos_emit, dim3(mn, 1, n_chunks), dim3(64), 0, A, a->d_rfq, CH, D, R, (const uint64_t*)qbase, (const uint64_t*)sbase, qdec,
-                sdec,
-                                     (const uint8_t*)B[DB_SEGS].as<uint8_t>(), (const int*)B[DB_SEGP].as<int>(), maxseg, (uint64_t)a->n, HH.n_normal, nstr);
-    } else hipLaunchKernelGGL(k_dec_unpack, dim3(bpc, n_chunks), dim3(256), 0, A, a->d_rfq, CH, R, (const uint64_t*)sbase, sdec, (uint64_t)a->n);
-    if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_join, A)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_join, 0)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_f, 0)); }
-    if (rle_h) hipLaunchKernelGGL(k_dec_rle, dim3(1, n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R, (const uint64_t*)qbase, qdec);
-    hipLaunchKernelGGL(k_dec_except, dim3(bpc, n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R, (const uint64_t*)qbase, qdec);
-    KCHK(ctx, "k_dec_streams");
-    ctx->timer.end(S);
-
+        DecExpanded E; const int rc = dec_streams_expanded(ctx, a, g, R, total_bases, pv_tot, true, &E);
+        if (rc) return rc;
+        qbase = E.qbase; sbase = E.sbase; qdec = E.qdec; sdec = E.sdec; qbytes = E.qbytes; sbytes = E.sbytes;
     }
 
     // ---- text
@@ -329,31 +354,50 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
     return RFQ_OK;
 }
 
-extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_decode_result* res) {
-    if (!ctx || !a || !res) return RFQ_E_ARG;
-    memset(res, 0, sizeof *res);
-    ctx->err.clear();
-    if (a->n && !a->d_rfq) return rfq_fail(ctx, RFQ_E_ARG, "null rfq pointer");
-    if (a->n == 0 && a->has_header) {
-        // an empty .rfq: every read of RfqHeader::read fails and the constructor's defaults stand (valid magic, flags 0;
-        // src/rfqheader.cpp:7-17,19-43), no chunk follows: the reference writes an empty FASTQ
-        if (a->split_pe) return rfq_fail(ctx, RFQ_E_DATA, "The input RFQ file was encoded by single-end FASTQ, you should not specify <out2>");
-        return RFQ_OK;
+// the range of chunks [CH, CH + n_chunks) with the walk's image-wide maxima
+static DecRange range_of(const DecStatus& hs, const DChunk* CH, uint32_t n_chunks, uint64_t reads, uint64_t bases) {
+    DecRange g; g.CH = CH; g.n_chunks = n_chunks; g.n_reads = (uint32_t)reads; g.max_reads = hs.max_reads; g.max_stream = hs.max_stream;
+            g.max_npos = hs.max_npos; g.max_len = hs.max_len; g.max_bases = hs.max_bases; g.max_nrec = hs.max_nrec; g.max_one = hs.max_one;
+            g.pieces = hs.per_read_pieces; g.piece_avg = hs.piece_avg; g.piece_n1 = hs.piece_n1; g.bases = bases;
+    return g;
+}
+// Reads, bases and text of one pass are placed by 32-bit prefix sums: a larger image is decoded range by range - contiguous chunks of about
+// slice_bases bases and fewer than 2^31 reads, cut out of every piece [c0, c1) of the image.  Returned as a stack: the first range on top.
+struct DecRng { uint32_t c0, c1; bool r1_only; };
+static std::vector<DecRng> plan_ranges(const std::vector<DecRng>& pieces, const std::vector<DChunk>& hc, uint64_t slice_bases) {
+    std::vector<DecRng> fw, todo;
+    for (auto& pc : pieces) {
+        uint32_t c0 = pc.c0; uint64_t acc = 0, rd = 0;
+        for (uint32_t c = pc.c0; c < pc.c1; c++) {
+            if (c > c0 && (acc + hc[c].bases > slice_bases || rd + hc[c].reads > 0x7FFFFFF0ull)) { fw.push_back({ c0, c, pc.r1_only }); c0 = c; acc = 0; rd = 0; }
+            acc += hc[c].bases; rd += hc[c].reads;
+        }
+        fw.push_back({ c0, pc.c1, pc.r1_only });
     }
-    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
+    for (size_t i = fw.size(); i-- > 0;) todo.push_back(fw[i]);
+    return todo;
+}
+
+// what every decode call does first: the device, the stage timers, the header (parsed from the image and set, or the one set before);
+// *start = where the image's chunks begin
+static int dec_open(rfq_ctx* ctx, const rfq_decode_args* a, uint64_t* start) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->timer.reset();
     ctx->pend.clear(); ctx->pin_used = 0;                                   // (read-backs an earlier call left behind on an error path)
-    uint64_t start = 0;
+    *start = 0;
     if (a->has_header) {
         uint8_t hb[RFQ_HEADER_MAX]; const size_t take = std::min<size_t>(a->n, sizeof hb);
         if (take) HIPCHK(ctx, hipMemcpy(hb, a->d_rfq, take, hipMemcpyDeviceToHost));
         int rc = rfq_upload_header(ctx, hb, take);
         if (rc) return rc;
-        start = ctx->h_hdr.len;
+        *start = ctx->h_hdr.len;
     } else if (!ctx->have_hdr) return rfq_fail(ctx, RFQ_E_STATE, "decode without a header: pass has_header=1 or call rfq_set_header first");
-    const DevHeader& HH = ctx->h_hdr;
-    if (a->split_pe && !(HH.flags & H_PAIRED)) return rfq_fail(ctx, RFQ_E_DATA, "The input RFQ file was encoded by single-end FASTQ, you should not specify <out2>");
+    return RFQ_OK;
+}
+// the chunk chain of the image: the caller's chunk index (verified), guess-and-verify or the exact walk, the verifying parse behind it.
+// hs: chunks, reads, bases, the longest read / stream / chunk, consumed - exact on every path
+static int dec_walk(rfq_ctx* ctx, const rfq_decode_args* a, uint64_t start, DecStatus& hs) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader& HH = ctx->h_hdr;
     if (HH.read_len_bytes != 1 && HH.read_len_bytes != 2 && HH.read_len_bytes != 4) return rfq_fail(ctx, RFQ_E_DATA,
             "header incorrect: read length bytes should be 1/2/4");
     const DevHeader* D = ctx->d_hdr.as<DevHeader>();
@@ -361,7 +405,7 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
     // ---- walk the chunk chain
     ctx->timer.begin("walk", S);
     HIPCHK(ctx, B[DB_STATUS].ensure(sizeof(DecStatus)));
-    DecStatus* dst = B[DB_STATUS].as<DecStatus>(); DecStatus hs;
+    DecStatus* dst = B[DB_STATUS].as<DecStatus>();
     uint32_t cap = (uint32_t)std::max<size_t>(B[DB_CHUNKS].cap / sizeof(DChunk), 4096);
     // the chunk starts: the caller's chunk index (verified below); else guess-and-verify (k_dec_gw_*: an index made on the device, verified the same
     // way); else the exact serial walk (one wave, a full parse per chunk: foreign writers, corrupt images)
@@ -437,6 +481,27 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
     if (ctx->opt.trace) fprintf(stderr, "[rfq] chunk starts: %s, %u chunks\n", use_table ? "caller's index" : (guess ? "guess-and-verify" : "exact walk"), hs.n_chunks);
     ctx->timer.end(S);
     if (hs.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "truncated or corrupt rfq chunk at byte %llu", (unsigned long long)hs.consumed);
+    return RFQ_OK;
+}
+
+extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_decode_result* res) {
+    if (!ctx || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    if (a->n && !a->d_rfq) return rfq_fail(ctx, RFQ_E_ARG, "null rfq pointer");
+    if (a->n == 0 && a->has_header) {
+        // an empty .rfq: every read of RfqHeader::read fails and the constructor's defaults stand (valid magic, flags 0;
+        // src/rfqheader.cpp:7-17,19-43), no chunk follows: the reference writes an empty FASTQ
+        if (a->split_pe) return rfq_fail(ctx, RFQ_E_DATA, "The input RFQ file was encoded by single-end FASTQ, you should not specify <out2>");
+        return RFQ_OK;
+    }
+    uint64_t start = 0;
+    { const int rc = dec_open(ctx, a, &start); if (rc) return rc; }
+    const DevHeader& HH = ctx->h_hdr;
+    if (a->split_pe && !(HH.flags & H_PAIRED)) return rfq_fail(ctx, RFQ_E_DATA, "The input RFQ file was encoded by single-end FASTQ, you should not specify <out2>");
+    DecStatus hs;
+    { const int rc = dec_walk(ctx, a, start, hs); if (rc) return rc; }
+    DBuf* B = ctx->b; hipStream_t S = ctx->stream;
     // 64-bit total of the read lengths: bases, qualities and text are placed by 32-bit prefix sums below (a corrupt length table
     // must be refused before any buffer is sized from a wrapped sum)
     uint64_t tb = 0; for (int i = 0; i < 16; i++) tb += hs.base_slots[i];
@@ -457,7 +522,7 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
     // when it is the R1 bit that is set.  The text is decoded piece by piece: runs of chunks that survive, R1 only where the reference drops R2.
     // Repaq::decompress (one output, :262-328) peeks the same way but keeps the peeked chunk in a variable that outlives the iteration and decodes it
     // next: nothing is lost there, and the only effect of the bit - the last chunk's final '\n' dropped - is the default behaviour.
-    struct Rng { uint32_t c0, c1; bool r1_only; };
+    typedef DecRng Rng;
     std::vector<Rng> pieces; std::vector<DChunk> hc; bool strip1 = (last_flags & C_NO_LB) != 0, strip2 = (last_flags & C_NO_LB_R2) != 0;
     const bool compat = a->bug_compat != 0 && split;
     if (compat) {
@@ -480,9 +545,7 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
         res->n_chunks = 0; for (auto& q : pieces) res->n_chunks += q.c1 - q.c0;
     }
     if (!compat && tb < one_pass && n_reads64 < 0x7FFFFFF0ull) {
-        DecRange g; g.CH = CHm; g.n_chunks = n_chunks; g.n_reads = (uint32_t)n_reads64; g.max_reads = hs.max_reads; g.max_stream = hs.max_stream;
-                g.max_npos = hs.max_npos; g.max_len = hs.max_len; g.max_bases = hs.max_bases; g.max_nrec = hs.max_nrec; g.max_one = hs.max_one;
-                g.pieces = hs.per_read_pieces; g.piece_avg = hs.piece_avg; g.piece_n1 = hs.piece_n1; g.bases = tb;
+        const DecRange g = range_of(hs, CHm, n_chunks, n_reads64, tb);
         rc = decode_range(ctx, a, g, a->d_out1, a->cap1, a->d_out2, a->cap2, &o1, &o2, &n1, &n2, &nb);
         if (rc != RFQ_OK && rc != RFQ_RANGE_TOO_BIG) return rc;
     }
@@ -492,17 +555,7 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
         // there to its place in the result.
         if (!compat) { hc.resize(n_chunks); HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
                 pieces.push_back({ 0, n_chunks, false }); }
-        std::vector<Rng> todo;                                               // stack of [c0, c1), first range on top
-        { std::vector<Rng> fw;
-          for (auto& pc : pieces) {
-              uint32_t c0 = pc.c0; uint64_t acc = 0, rd = 0;
-              for (uint32_t c = pc.c0; c < pc.c1; c++) {
-                  if (c > c0 && (acc + hc[c].bases > slice_bases || rd + hc[c].reads > 0x7FFFFFF0ull)) { fw.push_back({ c0, c, pc.r1_only }); c0 = c; acc = 0; rd = 0; }
-                  acc += hc[c].bases; rd += hc[c].reads;
-              }
-              fw.push_back({ c0, pc.c1, pc.r1_only });
-          }
-          for (size_t i = fw.size(); i-- > 0;) todo.push_back(fw[i]); }
+        std::vector<Rng> todo = plan_ranges(pieces, hc, slice_bases);        // stack of [c0, c1), first range on top
         size_t w1 = 0, w2 = 0; n1 = n2 = 0; nb = 0;
         std::vector<std::pair<const char*, float>> acc_ms;
         ctx->timer.collect();                                                // (the walk, and whatever a failed one-pass attempt got through)
@@ -512,9 +565,7 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
             const uint32_t c0 = r.c0, c1 = r.c1; uint64_t reads = 0, rbases = 0; for (uint32_t c = c0; c < c1; c++) { reads += hc[c].reads; rbases += hc[c].bases; }
             hipLaunchKernelGGL(k_dec_rebase, dim3((c1 - c0 + 255) / 256), dim3(256), 0, S, CHm + c0, c1 - c0, hc[c0].rbase_abs);
             KCHK(ctx, "k_dec_rebase");
-            DecRange g; g.CH = CHm + c0; g.n_chunks = c1 - c0; g.n_reads = (uint32_t)reads; g.max_reads = hs.max_reads; g.max_stream = hs.max_stream;
-                    g.max_npos = hs.max_npos; g.max_len = hs.max_len; g.max_bases = hs.max_bases; g.max_nrec = hs.max_nrec; g.max_one = hs.max_one;
-                    g.pieces = hs.per_read_pieces; g.piece_avg = hs.piece_avg; g.piece_n1 = hs.piece_n1; g.bases = rbases;
+            const DecRange g = range_of(hs, CHm + c0, c1 - c0, reads, rbases);
             uint8_t *q1 = nullptr, *q2 = nullptr; size_t m1 = 0, m2 = 0; uint64_t mb = 0;
             ctx->timer.reset();
             rc = reads > 0x7FFFFFF0ull ? RFQ_RANGE_TOO_BIG : decode_range(ctx, a, g, nullptr, 0, nullptr, 0, &q1, &q2, &m1, &m2, &mb);
@@ -552,5 +603,108 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
         if (split && strip2 && n2) n2--;
     }
     res->d_fq1 = o1; res->n1 = n1; res->d_fq2 = split ? o2 : nullptr; res->n2 = split ? n2 : 0;
+    return RFQ_OK;
+}
+
+// ---- rfq_decode_rows: the reads of an image as fixed-stride base / quality rows.  Always the expanded stage (qdec / sdec in HBM, whatever
+// RFQ_MATERIALISE says) with neither text lengths, name middles nor coordinates, then k_dec_rows (dec/rows.h).  Rows of a range start at the
+// running read count of the call (DChunk::rbase_abs).
+static int rows_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const RowsOut& o) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>(); DecStatus* dst = B[DB_STATUS].as<DecStatus>();
+    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(DecStatus), S));
+    ctx->timer.begin("read_table", S);
+    const size_t nr = (size_t)g.n_reads + 2;
+    HIPCHK(ctx, B[DB_LEN].ensure(nr * 4)); HIPCHK(ctx, B[DB_OV].ensure(nr * 4));
+    DReadTab R; memset(&R, 0, sizeof R); R.len = B[DB_LEN].as<uint32_t>(); R.ov = B[DB_OV].as<int32_t>();
+    uint32_t total_bases = 0; U4 pv_tot; memset(&pv_tot, 0, sizeof pv_tot);
+    int rc = dec_table_expanded(ctx, a, g, R, false, &total_bases, &pv_tot);
+    if (rc) return rc;
+    DecExpanded E; rc = dec_streams_expanded(ctx, a, g, R, total_bases, pv_tot, false, &E);
+    if (rc) return rc;
+    // the streams' verdict before any row is written (the text path refuses the same image here: "corrupt quality buffer")
+    DecStatus h; HIPCHK(ctx, ctx->fetch(&h, dst, sizeof h, S)); HIPCHK(ctx, ctx->fetch_sync(S));
+    if (h.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt quality buffer");
+    ctx->timer.begin("rows", S);
+    // (tiles of 32 reads; no LDS and few registers: eight workgroups per CU)
+    const uint32_t bx = grid_x_for(g.n_chunks, (std::max(g.max_reads, 1u) + 31u) / 32u, 8u * ctx->n_cu);
+    hipLaunchKernelGGL(k_dec_rows, dim3(bx, g.n_chunks), dim3(256), 0, S, g.CH, (const DevHeader*)D, R, (const uint64_t*)E.qbase, (const uint64_t*)E.sbase,
+                       (const uint8_t*)E.qdec, (const uint8_t*)E.sdec, o);
+    KCHK(ctx, "k_dec_rows");
+    ctx->timer.end(S);
+    HIPCHK(ctx, hipStreamSynchronize(S));
+    return RFQ_OK;
+}
+
+extern "C" int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* ra, rfq_decode_rows_result* res) {
+    if (!ctx || !ra || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    if (ra->n && !ra->d_rfq) return rfq_fail(ctx, RFQ_E_ARG, "null rfq pointer");
+    if (ra->base_mode != RFQ_ROWS_ASCII && ra->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "base_mode must be RFQ_ROWS_ASCII or RFQ_ROWS_CODE");
+    const bool query = !ra->d_bases && !ra->d_quals && !ra->d_lens;
+    if (!query && ra->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be at least 1");
+    if ((uintptr_t)ra->d_lens & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens must be 4-byte aligned");
+    // the walk and the expanded stage take the text decode's arguments (split_pe = 0, bug_compat = 0: Repaq::decompress order, nothing lost)
+    rfq_decode_args a; memset(&a, 0, sizeof a);
+    a.d_rfq = ra->d_rfq; a.n = ra->n; a.has_header = ra->has_header; a.final = ra->final; a.h_chunk_off = ra->h_chunk_off; a.n_chunk_off = ra->n_chunk_off;
+    if (a.n == 0 && a.has_header) return RFQ_OK;                              // an empty .rfq: no reads
+    uint64_t start = 0;
+    { const int rc = dec_open(ctx, &a, &start); if (rc) return rc; }
+    DecStatus hs;
+    { const int rc = dec_walk(ctx, &a, start, hs); if (rc) return rc; }
+    hipStream_t S = ctx->stream;
+    uint64_t tb = 0; for (int i = 0; i < 16; i++) tb += hs.base_slots[i];
+    const uint32_t n_chunks = hs.n_chunks; const uint64_t n_rows = n_chunks ? hs.total_reads : 0;
+    res->consumed = (size_t)hs.consumed; res->n_chunks = n_chunks; res->n_rows = n_rows; res->n_bases = n_chunks ? tb : 0; res->max_len = n_chunks ? hs.max_len : 0;
+    if (query || n_chunks == 0) { HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect(); return RFQ_OK; }
+    const uint64_t L = ra->row_len, need = n_rows * L;
+    if (L < res->max_len) return rfq_fail(ctx, RFQ_E_NOSPACE, "row_len %u is shorter than the longest read: need row_len >= %u", ra->row_len, res->max_len);
+    if (ra->d_bases && ra->bases_cap < need) return rfq_fail(ctx, RFQ_E_NOSPACE, "base rows too small: need %llu bytes (%llu rows of %u)", (unsigned long long)need,
+            (unsigned long long)n_rows, ra->row_len);
+    if (ra->d_quals && ra->quals_cap < need) return rfq_fail(ctx, RFQ_E_NOSPACE, "quality rows too small: need %llu bytes (%llu rows of %u)", (unsigned long long)need,
+            (unsigned long long)n_rows, ra->row_len);
+    if (ra->d_lens && ra->lens_cap < n_rows) return rfq_fail(ctx, RFQ_E_NOSPACE, "length array too small: need %llu entries", (unsigned long long)n_rows);
+    RowsOut o; memset(&o, 0, sizeof o);
+    o.bases = ra->d_bases; o.quals = ra->d_quals; o.lens = ra->d_lens; o.row_len = L; o.n_rows = n_rows;
+    o.codes = ra->base_mode == RFQ_ROWS_CODE ? 1u : 0u;
+    o.qoff4 = ra->qual_offset * 0x01010101u; o.pad_b4 = ra->pad_base * 0x01010101u; o.pad_q4 = ra->pad_qual * 0x01010101u;
+    o.vec = (L % 16u == 0 && !((uintptr_t)ra->d_bases & 15u) && !((uintptr_t)ra->d_quals & 15u)) ? 1u : 0u;
+    DChunk* CHm = ctx->b[DB_CHUNKS].as<DChunk>();
+    // the text path's ranges: bases and qualities of a pass are placed by 32-bit prefix sums (RFQ_SLICE_BASES forces ranges on small images)
+    const uint64_t slice_env = ctx->opt.slice_bases;
+    const uint64_t slice_bases = slice_env ? slice_env : 1500000000ull, one_pass = slice_env ? slice_env : 0xFFFFFFF0ull;
+    if (tb < one_pass && n_rows < 0x7FFFFFF0ull) {
+        const int rc = rows_range(ctx, &a, range_of(hs, CHm, n_chunks, n_rows, tb), o);
+        if (rc) return rc;
+        ctx->timer.collect();
+        return RFQ_OK;
+    }
+    std::vector<DChunk> hc(n_chunks);
+    HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
+    std::vector<DecRng> todo = plan_ranges(std::vector<DecRng>{ { 0, n_chunks, false } }, hc, slice_bases);
+    // stage times summed over the ranges, by name (the walk first)
+    std::vector<std::pair<const char*, float>> acc_ms;
+    auto add_ms = [&]() {
+        ctx->timer.collect();
+        for (size_t i = 0; i < ctx->timer.names.size(); i++) {
+            bool hit = false;
+            for (auto& q : acc_ms) if (q.first == ctx->timer.names[i]) { q.second += ctx->timer.ms[i]; hit = true; break; }
+            if (!hit) acc_ms.emplace_back(ctx->timer.names[i], ctx->timer.ms[i]);
+        }
+    };
+    HIPCHK(ctx, hipStreamSynchronize(S)); add_ms();
+    while (!todo.empty()) {
+        const DecRng r = todo.back(); todo.pop_back();
+        uint64_t reads = 0, rbases = 0; for (uint32_t c = r.c0; c < r.c1; c++) { reads += hc[c].reads; rbases += hc[c].bases; }
+        if (rbases >= 0xFFFFFFF0ull || reads >= 0x7FFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk holds 4 Gi bases or 2 Gi reads or more");
+        hipLaunchKernelGGL(k_dec_rebase, dim3((r.c1 - r.c0 + 255) / 256), dim3(256), 0, S, CHm + r.c0, r.c1 - r.c0, hc[r.c0].rbase_abs);
+        KCHK(ctx, "k_dec_rebase");
+        ctx->timer.reset();
+        const int rc = rows_range(ctx, &a, range_of(hs, CHm + r.c0, r.c1 - r.c0, reads, rbases), o);
+        if (rc) return rc;
+        add_ms();
+    }
+    ctx->timer.names.clear(); ctx->timer.ms.clear();
+    for (auto& q : acc_ms) { ctx->timer.names.push_back(q.first); ctx->timer.ms.push_back(q.second); }
     return RFQ_OK;
 }

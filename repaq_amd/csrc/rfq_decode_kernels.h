@@ -17,3 +17,4 @@
 #include "dec/text_len.h"                     // name middles and text lengths
 #include "dec/emit_expanded.h"                // text emission of the expanded path (tile emitter k_dec_emit)
 #include "dec/emit_tiles.h"                   // text emission, fused path: k_dec_emit3 (fixed tiles, no output tile)
+#include "dec/rows.h"                         // reads as fixed-stride base / quality rows (rfq_decode_rows): k_dec_rows over the expanded stage
