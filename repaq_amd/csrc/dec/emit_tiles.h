@@ -90,7 +90,7 @@ template <bool IMPL, uint32_t N1CAP = ET_N1CAP, bool SHARED = false> __global__ 
     if (rs >= re) return;
     // (list_cap != 0: launched WITHOUT the host having looked at the status behind the list chain and the read table - rfq_decode.hip, "speculative" - : whatever the host
     // would have stopped at stops the kernel; the host looks afterwards, once, and takes the path it would have taken)
-    if (list_cap && ((st->err & (uint32_t)(DE_CORRUPT | DE_CORRUPT_OV | DE_E3_RETRY)) || st->list_need > list_cap)) return;
+    if (list_cap && ((st->err & (uint32_t)(DE_CORRUPT | DE_CORRUPT_OV | DE_LIST_ALIAS | DE_E3_RETRY)) || st->list_need > list_cap)) return;
     // (SHARED is only taken for files with coded qualities: raw quality bytes - more than 64 values, rare - keep the general instantiation)
     const bool raw = !SHARED && (hf & H_DONT_QUAL) != 0, bycol = SHARED || (!raw && (hf & H_QUAL_BY_COL));
     const uint32_t nn = bycol ? (D->n_normal < NPOS_SLOT ? D->n_normal : NPOS_SLOT) : 0u; const bool hasn = (hf & H_N_POS) != 0;

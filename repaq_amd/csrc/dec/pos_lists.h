@@ -164,7 +164,7 @@ __global__ void k_dec_pos_link2(const uint8_t* __restrict__ segF, const int* __r
         // 16-bit list entries (plist_t) are unambiguous while a stream's positions stay within 32 K of the chunk's own extent - they do, unless the image codes positions its
         // length table does not cover (the reference's two-byte lengths of reads > 65535 bases, App. C; corrupt images): such ranges take the expanded path
         const unsigned long long ext = CH[t / nstr].bases;
-        if (cp >= 0 && (unsigned long long)cp >= ext + 32768ull) atomicOr(&st->err, (uint32_t)DE_E3_RETRY);
+        if (cp >= 0 && (unsigned long long)cp >= ext + 32768ull) atomicOr(&st->err, (uint32_t)DE_LIST_ALIAS);
     }
 }
 // exclusive prefix of the streams' entry counts (one workgroup; n_streams is some thousands) -> where each list starts in the arena; the total

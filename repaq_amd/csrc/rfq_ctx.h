@@ -49,6 +49,17 @@ struct StageTimer {
     }
     void destroy() { for (auto& s : stages) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); } stages.clear(); }
 };
+// stage times of a call that runs its stages once per range: add() sums what the timer collected by name, publish() makes the sums the timer's result
+struct StageSums {
+    std::vector<std::pair<const char*, float>> v;
+    void add(const StageTimer& t) {
+        for (size_t i = 0; i < t.names.size(); i++) {
+            auto q = std::find_if(v.begin(), v.end(), [&](const std::pair<const char*, float>& e) { return e.first == t.names[i]; });
+            if (q == v.end()) v.emplace_back(t.names[i], t.ms[i]); else q->second += t.ms[i];
+        }
+    }
+    void publish(StageTimer& t) const { t.names.clear(); t.ms.clear(); for (auto& q : v) { t.names.push_back(q.first); t.ms.push_back(q.second); } }
+};
 
 // Workgroups per chunk for a tile kernel whose grid is (x, n_chunks): the GPU holds `slots` of its workgroups at a time, and a grid that is not
 // a whole number of such rounds leaves the last round part empty (3360 chunks x 2 = 6720 workgroups on 1280 slots are 5.25 rounds: measured

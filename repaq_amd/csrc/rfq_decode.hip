@@ -15,17 +15,6 @@ enum DecBuf {   // indices into rfq_ctx::b (disjoint from the encoder's, so one 
 };
 static_assert(DB_END <= 120, "rfq_ctx::b too small");
 
-// fused path: k_dec_pos_list for the quality streams and the N-position stream (the arena is whatever B[DB_PLIST] holds)
-static void launch_pos_list(rfq_ctx* ctx, const rfq_decode_args* a, const DChunk* CH, uint32_t n_chunks, uint32_t maxseg, uint32_t ncell, uint32_t nstr,
-                            uint32_t mq, uint32_t mn, uint32_t nn, bool hasn, uint32_t segb, hipStream_t LS) {
-    DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>(); const DecStatus* dst = B[DB_STATUS].as<DecStatus>();
-    const unsigned long long cap = B[DB_PLIST].cap / sizeof(plist_t);
-#define RFQ_LIST_ARGS a->d_rfq, CH, D, (const uint8_t*)B[DB_SEGS].as<uint8_t>(), (const int*)B[DB_SEGP].as<int>(), (const uint32_t*)B[DB_SEGK].as<uint32_t>(), \
-                      (const unsigned long long*)B[DB_LOFF].as<unsigned long long>(), B[DB_PLIST].as<plist_t>(), cap, B[DB_CELL].as<uint32_t>(), maxseg, ncell, (uint64_t)a->n
-    if (nn) hipLaunchKernelGGL(k_dec_pos_list, dim3((mq + 3) / 4, nn, n_chunks), dim3(256), 0, LS, RFQ_LIST_ARGS, 0u, nstr, dst, segb);
-    if (hasn) hipLaunchKernelGGL(k_dec_pos_list, dim3((mn + 3) / 4, 1, n_chunks), dim3(256), 0, LS, RFQ_LIST_ARGS, ctx->h_hdr.n_normal, nstr, dst, segb);
-#undef RFQ_LIST_ARGS
-}
 #define RFQ_RANGE_TOO_BIG 2          // internal: the range's text would not fit the 32-bit text offsets of one pass
 // bases: sum of the range's read lengths (the walk's 64-bit total)
 struct DecRange { const DChunk* CH; uint32_t n_chunks, n_reads, max_reads, max_stream, max_npos, max_len, max_bases, max_nrec, max_one, pieces, piece_avg, piece_n1;
@@ -117,35 +106,20 @@ static int dec_streams_expanded(rfq_ctx* ctx, const rfq_decode_args* a, const De
     E->qbase = qbase; E->sbase = sbase; E->qdec = qdec; E->sdec = sdec; E->qbytes = qbytes; E->sbytes = sbytes;
     return RFQ_OK;
 }
-// RfqCodec::decodeChunk + Read::toString for the chunks of one range (reads, bases and text of a range are placed by 32-bit prefix sums).
-// out1 / out2: caller buffers (16-byte aligned) or null = the context's own result buffers; *p1 / *p2 = where the text went.
-// force_expanded: the retry of a range whose fused emit raised DE_E3_RETRY - straight to the expanded path, whatever made the tile test fail (the retry
-// must terminate by construction, not because a flag happens to be honoured: ADVICE r4)
-static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, uint8_t* out1, uint64_t ocap1, uint8_t* out2, uint64_t ocap2,
-                        uint8_t** p1, uint8_t** p2, size_t* n1, size_t* n2, uint64_t* nbases, bool force_expanded = false) {
-    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
-    // (RFQ_MATERIALISE: the expanding decode of a streaming caller's non-final slices, on every call)
-    const int tune = ctx->opt.materialise ? 2048 : 0;
-    const DevHeader& HH = ctx->h_hdr; const DevHeader* D = ctx->d_hdr.as<DevHeader>();
-    DecStatus* dst = B[DB_STATUS].as<DecStatus>(); DecStatus hs; memset(&hs, 0, sizeof hs);
-    hs.max_stream = g.max_stream; hs.max_npos = g.max_npos;
-    const uint32_t n_chunks = g.n_chunks, n_reads = g.n_reads, max_reads = std::max(g.max_reads, 1u);
-    const DChunk* CH = g.CH;
-    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(DecStatus), S));
-    // ---- the position-list chain of the fused path (rfq_decode_kernels.h "fused path"): the emitter builds qualities and bases tile by tile in LDS
-    // from the packed bytes and lists of coded positions; the lists need nothing but the chunk table, so their chain (stream summaries, link,
-    // offsets, lists + cell index) starts NOW on the second stream, beside read table, prefixes, coordinates and text lengths, and is joined in
-    // front of the last status read-back before the emitter.  Taken for files with few quality streams whose reads and exception lists fit a
-    // tile; RFQ_MATERIALISE=1 forces the materialising path.
-    const bool bycol_h = (HH.flags & H_QUAL_BY_COL) && !(HH.flags & H_DONT_QUAL);
+// ---- the fused path of a range (rfq_decode_kernels.h "fused path"): the emitter builds qualities and bases tile by tile in LDS from the packed bytes and
+// lists of coded positions.  It ends in k_dec_emit3 (no output tile, K reads per tile: the largest power of two whose qualities fit its tile).
+// on: the range takes it; e3k: log2 K; n1big: the instantiation with the 13 KB name tile; shared_pieces: no chunk stores name pieces per read
+struct FusedPlan { bool on; uint32_t e3k; bool n1big, shared_pieces; };
+// Names FastqMeta::parse does not take apart and strand lines with text are stored per read: K then also goes by the chunks' average piece size, a fifth of the
+// tile left for reads above the average, full tiles of 64 reads only (name1 has a second instantiation with a 13 KB tile: names of up to ~165 bytes on average,
+// e.g. the configs[4] shape).  What does not fit - longer names, reads of more than 2000 bases, chunks of more than 4096 exception records, legacy run-length
+// images - takes the ONE fallback: qualities and bases expanded in HBM, k_dec_emit.  A tile whose pieces turn out longer than the averages allowed for raises
+// DE_E3_RETRY: the range is decoded again on the fallback (force_expanded: the retry cannot come back here), and the context remembers it for the ranges that
+// follow until the next header is set or cleared.  Taken for files with few quality streams whose reads and exception lists fit a tile; RFQ_MATERIALISE=1 (the
+// expanding decode of a streaming caller's non-final slices, on every call) forces the materialising path.
+static FusedPlan plan_fused(const rfq_ctx* ctx, const DecRange& g, bool force_expanded) {
+    const DevHeader& HH = ctx->h_hdr;
     const bool rle_h = !(HH.flags & (H_DONT_QUAL | H_QUAL_BY_COL));          // legacy run-length quality coding: k_dec_rle on the materialising path
-    // The fused path ends in k_dec_emit3 (no output tile, K reads per tile: the largest power of two whose qualities fit its tile).  Names FastqMeta::parse does not
-    // take apart and strand lines with text are stored per read: K then also goes by the chunks' average piece size, a fifth of the tile left for reads above the
-    // average, full tiles of 64 reads only (name1 has a second instantiation with a 13 KB tile: names of up to ~165 bytes on average, e.g. the configs[4] shape).
-    // What does not fit - longer names, reads of more than 2000 bases, chunks of more than 4096 exception records, legacy run-length images - takes the ONE
-    // fallback: qualities and bases expanded in HBM, k_dec_emit.  A tile whose pieces turn out longer than the averages allowed for raises DE_E3_RETRY: the range
-    // is decoded again on the fallback (force_expanded: the retry cannot come back here), and the context remembers it for the ranges that follow until
-    // the next header is set or cleared.
     uint32_t e3k = 6; bool n1big = false;
     while (e3k >= 1 && ((uint64_t)g.max_len << e3k) > E3_QCAP) e3k--;
     if (g.pieces) {
@@ -155,198 +129,206 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
     }
     const bool e3_ok = e3k >= (g.pieces ? 6u : 1u) && !(g.pieces && ctx->e3_pieces_failed);
     // (chunks of 2^30 bases and more: the list chain's saturating position sums - POS_ADV_MAX, dec/pos_lists.h - would no longer be exact)
-    const bool fused = !force_expanded && !(tune & 2048) && !rle_h && g.max_len <= 2000u && g.max_nrec <= 4096u && e3_ok && g.max_bases < (1u << 30) - 65536u;
-    uint32_t f_maxseg = 1, f_ncell = 1, f_mq = 0, f_mn = 0, f_nn = 0, f_segb = POS2_SEG; bool f_lists = false, f_hasn = false, f_join = false; hipStream_t f_aux = S;
-            const uint32_t f_nstr = HH.n_normal + 1;
-    // (an early return must not leave the chain running over buffers the next call reuses)
-    struct AuxJoin { rfq_ctx* c; bool armed; ~AuxJoin() { if (armed) (void)hipStreamSynchronize(c->aux); } } aux_guard = { ctx, false };
-    if (fused) {
-        const bool hasn = (HH.flags & H_N_POS) != 0; const uint32_t nn = bycol_h ? std::min<uint32_t>(HH.n_normal, NPOS_SLOT) : 0u;
-        const bool forked = ctx->aux_ready(); hipStream_t A = forked ? ctx->aux : S;
-        if (nn || hasn) {
-            if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, S)); HIPCHK(ctx, hipStreamWaitEvent(A, ctx->ev_fork, 0)); aux_guard.armed = true; }
-            f_segb = ctx->opt.pos_seg ? (uint32_t)ctx->opt.pos_seg : (std::max(g.max_one, g.max_npos) >= 32768u ? POS2_SEG_BIG : POS2_SEG);
-            const uint32_t mq = nn ? g.max_one / f_segb + 1 : 0u, mn = hasn ? g.max_npos / f_segb + 1 : 0u; f_maxseg = std::max(1u, std::max(mq, mn));
-            f_ncell = g.max_bases / POS2_CELL + 2;
-            const size_t nst = (size_t)n_chunks * f_nstr, nseg = nst * f_maxseg, ncl = nst * f_ncell;
-            HIPCHK(ctx, B[DB_SEGF].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGA].ensure(nseg * 32 + 16)); HIPCHK(ctx, B[DB_SEGN].ensure(nst * 4 + 16));
-            HIPCHK(ctx, B[DB_SEGS].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGP].ensure(nseg * 4 + 16)); HIPCHK(ctx, B[DB_SEGK].ensure(nseg * 4 + 16));
-                    HIPCHK(ctx, B[DB_CELL].ensure(ncl * 4 + 16));
-            HIPCHK(ctx, B[DB_NENT].ensure(nst * 4 + 16)); HIPCHK(ctx, B[DB_LOFF].ensure(nst * 8 + 16));
-            // the arena of the position lists: a position belongs to at most one stream, the coded ones are a few percent of the bases; if a
-            // file needs more than the arena holds, k_dec_pos_list leaves it alone and the pass is repeated below with the right size
-            // (an entry per eight bases to begin with - half a byte per base; a NovaSeq-binned file codes one position in twelve.  A file that codes more
-            // - forty quality values code most positions - runs the list pass a second time, once per context: the arena keeps its size.  Round 3 asked for
-            // 2 bytes per base up front: 6.7 GB on 2 x 4 GB of text)
-            if (B[DB_PLIST].ensure((size_t)(g.bases / 8 + 1024) * sizeof(plist_t)) != hipSuccess) { (void)hipGetLastError();
-                    HIPCHK(ctx, B[DB_PLIST].ensure((size_t)(g.bases / 32 + 1024) * sizeof(plist_t))); }
-            { ClearList z; memset(&z, 0, sizeof z); z.add(B[DB_SEGN].p, nst * 4, 0u); z.add(B[DB_NENT].p, nst * 4, 0u); z.add(B[DB_CELL].p, ncl * 4, 0xFFFFFFFFu); clear_list(A, z); }
-#define RFQ_SUM2_ARGS a->d_rfq, CH, D, B[DB_SEGF].as<uint8_t>(), B[DB_SEGA].as<int>(), B[DB_SEGN].as<uint32_t>(), f_maxseg, dst, (uint64_t)a->n
-            if (nn) hipLaunchKernelGGL(k_dec_pos_sum2, dim3((mq + 3) / 4, nn, n_chunks), dim3(256), 0, A, RFQ_SUM2_ARGS, 0u, f_nstr, f_segb);
-            if (hasn) hipLaunchKernelGGL(k_dec_pos_sum2, dim3((mn + 3) / 4, 1, n_chunks), dim3(256), 0, A, RFQ_SUM2_ARGS, HH.n_normal, f_nstr, f_segb);
+    const bool on = !force_expanded && !ctx->opt.materialise && !rle_h && g.max_len <= 2000u && g.max_nrec <= 4096u && e3_ok && g.max_bases < (1u << 30) - 65536u;
+    // (the per-read piece prefixes only where some chunk stores pieces per read: sequencer names leave none, and the stored-base prefix alone is 4 bytes per read instead of 16)
+    return { on, e3k, n1big, E3_SHARED_OK && !g.pieces && !(HH.flags & H_DONT_QUAL) };
+}
+// what the position-list chain of a range left behind: the shape of its tables (B[DB_SEG*], B[DB_CELL], B[DB_NENT], B[DB_LOFF]), whether lists were built at
+// all (a file without quality streams and N positions has none), and the stream the emitter has to wait for (join: the chain ran beside the main stream)
+struct ListChain { uint32_t maxseg = 1, ncell = 1, nstr = 1, mq = 0, mn = 0, nn = 0, segb = POS2_SEG; bool hasn = false, built = false, join = false; hipStream_t aux = nullptr; };
+// (an early return must not leave the chain running over buffers the next call reuses)
+struct AuxJoin { rfq_ctx* c; bool armed; ~AuxJoin() { if (armed) (void)hipStreamSynchronize(c->aux); } };
+
+// k_dec_pos_list for the quality streams and the N-position stream (the arena is whatever B[DB_PLIST] holds)
+static void launch_pos_list(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const ListChain& L, hipStream_t LS) {
+    DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>(); const DecStatus* dst = B[DB_STATUS].as<DecStatus>();
+    const unsigned long long cap = B[DB_PLIST].cap / sizeof(plist_t);
+#define RFQ_LIST_ARGS a->d_rfq, g.CH, D, (const uint8_t*)B[DB_SEGS].as<uint8_t>(), (const int*)B[DB_SEGP].as<int>(), (const uint32_t*)B[DB_SEGK].as<uint32_t>(), \
+                      (const unsigned long long*)B[DB_LOFF].as<unsigned long long>(), B[DB_PLIST].as<plist_t>(), cap, B[DB_CELL].as<uint32_t>(), L.maxseg, L.ncell, (uint64_t)a->n
+    if (L.nn) hipLaunchKernelGGL(k_dec_pos_list, dim3((L.mq + 3) / 4, L.nn, g.n_chunks), dim3(256), 0, LS, RFQ_LIST_ARGS, 0u, L.nstr, dst, L.segb);
+    if (L.hasn) hipLaunchKernelGGL(k_dec_pos_list, dim3((L.mn + 3) / 4, 1, g.n_chunks), dim3(256), 0, LS, RFQ_LIST_ARGS, ctx->h_hdr.n_normal, L.nstr, dst, L.segb);
+#undef RFQ_LIST_ARGS
+}
+// The lists need nothing but the chunk table, so their chain (stream summaries, link, offsets, lists + cell index) starts at the top of a range on the second
+// stream, beside read table, prefixes, coordinates and text lengths, and is joined in front of the emitter.  guard: armed from the fork on.
+static int dec_list_chain(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, AuxJoin& guard, ListChain* L) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader& HH = ctx->h_hdr; const DevHeader* D = ctx->d_hdr.as<DevHeader>();
+    DecStatus* dst = B[DB_STATUS].as<DecStatus>(); const DChunk* CH = g.CH; const uint32_t n_chunks = g.n_chunks;
+    const bool bycol_h = (HH.flags & H_QUAL_BY_COL) && !(HH.flags & H_DONT_QUAL);
+    L->nstr = HH.n_normal + 1; L->hasn = (HH.flags & H_N_POS) != 0; L->nn = bycol_h ? std::min<uint32_t>(HH.n_normal, NPOS_SLOT) : 0u;
+    if (!L->nn && !L->hasn) return RFQ_OK;
+    const bool forked = ctx->aux_ready(); hipStream_t A = forked ? ctx->aux : S;
+    if (forked) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, S)); HIPCHK(ctx, hipStreamWaitEvent(A, ctx->ev_fork, 0)); guard.armed = true; }
+    L->segb = ctx->opt.pos_seg ? (uint32_t)ctx->opt.pos_seg : (std::max(g.max_one, g.max_npos) >= 32768u ? POS2_SEG_BIG : POS2_SEG);
+    L->mq = L->nn ? g.max_one / L->segb + 1 : 0u; L->mn = L->hasn ? g.max_npos / L->segb + 1 : 0u; L->maxseg = std::max(1u, std::max(L->mq, L->mn));
+    L->ncell = g.max_bases / POS2_CELL + 2;
+    const size_t nst = (size_t)n_chunks * L->nstr, nseg = nst * L->maxseg, ncl = nst * L->ncell;
+    HIPCHK(ctx, B[DB_SEGF].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGA].ensure(nseg * 32 + 16)); HIPCHK(ctx, B[DB_SEGN].ensure(nst * 4 + 16));
+    HIPCHK(ctx, B[DB_SEGS].ensure(nseg + 16)); HIPCHK(ctx, B[DB_SEGP].ensure(nseg * 4 + 16)); HIPCHK(ctx, B[DB_SEGK].ensure(nseg * 4 + 16));
+    HIPCHK(ctx, B[DB_CELL].ensure(ncl * 4 + 16));
+    HIPCHK(ctx, B[DB_NENT].ensure(nst * 4 + 16)); HIPCHK(ctx, B[DB_LOFF].ensure(nst * 8 + 16));
+    // the arena of the position lists: a position belongs to at most one stream, the coded ones are a few percent of the bases; if a
+    // file needs more than the arena holds, k_dec_pos_list leaves it alone and decode_range repeats the pass with the right size
+    // (an entry per eight bases to begin with - half a byte per base; a NovaSeq-binned file codes one position in twelve.  A file that codes more
+    // - forty quality values code most positions - runs the list pass a second time, once per context: the arena keeps its size.  Two bytes per base
+    // up front would be 6.7 GB on 2 x 4 GB of text)
+    if (B[DB_PLIST].ensure((size_t)(g.bases / 8 + 1024) * sizeof(plist_t)) != hipSuccess) { (void)hipGetLastError();
+            HIPCHK(ctx, B[DB_PLIST].ensure((size_t)(g.bases / 32 + 1024) * sizeof(plist_t))); }
+    { ClearList z; memset(&z, 0, sizeof z); z.add(B[DB_SEGN].p, nst * 4, 0u); z.add(B[DB_NENT].p, nst * 4, 0u); z.add(B[DB_CELL].p, ncl * 4, 0xFFFFFFFFu); clear_list(A, z); }
+#define RFQ_SUM2_ARGS a->d_rfq, CH, D, B[DB_SEGF].as<uint8_t>(), B[DB_SEGA].as<int>(), B[DB_SEGN].as<uint32_t>(), L->maxseg, dst, (uint64_t)a->n
+    if (L->nn) hipLaunchKernelGGL(k_dec_pos_sum2, dim3((L->mq + 3) / 4, L->nn, n_chunks), dim3(256), 0, A, RFQ_SUM2_ARGS, 0u, L->nstr, L->segb);
+    if (L->hasn) hipLaunchKernelGGL(k_dec_pos_sum2, dim3((L->mn + 3) / 4, 1, n_chunks), dim3(256), 0, A, RFQ_SUM2_ARGS, HH.n_normal, L->nstr, L->segb);
 #undef RFQ_SUM2_ARGS
-            hipLaunchKernelGGL(k_dec_pos_link2, dim3((uint32_t)((nst + 3) / 4)), dim3(256), 0, A, (const uint8_t*)B[DB_SEGF].as<uint8_t>(),
-                    (const int*)B[DB_SEGA].as<int>(),
-                               (const uint32_t*)B[DB_SEGN].as<uint32_t>(), B[DB_SEGS].as<uint8_t>(), B[DB_SEGP].as<int>(), B[DB_SEGK].as<uint32_t>(), B[DB_NENT].as<uint32_t>(), f_maxseg, (uint32_t)nst,
-                               CH, f_nstr, dst);
-            hipLaunchKernelGGL(k_dec_pos_off, dim3(1), dim3(256), 0, A, (const uint32_t*)B[DB_NENT].as<uint32_t>(), B[DB_LOFF].as<unsigned long long>(), (uint32_t)nst,
-                    dst);
-            launch_pos_list(ctx, a, CH, n_chunks, f_maxseg, f_ncell, f_nstr, mq, mn, nn, hasn, f_segb, A);
-            f_lists = true; f_mq = mq; f_mn = mn; f_nn = nn; f_hasn = hasn;
-            f_join = forked; f_aux = A;
-            KCHK(ctx, "k_dec_pos_*");
-        }
+    hipLaunchKernelGGL(k_dec_pos_link2, dim3((uint32_t)((nst + 3) / 4)), dim3(256), 0, A, (const uint8_t*)B[DB_SEGF].as<uint8_t>(), (const int*)B[DB_SEGA].as<int>(),
+                       (const uint32_t*)B[DB_SEGN].as<uint32_t>(), B[DB_SEGS].as<uint8_t>(), B[DB_SEGP].as<int>(), B[DB_SEGK].as<uint32_t>(), B[DB_NENT].as<uint32_t>(),
+                       L->maxseg, (uint32_t)nst, CH, L->nstr, dst);
+    hipLaunchKernelGGL(k_dec_pos_off, dim3(1), dim3(256), 0, A, (const uint32_t*)B[DB_NENT].as<uint32_t>(), B[DB_LOFF].as<unsigned long long>(), (uint32_t)nst, dst);
+    launch_pos_list(ctx, a, g, *L, A);
+    L->built = true; L->join = forked; L->aux = A;
+    KCHK(ctx, "k_dec_pos_*");
+    return RFQ_OK;
+}
+// fused read table: chunk-local prefixes made where the per-read values are made (k_dec_readtab2): no per-read scan inputs, no batch-wide scans, no read-back
+// here - the status word is looked at with the next one, the range's bases are the walk's 64-bit total.  R.len / R.ov / R.mid are the caller's.
+static int dec_table_fused(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const FusedPlan& P, const DReadTab& R, DFused* F) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
+    const size_t nr = (size_t)g.n_reads + 2, nc = (size_t)g.n_chunks + 2;
+    HIPCHK(ctx, B[DB_PQL].ensure((nr + nc) * 4)); HIPCHK(ctx, B[DB_TPL].ensure(nr * 8));
+    if (!P.shared_pieces) HIPCHK(ctx, B[DB_PVL].ensure((nr + nc) * 16));
+    HIPCHK(ctx, B[DB_CTEXT].ensure(nc * 16)); HIPCHK(ctx, B[DB_TBASE].ensure(nc * 16)); HIPCHK(ctx, B[DB_SCAN].ensure((nc / SCAN_TILE + 2) * 16 + 1024));
+    HIPCHK(ctx, B[DB_SDL].ensure((nr + nc) * 4));
+    U4* const pvl = P.shared_pieces ? (U4*)nullptr : B[DB_PVL].as<U4>();
+    F->len = R.len; F->ov = R.ov; F->pql = B[DB_PQL].as<uint32_t>(); F->pvl = pvl; F->sdl = B[DB_SDL].as<uint32_t>();
+    F->tpl = B[DB_TPL].as<uint2>(); F->tbase = B[DB_TBASE].as<U4>(); F->mid = R.mid;
+    hipLaunchKernelGGL(k_dec_readtab2, dim3(g.n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, ctx->d_hdr.as<DevHeader>(), R.len, R.ov, B[DB_PQL].as<uint32_t>(), pvl,
+                       B[DB_SDL].as<uint32_t>(), B[DB_STATUS].as<DecStatus>());
+    KCHK(ctx, "k_dec_readtab2");
+    ctx->timer.end(S);
+    return RFQ_OK;
+}
+// fused text lengths, timer stage "streams" (the list chain has been running beside it since the top of the range): the coordinate decoder, the lengths of
+// every read's text (k_dec_textlen2), where every chunk's text starts (entry n_chunks of B[DB_TBASE]: the totals)
+static int dec_textlen_fused(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const DReadTab& R) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>();
+    ctx->timer.begin("streams", S);
+    hipLaunchKernelGGL(k_dec_coords, dim3(2, g.n_chunks), dim3(64), 0, S, a->d_rfq, g.CH, D, B[DB_XV].as<uint32_t>(), B[DB_YV].as<uint32_t>());
+    KCHK(ctx, "k_dec_coords");
+    hipLaunchKernelGGL(k_dec_textlen2, dim3(g.n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, D, (const uint32_t*)R.len, R.mid, (const uint32_t*)B[DB_XV].as<uint32_t>(),
+                       (const uint32_t*)B[DB_YV].as<uint32_t>(), a->split_pe ? 1 : 0, B[DB_TPL].as<uint2>(), B[DB_CTEXT].as<U4>(), B[DB_STATUS].as<DecStatus>());
+    KCHK(ctx, "k_dec_textlen2");
+    scan_exclusive<U4>(S, B[DB_CTEXT].as<U4>(), B[DB_TBASE].as<U4>(), g.n_chunks, B[DB_SCAN].as<U4>(), 1);
+    return RFQ_OK;
+}
+// k_dec_emit3 into o1 / o2.  list_cap != 0: the speculative launch - the kernel looks at the status itself (dec/emit_tiles.h) -, 0: the host has looked.
+static void launch_emit3(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const FusedPlan& P, const ListChain& L, const DFused& F,
+                         uint8_t* o1, uint64_t cap1, uint8_t* o2, uint64_t cap2, unsigned long long list_cap) {
+    DBuf* B = ctx->b; const bool hasn = (ctx->h_hdr.flags & H_N_POS) != 0;
+    // (25 KB of LDS: six workgroups per CU; four with the large name tile)
+    const uint32_t K = 1u << P.e3k, bx = grid_x_for(g.n_chunks, (std::max(g.max_reads, 1u) + K - 1) / K, (P.n1big ? 4u : 6u) * ctx->n_cu);
+    const dim3 grid(bx, g.n_chunks);
+#define RFQ_EMIT3_ARGS a->d_rfq, g.CH, ctx->d_hdr.as<DevHeader>(), F, (uint64_t)a->n, a->split_pe ? 1 : 0, o1, cap1, o2, cap2, B[DB_STATUS].as<DecStatus>(), \
+                       (const plist_t*)B[DB_PLIST].as<plist_t>(), (const unsigned long long*)B[DB_LOFF].as<unsigned long long>(), (const uint32_t*)B[DB_NENT].as<uint32_t>(), \
+                       (const uint32_t*)B[DB_CELL].as<uint32_t>(), L.ncell, L.nstr, P.e3k, list_cap
+    if (P.n1big) {
+        if (hasn) hipLaunchKernelGGL((k_dec_emit3<false, E3_N1BIG>), grid, dim3(256), 0, ctx->stream, RFQ_EMIT3_ARGS);
+        else hipLaunchKernelGGL((k_dec_emit3<true, E3_N1BIG>), grid, dim3(256), 0, ctx->stream, RFQ_EMIT3_ARGS);
+    } else if (F.pvl == nullptr) {                                         // (every chunk shares its name pieces among its reads: the instantiation without per-read piece prefixes)
+        if (hasn) hipLaunchKernelGGL((k_dec_emit3<false, ET_N1CAP, true>), grid, dim3(256), 0, ctx->stream, RFQ_EMIT3_ARGS);
+        else hipLaunchKernelGGL((k_dec_emit3<true, ET_N1CAP, true>), grid, dim3(256), 0, ctx->stream, RFQ_EMIT3_ARGS);
     }
-    // ---- read table + prefixes
+    else if (hasn) hipLaunchKernelGGL(k_dec_emit3<false>, grid, dim3(256), 0, ctx->stream, RFQ_EMIT3_ARGS);
+    else hipLaunchKernelGGL(k_dec_emit3<true>, grid, dim3(256), 0, ctx->stream, RFQ_EMIT3_ARGS);
+#undef RFQ_EMIT3_ARGS
+}
+// RfqCodec::decodeChunk + Read::toString for the chunks of one range (reads, bases and text of a range are placed by 32-bit prefix sums).
+// out1 / out2: caller buffers (16-byte aligned) or null = the context's own result buffers; *p1 / *p2 = where the text went.
+// force_expanded: the retry of a range whose fused path gave up - straight to the expanded path, whatever made it give up (the retry must terminate by
+// construction, not because a flag happens to be honoured)
+static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, uint8_t* out1, uint64_t ocap1, uint8_t* out2, uint64_t ocap2,
+                        uint8_t** p1, uint8_t** p2, size_t* n1, size_t* n2, uint64_t* nbases, bool force_expanded = false) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>();
+    DecStatus* dst = B[DB_STATUS].as<DecStatus>(); DecStatus hs;
+    const uint32_t n_chunks = g.n_chunks, n_reads = g.n_reads, max_reads = std::max(g.max_reads, 1u);
+    const int split = a->split_pe ? 1 : 0;
+    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(DecStatus), S));
+    const FusedPlan P = plan_fused(ctx, g, force_expanded);
+    ListChain L; AuxJoin aux_guard = { ctx, false };
+    if (P.on) { const int rc = dec_list_chain(ctx, a, g, aux_guard, &L); if (rc) return rc; }
+    // ---- read table + prefixes, streams, text lengths
     ctx->timer.begin("read_table", S);
-    const size_t nr = (size_t)n_reads + 2, nc = (size_t)n_chunks + 2;
+    const size_t nr = (size_t)n_reads + 2;
     HIPCHK(ctx, B[DB_LEN].ensure(nr * 4)); HIPCHK(ctx, B[DB_OV].ensure(nr * 4));
     HIPCHK(ctx, B[DB_XV].ensure(nr * 4)); HIPCHK(ctx, B[DB_YV].ensure(nr * 4)); HIPCHK(ctx, B[DB_MID].ensure(nr * 40));
-    DReadTab R; memset(&R, 0, sizeof R); DFused F; memset(&F, 0, sizeof F);
+    DReadTab R; memset(&R, 0, sizeof R); DFused F; memset(&F, 0, sizeof F); DecExpanded E; memset(&E, 0, sizeof E);
     R.len = B[DB_LEN].as<uint32_t>(); R.ov = B[DB_OV].as<int32_t>(); R.mid = B[DB_MID].as<uint8_t>();
-    uint32_t total_bases = 0; U4 pv_tot; memset(&pv_tot, 0, sizeof pv_tot);
-    if (fused) {
-        // chunk-local prefixes made where the per-read values are made (k_dec_readtab2): no per-read scan inputs, no batch-wide scans, no read-back here - the
-        // status word is looked at with the next one, the range's bases are the walk's 64-bit total
-        HIPCHK(ctx, B[DB_PQL].ensure((nr + nc) * 4)); HIPCHK(ctx, B[DB_TPL].ensure(nr * 8));
-        if (g.pieces || !E3_SHARED_OK || (HH.flags & H_DONT_QUAL)) HIPCHK(ctx, B[DB_PVL].ensure((nr + nc) * 16));
-        HIPCHK(ctx, B[DB_CTEXT].ensure(nc * 16)); HIPCHK(ctx, B[DB_TBASE].ensure(nc * 16)); HIPCHK(ctx, B[DB_SCAN].ensure((nc / SCAN_TILE + 2) * 16 + 1024));
-        // (the per-read piece prefixes only where some chunk stores pieces per read: sequencer names leave none, and the stored-base prefix alone is 4 bytes per read instead of 16)
-        const bool shared_pieces = E3_SHARED_OK && !g.pieces && !(HH.flags & H_DONT_QUAL);
-        HIPCHK(ctx, B[DB_SDL].ensure((nr + nc) * 4));
-        F.len = R.len; F.ov = R.ov; F.pql = B[DB_PQL].as<uint32_t>(); F.pvl = shared_pieces ? (const U4*)nullptr : B[DB_PVL].as<U4>(); F.sdl = B[DB_SDL].as<uint32_t>();
-        F.tpl = B[DB_TPL].as<uint2>(); F.tbase = B[DB_TBASE].as<U4>(); F.mid = R.mid;
-        hipLaunchKernelGGL(k_dec_readtab2, dim3(n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R.len, R.ov, B[DB_PQL].as<uint32_t>(), shared_pieces ? (U4*)nullptr : B[DB_PVL].as<U4>(),
-                           B[DB_SDL].as<uint32_t>(), dst);
-        KCHK(ctx, "k_dec_readtab2");
-        ctx->timer.end(S);
+    if (P.on) {
+        int rc = dec_table_fused(ctx, a, g, P, R, &F);
+        if (!rc) rc = dec_textlen_fused(ctx, a, g, R);
+        if (rc) return rc;
         *nbases = g.bases;
     } else {
-        const int rc = dec_table_expanded(ctx, a, g, R, true, &total_bases, &pv_tot);
+        uint32_t total_bases = 0; U4 pv_tot; memset(&pv_tot, 0, sizeof pv_tot);
+        int rc = dec_table_expanded(ctx, a, g, R, true, &total_bases, &pv_tot);
+        if (!rc) rc = dec_streams_expanded(ctx, a, g, R, total_bases, pv_tot, true, &E);
         if (rc) return rc;
         *nbases = total_bases;
-    }
-
-    // ---- streams (fused path: the coordinate decoder here, the list chain has been running since the top)
-    if (fused) {
-        ctx->timer.begin("streams", S);
-        hipLaunchKernelGGL(k_dec_coords, dim3(2, n_chunks), dim3(64), 0, S, a->d_rfq, CH, D, B[DB_XV].as<uint32_t>(), B[DB_YV].as<uint32_t>());
-        KCHK(ctx, "k_dec_coords");
-    }
-    uint64_t* qbase = nullptr; uint64_t* sbase = nullptr; uint8_t* qdec = nullptr; uint8_t* sdec = nullptr; size_t qbytes = 0, sbytes = 0;
-    if (!fused) {
-        DecExpanded E; const int rc = dec_streams_expanded(ctx, a, g, R, total_bases, pv_tot, true, &E);
-        if (rc) return rc;
-        qbase = E.qbase; sbase = E.sbase; qdec = E.qdec; sdec = E.sdec; qbytes = E.qbytes; sbytes = E.sbytes;
-    }
-
-    // ---- text
-    if (!fused) ctx->timer.begin("textlen", S);                          // (fused path: still inside "streams", beside the list chain)
-    const int split = a->split_pe ? 1 : 0;
-    U4 tt;
-    if (fused) {
-        hipLaunchKernelGGL(k_dec_textlen2, dim3(n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, (const uint32_t*)R.len, R.mid, (const uint32_t*)B[DB_XV].as<uint32_t>(),
-                (const uint32_t*)B[DB_YV].as<uint32_t>(), split, B[DB_TPL].as<uint2>(), B[DB_CTEXT].as<U4>(), dst);
-        KCHK(ctx, "k_dec_textlen2");
-        scan_exclusive<U4>(S, B[DB_CTEXT].as<U4>(), B[DB_TBASE].as<U4>(), n_chunks, B[DB_SCAN].as<U4>(), 1);      // where every chunk's text starts; entry n_chunks: the totals
-    } else {
-        hipLaunchKernelGGL(k_dec_textlen, dim3((max_reads + 255) / 256, n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R, (const uint32_t*)B[DB_XV].as<uint32_t>(),
-                (const uint32_t*)B[DB_YV].as<uint32_t>(), split, dst);
+        ctx->timer.begin("textlen", S);
+        hipLaunchKernelGGL(k_dec_textlen, dim3((max_reads + 255) / 256, n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, D, R, (const uint32_t*)B[DB_XV].as<uint32_t>(),
+                           (const uint32_t*)B[DB_YV].as<uint32_t>(), split, dst);
         scan_exclusive<U4>(S, R.tin, R.tp, n_reads, B[DB_SCAN].as<U4>(), 1);
     }
-    if (f_join) { HIPCHK(ctx, hipEventRecord(ctx->ev_join, f_aux)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_join, 0)); }
+    if (L.join) { HIPCHK(ctx, hipEventRecord(ctx->ev_join, L.aux)); HIPCHK(ctx, hipStreamWaitEvent(S, ctx->ev_join, 0)); }
     aux_guard.armed = false;       // (everything below is ordered behind the chain on the main stream)
-    // Speculative emit (fused path, the caller's output buffers, lists that were built): the emitter is launched WITHOUT this read-back - it stops itself on what the checks
-    // below would have stopped at (k_dec_emit3: list_cap) -, and the host looks once, behind it: one round trip less per range (~35 us: 3 % of a 1 GB decode).
-    const bool spec = fused && f_lists && out1 && (!a->split_pe || out2) && !((uintptr_t)out1 & 15u) && !(out2 && ((uintptr_t)out2 & 15u)) && !ctx->opt.no_spec;
-    bool late = false;
-    auto pre_emit_sync = [&]() -> int {
-        HIPCHK(ctx, ctx->fetch(&tt, fused ? B[DB_TBASE].as<U4>() + n_chunks : R.tp + n_reads, 16, S));
-        HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
-        HIPCHK(ctx, ctx->fetch_sync(S));
-        return RFQ_OK;
-    };
-    if (!spec) { const int rc = pre_emit_sync(); if (rc) return rc; }
-    else {
+    // Speculative emit (fused path, the caller's output buffers, lists that were built): the emitter is launched WITHOUT the read-back below - it stops itself on what the
+    // checks would have stopped at (k_dec_emit3: list_cap) -, and the host looks once, behind it: one round trip less per range (~35 us: 3 % of a 1 GB decode).
+    bool emitted = P.on && L.built && out1 && (!a->split_pe || out2) && !((uintptr_t)out1 & 15u) && !(out2 && ((uintptr_t)out2 & 15u)) && !ctx->opt.no_spec;
+    if (emitted) {
         ctx->timer.end(S);
         ctx->timer.begin("emit", S);
-        const uint32_t K = 1u << e3k, b3 = grid_x_for(n_chunks, (max_reads + K - 1) / K, 6u * ctx->n_cu);
-        const unsigned long long lcap = B[DB_PLIST].cap / sizeof(plist_t);
-#define RFQ_EMIT3_SPEC a->d_rfq, CH, D, F, (uint64_t)a->n, a->split_pe ? 1 : 0, out1, ocap1, out2, ocap2, dst, (const plist_t*)B[DB_PLIST].as<plist_t>(), (const unsigned long long*)B[DB_LOFF].as<unsigned long long>(), \
-                       (const uint32_t*)B[DB_NENT].as<uint32_t>(), (const uint32_t*)B[DB_CELL].as<uint32_t>(), f_ncell, f_nstr, e3k, lcap
-        if (n1big) {
-            const uint32_t b4 = grid_x_for(n_chunks, (max_reads + K - 1) / K, 4u * ctx->n_cu);
-            if (HH.flags & H_N_POS) hipLaunchKernelGGL((k_dec_emit3<false, E3_N1BIG>), dim3(b4, n_chunks), dim3(256), 0, S, RFQ_EMIT3_SPEC);
-            else hipLaunchKernelGGL((k_dec_emit3<true, E3_N1BIG>), dim3(b4, n_chunks), dim3(256), 0, S, RFQ_EMIT3_SPEC);
-        }
-        else if (F.pvl == nullptr) {
-            if (HH.flags & H_N_POS) hipLaunchKernelGGL((k_dec_emit3<false, ET_N1CAP, true>), dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_SPEC);
-            else hipLaunchKernelGGL((k_dec_emit3<true, ET_N1CAP, true>), dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_SPEC);
-        }
-        else if (HH.flags & H_N_POS) hipLaunchKernelGGL(k_dec_emit3<false>, dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_SPEC);
-        else hipLaunchKernelGGL(k_dec_emit3<true>, dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_SPEC);
-#undef RFQ_EMIT3_SPEC
+        launch_emit3(ctx, a, g, P, L, F, out1, ocap1, out2, ocap2, B[DB_PLIST].cap / sizeof(plist_t));
         KCHK(ctx, "k_dec_emit");
         ctx->timer.end(S);
-        const int rc = pre_emit_sync(); if (rc) return rc;
-        late = true;
     }
-    if (hs.err & DE_CORRUPT_OV) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt overlap buffer");   // (k_dec_readtab2's verdict, a bit of its own: nothing reads the status in between, and the list chain's DE_CORRUPT means the quality buffer - the same two messages as on the expanded path)
-    // a stream codes positions far beyond its chunk's length table (k_dec_pos_link2): 16-bit list entries would alias - the range goes to the expanded path
-    if (fused && (hs.err & DE_E3_RETRY)) return decode_range(ctx, a, g, out1, ocap1, out2, ocap2, p1, p2, n1, n2, nbases, true);
-    if (hs.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt quality buffer");
-    // text prefix sums are 32-bit: one decode call emits < 4 GiB per output stream
-    if (fused && f_lists && hs.list_need > B[DB_PLIST].cap / sizeof(plist_t)) {            // the lists did not fit the arena: now that their size is known, build them
-        if (late) { late = false; ctx->timer.begin("streams", S); }                            // (the speculative emitter left at once: the ordinary order from here on)
-        HIPCHK(ctx, B[DB_PLIST].ensure((size_t)(hs.list_need + 1024) * sizeof(plist_t)));
-        launch_pos_list(ctx, a, CH, n_chunks, f_maxseg, f_ncell, f_nstr, f_mq, f_mn, f_nn, f_hasn, f_segb, S);
-        KCHK(ctx, "k_dec_pos_list");
-    }
-    hs.text1 = hs.text2 = 0; for (int i = 0; i < 64; i++) { hs.text1 += hs.text_slots[0][i]; hs.text2 += hs.text_slots[1][i]; }
-    if (hs.text1 >= 0xFFFFFFF0ull || hs.text2 >= 0xFFFFFFF0ull) return RFQ_RANGE_TOO_BIG;       // (the caller decodes the range in two halves)
-    uint8_t *o1, *o2; uint64_t cap1, cap2;
-    if ((out1 && ((uintptr_t)out1 & 15u)) || (out2 && ((uintptr_t)out2 & 15u))) return rfq_fail(ctx, RFQ_E_ARG, "output device pointers must be 16-byte aligned");
-    if (out1) { o1 = out1; cap1 = ocap1; } else { HIPCHK(ctx, ctx->out_fq1.ensure((size_t)tt.a + 64)); o1 = ctx->out_fq1.as<uint8_t>(); cap1 = ctx->out_fq1.cap; }
-    if (out2) { o2 = out2; cap2 = ocap2; } else { HIPCHK(ctx, ctx->out_fq2.ensure((size_t)tt.b + 64)); o2 = ctx->out_fq2.as<uint8_t>(); cap2 = ctx->out_fq2.cap; }
-    if (late) {                                                        // the emitter has run: what is left of the ordinary path below is its own verdict
-        if (hs.err & DE_E3_RETRY) { if (g.pieces) ctx->e3_pieces_failed = true; return decode_range(ctx, a, g, out1, ocap1, out2, ocap2, p1, p2, n1, n2, nbases, true); }
-        ctx->timer.collect();
-        if (hs.err & (1u << 31)) return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffer too small: need %u / %u bytes", tt.a, tt.b);
-        *n1 = tt.a; *n2 = split ? tt.b : 0; *p1 = o1; *p2 = o2;
-        return RFQ_OK;
-    }
-    ctx->timer.end(S);
-    ctx->timer.begin(fused ? "emit" : "emit_expanded", S);             // the emitter alone: the path's largest kernel (bench.py roofline)
-    {
-        if (fused) {
-            const uint32_t K = 1u << e3k, b3 = grid_x_for(n_chunks, (max_reads + K - 1) / K, 6u * ctx->n_cu);       // (25 KB of LDS: six workgroups per CU)
-#define RFQ_EMIT3_ARGS a->d_rfq, CH, D, F, (uint64_t)a->n, split, o1, cap1, o2, cap2, dst, (const plist_t*)B[DB_PLIST].as<plist_t>(), (const unsigned long long*)B[DB_LOFF].as<unsigned long long>(), \
-                       (const uint32_t*)B[DB_NENT].as<uint32_t>(), (const uint32_t*)B[DB_CELL].as<uint32_t>(), f_ncell, f_nstr, e3k, 0ull
-            if (n1big) {
-                const uint32_t b4 = grid_x_for(n_chunks, (max_reads + K - 1) / K, 4u * ctx->n_cu);
-                if (HH.flags & H_N_POS) hipLaunchKernelGGL((k_dec_emit3<false, E3_N1BIG>), dim3(b4, n_chunks), dim3(256), 0, S, RFQ_EMIT3_ARGS);
-                else hipLaunchKernelGGL((k_dec_emit3<true, E3_N1BIG>), dim3(b4, n_chunks), dim3(256), 0, S, RFQ_EMIT3_ARGS);
-            }
-            else if (F.pvl == nullptr) {                                          // (every chunk shares its name pieces among its reads: the instantiation without per-read piece prefixes)
-                if (HH.flags & H_N_POS) hipLaunchKernelGGL((k_dec_emit3<false, ET_N1CAP, true>), dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_ARGS);
-                else hipLaunchKernelGGL((k_dec_emit3<true, ET_N1CAP, true>), dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_ARGS);
-            }
-            else if (HH.flags & H_N_POS) hipLaunchKernelGGL(k_dec_emit3<false>, dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_ARGS);
-            else hipLaunchKernelGGL(k_dec_emit3<true>, dim3(b3, n_chunks), dim3(256), 0, S, RFQ_EMIT3_ARGS);
-#undef RFQ_EMIT3_ARGS
-        } else {
-            const uint32_t bx = grid_x_for(n_chunks, (max_reads + ET_READS - 1) / ET_READS, 4u * ctx->n_cu);   // (39 KB of LDS: four workgroups per CU)
-            hipLaunchKernelGGL(k_dec_emit, dim3(bx, n_chunks), dim3(256), 0, S, a->d_rfq, CH, D, R, (const uint64_t*)qbase, (const uint64_t*)sbase,
-                               (const uint8_t*)qdec, (const uint8_t*)sdec, (uint64_t)qbytes, (uint64_t)sbytes, (uint64_t)a->n, split, o1, cap1, o2, cap2, dst);
-        }
-        KCHK(ctx, "k_dec_emit");
-        ctx->timer.end(S);
+    // ---- the verdict: once in front of the emitter (unless it went ahead), once behind it
+    U4 tt; HIPCHK(ctx, ctx->fetch(&tt, P.on ? B[DB_TBASE].as<U4>() + n_chunks : R.tp + n_reads, 16, S));
+    uint8_t *o1, *o2;
+    for (;;) {
         HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
         HIPCHK(ctx, ctx->fetch_sync(S));
-        if (fused && (hs.err & DE_E3_RETRY)) {                             // per-read name pieces that did not fit a tile: once more, expanded
-            if (g.pieces) ctx->e3_pieces_failed = true;                    // (files like this one: the ranges that follow go straight to the expanded path)
+        // (k_dec_readtab2's verdict, a bit of its own: the list chain's DE_CORRUPT means the quality buffer - the same two messages as on the expanded path)
+        if (hs.err & DE_CORRUPT_OV) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt overlap buffer");
+        // once more, expanded.  DE_LIST_ALIAS: a stream codes positions far beyond its chunk's length table (k_dec_pos_link2): 16-bit list entries would alias.
+        // DE_E3_RETRY: per-read name pieces that did not fit a tile of k_dec_emit3 - files like this one: the ranges that follow go straight to the expanded path
+        if (P.on && (hs.err & (DE_LIST_ALIAS | DE_E3_RETRY))) {
+            if ((hs.err & DE_E3_RETRY) && g.pieces) ctx->e3_pieces_failed = true;
             return decode_range(ctx, a, g, out1, ocap1, out2, ocap2, p1, p2, n1, n2, nbases, true);
         }
+        if (hs.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt quality buffer");
+        if (L.built && hs.list_need > B[DB_PLIST].cap / sizeof(plist_t)) {       // the lists did not fit the arena: now that their size is known, build them
+            if (emitted) { emitted = false; ctx->timer.begin("streams", S); }        // (the speculative emitter left at once: the ordinary order from here on)
+            HIPCHK(ctx, B[DB_PLIST].ensure((size_t)(hs.list_need + 1024) * sizeof(plist_t)));
+            launch_pos_list(ctx, a, g, L, S);
+            KCHK(ctx, "k_dec_pos_list");
+        }
+        // text prefix sums are 32-bit: one decode call emits < 4 GiB per output stream
+        hs.text1 = hs.text2 = 0; for (int i = 0; i < 64; i++) { hs.text1 += hs.text_slots[0][i]; hs.text2 += hs.text_slots[1][i]; }
+        if (hs.text1 >= 0xFFFFFFF0ull || hs.text2 >= 0xFFFFFFF0ull) return RFQ_RANGE_TOO_BIG;       // (the caller decodes the range in two halves)
+        if ((out1 && ((uintptr_t)out1 & 15u)) || (out2 && ((uintptr_t)out2 & 15u))) return rfq_fail(ctx, RFQ_E_ARG, "output device pointers must be 16-byte aligned");
+        uint64_t cap1, cap2;
+        if (out1) { o1 = out1; cap1 = ocap1; } else { HIPCHK(ctx, ctx->out_fq1.ensure((size_t)tt.a + 64)); o1 = ctx->out_fq1.as<uint8_t>(); cap1 = ctx->out_fq1.cap; }
+        if (out2) { o2 = out2; cap2 = ocap2; } else { HIPCHK(ctx, ctx->out_fq2.ensure((size_t)tt.b + 64)); o2 = ctx->out_fq2.as<uint8_t>(); cap2 = ctx->out_fq2.cap; }
+        if (emitted) break;
+        ctx->timer.end(S);
+        ctx->timer.begin(P.on ? "emit" : "emit_expanded", S);              // the emitter alone: the path's largest kernel (bench.py roofline)
+        if (P.on) launch_emit3(ctx, a, g, P, L, F, o1, cap1, o2, cap2, 0ull);
+        else {
+            const uint32_t bx = grid_x_for(n_chunks, (max_reads + ET_READS - 1) / ET_READS, 4u * ctx->n_cu);   // (39 KB of LDS: four workgroups per CU)
+            hipLaunchKernelGGL(k_dec_emit, dim3(bx, n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, D, R, (const uint64_t*)E.qbase, (const uint64_t*)E.sbase,
+                               (const uint8_t*)E.qdec, (const uint8_t*)E.sdec, (uint64_t)E.qbytes, (uint64_t)E.sbytes, (uint64_t)a->n, split, o1, cap1, o2, cap2, dst);
+        }
+        KCHK(ctx, "k_dec_emit");
+        ctx->timer.end(S);
+        emitted = true;
     }
     ctx->timer.collect();
     if (hs.err & (1u << 31)) return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffer too small: need %u / %u bytes", tt.a, tt.b);
@@ -363,9 +345,10 @@ static DecRange range_of(const DecStatus& hs, const DChunk* CH, uint32_t n_chunk
 }
 // Reads, bases and text of one pass are placed by 32-bit prefix sums: a larger image is decoded range by range - contiguous chunks of about
 // slice_bases bases and fewer than 2^31 reads, cut out of every piece [c0, c1) of the image.  Returned as a stack: the first range on top.
-struct DecRng { uint32_t c0, c1; bool r1_only; };
-static std::vector<DecRng> plan_ranges(const std::vector<DecRng>& pieces, const std::vector<DChunk>& hc, uint64_t slice_bases) {
-    std::vector<DecRng> fw, todo;
+// ChunkSpan: the chunks [c0, c1) of the image (r1_only: a piece of which the reference writes the first mate only)
+struct ChunkSpan { uint32_t c0, c1; bool r1_only; };
+static std::vector<ChunkSpan> plan_ranges(const std::vector<ChunkSpan>& pieces, const std::vector<DChunk>& hc, uint64_t slice_bases) {
+    std::vector<ChunkSpan> fw, todo;
     for (auto& pc : pieces) {
         uint32_t c0 = pc.c0; uint64_t acc = 0, rd = 0;
         for (uint32_t c = pc.c0; c < pc.c1; c++) {
@@ -376,6 +359,14 @@ static std::vector<DecRng> plan_ranges(const std::vector<DecRng>& pieces, const 
     }
     for (size_t i = fw.size(); i-- > 0;) todo.push_back(fw[i]);
     return todo;
+}
+// the range of one span: its reads and bases summed from the host copy of the chunk table, its chunks' read bases made relative to it (k_dec_rebase)
+static int span_range(rfq_ctx* ctx, const DecStatus& hs, DChunk* CHm, const std::vector<DChunk>& hc, const ChunkSpan& r, DecRange* g, uint64_t* reads) {
+    uint64_t rd = 0, rbases = 0; for (uint32_t c = r.c0; c < r.c1; c++) { rd += hc[c].reads; rbases += hc[c].bases; }
+    hipLaunchKernelGGL(k_dec_rebase, dim3((r.c1 - r.c0 + 255) / 256), dim3(256), 0, ctx->stream, CHm + r.c0, r.c1 - r.c0, hc[r.c0].rbase_abs);
+    KCHK(ctx, "k_dec_rebase");
+    *g = range_of(hs, CHm + r.c0, r.c1 - r.c0, rd, rbases); *reads = rd;
+    return RFQ_OK;
 }
 
 // what every decode call does first: the device, the stage timers, the header (parsed from the image and set, or the one set before);
@@ -522,8 +513,7 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
     // when it is the R1 bit that is set.  The text is decoded piece by piece: runs of chunks that survive, R1 only where the reference drops R2.
     // Repaq::decompress (one output, :262-328) peeks the same way but keeps the peeked chunk in a variable that outlives the iteration and decodes it
     // next: nothing is lost there, and the only effect of the bit - the last chunk's final '\n' dropped - is the default behaviour.
-    typedef DecRng Rng;
-    std::vector<Rng> pieces; std::vector<DChunk> hc; bool strip1 = (last_flags & C_NO_LB) != 0, strip2 = (last_flags & C_NO_LB_R2) != 0;
+    std::vector<ChunkSpan> pieces; std::vector<DChunk> hc; bool strip1 = (last_flags & C_NO_LB) != 0, strip2 = (last_flags & C_NO_LB_R2) != 0;
     const bool compat = a->bug_compat != 0 && split;
     if (compat) {
         hc.resize(n_chunks);
@@ -555,30 +545,23 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
         // there to its place in the result.
         if (!compat) { hc.resize(n_chunks); HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
                 pieces.push_back({ 0, n_chunks, false }); }
-        std::vector<Rng> todo = plan_ranges(pieces, hc, slice_bases);        // stack of [c0, c1), first range on top
+        std::vector<ChunkSpan> todo = plan_ranges(pieces, hc, slice_bases);  // stack of [c0, c1), first range on top
         size_t w1 = 0, w2 = 0; n1 = n2 = 0; nb = 0;
-        std::vector<std::pair<const char*, float>> acc_ms;
-        ctx->timer.collect();                                                // (the walk, and whatever a failed one-pass attempt got through)
-        for (size_t i = 0; i < ctx->timer.names.size() && i < 1; i++) acc_ms.emplace_back(ctx->timer.names[i], ctx->timer.ms[i]);
+        StageSums sums; ctx->timer.collect(); sums.add(ctx->timer);             // (the walk, and whatever a failed one-pass attempt got through)
         while (!todo.empty()) {
-            const Rng r = todo.back(); todo.pop_back();
-            const uint32_t c0 = r.c0, c1 = r.c1; uint64_t reads = 0, rbases = 0; for (uint32_t c = c0; c < c1; c++) { reads += hc[c].reads; rbases += hc[c].bases; }
-            hipLaunchKernelGGL(k_dec_rebase, dim3((c1 - c0 + 255) / 256), dim3(256), 0, S, CHm + c0, c1 - c0, hc[c0].rbase_abs);
-            KCHK(ctx, "k_dec_rebase");
-            const DecRange g = range_of(hs, CHm + c0, c1 - c0, reads, rbases);
+            const ChunkSpan r = todo.back(); todo.pop_back();
+            DecRange g; uint64_t reads = 0;
+            rc = span_range(ctx, hs, CHm, hc, r, &g, &reads);
+            if (rc) return rc;
             uint8_t *q1 = nullptr, *q2 = nullptr; size_t m1 = 0, m2 = 0; uint64_t mb = 0;
             ctx->timer.reset();
             rc = reads > 0x7FFFFFF0ull ? RFQ_RANGE_TOO_BIG : decode_range(ctx, a, g, nullptr, 0, nullptr, 0, &q1, &q2, &m1, &m2, &mb);
             if (rc == RFQ_RANGE_TOO_BIG) {
-                if (c1 - c0 < 2) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk decodes to 4 GiB of text or more");
-                const uint32_t mid = c0 + (c1 - c0) / 2; todo.push_back({ mid, c1, r.r1_only }); todo.push_back({ c0, mid, r.r1_only }); continue;
+                if (r.c1 - r.c0 < 2) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk decodes to 4 GiB of text or more");
+                const uint32_t mid = r.c0 + (r.c1 - r.c0) / 2; todo.push_back({ mid, r.c1, r.r1_only }); todo.push_back({ r.c0, mid, r.r1_only }); continue;
             }
             if (rc != RFQ_OK) return rc;
-            for (size_t i = 0; i < ctx->timer.names.size(); i++) {
-                bool hit = false;
-                for (auto& q : acc_ms) if (q.first == ctx->timer.names[i]) { q.second += ctx->timer.ms[i]; hit = true; break; }
-                if (!hit) acc_ms.emplace_back(ctx->timer.names[i], ctx->timer.ms[i]);
-            }
+            sums.add(ctx->timer);
             for (int k = 0; k < (split ? 2 : 1); k++) {
                 uint8_t* src = k ? q2 : q1; const size_t m = k ? m2 : m1; size_t& w = k ? w2 : w1; uint8_t* dcall = k ? a->d_out2 : a->d_out1;
                         const size_t dcap = k ? a->cap2 : a->cap1;
@@ -594,8 +577,7 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
         }
         n1 = w1; n2 = w2;
         o1 = a->d_out1 ? a->d_out1 : ctx->out_acc1.as<uint8_t>(); o2 = a->d_out2 ? a->d_out2 : ctx->out_acc2.as<uint8_t>();
-        ctx->timer.names.clear(); ctx->timer.ms.clear();
-        for (auto& q : acc_ms) { ctx->timer.names.push_back(q.first); ctx->timer.ms.push_back(q.second); }
+        sums.publish(ctx->timer);
     }
     res->n_bases = nb;
     if (a->final) {   // Repaq::decompress*: drop the final '\n' when the last chunk carries the NO_LINE_BREAK bit
@@ -681,30 +663,20 @@ extern "C" int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* ra, rfq
     }
     std::vector<DChunk> hc(n_chunks);
     HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
-    std::vector<DecRng> todo = plan_ranges(std::vector<DecRng>{ { 0, n_chunks, false } }, hc, slice_bases);
-    // stage times summed over the ranges, by name (the walk first)
-    std::vector<std::pair<const char*, float>> acc_ms;
-    auto add_ms = [&]() {
-        ctx->timer.collect();
-        for (size_t i = 0; i < ctx->timer.names.size(); i++) {
-            bool hit = false;
-            for (auto& q : acc_ms) if (q.first == ctx->timer.names[i]) { q.second += ctx->timer.ms[i]; hit = true; break; }
-            if (!hit) acc_ms.emplace_back(ctx->timer.names[i], ctx->timer.ms[i]);
-        }
-    };
-    HIPCHK(ctx, hipStreamSynchronize(S)); add_ms();
+    std::vector<ChunkSpan> todo = plan_ranges(std::vector<ChunkSpan>{ { 0, n_chunks, false } }, hc, slice_bases);
+    HIPCHK(ctx, hipStreamSynchronize(S));
+    StageSums sums; ctx->timer.collect(); sums.add(ctx->timer);                 // (the walk)
     while (!todo.empty()) {
-        const DecRng r = todo.back(); todo.pop_back();
-        uint64_t reads = 0, rbases = 0; for (uint32_t c = r.c0; c < r.c1; c++) { reads += hc[c].reads; rbases += hc[c].bases; }
-        if (rbases >= 0xFFFFFFF0ull || reads >= 0x7FFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk holds 4 Gi bases or 2 Gi reads or more");
-        hipLaunchKernelGGL(k_dec_rebase, dim3((r.c1 - r.c0 + 255) / 256), dim3(256), 0, S, CHm + r.c0, r.c1 - r.c0, hc[r.c0].rbase_abs);
-        KCHK(ctx, "k_dec_rebase");
-        ctx->timer.reset();
-        const int rc = rows_range(ctx, &a, range_of(hs, CHm + r.c0, r.c1 - r.c0, reads, rbases), o);
+        const ChunkSpan r = todo.back(); todo.pop_back();
+        DecRange g; uint64_t reads = 0;
+        int rc = span_range(ctx, hs, CHm, hc, r, &g, &reads);
         if (rc) return rc;
-        add_ms();
+        if (g.bases >= 0xFFFFFFF0ull || reads >= 0x7FFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk holds 4 Gi bases or 2 Gi reads or more");
+        ctx->timer.reset();
+        rc = rows_range(ctx, &a, g, o);
+        if (rc) return rc;
+        ctx->timer.collect(); sums.add(ctx->timer);
     }
-    ctx->timer.names.clear(); ctx->timer.ms.clear();
-    for (auto& q : acc_ms) { ctx->timer.names.push_back(q.first); ctx->timer.ms.push_back(q.second); }
+    sums.publish(ctx->timer);
     return RFQ_OK;
 }

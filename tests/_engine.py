@@ -30,6 +30,50 @@ def build_emu():
     return EMU_LIB
 
 
+def handmade(n, name_of, len_of, strand_of, seed, qual_of=None):
+    import random
+    rnd = random.Random(seed); out = []
+    for i in range(n):
+        ln = len_of(i); seq = "".join(rnd.choice("ACGT") if rnd.random() > 0.01 else "N" for _ in range(ln))
+        qual = "".join("#" if c == "N" else (qual_of(i, j) if qual_of else rnd.choice("FFFFFF:,")) for j, c in enumerate(seq))
+        out.append("@%s\n%s\n%s\n%s\n" % (name_of(i), seq, strand_of(i), qual))
+    return "".join(out).encode()
+
+
+def check_pieces_remembered_behind_speculative_emit(make_codec):
+    """A file whose per-read name pieces do not fit a tile of k_dec_emit3, decoded into the caller's buffers (the emitter is launched ahead of the host's
+    look at the status): the emitter's DE_E3_RETRY sends the range to the expanded path AND the context remembers it - the same image's chunks decoded again
+    on that context without a header in between (has_header=False: the streaming contract of decode_in_slices) go to the expanded path at once, the
+    fused emitter is not launched a second time.  The list chain's own retry (DE_LIST_ALIAS, k_dec_pos_link2) is a bit of its own and is not remembered."""
+    import _sections
+    # (qualities that code one position in 29: with the default ones, a quarter of the positions, the lists do not fit the arena's first size - the emitter
+    # launched ahead leaves at once and the ordinary order, where the retry has always been remembered, takes over)
+    mixed = handmade(900, lambda i: ("SRR0123456.%d" % i) if not 400 <= i < 480 else ("L" * 110 + "%d" % i), lambda i: 100, lambda i: "+", seed=4,
+                     qual_of=lambda i, j: "F" if (i + j) % 29 else ",")
+    rfq = O.encode_file(mixed, b"", O.SE, 1_000_000)
+    sizer = make_codec()
+    cap = len(sizer.decode_bytes(rfq)) + 64
+    sizer.close()
+    codec = make_codec()                                                     # (a context that has not given up on such files yet)
+    d_out = codec.dev_put(b"\0" * cap)
+    assert d_out.value % 16 == 0
+    body = rfq[_sections.Header(rfq).len:]                                   # the chunks behind the header, as the reference's reader cuts it
+    try:
+        for image, has_header in ((rfq, True), (body, False)):
+            d = codec.dev_put(image)
+            try:
+                r = codec.decode(d, len(image), has_header=has_header, d_out1=d_out, cap1=cap)
+                assert codec.dev_get(r.d_fq1, r.n1) == mixed
+                t = dict(codec.timings())
+            finally:
+                codec.dev_free(d)
+            assert "emit_expanded" in t, t
+            assert has_header == ("emit" in t), t                            # (the first call ran the fused emitter and decoded again; the second: straight to the expanded path)
+    finally:
+        codec.dev_free(d_out)
+        codec.close()
+
+
 def nolb_args(fq1, fq2, paired):
     from repaq_amd import nolb_threshold
     t1 = nolb_threshold(len(fq1), fq1.endswith(b"\n"))

@@ -98,14 +98,7 @@ def test_emitters_are_the_ones_expected(codec):
     assert codec.decode_bytes(rfq) == fq
 
 
-def _handmade(n, name_of, len_of, strand_of, seed, qual_of=None):
-    import random
-    rnd = random.Random(seed); out = []
-    for i in range(n):
-        ln = len_of(i); seq = "".join(rnd.choice("ACGT") if rnd.random() > 0.01 else "N" for _ in range(ln))
-        qual = "".join("#" if c == "N" else (qual_of(i, j) if qual_of else rnd.choice("FFFFFF:,")) for j, c in enumerate(seq))
-        out.append("@%s\n%s\n%s\n%s\n" % (name_of(i), seq, strand_of(i), qual))
-    return "".join(out).encode()
+_handmade = E.handmade
 
 
 @pytest.mark.parametrize("label,name_of,strand_of", [
@@ -156,6 +149,11 @@ def test_fixed_tile_emitter_with_per_read_name_pieces():
     assert codec.decode_bytes(O.encode_file(mid, b"", O.SE, 1_000_000)) == mid
     assert "emit" in dict(codec.timings()), dict(codec.timings())
     codec.close()
+
+
+def test_per_read_name_pieces_remembered_behind_a_speculative_emit():
+    from repaq_amd import RfqCodec
+    E.check_pieces_remembered_behind_speculative_emit(lambda: RfqCodec(device=0, library=E.build_emu()))
 
 
 def test_position_lists_of_long_runs(codec):

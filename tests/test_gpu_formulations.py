@@ -110,6 +110,11 @@ def test_legacy_run_length_images_under_every_decode_formulation(codec, form):
             assert "emit_expanded" in dict(codec.timings())
 
 
+def test_per_read_name_pieces_remembered_behind_a_speculative_emit():
+    from repaq_amd import RfqCodec
+    E.check_pieces_remembered_behind_speculative_emit(lambda: RfqCodec(device=0, library=E.PRODUCT_LIB))
+
+
 def test_interleaved_chunk_whose_mate_test_fails_midway_under_every_encode_formulation(codec):
     """phase 2 of the gather (k_gather_redo_reset + the second k_gather2 launch): a chunk whose interleave test fails behind its first pairs is gathered
     once more with the mates as they stand - under every encode formulation"""
