@@ -195,6 +195,47 @@ typedef struct {
 } rfq_decode_rows_result;
 RFQ_API int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* args, rfq_decode_rows_result* res);
 
+/* The way back: per-read ARRAYS in HBM -> FASTQ text -> .rfq image, nothing on the host.  The row layout is rfq_decode_rows's: row i is record i,
+ * `name '\n' bases '\n' '+' '\n' quals '\n'` (the strand line is always "+", every text ends in '\n').  A base row holds the FASTQ bytes or the codes
+ * 0..4 (-> A C G T N), a quality row the quality characters minus qual_offset; bytes at positions >= the read's length are never read as data
+ * (whatever pad rfq_decode_rows wrote is ignored).  Names are not rows: all name lines back to back ('@' included, no line breaks) and n_rows + 1 offsets.
+ * The row buffers may have any alignment; with row_len % 16 == 0 and 16-byte alignment they are loaded in whole 16-byte groups, otherwise at their own
+ * alignment - never a byte outside [d_x, d_x + n_rows * row_len).  d_lens is 4-byte, d_name_off 8-byte aligned.  n_rows * row_len and the texts may
+ * exceed 4 GiB.
+ * Refused, judged on the device before anything is written (the context stays usable): RFQ_E_ARG for a length < 0 or > row_len, for name offsets that
+ * decrease or end past names_len, and for an odd n_rows with RFQ_PE_TWO_FILES; RFQ_E_DATA for a length of 0 (an empty sequence line ends the
+ * reference's reader, src/fastqreader.cpp:180-191) and for a name of 0 bytes.  Found by the writer itself, RFQ_E_DATA, what the output buffers hold
+ * is then unspecified (as with rfq_decode_args's caller buffers): a code above 4, an ASCII base or a quality character (after the offset) outside
+ * 0x21..0x7E, '\n' or '\r' in a name.  Everything else (lower-case bases, names over 255 bytes, coordinates) is the encoder's to judge. */
+typedef struct {
+    uint64_t n_rows;
+    uint32_t row_len;                     /* row stride in bytes (>= 1)                                                 */
+    int32_t  base_mode;                   /* RFQ_ROWS_ASCII / RFQ_ROWS_CODE                                             */
+    uint8_t  qual_offset;                 /* quality char = row byte + qual_offset (mod 256)                            */
+    uint8_t  reserved[3];
+    const uint8_t* d_bases;               /* [n_rows][row_len]                                                          */
+    const uint8_t* d_quals;               /* [n_rows][row_len]                                                          */
+    const int32_t* d_lens;                /* [n_rows], 1 <= len <= row_len                                              */
+    const uint8_t* d_names; size_t names_len;   /* the name lines, back to back                                         */
+    const uint64_t* d_name_off;           /* [n_rows + 1] device offsets into d_names, non-decreasing, last <= names_len */
+} rfq_rows_in;
+typedef struct {
+    const uint8_t* d_fq1; size_t n1;      /* the text (RFQ_PE_TWO_FILES: of the even rows)                              */
+    const uint8_t* d_fq2; size_t n2;      /* RFQ_PE_TWO_FILES: the text of the odd rows, else NULL / 0                  */
+    uint64_t n_reads, n_bases;
+} rfq_rows_text_result;
+/* rows -> text.  paired: RFQ_SE and RFQ_PE_INTERLEAVED write one text in row order, RFQ_PE_TWO_FILES rows 2k to text 1 and rows 2k + 1 to text 2.
+ * d_out1 / d_out2: caller buffers (16-byte aligned) of cap1 / cap2 bytes; NULL = context-owned buffers, valid until the next call on the context.
+ * size_only = 1: n1, n2, n_reads and n_bases are returned and nothing is written.  RFQ_E_NOSPACE (nothing written; the message says what is needed)
+ * when a cap is smaller than its text.  Synchronous: the text is in place when the call returns. */
+RFQ_API int rfq_rows_to_text(rfq_ctx* ctx, const rfq_rows_in* rows, int32_t paired, uint8_t* d_out1, size_t cap1, uint8_t* d_out2, size_t cap2,
+                             int32_t size_only, rfq_rows_text_result* res);
+/* rfq_rows_to_text into context-owned text, then rfq_encode_batch(enc) on it: enc->d_fq1 / d_fq2 / n1 / n2 must be NULL / 0 (the call fills them in), and
+ * final or flush_all must be set - a rows batch is always encoded whole, there is no text to report `consumed` against (RFQ_E_ARG otherwise).  paired,
+ * chunk_bases, emit_header, d_out / out_cap, the line-break fields and the header state behave as in rfq_encode_batch; several row batches make one
+ * file: the first with emit_header = 1, flush_all = 1, the last with final = 1.  A refusal of the rows leaves the encoder unrun. */
+RFQ_API int rfq_encode_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_encode_args* enc, rfq_encode_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);

@@ -168,6 +168,69 @@ class RfqCodec:
             for p in bufs:
                 self.dev_free(p)
 
+    # --- the way back: fixed-stride rows -> FASTQ text (rfq_rows_to_text) -> image (rfq_encode_rows)
+    @staticmethod
+    def _rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset):
+        return A.RowsIn(n_rows, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII, qual_offset, (C.c_uint8 * 3)(), d_bases, d_quals, d_lens, d_names, names_len, d_name_off)
+
+    def rows_to_text(self, n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, paired=SE, codes=False, qual_offset=33,
+                     d_out1=None, cap1=0, d_out2=None, cap2=0, size_only=False):
+        """rfq_rows_to_text: rows in the layout of decode_rows (device pointers; d_lens int32, d_name_off n_rows + 1 uint64 offsets into the name lines
+        d_names) -> the FASTQ text(s).  No output buffer = context-owned texts, valid until the next call.  Returns RowsTextResult."""
+        a = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset)
+        r = A.RowsTextResult()
+        self._check(self._L.rfq_rows_to_text(self._h, C.byref(a), paired, d_out1, cap1, d_out2, cap2, 1 if size_only else 0, C.byref(r)))
+        return r
+
+    def encode_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, paired=SE, codes=False, qual_offset=33,
+                    chunk_bases=1_000_000, final=True, emit_header=True, file_off1=0, file_off2=0, nolb_from1=U64_MAX, nolb_from2=U64_MAX,
+                    d_out=None, out_cap=0, flush_all=False, d_fq1=None):
+        """rfq_encode_rows: rows_to_text into the context's own text, then encode() on it (final or flush_all: a rows batch is encoded whole).
+        d_fq1 exists for the tests of the refusal: the call fills the text in itself.  Returns EncodeResult."""
+        a = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset)
+        e = A.EncodeArgs(d_fq1, 0, None, 0, paired, chunk_bases, 1 if final else 0, 1 if emit_header else 0,
+                         file_off1, file_off2, nolb_from1, nolb_from2, d_out, out_cap, 1 if flush_all else 0, 0)
+        r = A.EncodeResult()
+        self._check(self._L.rfq_encode_rows(self._h, C.byref(a), C.byref(e), C.byref(r)))
+        return r
+
+    def _put_rows(self, bases, quals, lens, names):
+        """numpy rows + a list of name lines -> device buffers: (pointers to free, positional arguments of rows_to_text / encode_rows)"""
+        import numpy as np
+        bases = np.ascontiguousarray(bases, dtype=np.uint8); quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        n = int(lens.shape[0]); L = int(bases.shape[1]) if bases.ndim == 2 else 0
+        assert bases.shape == quals.shape == (n, L) and len(names) == n and L >= 1, "bases / quals [n, L], lens [n], n names"
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum(np.fromiter((len(x) for x in names), dtype=np.uint64, count=n))
+        blob = b"".join(names)
+        ptrs = [self.dev_put(x) for x in (bases.tobytes(), quals.tobytes(), lens.tobytes(), blob, off.tobytes())]
+        return ptrs, (n, L, ptrs[0], ptrs[1], ptrs[2], ptrs[3], len(blob), ptrs[4])
+
+    def rows_to_text_bytes(self, bases, quals, lens, names, paired=SE, codes=False, qual_offset=33):
+        """host convenience: numpy bases / quals [n, L] uint8, lens [n], a list of n name lines (bytes, '@' included) -> the text, or the pair of
+        texts with PE_TWO_FILES"""
+        ptrs, rows = self._put_rows(bases, quals, lens, names)
+        try:
+            r = self.rows_to_text(*rows, paired=paired, codes=codes, qual_offset=qual_offset)
+            a = self.dev_get(r.d_fq1, r.n1) if r.n1 else b""
+            b = self.dev_get(r.d_fq2, r.n2) if (paired == PE_TWO_FILES and r.n2) else b""
+            return (a, b) if paired == PE_TWO_FILES else a
+        finally:
+            for p in ptrs:
+                self.dev_free(p)
+
+    def encode_rows_bytes(self, bases, quals, lens, names, paired=SE, chunk_bases=1_000_000, codes=False, qual_offset=33, **kw) -> bytes:
+        """host convenience: the same inputs -> the .rfq image (kw: the flags of encode())"""
+        ptrs, rows = self._put_rows(bases, quals, lens, names)
+        try:
+            r = self.encode_rows(*rows, paired=paired, codes=codes, qual_offset=qual_offset, chunk_bases=chunk_bases, **kw)
+            return self.dev_get(r.d_rfq, r.rfq_len) if r.rfq_len else b""
+        finally:
+            for p in ptrs:
+                self.dev_free(p)
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

@@ -104,6 +104,9 @@ extern "C" void rfq_destroy(rfq_ctx* c) {
     for (auto& b : c->b) b.release();
     c->d_hdr.release(); c->d_status.release(); c->d_cmp.release(); c->out_img.release(); c->out_fq1.release(); c->out_fq2.release(); c->out_acc.release();
             c->out_acc1.release(); c->out_acc2.release();
+    for (auto& b : c->rows_off) b.release();
+    for (auto& b : c->rows_txt) b.release();
+    c->rows_stat.release();
     c->timer.destroy();
     if (c->copy) { (void)hipStreamDestroy(c->copy); for (auto& e : c->copy_ev) if (e) (void)hipEventDestroy(e); }
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);

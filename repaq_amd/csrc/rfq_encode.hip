@@ -881,3 +881,116 @@ static int encode_impl(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result
     res->h_chunk_off = ctx->chunk_off.data();
     return RFQ_OK;
 }
+
+// ---------------------------------------------------------------- rows -> FASTQ text (-> image): rfq_rows_to_text, rfq_encode_rows of include/rfq_hip.h
+// The judged part (k_rows_sizes + one scan per text) ends in ONE read-back - the texts' sizes, the bases, the error bits - and the writer (k_rows_text)
+// runs only on rows that passed; what the writer itself finds in the bytes comes back with a second look at the same block.
+static int rows_text_impl(rfq_ctx* ctx, const rfq_rows_in* in, int32_t paired, uint8_t* d_out1, size_t cap1, uint8_t* d_out2, size_t cap2, bool size_only,
+        rfq_rows_text_result* res) {
+    memset(res, 0, sizeof *res);
+    if (paired < 0 || paired > 2) return rfq_fail(ctx, RFQ_E_ARG, "paired must be RFQ_SE, RFQ_PE_TWO_FILES or RFQ_PE_INTERLEAVED");
+    const bool two = paired == RFQ_PE_TWO_FILES; const int nt = two ? 2 : 1;
+    const uint64_t n = in->n_rows;
+    if (in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be >= 1");
+    if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "base_mode must be RFQ_ROWS_ASCII or RFQ_ROWS_CODE");
+    if (two && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_PE_TWO_FILES takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    if (n >= (1ull << 39)) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    if (n && (!in->d_bases || !in->d_quals || !in->d_lens || !in->d_name_off || (in->names_len && !in->d_names))) return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
+    if (((uintptr_t)in->d_lens & 3u) || ((uintptr_t)in->d_name_off & 7u)) return rfq_fail(ctx, RFQ_E_ARG, "d_lens must be 4-byte and d_name_off 8-byte aligned");
+    if ((((uintptr_t)d_out1) | ((uintptr_t)d_out2)) & 15u) return rfq_fail(ctx, RFQ_E_ARG, "output buffers must be 16-byte aligned");
+    if (!size_only && two && (d_out1 == nullptr) != (d_out2 == nullptr)) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_PE_TWO_FILES: give both output buffers or none");
+    hipStream_t S = ctx->stream;
+    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n == 0) { ctx->timer.collect(); return RFQ_OK; }
+    const uint64_t nrec[2] = { two ? n / 2 : n, two ? n / 2 : 0 };
+    RowsIn ri; memset(&ri, 0, sizeof ri);
+    ri.bases = in->d_bases; ri.quals = in->d_quals; ri.lens = in->d_lens; ri.names = in->d_names; ri.name_off = in->d_name_off;
+    ri.n_rows = n; ri.names_len = in->names_len; ri.row_len = in->row_len; ri.codes = in->base_mode == RFQ_ROWS_CODE ? 1u : 0u;
+    ri.qoff = in->qual_offset; ri.qoff4 = in->qual_offset * 0x01010101u;
+    ri.vec = (in->row_len % 16u == 0 && !(((uintptr_t)in->d_bases | (uintptr_t)in->d_quals) & 15u)) ? 1u : 0u;
+
+    ctx->timer.begin("rows_sizes", S);
+    HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(RowsStat)));
+    RowsStat* dst = ctx->rows_stat.as<RowsStat>();
+    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(RowsStat), S));
+    HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+    for (int t = 0; t < nt; t++) HIPCHK(ctx, ctx->rows_off[t].ensure((size_t)(nrec[t] + 2) * 8));
+    HIPCHK(ctx, ctx->b[B_SCANTMP].ensure(std::max<size_t>(1024, (size_t)(nrec[0] / SCAN_TILE + 2) * 16)));
+    uint64_t* off[2] = { ctx->rows_off[0].as<uint64_t>(), two ? ctx->rows_off[1].as<uint64_t>() : nullptr };
+    hipLaunchKernelGGL(k_rows_sizes, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S, ri, two ? 1u : 0u, off[0], off[1], dst);
+    KCHK(ctx, "k_rows_sizes");
+    for (int t = 0; t < nt; t++) scan_exclusive<uint64_t>(S, off[t], off[t], nrec[t], ctx->b[B_SCANTMP].as<uint64_t>(), 1);
+    KCHK(ctx, "scan_exclusive");
+    ctx->timer.end(S);
+    RowsStat hs; uint64_t total[2] = { 0, 0 };
+    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+    for (int t = 0; t < nt; t++) HIPCHK(ctx, ctx->fetch(&total[t], off[t] + nrec[t], 8, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    const unsigned long long br = hs.bad_row;
+    if (hs.err & RT_ERR_LEN) return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, br);
+    if (hs.err & RT_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
+    if (hs.err & RT_ERR_LEN0) return rfq_fail(ctx, RFQ_E_DATA, "a read of no bases (first such row: %llu): an empty sequence line ends the reference's reader", br);
+    if (hs.err & RT_ERR_NAME0) return rfq_fail(ctx, RFQ_E_DATA, "a name of no bytes (first such row: %llu)", br);
+    res->n1 = (size_t)total[0]; res->n2 = (size_t)total[1]; res->n_reads = n; res->n_bases = hs.n_bases;
+    if (size_only) { ctx->timer.collect(); return RFQ_OK; }
+
+    uint8_t* out[2] = { d_out1, two ? d_out2 : nullptr };
+    if (d_out1) {
+        if (cap1 < total[0] || (two && cap2 < total[1])) {
+            const unsigned long long n1 = total[0], n2 = total[1];
+            memset(res, 0, sizeof *res);
+            return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need %llu bytes of text 1 and %llu of text 2", n1, n2);
+        }
+    } else {
+        // (the encoder reads its text in 16-byte groups: a 256-byte aligned start and slack behind the last byte, like its normalised-text buffers)
+        for (int t = 0; t < nt; t++) { HIPCHK(ctx, ctx->rows_txt[t].ensure((size_t)total[t] + 64 + 16)); out[t] = ctx->rows_txt[t].as<uint8_t>(); }
+    }
+    ctx->timer.begin("rows_text", S);
+    for (int t = 0; t < nt; t++) {
+        if (!total[t]) continue;
+        const uint64_t blocks = (total[t] + RT_TILE - 1) / RT_TILE;
+        if (blocks > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "a text of %llu bytes is too large for one call", (unsigned long long)total[t]);
+        hipLaunchKernelGGL(k_rows_text, dim3((uint32_t)blocks), dim3(RT_TPB), 0, S, ri, (const uint64_t*)off[t], nrec[t], (uint32_t)t, two ? 2u : 1u, out[t], total[t], dst);
+        KCHK(ctx, "k_rows_text");
+    }
+    ctx->timer.end(S);
+    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    ctx->timer.collect();
+    if (hs.err) {
+        const unsigned long long wr = hs.bad_row;
+        memset(res, 0, sizeof *res);
+        if (hs.err & RT_ERR_NAMELB) return rfq_fail(ctx, RFQ_E_DATA, "a line break inside a name (first such row: %llu)", wr);
+        if (hs.err & RT_ERR_CODE) return rfq_fail(ctx, RFQ_E_DATA, "a base code above 4 (first such row: %llu)", wr);
+        if (hs.err & RT_ERR_BASE) return rfq_fail(ctx, RFQ_E_DATA, "a base outside 0x21..0x7E (first such row: %llu)", wr);
+        return rfq_fail(ctx, RFQ_E_DATA, "a quality character outside 0x21..0x7E after the offset %u (first such row: %llu)", (unsigned)in->qual_offset, wr);
+    }
+    res->d_fq1 = total[0] ? out[0] : nullptr; res->d_fq2 = (two && total[1]) ? out[1] : nullptr;
+    return RFQ_OK;
+}
+extern "C" int rfq_rows_to_text(rfq_ctx* ctx, const rfq_rows_in* in, int32_t paired, uint8_t* d_out1, size_t cap1, uint8_t* d_out2, size_t cap2, int32_t size_only,
+        rfq_rows_text_result* res) {
+    if (!ctx || !in || !res) return RFQ_E_ARG;
+    ctx->err.clear();
+    return rows_text_impl(ctx, in, paired, d_out1, cap1, d_out2, cap2, size_only != 0, res);
+}
+extern "C" int rfq_encode_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_encode_args* enc, rfq_encode_result* res) {
+    if (!ctx || !in || !enc || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    if (enc->d_fq1 || enc->d_fq2 || enc->n1 || enc->n2) return rfq_fail(ctx, RFQ_E_ARG, "rfq_encode_rows fills in the text: d_fq1 / d_fq2 / n1 / n2 must be NULL / 0");
+    if (!enc->final && !enc->flush_all) return rfq_fail(ctx, RFQ_E_ARG, "a rows batch is encoded whole: set final or flush_all");
+    rfq_rows_text_result t;
+    int rc = rows_text_impl(ctx, in, enc->paired, nullptr, 0, nullptr, 0, false, &t);
+    if (rc != RFQ_OK) return rc;
+    StageSums rows; rows.add(ctx->timer); ctx->timer.names.clear(); ctx->timer.ms.clear();
+    rfq_encode_args a = *enc;
+    a.d_fq1 = t.d_fq1; a.n1 = t.n1; a.d_fq2 = t.d_fq2; a.n2 = t.n2;
+    rc = encode_or_scan(ctx, &a, res, false);
+    // the rows stages, then the encoder's own
+    StageSums all = rows;
+    for (size_t i = 0; i < ctx->timer.names.size(); i++) all.v.emplace_back(ctx->timer.names[i], ctx->timer.ms[i]);
+    all.publish(ctx->timer);
+    return rc;
+}

@@ -21,3 +21,4 @@
 #include "enc/pos_coder_list.h"               // position coder for many value streams: work follows the coded positions
 #include "enc/coords.h"                       // coordinate coder (encodeCoords)
 #include "enc/assemble.h"                     // chunk layout (incl. the mSize bug) and image assembly
+#include "enc/rows_text.h"                    // rows -> FASTQ text in front of the encoder (rfq_rows_to_text, rfq_encode_rows)

@@ -6,8 +6,18 @@
     rfq = torch.from_file("x.rfq", size=n, dtype=torch.uint8).cuda()
     t = decode_tensors(codec, rfq)            # {"bases": [n, L] uint8 codes A0 C1 G2 T3 N4, "quals": [n, L] Phred, "lens": [n] int32}
 
+and back - reads a basecaller, a simulator, a filter or a trimmer holds as tensors, straight to an image (rfq_encode_rows) or to FASTQ text:
+
+    blob, off = pack_names([b"@r1", b"@r2"], device)
+    image = encode_tensors(codec, t["bases"], t["quals"], t["lens"], blob, off)      # uint8 tensor: the .rfq image
+    text = rows_to_fastq(codec, t["bases"], t["quals"], t["lens"], blob, off)        # uint8 tensor: the FASTQ text
+
 This is the only module of the package that imports torch."""
+import ctypes as C
+
 import torch
+
+from ._capi import SE, PE_TWO_FILES
 
 
 def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offset=33, pad=255):
@@ -31,3 +41,69 @@ def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offs
     finally:
         codec.set_stream(None)
     return {"bases": bases, "quals": quals, "lens": lens}
+
+
+def pack_names(names, device):
+    """a list of name lines (bytes, '@' included, no line breaks) -> (blob, offsets): the lines back to back as a uint8 tensor and their n + 1 int64
+    offsets, both on `device` - the names / name_off of encode_tensors and rows_to_fastq"""
+    import numpy as np
+    n = len(names)
+    off = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        off[1:] = np.cumsum(np.fromiter((len(x) for x in names), dtype=np.int64, count=n))
+    blob = np.frombuffer(b"".join(names), dtype=np.uint8)
+    return torch.from_numpy(blob.copy()).to(device), torch.from_numpy(off).to(device)
+
+
+def _rows_args(bases, quals, lens, names, name_off):
+    assert bases.dtype == torch.uint8 and quals.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.shape == quals.shape, \
+        "bases / quals: [n, L] uint8 tensors on the GPU"
+    assert bases.is_contiguous() and quals.is_contiguous() and bases.shape[1] >= 1
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n, "lens: [n] int32"
+    assert names.dtype == torch.uint8 and names.is_contiguous(), "names: a uint8 blob (pack_names)"
+    assert name_off.dtype in (torch.int64, torch.uint64) and name_off.is_contiguous() and name_off.numel() == n + 1, "name_off: [n + 1] int64"
+    assert all(t.device == bases.device for t in (quals, lens, names, name_off)), "all tensors on one device"
+    return (n, L, bases.data_ptr(), quals.data_ptr(), lens.data_ptr(), names.data_ptr() if names.numel() else None, names.numel(), name_off.data_ptr())
+
+
+def _own_copy(codec, d_ptr, n, device):
+    """a tensor of the caller's with the n bytes at d_ptr (a result buffer of the context), copied on torch's current stream"""
+    out = torch.empty((n,), dtype=torch.uint8, device=device)
+    if n:
+        codec._check(codec._L.rfq_copy_d2d(codec._h, C.c_void_p(out.data_ptr()), C.c_void_p(d_ptr), n))
+    return out
+
+
+def encode_tensors(codec, bases, quals, lens, names, name_off, paired=SE, chunk_bases=1_000_000, codes=True, qual_offset=33, final=True,
+                   emit_header=True, flush_all=False):
+    """Rows in the layout of decode_tensors (+ the names: pack_names) -> the .rfq image as a uint8 tensor, by rfq_encode_rows: the text is made
+    and encoded on the GPU.  A PE file: rows 2k / 2k + 1 are R1 / R2 of pair k.  Several batches make one file: the first with flush_all=True,
+    final=False, the last with emit_header=False.  Ordered with torch's current stream; the context goes back to its own stream afterwards."""
+    rows = _rows_args(bases, quals, lens, names, name_off)
+    codec.set_stream(torch.cuda.current_stream(bases.device).cuda_stream)
+    try:
+        r = codec.encode_rows(*rows, paired=paired, codes=codes, qual_offset=qual_offset, chunk_bases=chunk_bases, final=final, emit_header=emit_header,
+                              flush_all=flush_all)
+        return _own_copy(codec, r.d_rfq, int(r.rfq_len), bases.device)
+    finally:
+        codec.set_stream(None)
+
+
+def rows_to_fastq(codec, bases, quals, lens, names, name_off, paired=SE, codes=True, qual_offset=33):
+    """The same rows -> the FASTQ text as a uint8 tensor (rfq_rows_to_text, written straight into the tensor); a pair of tensors with PE_TWO_FILES
+    (rows 2k -> the first, rows 2k + 1 -> the second).  Ordered with torch's current stream."""
+    rows = _rows_args(bases, quals, lens, names, name_off)
+    codec.set_stream(torch.cuda.current_stream(bases.device).cuda_stream)
+    try:
+        q = codec.rows_to_text(*rows, paired=paired, codes=codes, qual_offset=qual_offset, size_only=True)
+        n1, n2 = int(q.n1), int(q.n2)
+        # (16 bytes more than the text: torch's allocations are 16-byte aligned, and the slack keeps a later rfq_encode_batch on the tensor inside it)
+        t1 = torch.empty((n1 + 16,), dtype=torch.uint8, device=bases.device)
+        t2 = torch.empty((n2 + 16,), dtype=torch.uint8, device=bases.device) if paired == PE_TWO_FILES else None
+        if rows[0]:
+            codec.rows_to_text(*rows, paired=paired, codes=codes, qual_offset=qual_offset, d_out1=t1.data_ptr(), cap1=n1 + 16,
+                               d_out2=t2.data_ptr() if t2 is not None else None, cap2=n2 + 16 if t2 is not None else 0)
+        return (t1[:n1], t2[:n2]) if paired == PE_TWO_FILES else t1[:n1]
+    finally:
+        codec.set_stream(None)
