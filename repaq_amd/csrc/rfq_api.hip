@@ -149,7 +149,7 @@ extern "C" int rfq_get_header(rfq_ctx* c, uint8_t* out, size_t* len) {
     memcpy(out, c->h_hdr.bytes, c->h_hdr.len); *len = c->h_hdr.len;
     return RFQ_OK;
 }
-extern "C" void rfq_clear_header(rfq_ctx* c) { if (c) { c->have_hdr = false; c->hdr_on_device = false; c->dense_ok = false; c->e3_pieces_failed = false; c->mixed_lengths = false; memset(&c->h_hdr, 0, sizeof c->h_hdr); } }
+extern "C" void rfq_clear_header(rfq_ctx* c) { if (c) { c->have_hdr = false; c->hdr_on_device = false; c->new_file(); memset(&c->h_hdr, 0, sizeof c->h_hdr); } }
 
 extern "C" int rfq_last_timings(const rfq_ctx* c, const char** names, float* ms, int cap) {
     if (!c) return 0;

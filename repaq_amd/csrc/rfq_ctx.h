@@ -160,6 +160,8 @@ struct rfq_ctx {
     bool retried_room = false;             // encode: the call in progress repeats a batch whose arenas were too small (a marker for rfq_last_timings)
     bool mixed_lengths = false;            // encode: this file has reads of several lengths (the prefix scans are launched up front; reset with the header)
     bool dense_ok = false;                 // encode, match-mask mode: DevHeader::dense of the device header is set (k_dense_order; reset with the header)
+    // another file (its header is set or cleared): what its name pieces fit, whether its reads have one length, which coded values are frequent is not known yet
+    void new_file() { dense_ok = false; e3_pieces_failed = false; mixed_lengths = false; }
     // encode, match-mask mode: the rare planes of b[B_QPLANE] may hold bits (fresh buffer, or a call that left early): zero them whole
     bool qplane_dirty = true;
     uint32_t qplane_nd = 0, qplane_mask = 0; // ... dense planes the last batch used: how many, which (the others must be all-zero)
@@ -247,7 +249,7 @@ template <class T> static inline void scan_exclusive(hipStream_t s, const T* in,
 // host enqueue apiece, in chains where the GPU waits for the host: profiles/r06_b_queue_timeline_256.txt).  words: 32-bit words of each region; val: the word it is filled with.
 #define CLEAR_MAX 8
 struct ClearList { uint32_t* p[CLEAR_MAX]; uint64_t words[CLEAR_MAX]; uint32_t val[CLEAR_MAX]; uint32_t n;
-    void add(void* p_, size_t bytes, uint32_t v) { p[n] = (uint32_t*)p_; words[n] = (bytes + 3) / 4; val[n] = v; n++; } };
+    bool add(void* p_, size_t bytes, uint32_t v) { if (n >= CLEAR_MAX) return false; p[n] = (uint32_t*)p_; words[n] = (bytes + 3) / 4; val[n] = v; n++; return true; } };   // (false: the list is full)
 template <int UNUSED> __global__ void k_clear_list(ClearList z) {
     const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, NT = (uint64_t)gridDim.x * blockDim.x;
     for (uint32_t r = 0; r < z.n; r++) {                                    // (uniform)

@@ -86,6 +86,42 @@ def encode(codec, fq1, fq2=b"", paired=O.SE, chunk_bases=1_000_000):
     return codec.encode_bytes(fq1, fq2, paired, chunk_bases, **nolb_args(fq1, fq2, paired))
 
 
+def check_every_repeat_in_one_call(make_codec):
+    """The encoder's ways of encoding a text again, in ONE call of a fresh context: '\\r\\n' line ends (the normalising path), an empty line behind the records (the
+    repeat that ends the input there), four equally frequent quality values (arenas sized in advance too small: the room repeat, which meets the empty line again).  The
+    same text on the same context then has room and knows the records per byte (the index without a read-back, its own repeats behind it): no room repeat.  Both images
+    are the oracle's; the result counts the records in front of the empty line, those behind it are never read.
+    The `retry_room` marker: the empty line's repeat resets the stage timer behind it, so the full text shows it in neither call, whether the batch repeated for room or
+    not (a known loss, not this test's to fix).  It is asserted - present in the first call, absent in the second - on the largest text that shows it: the same records
+    with '\\r\\n' line ends and no empty line, two calls on a context of its own."""
+    import random
+    rng = random.Random(5)                                                   # (the text of test_arenas_sized_in_advance_grow_and_the_batch_repeats)
+
+    def rec(i):
+        seq = bytes(rng.choice(b"ACGT") for _ in range(150)); q = bytes(rng.choice(b"F:,5") for _ in range(150))
+        return b"@M:1:FC:1:%d:%d:%d 1:N:0:AC\n" % (1101 + i // 500, rng.randrange(1000, 30000), rng.randrange(1000, 60000)) + seq + b"\n+\n" + q + b"\n"
+    n = 2400
+    recs = b"".join(rec(i) for i in range(n))
+    full = (recs + b"\n\n" + b"".join(rec(n + i) for i in range(3))).replace(b"\n", b"\r\n")
+    for fq, calls in ((full, (1, 2)), (recs.replace(b"\n", b"\r\n"), (1, 2))):
+        want = O.encode_file(fq, b"", O.SE, 100000)
+        c = make_codec()
+        d = c.dev_put(fq)
+        try:
+            for call in calls:
+                c.clearHeader()
+                r = c.encode(d, len(fq), None, 0, O.SE, 100000, **nolb_args(fq, b"", O.SE))
+                t = dict(c.timings())
+                assert c.dev_get(r.d_rfq, r.rfq_len) == want, (call, r.rfq_len, len(want))
+                assert r.n_reads == n, (call, r.n_reads)
+                if fq is not full and call == 1: assert "retry_room" in t, (call, sorted(t))
+                if call == 2: assert "retry_room" not in t, (call, sorted(t))
+                assert "quality_masks" in t, (call, sorted(t))
+        finally:
+            c.dev_free(d)
+            c.close()
+
+
 # text quirks of src/fastqreader.cpp ('\r', blank lines) — handled by the normalising path since SURVEY.md §8(f) #1 was built
 TEXT_QUIRK_CASES = {"se_crlf", "se_cr_only", "se_crlf_no_final", "se_blank_line_after_record", "se_two_blank_lines_truncate"}
 

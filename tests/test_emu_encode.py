@@ -384,3 +384,9 @@ def test_no_read_back_behind_the_index_from_the_second_batch_on():
         assert E.encode(c, crlf, b"", O.SE, 30000) == O.encode_file(crlf, b"", O.SE, 30000)
     finally:
         c.close()
+
+
+def test_every_repeat_of_a_batch_in_one_call():
+    """normalise + empty line + room in one call, the index without a read-back in the next (E.check_every_repeat_in_one_call)"""
+    from repaq_amd import RfqCodec
+    E.check_every_repeat_in_one_call(lambda: RfqCodec(device=0, library=E.build_emu()))

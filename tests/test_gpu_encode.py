@@ -149,3 +149,9 @@ def test_uniform_and_almost_uniform_read_lengths(codec, label, fq1, fq2, paired,
     if O.have_ref():
         assert O.ref_encode(fq1, fq2, paired, k=cb // 1000) == want
     assert E.encode(codec, fq1, fq2, paired, cb) == want
+
+
+def test_every_repeat_of_a_batch_in_one_call():
+    """normalise + empty line + room in one call, the index without a read-back in the next (E.check_every_repeat_in_one_call)"""
+    from repaq_amd import RfqCodec
+    E.check_every_repeat_in_one_call(lambda: RfqCodec(device=0, library=E.PRODUCT_LIB))
