@@ -195,6 +195,31 @@ typedef struct {
 } rfq_decode_rows_result;
 RFQ_API int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* args, rfq_decode_rows_result* res);
 
+/* The NAMES of the same rows, in the layout rfq_rows_in takes: name i = the bytes of the first line of record i of rfq_decode_batch (split_pe = 0,
+ * bug_compat = 0) - the '@' included, the line break not -, all of them back to back, and n_rows + 1 offsets (name_off[0] = 0, name_off[n_rows] =
+ * names_len; 64-bit: a blob may exceed 4 GiB).  Row i here is row i of rfq_decode_rows (a PE file: rows 2k / 2k + 1 are R1 / R2 of pair k); n_rows,
+ * n_chunks and consumed are what rfq_decode_rows reports for the same arguments, the streaming contract is the same.  Only the chunk table, the name
+ * sections and the coordinate streams of the image are read: none of the base / quality streams.  The text of the STRAND lines is not carried:
+ * rfq_rows_in always writes "+", so rows + names re-encode to the same image only for files whose strand lines are "+".
+ * size_only = 1: the counts alone, nothing is written.  RFQ_E_NOSPACE (nothing written; the message says "need ...") when a cap is too small,
+ * RFQ_E_ARG for a d_name_off that is not 8-byte aligned.  An image rfq_decode_batch refuses in its header or chunk walk is refused with the same
+ * code.  Synchronous: names and offsets are in place when the call returns; context-owned results stay valid until the next call on the context. */
+typedef struct {
+    const uint8_t* d_rfq; size_t n;       /* as rfq_decode_rows_args                                                    */
+    int32_t  has_header, final;
+    const uint64_t* h_chunk_off; uint32_t n_chunk_off;   /* optional chunk index, verified exactly as in rfq_decode_batch */
+    int32_t  size_only;                   /* 1: counts only, nothing written                                            */
+    uint8_t*  d_names;    size_t names_cap;   /* caller blob (any alignment) or NULL = context-owned                    */
+    uint64_t* d_name_off; size_t off_cap;     /* caller offsets, 8-byte aligned, cap in ENTRIES (>= n_rows + 1), or NULL = context-owned */
+} rfq_decode_names_args;
+typedef struct {
+    const uint8_t*  d_names;    uint64_t names_len;   /* where the blob is (the caller's or the context's)              */
+    const uint64_t* d_name_off;           /* [n_rows + 1], name_off[0] = 0, name_off[n_rows] = names_len                */
+    uint64_t n_rows; uint32_t n_chunks, max_name;     /* max_name: the longest name line in bytes                       */
+    size_t   consumed;
+} rfq_decode_names_result;
+RFQ_API int rfq_decode_names(rfq_ctx* ctx, const rfq_decode_names_args* args, rfq_decode_names_result* res);
+
 /* The way back: per-read ARRAYS in HBM -> FASTQ text -> .rfq image, nothing on the host.  The row layout is rfq_decode_rows's: row i is record i,
  * `name '\n' bases '\n' '+' '\n' quals '\n'` (the strand line is always "+", every text ends in '\n').  A base row holds the FASTQ bytes or the codes
  * 0..4 (-> A C G T N), a quality row the quality characters minus qual_offset; bytes at positions >= the read's length are never read as data

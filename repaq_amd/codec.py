@@ -168,6 +168,34 @@ class RfqCodec:
             for p in bufs:
                 self.dev_free(p)
 
+    # --- the name lines of the same rows (rfq_decode_names)
+    def decode_names(self, d_rfq, n, size_only=False, d_names=None, names_cap=0, d_name_off=None, off_cap=0, has_header=True, final=True, chunk_off=None, n_chunks=0):
+        """rfq_decode_names: name i = the first line of read i of decode(split_pe=False), '@' included, no line break - all of them back to back at
+        d_names and n_rows + 1 uint64 offsets at d_name_off, the layout rows_to_text / encode_rows take.  Row i is row i of decode_rows.  No buffers given =
+        context-owned results, valid until the next call; size_only: the counts alone.  The text of the strand lines is not carried (rows always write
+        "+").  Returns DecodeNamesResult (d_names, names_len, d_name_off, n_rows, n_chunks, max_name, consumed)."""
+        if chunk_off is not None and not isinstance(chunk_off, C.POINTER(C.c_uint64)):
+            n_chunks = len(chunk_off) - 1
+            chunk_off = C.cast((C.c_uint64 * len(chunk_off))(*chunk_off), C.POINTER(C.c_uint64))
+        a = A.DecodeNamesArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off if (chunk_off is not None and n_chunks) else None,
+                              n_chunks if chunk_off is not None else 0, 1 if size_only else 0, d_names, names_cap, d_name_off, off_cap)
+        r = A.DecodeNamesResult()
+        self._check(self._L.rfq_decode_names(self._h, C.byref(a), C.byref(r)))
+        return r
+
+    def decode_names_bytes(self, rfq: bytes, **kw):
+        """host bytes in, the list of name lines (bytes, '@' included) out"""
+        import numpy as np
+        d = self.dev_put(rfq)
+        try:
+            r = self.decode_names(d, len(rfq), **kw)
+            n = int(r.n_rows)
+            off = np.frombuffer(self.dev_get(r.d_name_off, 8 * (n + 1)), dtype=np.uint64)
+            blob = self.dev_get(r.d_names, int(r.names_len)) if r.names_len else b""
+            return [blob[int(off[i]):int(off[i + 1])] for i in range(n)]
+        finally:
+            self.dev_free(d)
+
     # --- the way back: fixed-stride rows -> FASTQ text (rfq_rows_to_text) -> image (rfq_encode_rows)
     @staticmethod
     def _rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset):

@@ -106,7 +106,7 @@ extern "C" void rfq_destroy(rfq_ctx* c) {
             c->out_acc1.release(); c->out_acc2.release();
     for (auto& b : c->rows_off) b.release();
     for (auto& b : c->rows_txt) b.release();
-    c->rows_stat.release();
+    c->rows_stat.release(); c->names_blob.release(); c->names_off.release();
     c->timer.destroy();
     if (c->copy) { (void)hipStreamDestroy(c->copy); for (auto& e : c->copy_ev) if (e) (void)hipEventDestroy(e); }
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);

@@ -168,6 +168,7 @@ struct rfq_ctx {
     size_t qplane_stride = 0;              // ... words per plane the buffer is laid out with (fixed while the buffer is)
     // rfq_rows_to_text / rfq_encode_rows: the record offsets of each text, the verdict block, the context-owned texts (they outlive the encoder's own buffers)
     DBuf rows_off[2], rows_stat, rows_txt[2];
+    DBuf names_blob, names_off;            // rfq_decode_names: the context-owned name lines and their offsets
     std::vector<uint64_t> chunk_off;
     std::vector<uint64_t> scan_end[2];     // rfq_scan_batch: end offset of every chunk in each input stream
     StageTimer timer;

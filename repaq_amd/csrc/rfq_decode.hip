@@ -680,3 +680,126 @@ extern "C" int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* ra, rfq
     sums.publish(ctx->timer);
     return RFQ_OK;
 }
+
+// ---- rfq_decode_names: the name lines of an image back to back and their offsets - what rfq_rows_in takes beside the rows of rfq_decode_rows.  The walk, then
+// per range (the ranges of rfq_decode_rows) the coordinate decoder, the lengths kernel, one 64-bit scan over the chunks' totals and the writer (dec/names.h):
+// neither the read table nor the expanded stage, a name needs none of the base / quality streams.  The sizes of every range are known before a byte is
+// written (a cap that is too small writes nothing); an image of several ranges runs the lengths of each range twice, its buffers are the next range's.
+// Workspace: the chunk-local name prefixes live in B[DB_PQL], the per-read piece prefixes in B[DB_PVL], the chunks' totals / bases in B[DB_CTEXT] / B[DB_TBASE].
+struct NamesSize { uint64_t bytes; uint32_t max_name; };
+static int names_lengths(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, NamesSize* z) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>(); DecStatus* dst = B[DB_STATUS].as<DecStatus>();
+    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(DecStatus), S));
+    ctx->timer.begin("name_lens", S);
+    const size_t nr = (size_t)g.n_reads + 2, nc = (size_t)g.n_chunks + 2;
+    HIPCHK(ctx, B[DB_XV].ensure(nr * 4)); HIPCHK(ctx, B[DB_YV].ensure(nr * 4)); HIPCHK(ctx, B[DB_PQL].ensure((nr + nc) * 4));
+    if (g.pieces) HIPCHK(ctx, B[DB_PVL].ensure((nr + nc) * 8));
+    HIPCHK(ctx, B[DB_CTEXT].ensure(nc * 8)); HIPCHK(ctx, B[DB_TBASE].ensure(nc * 8)); HIPCHK(ctx, B[DB_SCAN].ensure((nc / SCAN_TILE + 2) * 16 + 1024));
+    hipLaunchKernelGGL(k_dec_coords, dim3(2, g.n_chunks), dim3(64), 0, S, a->d_rfq, g.CH, D, B[DB_XV].as<uint32_t>(), B[DB_YV].as<uint32_t>());
+    KCHK(ctx, "k_dec_coords");
+    hipLaunchKernelGGL(k_dec_namelen, dim3(g.n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, D, (const uint32_t*)B[DB_XV].as<uint32_t>(), (const uint32_t*)B[DB_YV].as<uint32_t>(),
+                       B[DB_PQL].as<uint32_t>(), g.pieces ? B[DB_PVL].as<uint2>() : (uint2*)nullptr, B[DB_CTEXT].as<unsigned long long>(), dst);
+    KCHK(ctx, "k_dec_namelen");
+    scan_exclusive<unsigned long long>(S, B[DB_CTEXT].as<unsigned long long>(), B[DB_TBASE].as<unsigned long long>(), g.n_chunks, B[DB_SCAN].as<unsigned long long>(), 1);
+    ctx->timer.end(S);
+    unsigned long long total = 0; DecStatus h;
+    HIPCHK(ctx, ctx->fetch(&total, B[DB_TBASE].as<unsigned long long>() + g.n_chunks, 8, S));
+    HIPCHK(ctx, ctx->fetch(&h, dst, sizeof h, S)); HIPCHK(ctx, ctx->fetch_sync(S));
+    // (k_dec_namelen: list_need = the largest chunk's name bytes, max_one = the longest name; a chunk's prefixes are 32-bit)
+    if (h.list_need >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk holds 4 GiB of names or more");
+    z->bytes = total; z->max_name = h.max_one;
+    return RFQ_OK;
+}
+// the writer of a range whose lengths are in place (names_lengths right before it)
+static int names_write(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const NamesOut& o) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
+    ctx->timer.begin("names", S);
+    // (27 KB of LDS: five workgroups per CU)
+    const uint32_t bx = grid_x_for(g.n_chunks, (std::max(g.max_reads, 1u) + NM_READS - 1u) / NM_READS, 5u * ctx->n_cu);
+    hipLaunchKernelGGL(k_dec_names, dim3(bx, g.n_chunks), dim3(256), 0, S, a->d_rfq, (uint64_t)a->n, g.CH, ctx->d_hdr.as<DevHeader>(),
+                       (const uint32_t*)B[DB_XV].as<uint32_t>(), (const uint32_t*)B[DB_YV].as<uint32_t>(), (const uint32_t*)B[DB_PQL].as<uint32_t>(),
+                       g.pieces ? (const uint2*)B[DB_PVL].as<uint2>() : (const uint2*)nullptr, (const unsigned long long*)B[DB_TBASE].as<unsigned long long>(), o, g.n_chunks);
+    KCHK(ctx, "k_dec_names");
+    ctx->timer.end(S);
+    HIPCHK(ctx, hipStreamSynchronize(S));
+    return RFQ_OK;
+}
+
+extern "C" int rfq_decode_names(rfq_ctx* ctx, const rfq_decode_names_args* na, rfq_decode_names_result* res) {
+    if (!ctx || !na || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    if (na->n && !na->d_rfq) return rfq_fail(ctx, RFQ_E_ARG, "null rfq pointer");
+    if ((uintptr_t)na->d_name_off & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
+    const bool query = na->size_only != 0;
+    // the walk takes the text decode's arguments (split_pe = 0, bug_compat = 0: Repaq::decompress order, nothing lost)
+    rfq_decode_args a; memset(&a, 0, sizeof a);
+    a.d_rfq = na->d_rfq; a.n = na->n; a.has_header = na->has_header; a.final = na->final; a.h_chunk_off = na->h_chunk_off; a.n_chunk_off = na->n_chunk_off;
+    DecStatus hs; memset(&hs, 0, sizeof hs);
+    if (a.n == 0 && a.has_header) { HIPCHK(ctx, hipSetDevice(ctx->device)); ctx->timer.reset(); }      // an empty .rfq: no reads
+    else {
+        uint64_t start = 0;
+        { const int rc = dec_open(ctx, &a, &start); if (rc) return rc; }
+        { const int rc = dec_walk(ctx, &a, start, hs); if (rc) return rc; }
+    }
+    hipStream_t S = ctx->stream;
+    uint64_t tb = 0; for (int i = 0; i < 16; i++) tb += hs.base_slots[i];
+    const uint32_t n_chunks = hs.n_chunks; const uint64_t n_rows = n_chunks ? hs.total_reads : 0;
+    res->consumed = (size_t)hs.consumed; res->n_chunks = n_chunks; res->n_rows = n_rows;
+    // (the offsets' size is known here: a caller's array that cannot hold them is refused before any length is looked at)
+    if (!query && na->d_name_off && na->off_cap < n_rows + 1) return rfq_fail(ctx, RFQ_E_NOSPACE, "offset array too small: need %llu entries", (unsigned long long)(n_rows + 1));
+    DChunk* CHm = ctx->b[DB_CHUNKS].as<DChunk>();
+    // the ranges of rfq_decode_rows (RFQ_SLICE_BASES forces ranges on small images; the reads of a range count from 0 in 32 bits)
+    const uint64_t slice_env = ctx->opt.slice_bases;
+    const uint64_t slice_bases = slice_env ? slice_env : 1500000000ull, one_pass = slice_env ? slice_env : 0xFFFFFFF0ull;
+    const bool one = tb < one_pass && n_rows < 0x7FFFFFF0ull;
+    std::vector<DChunk> hc; std::vector<ChunkSpan> spans;                      // (spans: the first range LAST - plan_ranges' stack)
+    StageSums sums;
+    if (n_chunks && !one) {
+        hc.resize(n_chunks);
+        HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
+        spans = plan_ranges(std::vector<ChunkSpan>{ { 0, n_chunks, false } }, hc, slice_bases);
+        HIPCHK(ctx, hipStreamSynchronize(S));
+        ctx->timer.collect(); sums.add(ctx->timer);                         // (the walk)
+    }
+    // ---- every range's bytes; 64-bit from here on: range bases are sums on the host, chunk bases a 64-bit scan
+    uint64_t names_len = 0; uint32_t max_name = 0; DecRange g1; memset(&g1, 0, sizeof g1);
+    if (n_chunks && one) {
+        g1 = range_of(hs, CHm, n_chunks, n_rows, tb); NamesSize z;
+        const int rc = names_lengths(ctx, &a, g1, &z); if (rc) return rc;
+        names_len = z.bytes; max_name = z.max_name;
+    } else for (size_t i = spans.size(); i-- > 0;) {
+        DecRange g; uint64_t reads = 0; NamesSize z;
+        int rc = span_range(ctx, hs, CHm, hc, spans[i], &g, &reads); if (rc) return rc;
+        if (reads >= 0x7FFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk holds 2 Gi reads or more");
+        ctx->timer.reset();
+        rc = names_lengths(ctx, &a, g, &z); if (rc) return rc;
+        ctx->timer.collect(); sums.add(ctx->timer);
+        names_len += z.bytes; max_name = std::max(max_name, z.max_name);
+    }
+    res->names_len = names_len; res->max_name = max_name;
+    if (query) { HIPCHK(ctx, hipStreamSynchronize(S)); if (spans.empty()) ctx->timer.collect(); else sums.publish(ctx->timer); return RFQ_OK; }
+    if (na->d_names && na->names_cap < names_len) return rfq_fail(ctx, RFQ_E_NOSPACE, "name blob too small: need %llu bytes", (unsigned long long)names_len);
+    NamesOut o; memset(&o, 0, sizeof o);
+    if (na->d_names) o.names = na->d_names; else { HIPCHK(ctx, ctx->names_blob.ensure((size_t)names_len + 64)); o.names = ctx->names_blob.as<uint8_t>(); }
+    if (na->d_name_off) o.off = na->d_name_off; else { HIPCHK(ctx, ctx->names_off.ensure((size_t)(n_rows + 1) * 8)); o.off = ctx->names_off.as<uint64_t>(); }
+    o.end = names_len;
+    if (!n_chunks) { HIPCHK(ctx, hipMemsetAsync(o.off, 0, 8, S)); HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect(); }
+    else if (one) {
+        const int rc = names_write(ctx, &a, g1, o); if (rc) return rc;
+        ctx->timer.collect();
+    } else {
+        for (size_t i = spans.size(); i-- > 0;) {
+            DecRange g; uint64_t reads = 0; NamesSize z;
+            int rc = span_range(ctx, hs, CHm, hc, spans[i], &g, &reads); if (rc) return rc;
+            ctx->timer.reset();
+            rc = names_lengths(ctx, &a, g, &z); if (rc) return rc;
+            rc = names_write(ctx, &a, g, o); if (rc) return rc;
+            ctx->timer.collect(); sums.add(ctx->timer);
+            o.base += z.bytes;
+        }
+        sums.publish(ctx->timer);
+    }
+    res->d_names = o.names; res->d_name_off = o.off;
+    return RFQ_OK;
+}

@@ -18,3 +18,4 @@
 #include "dec/emit_expanded.h"                // text emission of the expanded path (tile emitter k_dec_emit)
 #include "dec/emit_tiles.h"                   // text emission, fused path: k_dec_emit3 (fixed tiles, no output tile)
 #include "dec/rows.h"                         // reads as fixed-stride base / quality rows (rfq_decode_rows): k_dec_rows over the expanded stage
+#include "dec/names.h"                        // the name lines alone (rfq_decode_names): k_dec_namelen, k_dec_names behind the coordinate decoder

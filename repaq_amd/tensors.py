@@ -12,6 +12,17 @@ and back - reads a basecaller, a simulator, a filter or a trimmer holds as tenso
     image = encode_tensors(codec, t["bases"], t["quals"], t["lens"], blob, off)      # uint8 tensor: the .rfq image
     text = rows_to_fastq(codec, t["bases"], t["quals"], t["lens"], blob, off)        # uint8 tensor: the FASTQ text
 
+decode -> filter -> encode, nothing on the host (rfq_decode_names gives the names in pack_names' layout):
+
+    t = decode_tensors(codec, rfq, names=True)                                        # + "names": uint8 blob, "name_off": [n + 1] int64
+    keep = t["lens"] >= 100                                                           # any mask over the rows
+    off, ln = t["name_off"], t["name_off"][1:] - t["name_off"][:-1]
+    new_off = torch.cat([off[:1], ln[keep].cumsum(0)])
+    src = torch.repeat_interleave(off[:-1][keep] - new_off[:-1], ln[keep]) + torch.arange(int(new_off[-1]), device=off.device)
+    image = encode_tensors(codec, t["bases"][keep], t["quals"][keep], t["lens"][keep], t["names"][src], new_off)
+
+The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
+
 This is the only module of the package that imports torch."""
 import ctypes as C
 
@@ -20,9 +31,10 @@ import torch
 from ._capi import SE, PE_TWO_FILES
 
 
-def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offset=33, pad=255):
+def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offset=33, pad=255, names=False):
     """One .rfq image (a uint8 tensor on the codec's device) -> {"bases", "quals", "lens"}: row i = read i of the image in Repaq::decompress order
     (a PE file: rows 2k / 2k + 1 are R1 / R2 of pair k - `bases.view(-1, 2, L)`), padded with `pad` to L = row_len (None: the longest read).
+    names=True adds "names" and "name_off" (decode_names).
     A size query and the decode, both ordered with torch's current stream; the context goes back to its own stream afterwards."""
     assert rfq.dtype == torch.uint8 and rfq.is_cuda and rfq.is_contiguous(), "rfq must be a contiguous uint8 tensor on the GPU"
     n = rfq.numel()
@@ -40,7 +52,26 @@ def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offs
                               d_lens=lens.data_ptr(), lens_cap=rows)
     finally:
         codec.set_stream(None)
-    return {"bases": bases, "quals": quals, "lens": lens}
+    out = {"bases": bases, "quals": quals, "lens": lens}
+    if names:
+        out["names"], out["name_off"] = decode_names(codec, rfq)
+    return out
+
+
+def decode_names(codec, rfq: torch.Tensor):
+    """One .rfq image -> (blob, offsets): the name lines of its reads back to back ('@' included, no line breaks) as a uint8 tensor and their n + 1 int64
+    offsets - the names / name_off of encode_tensors and rows_to_fastq, row i = row i of decode_tensors (rfq_decode_names: the chunk table, the name
+    sections and the coordinate streams are read, none of the bases or qualities).  The text of the strand lines is not carried.  One call with
+    context-owned results, copied into tensors of the caller's; ordered with torch's current stream."""
+    assert rfq.dtype == torch.uint8 and rfq.is_cuda and rfq.is_contiguous(), "rfq must be a contiguous uint8 tensor on the GPU"
+    codec.set_stream(torch.cuda.current_stream(rfq.device).cuda_stream)
+    try:
+        r = codec.decode_names(rfq.data_ptr(), rfq.numel())
+        blob = _own_copy(codec, r.d_names, int(r.names_len), rfq.device)
+        off = _own_copy(codec, r.d_name_off, 8 * (int(r.n_rows) + 1), rfq.device).view(torch.int64)
+        return blob, off
+    finally:
+        codec.set_stream(None)
 
 
 def pack_names(names, device):
