@@ -261,6 +261,47 @@ RFQ_API int rfq_rows_to_text(rfq_ctx* ctx, const rfq_rows_in* rows, int32_t pair
  * file: the first with emit_header = 1, flush_all = 1, the last with final = 1.  A refusal of the rows leaves the encoder unrun. */
 RFQ_API int rfq_encode_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_encode_args* enc, rfq_encode_result* res);
 
+/* The front door of the row interface: FASTQ TEXT in HBM -> per-read rows, lengths and names, without an image in between.  Row i is the i-th record the
+ * reference's reader hands the codec for this text - exactly the records rfq_encode_batch would encode, by the same line index and the same rules: line ends
+ * '\n', '\r' and "\r\n", a single blank line is swallowed, the reader stops for good at the first empty line (input_ended), a trailing partial record is dropped,
+ * RFQ_PE_TWO_FILES stops with the shorter file (rows 2k / 2k + 1 = record k of file 1 / file 2), RFQ_PE_INTERLEAVED gives an even number of rows in text order.
+ * The bytes are the text's own, in their original orientation: a base row in ASCII mode holds the sequence line verbatim (lower case, IUPAC codes and all), in
+ * code mode A C G T N -> 0..4 and any other byte is RFQ_E_DATA (the message names the first such row; what the buffers hold is then unspecified); a quality row
+ * holds the quality characters minus qual_offset (mod 256), of a quality line longer than its sequence line the first `length` characters (what the codec keeps);
+ * positions >= the read's length hold pad_*; lens[i] = bytes of the sequence line.  A quality line SHORTER than its sequence line is RFQ_E_UNPINNED, as in the
+ * encoder.  Name i = the first line of record i, '@' included, without its line break (no '\r' either), in rfq_rows_in's layout: name_off[0] = 0,
+ * name_off[n_rows] = names_len.  The text of the STRAND lines is not carried, like everywhere in the row interface: rows + names re-encode (rfq_encode_rows) to
+ * the text's image only for files whose strand lines are "+".
+ * All five output pointers NULL = a size query: every field of the result is filled, nothing is written (row_len is not looked at).  An output that is NULL is
+ * not produced.  RFQ_E_NOSPACE (nothing written; the message says "need ...") when row_len < max_len or a cap is too small; RFQ_E_ARG for a bad paired /
+ * base_mode, row_len == 0, a d_lens that is not 4-byte or a d_name_off that is not 8-byte aligned, a d_fq2 without RFQ_PE_TWO_FILES.  After any refusal the
+ * context stays usable.
+ * Streaming: one call indexes with 32-bit offsets, so it takes of each stream at most the encoder's slice (3 GiB; RFQ_SLICE_BYTES sets a small one) - what lies
+ * beyond is treated as if final = 0.  consumed1 / consumed2 say where the next call starts, in the caller's bytes (also when the text was normalised); the rows
+ * of consecutive calls, concatenated by the caller, are the one-shot rows.  With final = 0 only whole records are taken (an unterminated last line is not a
+ * line).  n_rows * row_len may exceed 4 GiB.  Synchronous on the context's stream, like rfq_decode_rows. */
+typedef struct {
+    const uint8_t* d_fq1; size_t n1;      /* as rfq_encode_args: any alignment, up to 15 bytes in front may be read */
+    const uint8_t* d_fq2; size_t n2;      /* RFQ_PE_TWO_FILES only */
+    int32_t  paired;                      /* RFQ_SE / RFQ_PE_TWO_FILES / RFQ_PE_INTERLEAVED */
+    int32_t  final;                       /* 1: end of the input (an unterminated last line is a line); 0: whole records only, see consumed */
+    uint64_t file_off1, file_off2;        /* offset of this text in its file: the reader's 1 MiB block rule, as in rfq_encode_args */
+    uint32_t row_len; int32_t base_mode;  /* as rfq_decode_rows_args */
+    uint8_t  qual_offset, pad_base, pad_qual, reserved;
+    uint8_t* d_bases; size_t bases_cap;   /* [n_rows][row_len] or NULL */
+    uint8_t* d_quals; size_t quals_cap;   /* [n_rows][row_len] or NULL */
+    int32_t* d_lens;  size_t lens_cap;    /* [n_rows] (entries) or NULL */
+    uint8_t* d_names; size_t names_cap;   /* blob, any alignment, or NULL */
+    uint64_t* d_name_off; size_t off_cap; /* [n_rows + 1] (entries), 8-byte aligned, or NULL */
+} rfq_text_rows_args;
+typedef struct {
+    uint64_t n_rows, n_bases, names_len;
+    uint32_t max_len, max_name;
+    size_t   consumed1, consumed2;        /* bytes of each stream covered by the rows */
+    int32_t  input_ended, reserved;       /* as rfq_encode_result */
+} rfq_text_rows_result;
+RFQ_API int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* args, rfq_text_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);

@@ -259,6 +259,48 @@ class RfqCodec:
             for p in ptrs:
                 self.dev_free(p)
 
+    # --- the front door: FASTQ text -> rows, lengths and names (rfq_text_rows)
+    def text_rows(self, d_fq1, n1, d_fq2=None, n2=0, paired=SE, final=True, file_off1=0, file_off2=0, row_len=0, codes=False, qual_offset=33,
+                  pad_base=255, pad_qual=255, d_bases=None, bases_cap=0, d_quals=None, quals_cap=0, d_lens=None, lens_cap=0,
+                  d_names=None, names_cap=0, d_name_off=None, off_cap=0):
+        """rfq_text_rows: row i of d_bases / d_quals (n_rows * row_len bytes each) = record i the reference's reader makes of the text(s) - the
+        records encode() would encode -, d_lens n_rows int32 lengths, d_names / d_name_off the name lines and their n_rows + 1 uint64 offsets (the
+        layout rows_to_text / encode_rows take).  No output pointer at all = a size query; an output that is None is not produced.  The bytes are
+        the text's own (nothing is lost that an image would lose); codes: A0 C1 G2 T3 N4, any other base is refused.  Returns TextRowsResult
+        (n_rows, n_bases, names_len, max_len, max_name, consumed1, consumed2, input_ended)."""
+        a = A.TextRowsArgs(d_fq1, n1, d_fq2, n2, paired, 1 if final else 0, file_off1, file_off2, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII,
+                           qual_offset, pad_base, pad_qual, 0, d_bases, bases_cap, d_quals, quals_cap, d_lens, lens_cap, d_names, names_cap, d_name_off, off_cap)
+        r = A.TextRowsResult()
+        self._check(self._L.rfq_text_rows(self._h, C.byref(a), C.byref(r)))
+        return r
+
+    def text_rows_bytes(self, fq1: bytes, fq2: bytes = b"", paired=SE, row_len=None, codes=False, qual_offset=33, pad_base=255, pad_qual=255, final=True, **kw):
+        """host bytes in, numpy arrays out: (result of the call, bases [n, L] uint8, quals [n, L] uint8, lens [n] int32, the list of name lines).
+        row_len=None: the text's longest read (a size query first)."""
+        import numpy as np
+        two = paired == PE_TWO_FILES
+        d1 = self.dev_put(fq1); d2 = self.dev_put(fq2) if two else None
+        bufs = [d1] + ([d2] if two else [])
+        try:
+            src = dict(d_fq2=d2, n2=len(fq2) if two else 0, paired=paired, final=final, **kw)
+            q = self.text_rows(d1, len(fq1), **src)
+            n = int(q.n_rows); L = max(int(q.max_len), 1) if row_len is None else int(row_len); nl = int(q.names_len)
+            ob, oq, ol, on, oo = (self.dev_put(b"\0" * max(k, 1)) for k in (n * L, n * L, 4 * n, nl, 8 * (n + 1)))
+            bufs += [ob, oq, ol, on, oo]
+            r = self.text_rows(d1, len(fq1), row_len=L, codes=codes, qual_offset=qual_offset, pad_base=pad_base, pad_qual=pad_qual,
+                               d_bases=ob, bases_cap=n * L, d_quals=oq, quals_cap=n * L, d_lens=ol, lens_cap=n, d_names=on, names_cap=nl,
+                               d_name_off=oo, off_cap=n + 1, **src)
+            n = int(r.n_rows)
+            B = np.frombuffer(self.dev_get(ob, n * L), dtype=np.uint8).reshape(n, L)
+            Q = np.frombuffer(self.dev_get(oq, n * L), dtype=np.uint8).reshape(n, L)
+            lens = np.frombuffer(self.dev_get(ol, 4 * n), dtype=np.int32)
+            off = np.frombuffer(self.dev_get(oo, 8 * (n + 1)), dtype=np.uint64)
+            blob = self.dev_get(on, int(r.names_len)) if r.names_len else b""
+            return r, B, Q, lens, [blob[int(off[i]):int(off[i + 1])] for i in range(n)]
+        finally:
+            for p in bufs:
+                self.dev_free(p)
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

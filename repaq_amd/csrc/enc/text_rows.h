@@ -1,0 +1,189 @@
+// enc/text_rows.h - FASTQ text -> fixed-stride base / quality rows, read lengths, name lines + offsets (rfq_text_rows): the reverse of enc/rows_text.h
+// Part of rfq_encode_kernels.h (included from there, last; not a stand-alone header).
+#pragma once
+// Row g is read g of the batch in interleaved order (read_loc: RFQ_PE_TWO_FILES rows 2k / 2k + 1 are record k of stream 0 / 1), its four lines are entries
+// 4r .. 4r + 4 of the stream's line table (enc/index.h).  k_text_rows_sizes judges the rows from the line table alone and leaves lengths, name sizes
+// (scanned to offsets by the host's scan_exclusive), maxima and sums; k_text_rows writes base and quality rows, k_text_names the name blob.  The bytes are
+// the text's own: nothing is complemented, folded or dropped.
+#define TR_ERR_EMPTY   (1u << 0)      // an empty line inside a row's record: the reader stops there (first_empty)
+#define TR_ERR_QSHORT  (1u << 1)      // a quality line shorter than its sequence line                             (RFQ_E_UNPINNED)
+#define TR_ERR_BASE    (1u << 2)      // writer, code mode: a base that is not one of A C G T N                    (RFQ_E_DATA)
+// what the host reads back: zeroed per pass, first_empty = bad_row = ~0
+struct TextRowsStat { uint32_t err, max_len, max_name, first_empty; unsigned long long bad_row, n_bases; };
+
+// grid ceil(n_rows / TS_ROWS) x 256 threads, a thread per row and TS_ITER rows per thread.  A workgroup ends in three atomics on the same three words (longest
+// read, longest name, bases) - eight times fewer of them than with a workgroup per 256 rows - and, only where a row is at fault, one atomicOr of the error bits
+// per wave and one atomicMin of the row per offending thread (rare: both end the call or the rows).  lens[g] = bases of row g, nsz[g] = bytes of its name line
+// (64-bit: scanned in place to the offsets).
+#define TS_ITER 8u
+#define TS_ROWS (256u * TS_ITER)
+__global__ void __launch_bounds__(256) k_text_rows_sizes(Text T, uint32_t n_rows, int32_t* __restrict__ lens, uint64_t* __restrict__ nsz, TextRowsStat* __restrict__ st) {
+    __shared__ uint32_t s_ml[4], s_mn[4]; __shared__ unsigned long long s_nb[4];
+    uint32_t ml = 0, mn = 0, err = 0; unsigned long long nb = 0;
+    for (uint32_t it = 0; it < TS_ITER; it++) {
+        const uint64_t g64 = (uint64_t)blockIdx.x * TS_ROWS + it * 256u + threadIdx.x;
+        if (g64 >= n_rows) break;
+        const uint32_t g = (uint32_t)g64;
+        int s; uint32_t r; read_loc(T, g, s, r); const uint32_t* p = t_lo(T, s) + 4 * (size_t)r;
+        const uint32_t p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3], p4 = p[4];
+        const uint32_t nl = p1 - 1 - p0, sl = p2 - 1 - p1, tl = p3 - 1 - p2, ql = p4 - 1 - p3;
+        if (nl == 0 || sl == 0 || tl == 0 || ql == 0) { err |= TR_ERR_EMPTY; atomicMin(&st->first_empty, g); }
+        if (ql < sl) { err |= TR_ERR_QSHORT; atomicMin(&st->bad_row, (unsigned long long)g); }
+        lens[g] = (int32_t)sl; nsz[g] = nl;
+        if (sl > ml) ml = sl; if (nl > mn) mn = nl; nb += sl;
+    }
+    ml = wave_max(ml); mn = wave_max(mn); const uint32_t e = wave_or(err); nb = wave_sum<unsigned long long>(nb);
+    if (lane_id() == 0) { s_ml[wave_id()] = ml; s_mn[wave_id()] = mn; s_nb[wave_id()] = nb; if (e) atomicOr(&st->err, e); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t a = s_ml[0], b = s_mn[0]; unsigned long long c = s_nb[0];
+        for (uint32_t i = 1; i < 4u; i++) { if (s_ml[i] > a) a = s_ml[i]; if (s_mn[i] > b) b = s_mn[i]; c += s_nb[i]; }
+        if (a) atomicMax(&st->max_len, a);
+        if (b) atomicMax(&st->max_name, b);
+        if (c) atomicAdd(&st->n_bases, c);
+    }
+}
+
+struct TextRowsOut {
+    uint8_t* bases; uint8_t* quals;                   // [n_rows][row_len]; null = not wanted
+    uint64_t row_len; uint32_t n_rows;
+    uint32_t codes;                                   // bases as A0 C1 G2 T3 N4 instead of the text's bytes
+    uint32_t qoff4, pad_b4, pad_q4;                   // quality offset / pad bytes, repeated in the four bytes of a word
+    uint32_t vec;                                     // row_len % 16 == 0 and both row buffers 16-byte aligned: one 16-byte store per group
+    uint32_t per;                                     // rows of a workgroup
+};
+// x - y in each byte, mod 256 (dec/rows.h sub_bytes, which this translation unit does not see)
+__device__ __forceinline__ uint32_t tr_sub_bytes(uint32_t x, uint32_t y) { return ((x | 0x80808080u) - (y & 0x7F7F7F7Fu)) ^ ((x ^ ~y) & 0x80808080u); }
+// A C G T N -> 0 1 2 3 4 and the test in one go: bits 1-3 of the byte (A 0, C 1, T 2, G 3, N 7) index an 8-entry table whose other entries are 7; the code
+// looked up in the table of ascii4_of_code (7 -> 0x00) gives the byte back exactly when it was one of the five.  bad: non-zero bytes = not A C G T N
+__device__ __forceinline__ uint32_t tr_code4(uint32_t w, uint32_t& bad) {
+    const uint32_t c = __builtin_amdgcn_perm(0x04070707u, 0x02030100u, (w >> 1) & 0x07070707u);
+    bad |= ascii4_of_code(c) ^ w;
+    return c;
+}
+// the low n bytes (n <= 4 counts as all) of a word as a mask
+__device__ __forceinline__ uint32_t tr_low_bytes(int n) { return n >= 4 ? 0xFFFFFFFFu : (n <= 0 ? 0u : (1u << (8 * n)) - 1u); }
+// grid ceil(n_rows / per) x 256 threads.  The work follows the OUTPUT: a workgroup owns `per` consecutive rows, a thread one 16-byte group [k0, k0 + 16) of one
+// row at a time, consecutive threads consecutive groups of consecutive rows (k_dec_rows' order: with row_len % 16 == 0 a wave's stores are one contiguous span of
+// whole groups).  A group that holds bases is ONE 16-byte load from the text at the text's own alignment per source - also the read's last, partial group wherever
+// 16 bytes from there still lie inside the stream (what follows the line is masked off in registers); only at the very end of a stream is it read byte by byte.
+// The tail of a read and the pad are merged in registers, so every group of the output is stored once.  No LDS.
+__global__ void __launch_bounds__(256) k_text_rows(Text T, TextRowsOut o, TextRowsStat* __restrict__ st) {
+    const uint32_t rs = blockIdx.x * o.per;
+    if (rs >= o.n_rows) return;
+    const uint32_t nr = (o.n_rows - rs < o.per) ? o.n_rows - rs : o.per;
+    const uint32_t G = (uint32_t)((o.row_len + 15u) / 16u);                  // groups per row
+    const uint32_t sj = 256u / G, sk = 256u % G;                             // one step of 256 groups: sj rows and sk groups further
+    uint32_t j = threadIdx.x / G, k = threadIdx.x % G;
+    uint32_t bad = 0; unsigned long long bad_row = ~0ull;
+    while (j < nr) {
+        const uint32_t g = rs + j; int s; uint32_t r; read_loc(T, g, s, r);
+        const uint32_t* p = t_lo(T, s) + 4 * (size_t)r;
+        const uint32_t p1 = p[1], p2 = p[2], p3 = p[3], len = p2 - 1 - p1, n = t_n(T, s);
+        const uint8_t* const fq = s ? T.fq[1] : T.fq[0];
+        const uint64_t k0 = 16ull * k;
+        uint32_t wb[4] = { o.pad_b4, o.pad_b4, o.pad_b4, o.pad_b4 }, wq[4] = { o.pad_q4, o.pad_q4, o.pad_q4, o.pad_q4 };
+        if (k0 < len) {
+            const uint32_t at = (uint32_t)k0, have = len - at < 16u ? len - at : 16u;        // bytes of the read in this group
+            uint32_t b[4] = { 0, 0, 0, 0 }, q[4] = { 0, 0, 0, 0 };
+            // (the quality line is at least as long as the sequence line - the sizes kernel saw to it - and lies behind it: its 16 bytes decide)
+            if ((uint64_t)p3 + at + 16u <= n) {
+                if (o.bases) rt_ld16(fq + p1 + at, false, b);
+                if (o.quals) rt_ld16(fq + p3 + at, false, q);
+            } else {
+                for (uint32_t i = 0; i < have; i++) {
+                    const uint32_t sh = 8u * (i & 3u);
+                    if (o.bases) b[i >> 2] |= (uint32_t)fq[p1 + at + i] << sh;
+                    if (o.quals) q[i >> 2] |= (uint32_t)fq[p3 + at + i] << sh;
+                }
+            }
+            uint32_t bb = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t m = tr_low_bytes((int)have - 4 * i);
+                uint32_t x = b[i];
+                if (o.codes) x = tr_code4((x & m) | (0x41414141u & ~m), bb);                     // (bytes behind the read count as 'A': never an offender)
+                wb[i] = (x & m) | (o.pad_b4 & ~m);
+                wq[i] = (tr_sub_bytes(q[i], o.qoff4) & m) | (o.pad_q4 & ~m);
+            }
+            if (bb && o.bases) { bad |= TR_ERR_BASE; if (bad_row == ~0ull) bad_row = g; }
+        }
+        const uint64_t dst = (uint64_t)g * o.row_len + k0;
+        if (o.vec) {
+            if (o.bases) *(uint4*)(o.bases + dst) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+            if (o.quals) *(uint4*)(o.quals + dst) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
+        } else {
+            const uint32_t cnt = o.row_len - k0 < 16u ? (uint32_t)(o.row_len - k0) : 16u;
+            for (uint32_t i = 0; i < cnt; i++) {
+                if (o.bases) o.bases[dst + i] = (uint8_t)(wb[i >> 2] >> (8u * (i & 3u)));
+                if (o.quals) o.quals[dst + i] = (uint8_t)(wq[i >> 2] >> (8u * (i & 3u)));
+            }
+        }
+        j += sj; k += sk; if (k >= G) { k -= G; j++; }
+    }
+    if (bad) { atomicOr(&st->err, bad); atomicMin(&st->bad_row, bad_row); }
+}
+
+// ---- names: the first line of every row, back to back
+#define TN_TPB 256
+#define TN_TILE (TN_TPB * 16u)                // blob bytes of a workgroup: 4 KiB
+#define TN_RECS (TN_TILE + 1u)                // a name has a byte or more (an empty line ends the rows): those that start inside a tile, the end of the last
+__device__ __forceinline__ const uint8_t* tn_name(const Text& T, uint32_t g) {
+    int s; uint32_t r; read_loc(T, g, s, r);
+    return (s ? T.fq[1] : T.fq[0]) + t_lo(T, s)[4 * (size_t)r];
+}
+// grid ceil((names_len + shift) / TN_TILE) x 256 threads.  The work follows the BLOB: positions count from the 16-byte boundary at or below it (shift = blob & 15),
+// a workgroup owns TN_TILE of them and a thread one aligned 16-byte group.  Thread 0 finds the name the tile starts in (binary search in off[], the exclusive scan
+// of the name sizes, off[n_rows] = names_len); where the names behind it start, relative to the tile, goes to LDS and every thread finds its group's name there.  A group inside
+// one name is one 16-byte load at the text's own alignment and one aligned store; a group that holds a boundary is put together byte by byte in registers; the
+// blob's first and last group, where they are not whole, are stored byte by byte.
+__global__ void __launch_bounds__(TN_TPB) k_text_names(Text T, const uint64_t* __restrict__ off, uint32_t n_rows, uint8_t* __restrict__ blob, uint64_t names_len) {
+    __shared__ uint32_t s_rel[TN_RECS + 1]; __shared__ uint32_t s_r0, s_cnt;
+    const uint32_t shift = (uint32_t)((uintptr_t)blob & 15u); uint8_t* const nb = blob - shift;
+    const uint64_t A0 = (uint64_t)blockIdx.x * TN_TILE;                      // (position from nb)
+    const uint64_t q0 = A0 > shift ? A0 - shift : 0ull;                      // the tile's first blob byte
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = n_rows;                                         // off[lo] <= q0 < off[hi]
+        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] <= q0) lo = mid; else hi = mid; }
+        s_r0 = lo;
+        // ... and the first name that starts at or behind the tile's end (n_rows: none does - off[n_rows] = names_len ends the last one): the entries in between are
+        // all a group of this tile can ask for (names of 53 bytes: 80 of the 4,098 entries)
+        const uint64_t qt = A0 + TN_TILE - shift;
+        uint32_t hi2 = n_rows;                                                // off[lo] < qt <= off[hi2], or hi2 = n_rows
+        while (hi2 - lo > 1) { const uint32_t mid = lo + (hi2 - lo) / 2; if (off[mid] < qt) lo = mid; else hi2 = mid; }
+        s_cnt = hi2 - s_r0 < TN_RECS ? hi2 - s_r0 : TN_RECS;
+    }
+    __syncthreads();
+    const uint32_t r0 = s_r0, cnt = s_cnt;
+    // s_rel[k]: start of name r0 + k, in blob bytes from q0 (name r0 itself starts at or before q0: 0); beyond the tile or the rows: ~0
+    for (uint32_t k = threadIdx.x; k <= cnt; k += TN_TPB) {
+        uint32_t v = 0xFFFFFFFFu;
+        if (k == 0) v = 0;
+        else if ((uint64_t)r0 + k <= n_rows) { const uint64_t d = off[r0 + k] - q0; if (d < 0xFFFFFFFFull) v = (uint32_t)d; }
+        s_rel[k] = v;
+    }
+    __syncthreads();
+    const uint64_t A = A0 + 16ull * threadIdx.x;
+    if (A >= names_len + shift) return;
+    const uint64_t qa = A > shift ? A - shift : 0ull, qe = (A + 16u - shift < names_len) ? A + 16u - shift : names_len;   // this group's blob bytes [qa, qe)
+    const uint32_t rel = (uint32_t)(qa - q0);
+    uint32_t lo = 0, hi = cnt;                                                // s_rel[lo] <= rel < s_rel[hi]: name r0 + cnt starts at or behind the tile's end
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s_rel[mid] <= rel) lo = mid; else hi = mid; }
+    uint32_t g = r0 + lo; uint64_t beg = off[g], end = off[g + 1];
+    const bool whole = qe - qa == 16u;
+    if (whole && qe <= end) {
+        uint32_t w[4]; rt_ld16(tn_name(T, g) + (qa - beg), false, w);
+        *(uint4*)(nb + A) = make_uint4(w[0], w[1], w[2], w[3]);
+        return;
+    }
+    unsigned long long h0 = 0, h1 = 0; const uint32_t nby = (uint32_t)(qe - qa);
+    const uint8_t* src = tn_name(T, g);
+    for (uint32_t i = 0; i < nby; i++) {
+        const uint64_t q = qa + i;
+        while (q >= end) { g++; beg = end; end = off[g + 1]; src = tn_name(T, g); }
+        const unsigned long long c = src[q - beg];
+        if (i < 8u) h0 |= c << (8u * i); else h1 |= c << (8u * (i - 8u));
+    }
+    if (whole) *(uint4*)(nb + A) = make_uint4((uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32));
+    else for (uint32_t i = 0; i < nby; i++) blob[qa + i] = (uint8_t)(i < 8u ? h0 >> (8u * i) : h1 >> (8u * (i - 8u)));
+}

@@ -785,26 +785,42 @@ static int encode_settled(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_res
     return rfq_fail(ctx, RFQ_E_HIP, "internal: the stream arenas did not settle");
 }
 
-// One call's worth of text (< 4 GiB per stream; the stream pointers may sit at any byte address: they are rounded down to 16 bytes and the
-// bytes in front are skipped by the indexer)
-static int encode_one(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result* res, bool scan_only) {   // (every attempt starts from a cleared *res)
-    rfq_encode_args al = *a; uint32_t skip[2] = { 0, 0 };
+// ---- the front end every call on FASTQ text shares (rfq_encode_batch / rfq_scan_batch: encode_one, encode_or_scan; rfq_text_rows)
+// The stream pointers may sit at any byte address: they are rounded down to 16 bytes and the bytes in front are skipped by the indexer (skip[s] < 16)
+static void align_streams(const rfq_encode_args* a, rfq_encode_args& al, uint32_t (&skip)[2]) {
+    al = *a; skip[0] = skip[1] = 0;
     if (a->n1 && a->d_fq1) { skip[0] = (uint32_t)((uintptr_t)a->d_fq1 & 15u); al.d_fq1 = a->d_fq1 - skip[0]; al.n1 = a->n1 + skip[0];
             al.file_off1 = a->file_off1 - skip[0]; }
     if (a->paired == RFQ_PE_TWO_FILES && a->n2 && a->d_fq2) { skip[1] = (uint32_t)((uintptr_t)a->d_fq2 & 15u); al.d_fq2 = a->d_fq2 - skip[1]; al.n2 = a->n2 + skip[1];
             al.file_off2 = a->file_off2 - skip[1]; }
-    int rc = encode_settled(ctx, &al, res, nullptr, scan_only, skip);
-    if (rc != RFQ_NEED_NORM) return rc;
-    // slow path: '\r' line ends or blank lines (src/fastqreader.cpp:94-196)
-    NormMap nm; memset(&nm, 0, sizeof nm);
-    rfq_encode_args a2 = *a;
-    const uint8_t* p; size_t pn; const uint32_t noskip[2] = { 0, 0 };
+}
+// slow path: '\r' line ends or blank lines (src/fastqreader.cpp:94-196): the call's stream(s) rewritten by normalize_stream, a2 = the call on the normalised text
+static int normalize_streams(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_args& a2, NormMap& nm) {
+    memset(&nm, 0, sizeof nm); a2 = *a;
+    const uint8_t* p; size_t pn; int rc;
     if ((rc = normalize_stream(ctx, a->d_fq1, a->n1, a->file_off1, a->final != 0, 0, nm, &p, &pn)) != RFQ_OK) return rc;
     a2.d_fq1 = p; a2.n1 = pn;
     if (a->paired == RFQ_PE_TWO_FILES) {
         if ((rc = normalize_stream(ctx, a->d_fq2, a->n2, a->file_off2, a->final != 0, 1, nm, &p, &pn)) != RFQ_OK) return rc;
         a2.d_fq2 = p; a2.n2 = pn;
     }
+    return RFQ_OK;
+}
+// what one call indexes of a stream (offsets inside one call are 32-bit): streams below `lim` bytes whole, else slices of `slice` bytes
+// (RFQ_SLICE_BYTES: test aid - slices of that many bytes, so that the slicing logic runs on small inputs)
+#define RFQ_SLICE ((size_t)3 << 30)
+static void slice_limits(const rfq_ctx* ctx, size_t& slice, size_t& lim) {
+    const size_t slice_env = ctx->opt.slice_bytes;
+    slice = slice_env ? slice_env : RFQ_SLICE; lim = slice_env ? slice_env : 0xFFFFFFF0ull - 16;
+}
+// One call's worth of text (< 4 GiB per stream)
+static int encode_one(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result* res, bool scan_only) {   // (every attempt starts from a cleared *res)
+    rfq_encode_args al; uint32_t skip[2];
+    align_streams(a, al, skip);
+    int rc = encode_settled(ctx, &al, res, nullptr, scan_only, skip);
+    if (rc != RFQ_NEED_NORM) return rc;
+    NormMap nm; rfq_encode_args a2; const uint32_t noskip[2] = { 0, 0 };
+    if ((rc = normalize_streams(ctx, a, a2, nm)) != RFQ_OK) return rc;
     rc = encode_settled(ctx, &a2, res, &nm, scan_only, noskip);
     return rc == RFQ_NEED_NORM ? rfq_fail(ctx, RFQ_E_HIP, "internal: normalised text still needs normalisation") : rc;
 }
@@ -812,16 +828,14 @@ static int encode_one(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result*
 // Texts of 4 GiB and more per stream (offsets inside one call are 32-bit): the call is cut into slices of RFQ_SLICE bytes per stream.  A slice
 // that is not the last one stops at its last full chunk (final = 0) and the next slice starts right behind the bytes it consumed - in
 // place, nothing is copied.  Chunk images are appended in order, so the result is the one-shot image.
-#define RFQ_SLICE ((size_t)3 << 30)
 static int encode_or_scan(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result* res, bool scan_only) {
     if (!ctx || !a || !res) return RFQ_E_ARG;
     memset(res, 0, sizeof *res);
     ctx->err.clear();
     if (a->paired < 0 || a->paired > 2) return rfq_fail(ctx, RFQ_E_ARG, "paired must be RFQ_SE, RFQ_PE_TWO_FILES or RFQ_PE_INTERLEAVED");
     const bool two = a->paired == RFQ_PE_TWO_FILES;
-    // (RFQ_SLICE_BYTES: test aid - slices of that many bytes, so that the slicing logic runs on small inputs)
-    const size_t slice_env = ctx->opt.slice_bytes;
-    const size_t slice = slice_env ? slice_env : RFQ_SLICE, lim = slice_env ? slice_env : 0xFFFFFFF0ull - 16;
+    const size_t slice_env = ctx->opt.slice_bytes; size_t slice, lim;
+    slice_limits(ctx, slice, lim);
     if (a->n1 < lim && (!two || a->n2 < lim)) return encode_one(ctx, a, res, scan_only);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t pos1 = 0, pos2 = 0, written = 0; bool first = true;
@@ -993,4 +1007,144 @@ extern "C" int rfq_encode_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_en
     rc = encode_or_scan(ctx, &a, res, false);
     sums.add(ctx->timer); sums.publish(ctx->timer);                         // the rows stages, then the encoder's own (add merges by name: the two sets of names stay disjoint)
     return rc;
+}
+// ---------------------------------------------------------------- FASTQ text -> rows, lengths, names: rfq_text_rows of include/rfq_hip.h
+// The encoder's own front end - EncBatch, enc_index (without the lazy guess: the totals are needed on the host anyway), normalize_stream on RFQ_NEED_NORM exactly as
+// encode_one does - then the sizes kernel, ONE scan of the name sizes and ONE read-back (totals, maxima, error bits, the first bad row, the first empty line, where the
+// rows end in each stream); the host decides and launches the writers.  An empty line on normalised text is where the reader stops for good: the sizes pass runs once
+// more over the rows in front of it.
+struct TextRowsAttempt { uint64_t n_rows, n_bases, names_len; uint32_t max_len, max_name; size_t consumed[2]; bool ended; };
+static int text_rows_impl(rfq_ctx* ctx, const rfq_text_rows_args* a, const rfq_encode_args* ea, const NormMap* nm, const uint32_t* skip, bool size_query, TextRowsAttempt* out) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; int rc;
+    EncBatch b = {}; EncCut cut = {};
+    b.a = ea; b.nm = nm; b.skip = skip; b.unit_cap = ~0u; b.fin = ea->final != 0; b.is_pe = ea->paired != RFQ_SE;
+    const int nstreams = b.nstreams = ea->paired == RFQ_PE_TWO_FILES ? 2 : 1;
+    b.fq[0] = ea->d_fq1; b.fq[1] = nstreams == 2 ? ea->d_fq2 : nullptr;
+    b.nbytes[0] = ea->n1 > skip[0] ? ea->n1 : 0; b.nbytes[1] = nstreams == 2 ? (ea->n2 > skip[1] ? ea->n2 : 0) : 0;
+    for (int s = 0; s < nstreams; s++) {                                    // (encode_impl's guards: the caller's slice keeps a stream below 4 GiB, the index cannot go without it)
+        if (b.nbytes[s] >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a FASTQ stream of one call must be < 4 GiB (got %zu bytes)", b.nbytes[s]);
+        if (b.nbytes[s] && !b.fq[s]) return rfq_fail(ctx, RFQ_E_ARG, "null FASTQ pointer");
+        if (b.nbytes[s] && (((uintptr_t)b.fq[s]) & 15u)) return rfq_fail(ctx, RFQ_E_HIP, "internal: FASTQ stream not rounded down to 16 bytes");
+    }
+    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // (a marker, not a phase: the text has '\r' line ends or blank lines and was rewritten by the normaliser - tests look for it)
+    if (nm) { ctx->timer.begin("normalise", S); ctx->timer.end(S); }
+    HIPCHK(ctx, table(ctx->d_status, sizeof(DevStatus), b.dst));
+    HIPCHK(ctx, fresh_status(ctx, b));
+    ctx->lazy_block = true;                                                 // (enc_index takes the flag down again: this index reads its totals back)
+    if ((rc = enc_index(ctx, b, cut)) != RFQ_OK) return rc;
+    uint32_t n_units = ea->paired == RFQ_SE ? cut.nrec[0] : (ea->paired == RFQ_PE_TWO_FILES ? std::min(cut.nrec[0], cut.nrec[1]) : cut.nrec[0] / 2);
+    memset(out, 0, sizeof *out);
+    TextRowsStat hs; memset(&hs, 0, sizeof hs); uint64_t names_len = 0; uint32_t cons[2] = { 0, 0 };
+    HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(TextRowsStat)));
+    TextRowsStat* dst = ctx->rows_stat.as<TextRowsStat>();
+    int32_t* lens = nullptr; uint64_t* off = nullptr;
+    for (;;) {
+        const uint32_t n_rows = n_units * b.T.upr; b.T.n_reads = n_rows;
+        if (n_rows == 0) break;
+        ctx->timer.begin("text_rows:sizes", S);
+        HIPCHK(ctx, table(B[B_LEN], ((size_t)n_rows + 2) * 4, lens)); HIPCHK(ctx, table(B[B_P], ((size_t)n_rows + 2) * 8, off));
+        HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)n_rows / SCAN_TILE + 2) * 16)));
+        HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(TextRowsStat), S));
+        HIPCHK(ctx, hipMemsetAsync(&dst->first_empty, 0xFF, sizeof dst->first_empty, S)); HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+        hipLaunchKernelGGL(k_text_rows_sizes, dim3((n_rows + TS_ROWS - 1u) / TS_ROWS), dim3(256), 0, S, b.T, n_rows, lens, off, dst);
+        KCHK(ctx, "k_text_rows_sizes");
+        scan_exclusive<uint64_t>(S, off, off, n_rows, B[B_SCANTMP].as<uint64_t>(), 1);
+        KCHK(ctx, "scan_exclusive");
+        ctx->timer.end(S);
+        HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+        HIPCHK(ctx, ctx->fetch(&names_len, off + n_rows, 8, S));
+        for (int s = 0; s < nstreams; s++) {                                // where the rows end in each stream (enc_verdict's rule)
+            const uint32_t recs = ea->paired == RFQ_PE_TWO_FILES ? n_units : n_rows;
+            if (nm) HIPCHK(ctx, ctx->fetch(&cons[s], nm->onx[s] + 4 * (size_t)recs - 1, 4, S));
+            else HIPCHK(ctx, ctx->fetch(&cons[s], b.T.lo[s] + 4 * (size_t)recs, 4, S));
+        }
+        HIPCHK(ctx, ctx->fetch_sync(S));
+        if (!(hs.err & TR_ERR_EMPTY)) break;
+        // "\n\n" is a swallowed blank line, not an empty one: classify the text properly first.  On normalised text an empty line is where
+        // FastqReader::read returns NULL (src/fastqreader.cpp:180-191): the record and everything after it are never read.
+        if (!nm) return RFQ_NEED_NORM;
+        n_units = hs.first_empty / b.T.upr; out->ended = true;
+        memset(&hs, 0, sizeof hs); names_len = 0; cons[0] = cons[1] = 0;
+    }
+    const uint64_t n_rows = (uint64_t)n_units * b.T.upr;
+    if (hs.err & TR_ERR_QSHORT) return rfq_fail(ctx, RFQ_E_UNPINNED, "a quality line is shorter than its sequence line (the reference reads past the string: undefined)");
+    out->n_rows = n_rows; out->n_bases = hs.n_bases; out->names_len = names_len; out->max_len = hs.max_len; out->max_name = hs.max_name;
+    for (int s = 0; s < nstreams; s++) out->consumed[s] = n_rows ? (size_t)consumed_of(b, s, cons[s]) : 0;
+    if (size_query) { ctx->timer.collect(); return RFQ_OK; }
+    {   // room for everything asked for, or nothing is written
+        const unsigned long long rowb = (unsigned long long)n_rows * a->row_len;
+        if ((n_rows && a->row_len < hs.max_len) || (a->d_bases && a->bases_cap < rowb) || (a->d_quals && a->quals_cap < rowb) || (a->d_lens && a->lens_cap < n_rows) ||
+            (a->d_names && a->names_cap < names_len) || (a->d_name_off && a->off_cap < n_rows + 1))
+            return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need row_len >= %u, %llu bytes per row buffer (at that row_len: %llu), %llu lens, %llu name bytes, %llu offsets",
+                            hs.max_len, rowb, (unsigned long long)n_rows * std::max(a->row_len, hs.max_len), (unsigned long long)n_rows, (unsigned long long)names_len,
+                            (unsigned long long)n_rows + 1);
+    }
+    if (n_rows == 0) {
+        if (a->d_name_off) HIPCHK(ctx, hipMemsetAsync(a->d_name_off, 0, 8, S));
+        HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect();
+        return RFQ_OK;
+    }
+    ctx->timer.begin("text_rows:rows", S);
+    if (a->d_lens) HIPCHK(ctx, hipMemcpyAsync(a->d_lens, lens, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, S));
+    if (a->d_bases || a->d_quals) {
+        TextRowsOut o; memset(&o, 0, sizeof o);
+        o.bases = a->d_bases; o.quals = a->d_quals; o.row_len = a->row_len; o.n_rows = (uint32_t)n_rows; o.codes = a->base_mode == RFQ_ROWS_CODE ? 1u : 0u;
+        o.qoff4 = a->qual_offset * 0x01010101u; o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
+        o.vec = (a->row_len % 16u == 0 && !(((uintptr_t)a->d_bases | (uintptr_t)a->d_quals) & 15u)) ? 1u : 0u;
+        const uint32_t G = (a->row_len + 15u) / 16u;
+        o.per = std::max(1u, 1024u / G);                                    // about four groups per thread
+        hipLaunchKernelGGL(k_text_rows, dim3((uint32_t)((n_rows + o.per - 1) / o.per)), dim3(256), 0, S, b.T, o, dst);
+        KCHK(ctx, "k_text_rows");
+    }
+    ctx->timer.end(S);
+    ctx->timer.begin("text_rows:names", S);
+    if (a->d_name_off) HIPCHK(ctx, hipMemcpyAsync(a->d_name_off, off, (size_t)(n_rows + 1) * 8, hipMemcpyDeviceToDevice, S));
+    if (a->d_names && names_len) {
+        const uint64_t span = names_len + ((uintptr_t)a->d_names & 15u), blocks = (span + TN_TILE - 1) / TN_TILE;
+        if (blocks > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "a name blob of %llu bytes is too large for one call", (unsigned long long)names_len);
+        hipLaunchKernelGGL(k_text_names, dim3((uint32_t)blocks), dim3(TN_TPB), 0, S, b.T, (const uint64_t*)off, (uint32_t)n_rows, a->d_names, names_len);
+        KCHK(ctx, "k_text_names");
+    }
+    ctx->timer.end(S);
+    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    ctx->timer.collect();
+    if (hs.err & TR_ERR_BASE) return rfq_fail(ctx, RFQ_E_DATA, "a base that is not one of A C G T N cannot be a code (first such row: %llu)", (unsigned long long)hs.bad_row);
+    return RFQ_OK;
+}
+extern "C" int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* a, rfq_text_rows_result* res) {
+    if (!ctx || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    if (a->paired < 0 || a->paired > 2) return rfq_fail(ctx, RFQ_E_ARG, "paired must be RFQ_SE, RFQ_PE_TWO_FILES or RFQ_PE_INTERLEAVED");
+    const bool two = a->paired == RFQ_PE_TWO_FILES;
+    if (!two && a->d_fq2) return rfq_fail(ctx, RFQ_E_ARG, "d_fq2 is for RFQ_PE_TWO_FILES");
+    const bool size_query = !a->d_bases && !a->d_quals && !a->d_lens && !a->d_names && !a->d_name_off;
+    if (!size_query && a->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be >= 1");
+    if (a->base_mode != RFQ_ROWS_ASCII && a->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "base_mode must be RFQ_ROWS_ASCII or RFQ_ROWS_CODE");
+    if (((uintptr_t)a->d_lens & 3u) || ((uintptr_t)a->d_name_off & 7u)) return rfq_fail(ctx, RFQ_E_ARG, "d_lens must be 4-byte and d_name_off 8-byte aligned");
+    // One call indexes with 32-bit offsets: of each stream at most the encoder's slice; what lies beyond it is the next call's (this one is then not final)
+    size_t slice, lim; slice_limits(ctx, slice, lim);
+    rfq_encode_args ea; memset(&ea, 0, sizeof ea);
+    ea.paired = a->paired; ea.chunk_bases = 1; ea.final = a->final ? 1 : 0;
+    ea.d_fq1 = a->d_fq1; ea.n1 = a->n1; ea.file_off1 = a->file_off1;
+    if (two) { ea.d_fq2 = a->d_fq2; ea.n2 = a->n2; ea.file_off2 = a->file_off2; }
+    if (ea.n1 >= lim) { ea.n1 = slice; ea.final = 0; }
+    if (two && ea.n2 >= lim) { ea.n2 = slice; ea.final = 0; }
+    rfq_encode_args al; uint32_t skip[2];
+    align_streams(&ea, al, skip);
+    TextRowsAttempt t;
+    int rc = text_rows_impl(ctx, a, &al, nullptr, skip, size_query, &t);
+    if (rc == RFQ_NEED_NORM) {
+        NormMap nm; rfq_encode_args a2; const uint32_t noskip[2] = { 0, 0 };
+        if ((rc = normalize_streams(ctx, &ea, a2, nm)) != RFQ_OK) return rc;
+        rc = text_rows_impl(ctx, a, &a2, &nm, noskip, size_query, &t);
+        if (rc == RFQ_NEED_NORM) return rfq_fail(ctx, RFQ_E_HIP, "internal: normalised text still needs normalisation");
+    }
+    if (rc != RFQ_OK) return rc;
+    res->n_rows = t.n_rows; res->n_bases = t.n_bases; res->names_len = t.names_len; res->max_len = t.max_len; res->max_name = t.max_name;
+    res->consumed1 = t.consumed[0]; res->consumed2 = two ? t.consumed[1] : 0; res->input_ended = t.ended ? 1 : 0;
+    return RFQ_OK;
 }

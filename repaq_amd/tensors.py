@@ -21,6 +21,12 @@ decode -> filter -> encode, nothing on the host (rfq_decode_names gives the name
     src = torch.repeat_interleave(off[:-1][keep] - new_off[:-1], ln[keep]) + torch.arange(int(new_off[-1]), device=off.device)
     image = encode_tensors(codec, t["bases"][keep], t["quals"][keep], t["lens"][keep], t["names"][src], new_off)
 
+fastq -> filter -> encode, the same without an image in front (rfq_text_rows: the text's own bytes, nothing an image would lose is lost):
+
+    fq = torch.from_file("x.fastq", size=n, dtype=torch.uint8).cuda()
+    t = fastq_to_tensors(codec, fq)                                                   # "bases", "quals", "lens", "names", "name_off", "consumed"
+    keep = t["lens"] >= 100                                                           # ... and on as above
+
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
 
 This is the only module of the package that imports torch."""
@@ -55,6 +61,41 @@ def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offs
     out = {"bases": bases, "quals": quals, "lens": lens}
     if names:
         out["names"], out["name_off"] = decode_names(codec, rfq)
+    return out
+
+
+def fastq_to_tensors(codec, fq1: torch.Tensor, fq2: torch.Tensor = None, paired=SE, row_len=None, codes=True, qual_offset=33, pad=255, names=True, final=True):
+    """FASTQ text (uint8 tensors on the codec's device; fq2 with PE_TWO_FILES) -> {"bases", "quals", "lens", "names", "name_off", "consumed"}: row i = the
+    i-th record the reference's reader makes of the text - the records encode() would take; two files: rows 2k / 2k + 1 are record k of fq1 / fq2 -,
+    padded with `pad` to L = row_len (None: the longest read).  codes: A0 C1 G2 T3 N4 (any other base is refused; codes=False keeps the text's bytes,
+    lower case and IUPAC included).  names=False leaves "names" / "name_off" out.  "consumed": (bytes of fq1, bytes of fq2) the rows cover - with
+    final=False, or a text beyond one call's slice, the next call starts there.  A size query and one call, both ordered with torch's current stream;
+    the context goes back to its own stream afterwards."""
+    two = paired == PE_TWO_FILES
+    for t in (fq1,) + ((fq2,) if two else ()):
+        assert t is not None and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous(), "fq1 / fq2 must be contiguous uint8 tensors on the GPU"
+    dev = fq1.device
+    src = dict(d_fq2=fq2.data_ptr() if two else None, n2=fq2.numel() if two else 0, paired=paired, final=final)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        q = codec.text_rows(fq1.data_ptr(), fq1.numel(), **src)
+        L = max(int(q.max_len), 1) if row_len is None else int(row_len)
+        rows, nl = int(q.n_rows), int(q.names_len)
+        bases = torch.empty((rows, L), dtype=torch.uint8, device=dev)
+        quals = torch.empty((rows, L), dtype=torch.uint8, device=dev)
+        lens = torch.empty((rows,), dtype=torch.int32, device=dev)
+        blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if names else None
+        off = torch.zeros((rows + 1,), dtype=torch.int64, device=dev) if names else None
+        if rows:
+            codec.text_rows(fq1.data_ptr(), fq1.numel(), row_len=L, codes=codes, qual_offset=qual_offset, pad_base=pad, pad_qual=pad,
+                            d_bases=bases.data_ptr(), bases_cap=rows * L, d_quals=quals.data_ptr(), quals_cap=rows * L, d_lens=lens.data_ptr(), lens_cap=rows,
+                            d_names=blob.data_ptr() if (names and nl) else None, names_cap=nl if names else 0,
+                            d_name_off=off.data_ptr() if names else None, off_cap=rows + 1 if names else 0, **src)
+    finally:
+        codec.set_stream(None)
+    out = {"bases": bases, "quals": quals, "lens": lens, "consumed": (int(q.consumed1), int(q.consumed2))}
+    if names:
+        out["names"], out["name_off"] = blob, off
     return out
 
 
