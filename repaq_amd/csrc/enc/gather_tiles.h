@@ -89,7 +89,8 @@ __device__ __forceinline__ void g2_stage1(const uint8_t* __restrict__ fq, uint32
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 16 * (size_t)i),
                 (__attribute__((address_space(3))) void*)(l4 + (i - (tid & 63u))), 16, 0, 0);
     if (nfull < ng && tid == 0) { uint8_t* const bytes = (uint8_t*)l4;
-            for (uint32_t k = 0; k < 16 && a0 + 16 * nfull + k < n; k++) bytes[16 * nfull + k] = src[16 * (size_t)nfull + k]; }
+            // (what lies behind the text's end is put down as 0xFF, not left as whatever the LDS held: g2_ctl_count looks at whole groups)
+            for (uint32_t k = 0; k < 16; k++) bytes[16 * nfull + k] = a0 + 16 * nfull + k < n ? src[16 * (size_t)nfull + k] : (uint8_t)0xFF; }
 }
 __device__ __forceinline__ void g2_stage(const Text& T, bool two, const G2Geo& g, uint4* buf4, uint32_t tid) {
     g2_stage1(T.fq[0], T.n[0], g.a00, g.end0, buf4, tid);
@@ -349,6 +350,20 @@ __device__ __forceinline__ void g2_parse(const Text& T, const ReadTab& R, const 
         }
     }
 }
+// two files, one line table (see g2_ctl_count): a lane per read of the tile - the four line ends of a stream-1 record must be line feeds (the last one may be the
+// virtual terminator behind an unterminated text).  The parsing wave runs it behind g2_parse, on its own registers.
+__device__ __forceinline__ void g2_mirror_ends(const Text& T, const uint8_t* tx, const G2Geo& g, uint32_t cur, uint32_t cnt, uint32_t* mirror_err) {
+    const uint32_t l = (uint32_t)lane_id(); bool bad = false;
+    if (l < cnt) {
+        int s_; uint32_t r_; read_loc(T, cur + l, s_, r_);
+        if (s_ == 1) {
+            const uint32_t* const p = t_lo(T, 1) + 4 * (size_t)r_; const uint32_t o = g.base1 - g.a01, n = T.n[1];
+            const uint32_t e1 = p[1], e2 = p[2], e3 = p[3], e4 = p[4];
+            bad = tx[o + e1 - 1u] != '\n' || tx[o + e2 - 1u] != '\n' || tx[o + e3 - 1u] != '\n' || (e4 - 1u < n && tx[o + e4 - 1u] != '\n');
+        }
+    }
+    if (__any(bad)) { if (l == 0u) atomicOr(mirror_err, (uint32_t)DE_MIRROR_FAIL); }      // (wave-uniform; only where something is wrong)
+}
 // ---- MASKS mode (files with at most four coded quality values - a NovaSeq-binned file has three, or four with the table's 0xFF entry): no quality bytes leave the kernel.  A lane turns its 16
 // bytes into one 16-bit match mask per value and ORs them, shifted to their chunk position, into bit planes of the tile in LDS (ds_or, no return); after the
 // barrier the planes leave as whole 32-bit words - coalesced, plain stores - and are counted on the way (popcount per segment, last match: what QualCount
@@ -365,7 +380,29 @@ __device__ __forceinline__ void g2_parse(const Text& T, const ReadTab& R, const 
 #define G2_PLANE_EXC 4u
 #define G2_RARE_LIST 255u          // words of rare planes a chunk may touch before the cleanup zeroes its whole extent instead
 // pw: words per LDS plane; nd: dense planes; rare: [n_chunks][1 + G2_RARE_LIST]: count, then (plane << 28 | word of the chunk)
-struct G2Planes { uint32_t* planes; uint64_t pstride; uint32_t pw, nd; uint32_t* rare; };
+// mirror_err: two files through stream 0's line table (enc_index) - the status word that takes DE_MIRROR_FAIL; null: every stream has its own table
+struct G2Planes { uint32_t* planes; uint64_t pstride; uint32_t pw, nd; uint32_t* rare; uint32_t* mirror_err; };
+// ---- two files, one line table: what the gather proves about stream 1 as it goes (the host acts on DE_MIRROR_FAIL, rfq_encode.hip).  Every record a tile owns must hold
+// exactly four '\n', at its four line ends, and no '\r'.  In two parts: the parsing wave looks at the four line-end bytes of each of its stream-1 records (g2_mirror_ends), and
+// every thread counts the bytes below 0x10 in its share of the tile's staged stream-1 span; the workgroup's count must be its number of line ends.  Line ends that are all
+// '\n' and no control byte more than there are line ends: the line feeds are those, and there is no '\r'.  (The test also fires on the other bytes below 0x10 and - through
+// a borrow - on a 0x10 right behind one of them: it can only count too many, and a false alarm costs the repeat, nothing else.  Four instructions per four bytes.)
+__device__ __forceinline__ uint32_t ctl_flags4(uint32_t w) { return (w - 0x10101010u) & ~w & 0x80808080u; }
+__device__ __forceinline__ uint32_t ctl_count16(const uint4& q) {       // flagged bytes of a 16-byte group
+    return (uint32_t)__popc(ctl_flags4(q.x)) + (uint32_t)__popc(ctl_flags4(q.y)) + (uint32_t)__popc(ctl_flags4(q.z)) + (uint32_t)__popc(ctl_flags4(q.w));
+}
+// bytes below 0x10 among bytes [head, nb) of the span staged at l4 (head < 16), this thread's share: whole 16-byte groups in a loop every lane leaves together, then
+// what the first and the last group hold outside the span is taken off again, a byte per lane (a share may pass through "negative": the workgroup's sum is taken
+// modulo 2^32; the byte-wise test is exact, so the sum still cannot come out too small)
+__device__ __forceinline__ uint32_t g2_ctl_count(const uint4* l4, uint32_t head, uint32_t nb, uint32_t tid) {
+    const uint32_t ng = (nb + 15u) >> 4; uint32_t c = 0;
+    for (uint32_t i0 = 0; i0 < ng; i0 += 256u) { const uint32_t i = i0 + tid; if (i < ng) c += ctl_count16(l4[i]); }      // (uniform trip count)
+    if (tid < 32u) {
+        const uint32_t k = tid & 15u, p = tid < 16u ? k : nb + k;          // a byte in front of the span / behind it
+        if (tid < 16u ? k < head : p < 16u * ng) c -= ((const uint8_t*)l4)[p] < 0x10u ? 1u : 0u;
+    }
+    return c;
+}
 __device__ __forceinline__ void g2_rare_or(uint32_t* __restrict__ gpl, uint64_t pstride, uint32_t* __restrict__ rare_c, uint32_t plane, uint32_t pos) {
     const uint32_t old = atomicOr(&gpl[(size_t)plane * pstride + (pos >> 5)], 1u << (pos & 31u));
     // the word's first bit: remember the word
@@ -460,7 +497,7 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
     constexpr bool PE = PAIRED != 0;
     RFQ_DYN_SHARED(uint4, g2_lds);
     __shared__ uint32_t sh[MASKS ? 1 : G2_CNT]; __shared__ int sh_last[MASKS ? 1 : G2_CNT]; __shared__ uint8_t s_slot[MASKS ? 16 : 256];
-            __shared__ uint32_t s_r0[8], s_carry[4];
+            __shared__ uint32_t s_r0[8], s_carry[4], s_mctl;
     const uint32_t REFN = (text4 - 1u) * 16u, REFS = REFN + G2_REFN + 16u;      // (byte offsets from the tile's first byte)
     uint32_t* const pl = (uint32_t*)(g2_lds + text4 + (G2_REFN + G2_REFS + 32u) / 16u);
     const uint32_t c = blockIdx.y;
@@ -478,6 +515,7 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
         for (uint32_t i = tid; i < M.nd * M.pw; i += blockDim.x) pl[i] = 0u;
         if (tid < 4u) s_carry[tid] = 0u;
     }
+    if (tid == 0) s_mctl = 0u;
     const uint32_t f = first[c], e = first[c + 1];
     const bool two = PE && T.paired == 1, can0 = PE && T.paired != 0 && D->support_interleaved != 0, il = can0 && !redo;
     const uint32_t dpos = D->name2_diff_pos, dch = D->name2_diff_char;
@@ -497,6 +535,10 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
     uint4* const buf4 = g2_lds + 1; const uint8_t* const tx = (const uint8_t*)buf4;
     G2Ref r0 = {}; G2Acc acc; acc.bits = CF_ALL; acc.fail = 0xFFFFFFFFu;
     const bool parse = !redo && gs < ge;                                    // block-uniform
+    // two files through one line table (phase 1 proves it; phase 2 repeats chunks it has seen): my count of stream 1's control bytes, the line ends my workgroup owns
+    // (the instantiations that take two files: <MASKS, 1> and the generic byte-stream form; the generic match-mask form is interleaved input's and stays as it was)
+    const bool mirror = (PAIRED == 1 || (PAIRED == -1 && !MASKS)) && two && !redo && M.mirror_err != nullptr;
+    uint32_t mwant = 0;
     if (parse) {
         // read 0 of the chunk: the first bytes of its name and strand lines into LDS, its name parsed by one lane
         uint32_t r_; read_loc(T, f, r0.s, r_); const uint32_t* p = t_lo(T, r0.s) + 4 * (size_t)r_;
@@ -530,13 +572,20 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
         __syncthreads();                                                    // (drains the LDS-DMA)
         qc.seg0 = qbeg / PC_SEG_POS;
         // (wave-uniform: this tile's parsing wave)
-        if (parse && (uint32_t)wave_id() == (tix & 3u)) g2_parse(T, R, tx, REFN, REFS, g, r0, f, cur, cnt, can0, dpos, dch, acc);
+        if (parse && (uint32_t)wave_id() == (tix & 3u)) { g2_parse(T, R, tx, REFN, REFS, g, r0, f, cur, cnt, can0, dpos, dch, acc);
+                if (mirror) g2_mirror_ends(T, tx, g, cur, cnt, M.mirror_err); }
         if (MASKS) {
             if (tid < nd && s_carry[tid]) atomicOr(&pl[tid * M.pw], s_carry[tid]);       // the word the tile in front left unfinished
             g2_quals_masks(tx, m, part, P, pl, M.pw, qbeg & ~31u, nd, pat0, pat1, pat2, patm, D, qd, gpl, M.pstride, segm + (size_t)c * MAX_STREAMS * n_seg,
                     segc + (size_t)c * MAX_STREAMS * n_seg, n_seg, M.rare + (size_t)c * (1u + G2_RARE_LIST));
             g2_bases(tx, m, part, P, lpk, lnb, rflag, rn);
         } else g2_compose(tx, m, part, P, qd, lpk, lnb, rflag, rn, qc);
+        if (mirror) {                                                       // (block-uniform) stream 1's staged span, up to the text's end: two line ends per read of the tile
+            const uint32_t end1 = g.end1 < T.n[1] ? g.end1 : T.n[1];
+            const uint32_t mctl = wave_sum(g2_ctl_count(buf4 + g.base1 / 16u, b0.l1 - g.a01, end1 - g.a01, tid));
+            if ((tid & 63u) == 0 && mctl) atomicAdd(&s_mctl, mctl);
+            mwant += 2u * cnt - (g.end1 > T.n[1] ? 1u : 0u);
+        }
         __syncthreads();                                                    // the text is free for the next tile; the tile's counts / planes are complete
         if (t + 1u < ntile) g2_stage(T, two, g2_geo(b1, b2, two), buf4, tid);  // the next tile's text is on its way while the planes / counters of this one leave
         if (MASKS) {
@@ -550,6 +599,10 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
     if (parse) {
         const uint32_t bits = wave_and(acc.bits), fail = wave_min(acc.fail);
         if ((tid & 63u) == 0) { if (bits != CF_ALL) atomicAnd(&cbits[c], bits); if (fail != 0xFFFFFFFFu) atomicMin(&cfail[c], fail); }
+    }
+    if (mirror) {
+        __syncthreads();
+        if (tid == 0 && s_mctl != mwant) atomicOr(M.mirror_err, (uint32_t)DE_MIRROR_FAIL);
     }
 }
 // phase 2 of the gather re-counts the qualities of the chunks it repeats: their per-(stream, segment) entries back to "nothing seen"

@@ -164,9 +164,11 @@ template <int NLF_T> __global__ void __launch_bounds__(256) k_line_index(const u
 // partition take their unit count from st->idx_units, the host learns everything with the partition's results - one round trip less per batch.  guess: the units the
 // host sized the per-read tables for (from the bytes per record of the context's earlier batches); more than that: DE_UNITS_GUESS, the batch is repeated the slow way.
 __global__ void k_index_totals(const uint32_t* __restrict__ tot0, const uint32_t* __restrict__ tot1, const uint8_t* __restrict__ fq0, uint32_t n0, const uint8_t* __restrict__ fq1, uint32_t n1,
-                               uint32_t* lo0, uint32_t* lo1, int final_batch, int paired, uint32_t unit_cap, uint32_t guess, DevStatus* st) {
+                               uint32_t* lo0, uint32_t* lo1, int final_batch, int paired, uint32_t unit_cap, uint32_t guess, DevStatus* st, int mirror) {
     if (threadIdx.x || blockIdx.x) return;
     uint32_t rec[2] = { 0, 0 };
+    // (mirror: tot1 / lo1 are stream 0's and n1 == n0 - stream 1 still ends in a byte of its own, and only a line end where stream 0 has one lets the table serve both)
+    if (mirror && n0 > 0 && (fq0[n0 - 1] != '\n') != (fq1[n1 - 1] != '\n')) atomicOr(&st->err, (uint32_t)DE_MIRROR_FAIL);
     for (int s = 0; s < (paired == 1 ? 2 : 1); s++) {
         const uint32_t nl = s ? *tot1 : *tot0, n = s ? n1 : n0; const uint8_t* fq = s ? fq1 : fq0; uint32_t* lo = s ? lo1 : lo0;
         // (an unterminated tail is the file's last line only in the final batch)
@@ -178,6 +180,30 @@ __global__ void k_index_totals(const uint32_t* __restrict__ tot0, const uint32_t
     if (units > unit_cap) units = unit_cap;
     st->idx_units_true = units; st->idx_units = units < guess ? units : guess;
     if (units > guess) atomicOr(&st->err, (uint32_t)DE_UNITS_GUESS);
+}
+// Two files through ONE line table (the mates of untrimmed sequencer output have their line ends at the same offsets: stream 1 is read through stream 0's lo[]).
+// k_gather2 proves that for every record it stages; this kernel for what lies behind the last encoded unit - the tail chunk's failed attempt (k_assemble), consumed2,
+// an unterminated or truncated last record: over [lo0[4 * units_used], n) both streams must hold their '\n' and '\r' at the same offsets.  At most about a chunk of
+// text.  A difference raises DE_MIRROR_FAIL; the host repeats the batch with an index per stream.
+__global__ void __launch_bounds__(256) k_mirror_tail(const uint8_t* __restrict__ fq0, const uint8_t* __restrict__ fq1, uint32_t n, const uint32_t* __restrict__ lo0,
+        uint32_t units_used, DevStatus* st) {
+    uint32_t start = lo0[4 * (size_t)units_used]; if (start > n) start = n;        // (n + 1: the virtual terminator of an unterminated last line)
+    bool bad = false;
+    for (uint64_t g = (uint64_t)(start >> 4) + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g * 16ull < n; g += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t base = (uint32_t)(g * 16ull), have = n - base < 16u ? n - base : 16u;
+        uint32_t lf0 = 0, lf1 = 0, cr0 = 0, cr1 = 0;
+        if (have == 16u) {
+            const uint4 a = *(const uint4*)(fq0 + base), b = *(const uint4*)(fq1 + base);
+            lf0 = eq_mask16c(a, 0x0A0A0A0Au); lf1 = eq_mask16c(b, 0x0A0A0A0Au); cr0 = eq_mask16c(a, 0x0D0D0D0Du); cr1 = eq_mask16c(b, 0x0D0D0D0Du);
+        } else for (uint32_t i = 0; i < have; i++) {
+            const uint8_t a = fq0[base + i], b = fq1[base + i];
+            if (a == '\n') lf0 |= 1u << i; if (b == '\n') lf1 |= 1u << i; if (a == '\r') cr0 |= 1u << i; if (b == '\r') cr1 |= 1u << i;
+        }
+        const uint32_t from = start > base ? start - base : 0u;                      // (bytes in front of `start`: the gather's)
+        const uint32_t valid = from >= 16u ? 0u : (0xFFFFu << from) & 0xFFFFu;
+        if (((lf0 ^ lf1) | (cr0 ^ cr1)) & valid) bad = true;
+    }
+    if (__any(bad) && lane_id() == 0) atomicOr(&st->err, (uint32_t)DE_MIRROR_FAIL);
 }
 __global__ void k_line_tail(uint32_t* lo, uint32_t n_newlines, uint32_t n, int unterminated) {
     if (threadIdx.x == 0 && blockIdx.x == 0 && unterminated) lo[n_newlines + 1] = n + 1;

@@ -54,6 +54,7 @@
 #define DE_SCRATCHN_SMALL  (1u << 13) // ... the N-position streams' arena
 #define DE_NEED_SCAN       (1u << 14) // encode: reads of several lengths - the closed-form prefixes do not apply, the host runs the scans and the partition again
 #define DE_UNITS_GUESS     (1u << 15) // encode: the batch holds more units than the host sized its tables for without waiting for the index's totals: once more, with the totals
+#define DE_MIRROR_FAIL     (1u << 16) // encode, two files indexed once (R2 read through R1's line table): R2's line ends are not where R1's are - the batch is repeated with both indexes, the caller never sees this
 #define DE_TAIL_BLANK      (1u << 9)  // an empty line in the \n-only text right behind the encoded records: blank or empty is for the normaliser to say
 
 // Device-resident file header + derived tables (RfqHeader, src/rfqheader.h:44-108)

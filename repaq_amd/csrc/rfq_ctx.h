@@ -98,6 +98,7 @@ struct RfqOpts {
     uint32_t sp_pad = 0;
     bool no_spec = false;             // RFQ_SPEC=0         decode: the emitter only behind the host's look at the status (default: launched ahead of it where the caller gave the output buffers)
     int  pos_seg = 0;                 // RFQ_POS_SEG=1024|2048   decode, list chain: bytes of a position stream per wave (default: by the largest stream, dec/pos_lists.h)
+    bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)
 };
 struct rfq_ctx {
     RfqOpts opt;
@@ -161,7 +162,10 @@ struct rfq_ctx {
     bool mixed_lengths = false;            // encode: this file has reads of several lengths (the prefix scans are launched up front; reset with the header)
     bool dense_ok = false;                 // encode, match-mask mode: DevHeader::dense of the device header is set (k_dense_order; reset with the header)
     // another file (its header is set or cleared): what its name pieces fit, whether its reads have one length, which coded values are frequent is not known yet
-    void new_file() { dense_ok = false; e3_pieces_failed = false; mixed_lengths = false; }
+    void new_file() { dense_ok = false; e3_pieces_failed = false; mixed_lengths = false; mirror_block = false; }
+    // encode, two files through one line index: this input's mates do not share their line ends (a batch had to be repeated) - both indexes from now on;
+    // "the attempt in progress is such a repeat" (a marker for rfq_last_timings)
+    bool mirror_block = false, mirror_fell = false;
     // encode, match-mask mode: the rare planes of b[B_QPLANE] may hold bits (fresh buffer, or a call that left early): zero them whole
     bool qplane_dirty = true;
     uint32_t qplane_nd = 0, qplane_mask = 0; // ... dense planes the last batch used: how many, which (the others must be all-zero)

@@ -97,10 +97,14 @@ static int normalize_stream(rfq_ctx* ctx, const uint8_t* fq, size_t n, uint64_t 
 // ---------------------------------------------------------------- one attempt at one text: the batch as values, its stages, encode_impl
 #define RFQ_AGAIN_LAZY 2           // internal: the index without a read-back could not take this batch (ctx->lazy_block is up): the attempt once more
 #define RFQ_AGAIN_ENDED 4          // internal: the reader stops at an empty line: the attempt once more, the input ended there (EncAgain)
+#define RFQ_AGAIN_MIRROR 5         // internal: stream 1 could not be read through stream 0's line table after all: the attempt once more with an index per stream (encode_impl)
 struct EncAgain { uint32_t unit_cap = ~0u; bool ended = false; };   // what a repeat of the attempt starts from: the call's own arguments, or the unit the reader stopped at
 // The call as one attempt sees it (the head of encode_impl).  hs, the host copy of the status block, is also what the upload of a fresh block reads: it lives as long as the attempt.
 struct EncBatch {
-    const rfq_encode_args* a; const NormMap* nm; const uint32_t* skip; bool scan_only, ended, fin, is_pe; uint32_t unit_cap; int nstreams; const uint8_t* fq[2]; size_t nbytes[2]; Text T; DevStatus* dst; DevStatus hs;
+    const rfq_encode_args* a; const NormMap* nm; const uint32_t* skip; bool scan_only, ended, fin, is_pe;
+    // mirror_ok: the caller has a gather behind the index and may be given stream 0's line table for both streams; mirrored: enc_index did so; mirror_proven: the
+    // final read-back says that stream 1's line ends are where stream 0's are
+    bool mirror_ok, mirrored, mirror_proven; uint32_t unit_cap; int nstreams; const uint8_t* fq[2]; size_t nbytes[2]; Text T; DevStatus* dst; DevStatus hs;
     uint64_t orig_n(int s) const { return nm ? nm->orig_n[s] : nbytes[s]; }
 };
 // what index + cut produced (enc_index: lazy, guess_units, nlines, nrec; enc_cut: the rest, the maxima from the partition's read-back).  n_chunks == 0: nothing to encode
@@ -141,6 +145,12 @@ static int enc_index(rfq_ctx* ctx, EncBatch& b, EncCut& cut) {
     for (int s = 0; s < b.nstreams; s++) nidx[s] = (uint32_t)((b.nbytes[s] + idx_tiles * 16384u - 1) / (idx_tiles * 16384u));
     uint32_t n_newlines[2] = { 0, 0 }; uint8_t lastbyte[2] = { '\n', '\n' };
     bool one_pass = !ctx->opt.index_2pass;
+    // MIRROR: the mates of untrimmed sequencer output differ in one digit of their names - two texts of one size with their line ends at the same offsets.  Stream 1 is
+    // not indexed then: it is read through stream 0's table (every offset in it is < n[0] == n[1]: nothing reads outside stream 1), k_gather2 proves as it goes that each
+    // record it stages has its four line feeds where the table says and no '\r', k_mirror_tail does the same for the text behind the last encoded unit, and the verdict
+    // comes back with the batch's own read-backs.  Where it does not hold the attempt is thrown away and repeated with both indexes (encode_impl; ctx->mirror_block).
+    const bool mirror = b.mirrored = b.mirror_ok && one_pass && b.nstreams == 2 && !b.nm && !ctx->opt.no_mirror && !ctx->mirror_block && nblk[0] != 0 &&
+                                     b.nbytes[0] == b.nbytes[1] && b.skip[0] == b.skip[1];
     // LAZY: no read-back behind the index.  The per-read tables are sized for a unit count guessed from the records per byte of the context's earlier batches; the
     // index's totals stay on the device (k_index_totals: lines, units, the unterminated tail) and reach the host with the partition's results.  A batch that holds
     // more units than guessed, an index that has to fall back to two passes: once more with the read-back (ctx->lazy_block).
@@ -158,6 +168,7 @@ static int enc_index(rfq_ctx* ctx, EncBatch& b, EncCut& cut) {
         size_t cap[2] = { 0, 0 };
         for (int s = 0; s < b.nstreams; s++) {
             if (!nblk[s]) continue;
+            if (mirror && s == 1) { if (!lazy) HIPCHK(ctx, ctx->fetch(&lastbyte[1], b.fq[1] + b.nbytes[1] - 1, 1, S)); continue; }   // (its own last byte, nothing else)
             cap[s] = std::max(B[B_LO0 + s].cap / 4, b.nbytes[s] / 16 + 4096);
             HIPCHK(ctx, B[B_LO0 + s].ensure(cap[s] * 4));
             HIPCHK(ctx, B[B_BLK0 + s].ensure((size_t)nidx[s] * 8 + 64));                  // state words, then the ticket and the total
@@ -174,13 +185,19 @@ static int enc_index(rfq_ctx* ctx, EncBatch& b, EncCut& cut) {
         }
         if (lazy) {
             const uint32_t* t0 = (const uint32_t*)(B[B_BLK0].as<unsigned long long>() + nidx[0]) + 1;
-            const uint32_t* t1 = b.nstreams == 2 ? (const uint32_t*)(B[B_BLK1].as<unsigned long long>() + nidx[1]) + 1 : t0;
+            const uint32_t* t1 = b.nstreams == 2 && !mirror ? (const uint32_t*)(B[B_BLK1].as<unsigned long long>() + nidx[1]) + 1 : t0;
             hipLaunchKernelGGL(k_index_totals, dim3(1), dim3(64), 0, S, t0, t1, b.fq[0], (uint32_t)b.nbytes[0], b.fq[1], (uint32_t)b.nbytes[1], B[B_LO0].as<uint32_t>(),
-                               b.nstreams == 2 ? B[B_LO1].as<uint32_t>() : (uint32_t*)nullptr, b.a->final ? 1 : 0, (int)b.a->paired, b.unit_cap, guess_units, b.dst);
+                               b.nstreams == 2 ? B[mirror ? B_LO0 : B_LO1].as<uint32_t>() : (uint32_t*)nullptr, b.a->final ? 1 : 0, (int)b.a->paired, b.unit_cap, guess_units, b.dst,
+                               mirror ? 1 : 0);
             KCHK(ctx, "k_index_totals");
         } else {
             HIPCHK(ctx, ctx->fetch(&b.hs, b.dst, sizeof b.hs, S));
             HIPCHK(ctx, ctx->fetch_sync(S));
+            if (mirror) {
+                // stream 0's totals for both; a table that needs the two-pass index, a last byte that ends a line in one stream only: not this way
+                n_newlines[1] = n_newlines[0];
+                if ((b.hs.err & DE_INDEX_RETRY) || (lastbyte[0] != '\n') != (lastbyte[1] != '\n')) return RFQ_AGAIN_MIRROR;
+            }
         }
         if (!lazy && (b.hs.err & DE_INDEX_RETRY)) {                                                    // start over with a clean status block
             one_pass = false;
@@ -220,6 +237,7 @@ static int enc_index(rfq_ctx* ctx, EncBatch& b, EncCut& cut) {
         // batch boundary and belongs to the next batch
         const int unterm = b.a->final && b.nbytes[s] > 0 && lastbyte[s] != '\n';
         cut.nlines[s] = n_newlines[s] + (unterm ? 1u : 0u); cut.nrec[s] = cut.nlines[s] / 4;
+        if (mirror && s == 1) continue;                                     // (stream 0's table, virtual terminator included)
         if (!one_pass || !nblk[s]) HIPCHK(ctx, B[B_LO0 + s].ensure(((size_t)cut.nlines[s] + 4) * 4));
         if (nblk[s]) {
             if (!one_pass) hipLaunchKernelGGL(k_line_offsets, dim3(nblk[s]), dim3(256), 0, S, B[B_BITMAP0 + s].as<uint64_t>(), B[B_BLK0 + s].as<uint32_t>(),
@@ -231,9 +249,10 @@ static int enc_index(rfq_ctx* ctx, EncBatch& b, EncCut& cut) {
     ctx->timer.end(S);
     // (a marker, not a phase: the index's totals stay on the device until the partition's read-back - tests look for it)
     if (lazy) { ctx->timer.begin("lazy_index", S); ctx->timer.end(S); }
+    if (mirror) { ctx->timer.begin("mirror_index", S); ctx->timer.end(S); }     // (the same: one line index served both streams)
     cut.lazy = lazy; cut.guess_units = guess_units;
     Text& T = b.T; memset(&T, 0, sizeof T);
-    for (int s = 0; s < 2; s++) { T.fq[s] = b.fq[s]; T.n[s] = (uint32_t)b.nbytes[s]; T.lo[s] = s < b.nstreams ? B[B_LO0 + s].as<uint32_t>() : nullptr;
+    for (int s = 0; s < 2; s++) { T.fq[s] = b.fq[s]; T.n[s] = (uint32_t)b.nbytes[s]; T.lo[s] = s < b.nstreams ? B[mirror ? B_LO0 : B_LO0 + s].as<uint32_t>() : nullptr;
             T.ot[s] = b.nm && s < b.nstreams ? b.nm->ot[s] : nullptr; }
     T.paired = b.a->paired; T.upr = b.a->paired == RFQ_SE ? 1u : 2u;
     return RFQ_OK;
@@ -290,6 +309,7 @@ static int enc_cut(rfq_ctx* ctx, EncBatch& b, EncCut& cut, EncTables& t, rfq_enc
     }
     b.hs.err &= ~(uint32_t)DE_NEED_SCAN;
     ctx->timer.end(S);
+    if (b.mirrored && (b.hs.err & DE_MIRROR_FAIL)) return RFQ_AGAIN_MIRROR;     // (k_index_totals: the streams' last bytes)
     if (cut.lazy) {
         // the index's verdict, which the other form reads right behind it
         if (b.hs.err & (DE_INDEX_RETRY | DE_UNITS_GUESS | DE_NEED_SCAN)) { ctx->lazy_block = true; if (b.hs.err & DE_NEED_SCAN) ctx->mixed_lengths = true;
@@ -441,6 +461,7 @@ static void chunk_layout(hipStream_t Q, const EncBatch& b, const EncCut& cut, co
 static int enc_gather_tiles(rfq_ctx* ctx, const EncBatch& b, const EncCut& cut, EncTables& t, EncForm& f, AuxGuard& guard) {
     hipStream_t S = ctx->stream; DBuf* B = ctx->b;
     const uint32_t np = cut.reads_used / 2;
+    if (b.mirrored && f.masks && !G2_SE_OK) return RFQ_AGAIN_MIRROR;         // (a build without k_gather2<true, 1>: the generic match-mask form does not check stream 1)
     // every table of the batch that starts all-zero / all-ones, in one launch (k_clear_list)
     uint8_t *rflag, *rn; HIPCHK(ctx, table(B[B_RFLAG], (t.nr + 15) & ~(size_t)15, rflag)); HIPCHK(ctx, table(B[B_RN], (t.nr + 15) & ~(size_t)15, rn));
     ClearList z; memset(&z, 0, sizeof z);
@@ -463,7 +484,7 @@ static int enc_gather_tiles(rfq_ctx* ctx, const EncBatch& b, const EncCut& cut, 
     // dynamic LDS of k_gather2: the staged text of K of the batch's longest records (+ slack), read 0's name / strand line, and - match-mask mode - three
     // bit planes of K of the longest reads.  Six workgroups per CU need <= 26.8 KB each (measured: with five the kernel is 10 % slower).
     const uint32_t text4 = (uint32_t)((((uint64_t)cut.max_rec << f.kshift) + 64u + 15u) / 16u) + 8u;
-    G2Planes M; M.planes = nullptr; M.rare = nullptr; M.pstride = 0; M.nd = 0; M.pw = (uint32_t)((((uint64_t)cut.max_len << f.kshift) + 31u) / 32u) + 2u;
+    G2Planes M; M.planes = nullptr; M.rare = nullptr; M.pstride = 0; M.nd = 0; M.mirror_err = b.mirrored ? &b.dst->err : (uint32_t*)nullptr; M.pw = (uint32_t)((((uint64_t)cut.max_len << f.kshift) + 31u) / 32u) + 2u;
     auto dyn_of = [&](uint32_t nd_) -> uint32_t { return text4 * 16u + (G2_REFN + G2_REFS + 32u) + 4u * nd_ * M.pw; };
     if (f.masks) {
         // dense planes: three if the workgroup still fits six to a CU (26.8 KB of LDS each: with five the kernel is 10 % slower), else two
@@ -713,6 +734,8 @@ static int enc_verdict(rfq_ctx* ctx, EncBatch& b, const EncCut& cut, const EncTa
     HIPCHK(ctx, ctx->fetch(&b.hs, b.dst, sizeof b.hs, S));
     HIPCHK(ctx, ctx->fetch_sync(S));
     guard.armed = false; ctx->timer.collect();                              // (the second chain was joined in front of the assembler)
+    // one line table for two files: the gather's and k_mirror_tail's verdict in front of everything else this read-back says (it was all made from that table)
+    if (b.mirrored) { if (b.hs.err & DE_MIRROR_FAIL) return RFQ_AGAIN_MIRROR; b.mirror_proven = true; }
     if (b.hs.err & DE_COORD_RANGE) {
         // RfqCodec::encodeCoords error_exit, src/rfqcodec.cpp:1315-1317: first offender in (chunk, x-before-y, index) order
         const uint32_t c = (uint32_t)(b.hs.coord_key >> 34), axis = (uint32_t)((b.hs.coord_key >> 33) & 1u), i = (uint32_t)(b.hs.coord_key & 0xFFFFFFFFu);
@@ -738,11 +761,14 @@ static int enc_verdict(rfq_ctx* ctx, EncBatch& b, const EncCut& cut, const EncTa
     res->h_chunk_off = ctx->chunk_off.data();
     return RFQ_OK;
 }
-// One attempt: the stages and the checks between them.  RFQ_OK, an error, or what encode_settled / encode_one do next (RFQ_AGAIN_*, with *again; RFQ_RETRY_ROOM; RFQ_NEED_NORM)
-static int encode_impl(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result* res, const NormMap* nm, EncAgain* again, bool scan_only, const uint32_t* skip) {
+// One attempt: the stages and the checks between them.  RFQ_OK, an error, or what encode_impl / encode_settled / encode_one do next (RFQ_AGAIN_*, with *again; RFQ_RETRY_ROOM; RFQ_NEED_NORM)
+// *mirror: 0 - every stream had its own line index; 1 - stream 0's served both and that is not proven: whatever the attempt says does not count; 2 - proven
+static int encode_attempt(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result* res, const NormMap* nm, EncAgain* again, bool scan_only, const uint32_t* skip, bool mirror_ok,
+        int* mirror) {
     EncBatch b = {}; EncCut cut = {}; EncTables t = {}; AuxGuard guard = { ctx, false }; int rc;
+    struct MirrorOut { const EncBatch& b; int* out; ~MirrorOut() { *out = b.mirrored ? (b.mirror_proven ? 2 : 1) : 0; } } mirror_out = { b, mirror };
     memset(res, 0, sizeof *res); res->input_ended = again->ended ? 1 : 0;
-    b.a = a; b.nm = nm; b.skip = skip; b.scan_only = scan_only; b.ended = again->ended; b.unit_cap = again->unit_cap;
+    b.a = a; b.nm = nm; b.skip = skip; b.scan_only = scan_only; b.ended = again->ended; b.unit_cap = again->unit_cap; b.mirror_ok = mirror_ok;
     b.fin = a->final || again->ended || a->flush_all; b.is_pe = a->paired != RFQ_SE;
     if (a->chunk_bases == 0) return rfq_fail(ctx, RFQ_E_ARG, "chunk_bases must be >= 1");
     const int nstreams = b.nstreams = a->paired == RFQ_PE_TWO_FILES ? 2 : 1;
@@ -760,18 +786,43 @@ static int encode_impl(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // (a marker, not a phase: this is the repeat of a batch whose arenas were too small - tests look for it)
     if (ctx->retried_room) { ctx->timer.begin("retry_room", ctx->stream); ctx->timer.end(ctx->stream); ctx->retried_room = false; }
+    // (the same: a batch of this call was repeated because its second stream did not fit the first one's line table - up for the rest of the call, encode_one takes it down:
+    // the room repeat or the lazy index's may still come behind it)
+    if (ctx->mirror_fell) { ctx->timer.begin("mirror_fallback", ctx->stream); ctx->timer.end(ctx->stream); }
     HIPCHK(ctx, table(ctx->d_status, sizeof(DevStatus), b.dst));            // ---- status block
     HIPCHK(ctx, fresh_status(ctx, b));
     if ((rc = enc_index(ctx, b, cut)) != RFQ_OK) return rc;
     if ((rc = enc_cut(ctx, b, cut, t, res, again)) != RFQ_OK || cut.n_chunks == 0) return rc;   // (no unit, no chunk: the empty result is made)
     if (scan_only) return enc_chunk_ends(ctx, b, cut, t, res);
     EncForm f = {}; enc_form(ctx, cut, f, false);
+    if (b.mirrored) {
+        // only the tile gather checks stream 1 against the table (reads too long for a tile, RFQ_GATHER=old: the byte-wise gather does not)
+        if (!f.fast) return RFQ_AGAIN_MIRROR;
+        hipLaunchKernelGGL(k_mirror_tail, dim3(64), dim3(256), 0, ctx->stream, b.fq[0], b.fq[1], (uint32_t)b.nbytes[0], (const uint32_t*)b.T.lo[0], cut.units_used, b.dst);
+        KCHK(ctx, "k_mirror_tail");
+    }
     if ((rc = enc_tables(ctx, b, cut, t)) != RFQ_OK) return rc;
     if ((rc = enc_header(ctx, b, cut, t, f)) != RFQ_OK) return rc;
     if ((rc = f.fast ? enc_gather_tiles(ctx, b, cut, t, f, guard) : enc_gather_bytes(ctx, b, cut, t, f)) != RFQ_OK) return rc;
     if ((rc = enc_coders(ctx, b, cut, t, f)) != RFQ_OK) return rc;
     if ((rc = enc_assemble(ctx, b, cut, t)) != RFQ_OK) return rc;
     return enc_verdict(ctx, b, cut, t, f, guard, res);
+}
+// An attempt, and where it read stream 1 through stream 0's line table without that being proven at its end, a second one with an index per stream.  Such a first attempt
+// counts for nothing, whatever it returned: an error may be the table's doing, an empty result was never checked; a header it made from chunk 0 is forgotten.  The
+// context remembers a real mismatch (mirror_block, until the header is cleared or set: this input's mates are not aligned); an empty result was merely not looked at.
+static int encode_impl(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result* res, const NormMap* nm, EncAgain* again, bool scan_only, const uint32_t* skip) {
+    const bool had_hdr = ctx->have_hdr, had_dense = ctx->dense_ok; int mirror = 0;
+    const int rc = encode_attempt(ctx, a, res, nm, again, scan_only, skip, !scan_only, &mirror);
+    if (mirror != 1 || rc == RFQ_AGAIN_LAZY) return rc;                        // (the lazy index's repeat has produced nothing yet)
+    if (!had_hdr) { ctx->have_hdr = false; ctx->hdr_on_device = false; memset(&ctx->h_hdr, 0, sizeof ctx->h_hdr); }
+    if (!had_dense) ctx->dense_ok = false;
+    if (rc != RFQ_OK) ctx->mirror_block = true;
+    ctx->mirror_fell = true; ctx->err.clear();
+    const int rc2 = encode_attempt(ctx, a, res, nm, again, scan_only, skip, false, &mirror);
+    // (an error leaves the stage timer as it stands: the repeat's marker is collected here, for whoever asks which way the call went)
+    if (rc2 < 0 && hipStreamSynchronize(ctx->stream) == hipSuccess) ctx->timer.collect();
+    return rc2;
 }
 // One text to a settled result.  RFQ_RETRY_ROOM starts again from the call's own arguments, three times at the most; the lazy index's repeat and the empty line's stay inside
 // the attempt and do not count (the first takes the lazy form away: a second one is an internal error; the second cuts in front of the line, so it cannot come up twice).
@@ -817,6 +868,7 @@ static void slice_limits(const rfq_ctx* ctx, size_t& slice, size_t& lim) {
 static int encode_one(rfq_ctx* ctx, const rfq_encode_args* a, rfq_encode_result* res, bool scan_only) {   // (every attempt starts from a cleared *res)
     rfq_encode_args al; uint32_t skip[2];
     align_streams(a, al, skip);
+    ctx->mirror_fell = false;
     int rc = encode_settled(ctx, &al, res, nullptr, scan_only, skip);
     if (rc != RFQ_NEED_NORM) return rc;
     NormMap nm; rfq_encode_args a2; const uint32_t noskip[2] = { 0, 0 };
