@@ -302,6 +302,46 @@ typedef struct {
 } rfq_text_rows_result;
 RFQ_API int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* args, rfq_text_rows_result* res);
 
+/* The step in the middle of the row interface: rows (rfq_decode_rows / rfq_text_rows + their names) -> the rows a caller KEEPS, each TRIMMED to a window, compacted,
+ * with their lengths, names and name offsets - what rfq_encode_rows / rfq_rows_to_text take.  The caller decides (a mask, a window per row - its own code over the
+ * row arrays); this call moves the bytes, nothing on the host.
+ * Kept rows: output row j is the j-th kept input row, in input order.  Its bytes are input bytes [start, start + len) of the base and of the quality row, unchanged
+ * - no code / ASCII or quality-offset transform: base_mode and qual_offset of `rows` are not looked at -, positions >= the new length hold pad_*, lens[j] is the window
+ * length, its name is the whole input name; name_off[0] = 0, name_off[n_out] = names_len.
+ * Why a row is dropped, counted once, in this order: dropped_mask - keep[i] == 0; dropped_short - its window is shorter than min_len; dropped_mate (pairs only) - the
+ * row would stand, its mate (row i ^ 1) does not.  n_in == n_rows + the three.
+ * rows->d_name_off == NULL means rows without names: d_names / d_name_off of the arguments must then be NULL too (RFQ_E_ARG), names_len and max_name are 0.
+ * All five output pointers NULL = a size query: the whole result is filled, nothing is written (row_len is not looked at).  An output that is NULL is not produced
+ * (rows->d_bases / d_quals may be NULL with theirs).  RFQ_E_NOSPACE (nothing written; the message says "need ...") when row_len < max_len or a cap is too small.
+ * RFQ_E_ARG, judged on the host: an odd n_rows with pairs, row_len == 0 on a call that is not a size query, a d_lens / d_start / d_len that is not 4-byte or a
+ * d_name_off that is not 8-byte aligned, an output buffer that overlaps an input buffer (the byte ranges are compared - of an output the bytes a call can write: its
+ * cap, at most n_rows rows; selection in place is not offered).  RFQ_E_ARG, judged on the device before anything is written, the message names the first such row:
+ * lens[i] < 0 or > rows->row_len; start < 0, len < 0 or start + len > lens[i] (formed in 64 bits); name offsets that decrease or end past names_len.  ALL rows are
+ * judged, kept or not.  After any refusal the context stays usable.
+ * The row buffers may have any alignment, in and out: with row_len % 16 == 0 and 16-byte alignment they are loaded / stored in whole 16-byte groups, otherwise at
+ * their own alignment - never a byte outside [d_x, d_x + n * row_len) of either side.  n_rows * row_len and the blob may exceed 4 GiB (n_rows < 2^32 - 16).
+ * Synchronous on the context's stream, like rfq_text_rows; stage times through rfq_last_timings (select:judge, select:tables, select:rows, select:names). */
+typedef struct {
+    const uint8_t* d_keep;                /* [n_rows] bytes, non-zero = keep (a torch.bool tensor as it lies); NULL = every row */
+    const int32_t* d_start;               /* [n_rows] first base kept of row i; NULL = 0                                */
+    const int32_t* d_len;                 /* [n_rows] bases kept from there; NULL = to the end of the read (lens[i] - start[i]) */
+    int32_t  pairs;                       /* 1: rows 2k / 2k + 1 stand or fall together (n_rows must be even)           */
+    uint32_t min_len;                     /* a row whose window is shorter is dropped; 0 lets empty rows through (the encoder refuses them later) */
+    uint32_t row_len;                     /* OUTPUT stride (>= 1, >= the longest kept window; may differ from rows->row_len) */
+    uint8_t  pad_base, pad_qual, reserved[2];
+    uint8_t* d_bases; size_t bases_cap;   /* [n_out][row_len] or NULL                                                   */
+    uint8_t* d_quals; size_t quals_cap;   /* [n_out][row_len] or NULL                                                   */
+    int32_t* d_lens;  size_t lens_cap;    /* [n_out] (entries) or NULL                                                  */
+    uint8_t* d_names; size_t names_cap;   /* blob, any alignment, or NULL                                               */
+    uint64_t* d_name_off; size_t off_cap; /* [n_out + 1] (entries), 8-byte aligned, or NULL                             */
+} rfq_select_rows_args;
+typedef struct {
+    uint64_t n_rows, n_bases, names_len;  /* of the OUTPUT                                                              */
+    uint32_t max_len, max_name;
+    uint64_t n_in, dropped_mask, dropped_short, dropped_mate;   /* n_in == n_rows + the three                           */
+} rfq_select_rows_result;
+RFQ_API int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_select_rows_args* args, rfq_select_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);

@@ -301,6 +301,22 @@ class RfqCodec:
             for p in bufs:
                 self.dev_free(p)
 
+    # --- the step in the middle: rows -> the kept rows, trimmed, with their names (rfq_select_rows)
+    def select_rows(self, n_rows, row_len_in, d_bases, d_quals, d_lens, d_names=None, names_len=0, d_name_off=None, d_keep=None, d_start=None, d_len=None,
+                    pairs=False, min_len=1, row_len=0, pad_base=255, pad_qual=255, out_bases=None, bases_cap=0, out_quals=None, quals_cap=0,
+                    out_lens=None, lens_cap=0, out_names=None, names_cap=0, out_name_off=None, off_cap=0):
+        """rfq_select_rows: the first eight arguments are the rows as rows_to_text / encode_rows take them (d_name_off None: rows without names); d_keep
+        n_rows mask bytes (non-zero = keep; None: every row), d_start / d_len n_rows int32 windows (None: 0 / to the end of the read), pairs: rows
+        2k / 2k + 1 stand or fall together, min_len: a shorter window drops the row.  out_*: the kept rows at stride row_len, their lengths, name lines
+        and n_out + 1 uint64 offsets; no output pointer at all = a size query, an output that is None is not produced.  The bytes are the rows' own.
+        Returns SelectRowsResult (n_rows, n_bases, names_len, max_len, max_name, n_in, dropped_mask, dropped_short, dropped_mate)."""
+        rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, False, 0)
+        a = A.SelectRowsArgs(d_keep, d_start, d_len, 1 if pairs else 0, min_len, row_len, pad_base, pad_qual, (C.c_uint8 * 2)(),
+                             out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap, out_name_off, off_cap)
+        r = A.SelectRowsResult()
+        self._check(self._L.rfq_select_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

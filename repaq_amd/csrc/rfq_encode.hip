@@ -1200,3 +1200,127 @@ extern "C" int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* a, rfq_text
     res->consumed1 = t.consumed[0]; res->consumed2 = two ? t.consumed[1] : 0; res->input_ended = t.ended ? 1 : 0;
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- rows -> kept, trimmed rows with their names: rfq_select_rows of include/rfq_hip.h
+// The judging pass (k_sel_judge), TWO scans - the kept flags to output row indices (32-bit), the kept name sizes to output name offsets (64-bit: a blob may exceed
+// 4 GiB, and the block scan's wave primitives take 4- and 8-byte values, not a two-field struct) - and ONE read-back: the verdict block and the two totals.  The host
+// refuses or goes on; k_sel_tables makes the per-output-row tables (and the caller's lens / name_off), k_sel_rows and k_sel_names follow them.
+static bool sel_overlap(const void* a, unsigned long long an, const void* b, unsigned long long bn) {
+    if (!a || !b || !an || !bn) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    const uintptr_t a1 = an > UINTPTR_MAX - a0 ? UINTPTR_MAX : a0 + (uintptr_t)an, b1 = bn > UINTPTR_MAX - b0 ? UINTPTR_MAX : b0 + (uintptr_t)bn;
+    return a0 < b1 && b0 < a1;
+}
+extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_select_rows_args* a, rfq_select_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows; const bool named = in->d_name_off != nullptr;
+    const bool size_query = !a->d_bases && !a->d_quals && !a->d_lens && !a->d_names && !a->d_name_off;
+    if (a->pairs != 0 && a->pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
+    if (a->pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    if (!size_query && a->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be >= 1");
+    if (in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if (n >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    if (!named && (a->d_names || a->d_name_off)) return rfq_fail(ctx, RFQ_E_ARG, "rows without names (d_name_off == NULL) have no name outputs: d_names / d_name_off must be NULL");
+    if (n && (!in->d_lens || (a->d_bases && !in->d_bases) || (a->d_quals && !in->d_quals) || (a->d_names && in->names_len && !in->d_names)))
+        return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_lens | (uintptr_t)a->d_start | (uintptr_t)a->d_len) & 3u)
+        return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_start and d_len must be 4-byte aligned");
+    if (((uintptr_t)in->d_name_off | (uintptr_t)a->d_name_off) & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
+    {   // no output may lie on an input: the bytes a call can write (its cap, and never more than n_rows rows of row_len) against the bytes it reads
+        const unsigned long long rows_in = (unsigned long long)n * in->row_len, rows_out = (unsigned long long)n * a->row_len;
+        const struct { const void* p; unsigned long long n; const char* what; } ins[] = {
+            { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" },
+            { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }, { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" },
+            { a->d_keep, n, "d_keep" }, { a->d_start, n * 4ull, "d_start" }, { a->d_len, n * 4ull, "d_len" } };
+        const struct { const void* p; unsigned long long n; const char* what; } outs[] = {
+            { a->d_bases, std::min<unsigned long long>(a->bases_cap, rows_out), "d_bases" }, { a->d_quals, std::min<unsigned long long>(a->quals_cap, rows_out), "d_quals" },
+            { a->d_lens, std::min<unsigned long long>(a->lens_cap, n) * 4ull, "d_lens" }, { a->d_names, std::min<unsigned long long>(a->names_cap, in->names_len), "d_names" },
+            { a->d_name_off, std::min<unsigned long long>(a->off_cap, n + 1) * 8ull, "d_name_off" } };
+        for (const auto& o : outs) for (const auto& i : ins)
+            if (sel_overlap(o.p, o.n, i.p, i.n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the input %s: selection in place is not offered", o.what, i.what);
+    }
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
+    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    res->n_in = n;
+    SelStat hs; memset(&hs, 0, sizeof hs); uint32_t n_out = 0; uint64_t names_len = 0;
+    SelIn si; memset(&si, 0, sizeof si);
+    si.lens = in->d_lens; si.name_off = in->d_name_off; si.keep = a->d_keep; si.start = a->d_start; si.len = a->d_len;
+    si.names_len = in->names_len; si.n_rows = (uint32_t)n; si.row_len = in->row_len; si.pairs = a->pairs ? 1u : 0u; si.min_len = a->min_len;
+    uint32_t* pos = nullptr; uint64_t* noff = nullptr;
+    if (n) {
+        ctx->timer.begin("select:judge", S);
+        HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(SelStat)));
+        SelStat* dst = ctx->rows_stat.as<SelStat>();
+        HIPCHK(ctx, table(B[B_LEN], ((size_t)n + 2) * 4, pos));
+        if (named) HIPCHK(ctx, table(B[B_P], ((size_t)n + 2) * 8, noff));
+        HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)n / SCAN_TILE + 2) * 16)));
+        HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(SelStat), S));
+        HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+        hipLaunchKernelGGL(k_sel_judge, dim3((uint32_t)((n + SJ_ROWS - 1u) / SJ_ROWS)), dim3(256), 0, S, si, pos, noff, dst);
+        KCHK(ctx, "k_sel_judge");
+        scan_exclusive<uint32_t>(S, pos, pos, n, B[B_SCANTMP].as<uint32_t>(), 1);
+        if (named) scan_exclusive<uint64_t>(S, noff, noff, n, B[B_SCANTMP].as<uint64_t>(), 1);
+        KCHK(ctx, "scan_exclusive");
+        ctx->timer.end(S);
+        HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+        HIPCHK(ctx, ctx->fetch(&n_out, pos + n, 4, S));
+        if (named) HIPCHK(ctx, ctx->fetch(&names_len, noff + n, 8, S));
+        HIPCHK(ctx, ctx->fetch_sync(S));
+        const unsigned long long br = hs.bad_row;
+        if (hs.err & SL_ERR_LEN) return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, br);
+        if (hs.err & SL_ERR_WIN) return rfq_fail(ctx, RFQ_E_ARG, "a window starts below 0, has a negative length or ends behind its read (first such row: %llu)", br);
+        if (hs.err & SL_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
+    }
+    res->n_rows = n_out; res->n_bases = hs.n_bases; res->names_len = names_len; res->max_len = hs.max_len; res->max_name = hs.max_name;
+    res->dropped_mask = hs.d_mask; res->dropped_short = hs.d_short; res->dropped_mate = hs.d_mate;
+    if (size_query) { ctx->timer.collect(); return RFQ_OK; }
+    {   // room for everything asked for, or nothing is written
+        const unsigned long long rowb = (unsigned long long)n_out * a->row_len;
+        if ((n_out && a->row_len < hs.max_len) || (a->d_bases && a->bases_cap < rowb) || (a->d_quals && a->quals_cap < rowb) || (a->d_lens && a->lens_cap < n_out) ||
+            (a->d_names && a->names_cap < names_len) || (a->d_name_off && a->off_cap < (size_t)n_out + 1)) {
+            const unsigned long long at = (unsigned long long)n_out * std::max(a->row_len, hs.max_len);
+            memset(res, 0, sizeof *res);
+            return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need row_len >= %u, %llu bytes per row buffer (at that row_len: %llu), %llu lens, %llu name bytes, %llu offsets",
+                            hs.max_len, rowb, at, (unsigned long long)n_out, (unsigned long long)names_len, (unsigned long long)n_out + 1);
+        }
+    }
+    if (n_out == 0) {
+        if (a->d_name_off) HIPCHK(ctx, hipMemsetAsync(a->d_name_off, 0, 8, S));
+        HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect();
+        return RFQ_OK;
+    }
+    ctx->timer.begin("select:tables", S);
+    SelRow* tab = nullptr; uint64_t* ooff = nullptr;
+    HIPCHK(ctx, table(B[B_X], (size_t)n_out * sizeof(SelRow), tab));
+    if (named) HIPCHK(ctx, table(B[B_Y], ((size_t)n_out + 1) * 8, ooff));
+    hipLaunchKernelGGL(k_sel_tables, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S, si, (const uint32_t*)pos, (const uint64_t*)noff, tab, ooff, a->d_lens, a->d_name_off);
+    KCHK(ctx, "k_sel_tables");
+    ctx->timer.end(S);
+    ctx->timer.begin("select:rows", S);
+    if (a->d_bases || a->d_quals) {
+        SelRowsOut o; memset(&o, 0, sizeof o);
+        o.sb = in->d_bases; o.sq = in->d_quals; o.bases = a->d_bases; o.quals = a->d_quals;
+        o.row_len_in = in->row_len; o.total_in = n * in->row_len; o.row_len = a->row_len; o.n_out = n_out;
+        o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
+        o.vec_in = (in->row_len % 16u == 0 && !(((a->d_bases ? (uintptr_t)in->d_bases : 0) | (a->d_quals ? (uintptr_t)in->d_quals : 0)) & 15u)) ? 1u : 0u;
+        o.vec = (a->row_len % 16u == 0 && !(((uintptr_t)a->d_bases | (uintptr_t)a->d_quals) & 15u)) ? 1u : 0u;
+        const uint32_t G = (a->row_len + 15u) / 16u;
+        o.per = std::max(1u, 1024u / G);                                    // about four groups per thread
+        hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)n_out + o.per - 1) / o.per)), dim3(256), 0, S, o, (const SelRow*)tab);
+        KCHK(ctx, "k_sel_rows");
+    }
+    ctx->timer.end(S);
+    ctx->timer.begin("select:names", S);
+    if (a->d_names && names_len) {
+        const uint64_t span = names_len + ((uintptr_t)a->d_names & 15u), blocks = (span + TN_TILE - 1) / TN_TILE;
+        if (blocks > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "a name blob of %llu bytes is too large for one call", (unsigned long long)names_len);
+        hipLaunchKernelGGL(k_sel_names, dim3((uint32_t)blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, names_len);
+        KCHK(ctx, "k_sel_names");
+    }
+    ctx->timer.end(S);
+    HIPCHK(ctx, hipStreamSynchronize(S));
+    ctx->timer.collect();
+    return RFQ_OK;
+}

@@ -12,20 +12,21 @@ and back - reads a basecaller, a simulator, a filter or a trimmer holds as tenso
     image = encode_tensors(codec, t["bases"], t["quals"], t["lens"], blob, off)      # uint8 tensor: the .rfq image
     text = rows_to_fastq(codec, t["bases"], t["quals"], t["lens"], blob, off)        # uint8 tensor: the FASTQ text
 
-decode -> filter -> encode, nothing on the host (rfq_decode_names gives the names in pack_names' layout):
+decode -> filter / trim -> encode, three calls and nothing on the host (rfq_decode_names gives the names in pack_names' layout, rfq_select_rows compacts rows,
+lengths, names and offsets in one pass):
 
     t = decode_tensors(codec, rfq, names=True)                                        # + "names": uint8 blob, "name_off": [n + 1] int64
-    keep = t["lens"] >= 100                                                           # any mask over the rows
-    off, ln = t["name_off"], t["name_off"][1:] - t["name_off"][:-1]
-    new_off = torch.cat([off[:1], ln[keep].cumsum(0)])
-    src = torch.repeat_interleave(off[:-1][keep] - new_off[:-1], ln[keep]) + torch.arange(int(new_off[-1]), device=off.device)
-    image = encode_tensors(codec, t["bases"][keep], t["quals"][keep], t["lens"][keep], t["names"][src], new_off)
+    s = select_rows(codec, t, keep=t["lens"] >= 100, pairs=True)                      # any mask over the rows; a pair stands or falls together
+    image = encode_tensors(codec, s["bases"], s["quals"], s["lens"], s["names"], s["name_off"], paired=PE_TWO_FILES)
 
-fastq -> filter -> encode, the same without an image in front (rfq_text_rows: the text's own bytes, nothing an image would lose is lost):
+fastq -> trim -> encode, the same without an image in front (rfq_text_rows: the text's own bytes, nothing an image would lose is lost); a window per row
+keeps bases [start, start + length) of it, a read trimmed below min_len is dropped:
 
     fq = torch.from_file("x.fastq", size=n, dtype=torch.uint8).cuda()
     t = fastq_to_tensors(codec, fq)                                                   # "bases", "quals", "lens", "names", "name_off", "consumed"
-    keep = t["lens"] >= 100                                                           # ... and on as above
+    s = select_rows(codec, t, start=torch.full_like(t["lens"], 5), length=t["lens"] - 10, min_len=30)
+
+A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
 
@@ -95,6 +96,46 @@ def fastq_to_tensors(codec, fq1: torch.Tensor, fq2: torch.Tensor = None, paired=
         codec.set_stream(None)
     out = {"bases": bases, "quals": quals, "lens": lens, "consumed": (int(q.consumed1), int(q.consumed2))}
     if names:
+        out["names"], out["name_off"] = blob, off
+    return out
+
+
+def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_len=1, row_len=None, pad=255):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "quals", "lens", optionally "names" + "name_off") -> a new dict with the same keys for the
+    rows that are KEPT, each TRIMMED to bases [start, start + length) (rfq_select_rows), plus "dropped": {"mask", "short", "mate"}.  keep: [n] bool or uint8,
+    non-zero = keep (None: every row); start / length: [n] int32 (None: 0 / to the end of the read); pairs: rows 2k / 2k + 1 stand or fall together; a row
+    whose window is shorter than min_len is dropped (and with pairs its mate); rows are padded with `pad` to row_len (None: the longest kept window).  The
+    bytes are the rows' own, names are kept whole.  A size query and one call, both ordered with torch's current stream; the context goes back to its own
+    stream afterwards."""
+    bases, quals, lens = t["bases"], t["quals"], t["lens"]
+    named = t.get("name_off") is not None
+    names, name_off = (t["names"], t["name_off"]) if named else (bases.new_empty((0,)), torch.zeros((int(bases.shape[0]) + 1,), dtype=torch.int64, device=bases.device))
+    n, L_in, p_b, p_q, p_l, p_n, nl_in, p_o = _rows_args(bases, quals, lens, names, name_off)
+    dev = bases.device
+    sel = {}
+    for key, v, dts in (("d_keep", keep, (torch.bool, torch.uint8)), ("d_start", start, (torch.int32,)), ("d_len", length, (torch.int32,))):
+        if v is not None:
+            assert v.dtype in dts and v.is_contiguous() and v.numel() == n and v.device == dev, "keep: [n] bool / uint8, start / length: [n] int32, on the rows' device"
+            sel[key] = v.data_ptr()
+    rows = (n, L_in, p_b, p_q, p_l, p_n if named else None, nl_in if named else 0, p_o if named else None)
+    kw = dict(pairs=pairs, min_len=min_len, **sel)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        q = codec.select_rows(*rows, **kw)
+        L = max(int(q.max_len), 1) if row_len is None else int(row_len)
+        m, nl = int(q.n_rows), int(q.names_len)
+        ob = torch.empty((m, L), dtype=torch.uint8, device=dev); oq = torch.empty((m, L), dtype=torch.uint8, device=dev)
+        ol = torch.empty((m,), dtype=torch.int32, device=dev)
+        blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if named else None
+        off = torch.zeros((m + 1,), dtype=name_off.dtype, device=dev) if named else None
+        if m:
+            codec.select_rows(*rows, row_len=L, pad_base=pad, pad_qual=pad, out_bases=ob.data_ptr(), bases_cap=m * L, out_quals=oq.data_ptr(), quals_cap=m * L,
+                              out_lens=ol.data_ptr(), lens_cap=m, out_names=blob.data_ptr() if (named and nl) else None, names_cap=nl if named else 0,
+                              out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **kw)
+    finally:
+        codec.set_stream(None)
+    out = {"bases": ob, "quals": oq, "lens": ol, "dropped": {"mask": int(q.dropped_mask), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}}
+    if named:
         out["names"], out["name_off"] = blob, off
     return out
 
