@@ -15,6 +15,8 @@
 #define G2_CAP 23552u             // staged text of a tile (64 x 357-byte records are 22.9 KB)
 #define G2_SE_OK 1                // 0: never take the single-end instantiation (A/B on the box: tools/build_variant.sh)
 #define G2_CNT 256u               // replicated quality counters (see QualCount)
+// bytes below 0x10 of a dword: 0x80 in their place (and - through a borrow - in a 0x10 right behind one of them: it can only flag too many).  Four instructions per four bytes.
+__device__ __forceinline__ uint32_t ctl_flags4(uint32_t w) { return (w - 0x10101010u) & ~w & 0x80808080u; }
 struct __attribute__((packed, aligned(1))) GU16g { uint32_t a, b, c, d; };
 // four bases -> four 2-bit codes (exact upper-case A/C/G/T, anything else 0), four "is N" bits, four "neither" bits
 __device__ __forceinline__ void pack4_codes(uint32_t w, uint32_t& code, uint32_t& nb, uint32_t& bad) {
@@ -51,7 +53,7 @@ __device__ __forceinline__ uint32_t g2_rev2x16(uint32_t v) {                // t
 }
 struct G2Geo { uint32_t a00, a01, end0, end1, base1; };                         // a tile's text spans: 16-aligned begin and end per stream, LDS offset of stream 1's span
 // my read: lengths, LDS offsets of its quality / sequence line, chunk-relative quality position, loose slot
-struct G2Read { bool on, rc; uint32_t len, qsrc, ssrc, qpos, ld, gi; };
+struct G2Read { bool on, rc; uint32_t len, qsrc, ssrc, qpos, ld, gi, nsrc; };       // (nsrc: LDS offset of its name line - the shared-table form's check alone uses it)
 // ---- what a tile needs before its text can be requested.  A tile BOUNDARY (where the text of tile k starts in each stream, its first quality position)
 // is a scalar load issued three tiles ahead, the lines of my read in the next tile are requested a tile ahead: the tile's only round trip at its start
 // is the text's own (they used to be two: boundaries, then text + lines).  (The text itself cannot be requested a tile ahead: into registers it costs 24
@@ -65,15 +67,16 @@ __device__ __forceinline__ uint32_t ld_uniform(const uint32_t* p) { return *p; }
 // a load whose address is the same in every lane, from memory no kernel in flight writes: constant address space -> s_load_dword, the value in an SGPR
 __device__ __forceinline__ uint32_t ld_uniform(const uint32_t* p) { return *(const __attribute__((address_space(4))) uint32_t*)(uintptr_t)p; }
 #endif
-__device__ __forceinline__ G2Bound g2_bound(const Text& T, bool two, const uint32_t* __restrict__ pq, uint32_t r) {   // r: uniform; even when `two`
+// SH: stream 1 is read through stream 0's line table (two files of one size) - one boundary, one geometry: l1 = l0, a01 = a00, end1 = end0 are the same values, not equal ones
+template <bool SH = false> __device__ __forceinline__ G2Bound g2_bound(const Text& T, bool two, const uint32_t* __restrict__ pq, uint32_t r) {   // r: uniform; even when `two`
     G2Bound b;
-    if (two) { const size_t k = 4 * (size_t)(r >> 1); b.l0 = ld_uniform(T.lo[0] + k); b.l1 = ld_uniform(T.lo[1] + k); }
+    if (two) { const size_t k = 4 * (size_t)(r >> 1); b.l0 = ld_uniform(T.lo[0] + k); b.l1 = SH ? b.l0 : ld_uniform(T.lo[1] + k); }
     else { b.l0 = ld_uniform(T.lo[0] + 4 * (size_t)r); b.l1 = 0u; }
     b.q = ld_uniform(pq + r);
     return b;
 }
-__device__ __forceinline__ G2Geo g2_geo(const G2Bound& b, const G2Bound& e, bool two) {
-    G2Geo g; g.a00 = b.l0 & ~15u; g.end0 = e.l0; g.a01 = two ? b.l1 & ~15u : 0u; g.end1 = two ? e.l1 : 0u;
+template <bool SH = false> __device__ __forceinline__ G2Geo g2_geo(const G2Bound& b, const G2Bound& e, bool two) {
+    G2Geo g; g.a00 = b.l0 & ~15u; g.end0 = e.l0; g.a01 = SH ? g.a00 : (two ? b.l1 & ~15u : 0u); g.end1 = SH ? g.end0 : (two ? e.l1 : 0u);
     g.base1 = two ? (((g.end0 - g.a00 + 15u) & ~15u) + 16u) : 0u;
     return g;
 }
@@ -92,7 +95,24 @@ __device__ __forceinline__ void g2_stage1(const uint8_t* __restrict__ fq, uint32
             // (what lies behind the text's end is put down as 0xFF, not left as whatever the LDS held: g2_ctl_count looks at whole groups)
             for (uint32_t k = 0; k < 16; k++) bytes[16 * nfull + k] = a0 + 16 * nfull + k < n ? src[16 * (size_t)nfull + k] : (uint8_t)0xFF; }
 }
-__device__ __forceinline__ void g2_stage(const Text& T, bool two, const G2Geo& g, uint4* buf4, uint32_t tid) {
+// the same for two files of one size behind one line table: both spans have the same begin, end and group count - one loop, the same group index for both
+__device__ __forceinline__ void g2_stage_shared(const uint8_t* __restrict__ fq0, const uint8_t* __restrict__ fq1, uint32_t n, uint32_t a0, uint32_t end, uint4* l40, uint4* l41,
+        uint32_t tid) {
+    const uint32_t nb = end - a0, ng = (nb + 15u) / 16u;
+    const uint8_t* s0 = fq0 + a0; const uint8_t* s1 = fq1 + a0;
+    const uint32_t nfull = (uint64_t)a0 + 16ull * ng <= (uint64_t)n ? ng : ng - 1u;
+    for (uint32_t i = tid; i < nfull; i += blockDim.x) {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + 16 * (size_t)i),
+                (__attribute__((address_space(3))) void*)(l40 + (i - (tid & 63u))), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s1 + 16 * (size_t)i),
+                (__attribute__((address_space(3))) void*)(l41 + (i - (tid & 63u))), 16, 0, 0);
+    }
+    if (nfull < ng && tid == 0) { uint8_t* const b0 = (uint8_t*)l40; uint8_t* const b1 = (uint8_t*)l41;
+            for (uint32_t k = 0; k < 16; k++) { const bool in = a0 + 16 * nfull + k < n; b0[16 * nfull + k] = in ? s0[16 * (size_t)nfull + k] : (uint8_t)0xFF;
+                    b1[16 * nfull + k] = in ? s1[16 * (size_t)nfull + k] : (uint8_t)0xFF; } }
+}
+template <bool SH = false> __device__ __forceinline__ void g2_stage(const Text& T, bool two, const G2Geo& g, uint4* buf4, uint32_t tid) {
+    if (SH) { g2_stage_shared(T.fq[0], T.fq[1], T.n[0], g.a00, g.end0, buf4, buf4 + g.base1 / 16, tid); return; }
     g2_stage1(T.fq[0], T.n[0], g.a00, g.end0, buf4, tid);
     if (two) g2_stage1(T.fq[1], T.n[1], g.a01, g.end1, buf4 + g.base1 / 16, tid);
 }
@@ -103,11 +123,11 @@ __device__ __forceinline__ G2MRaw g2_mraw(const Text& T, const uint32_t* __restr
     return r;
 }
 __device__ __forceinline__ G2Read g2_read(const Text& T, const G2MRaw& r, const G2Geo& g, uint32_t f, uint32_t pq0, bool il, uint32_t cur, uint32_t j, uint32_t cnt) {
-    G2Read m; m.on = j < cnt; m.rc = false; m.len = m.qsrc = m.ssrc = m.qpos = m.ld = 0; m.gi = cur + j;
+    G2Read m; m.on = j < cnt; m.rc = false; m.len = m.qsrc = m.ssrc = m.qpos = m.ld = m.nsrc = 0; m.gi = cur + j;
     if (m.on) {
         const uint32_t gi = cur + j; int s_; uint32_t r_; read_loc(T, gi, s_, r_);
         const uint32_t lb = s_ ? g.base1 : 0u, a = s_ ? g.a01 : g.a00;
-        m.len = r.lo4.z - 1u - r.lo4.y; m.ssrc = lb + (r.lo4.y - a); m.qsrc = lb + (r.lo4.w - a);
+        m.len = r.lo4.z - 1u - r.lo4.y; m.ssrc = lb + (r.lo4.y - a); m.qsrc = lb + (r.lo4.w - a); m.nsrc = lb + (r.lo4.x - a);
         m.qpos = r.pg - pq0; m.ld = (r.pg >> 4) + gi;
         m.rc = il && ((gi - f) & 1u);
     }
@@ -115,8 +135,9 @@ __device__ __forceinline__ G2Read g2_read(const Text& T, const G2MRaw& r, const 
 }
 // my share (groups part, part + P, ...) of my read's sequence line: 16 bases per step -> one dword of codes + 16 N bits into the read's loose slot, in STORED
 // orientation (an interleaved chunk's mate reverse-complemented, src/rfqcodec.cpp:371-407) but untrimmed: k_seqpack skips what the overlap with R1 implies
-__device__ __forceinline__ void g2_bases(const uint8_t* s_text, const G2Read& m, uint32_t part, uint32_t P, uint32_t* __restrict__ lpk, uint16_t* __restrict__ lnb,
-        uint8_t* __restrict__ rflag, uint8_t* __restrict__ rn) {
+// CHK (two files, one line table - see g2_ctl_line): a stream-1 read's group that is not all A/C/G/T raises the workgroup's flag (*s_bad, in LDS) when it holds a byte below 0x10
+template <bool CHK = false> __device__ __forceinline__ void g2_bases(const uint8_t* s_text, const G2Read& m, uint32_t part, uint32_t P, uint32_t* __restrict__ lpk, uint16_t* __restrict__ lnb,
+        uint8_t* __restrict__ rflag, uint8_t* __restrict__ rn, uint32_t* s_bad) {
     const uint32_t ng = (m.len + 15u) >> 4;
     for (uint32_t gi = part; gi < ng; gi += P) {
         uint32_t w[4], code = 0, nbits = 0;
@@ -137,12 +158,16 @@ __device__ __forceinline__ void g2_bases(const uint8_t* s_text, const G2Read& m,
                 for (int i = 0; i < 4; i++) { uint32_t c4, n4, b4; pack4_codes(w[i], c4, n4, b4); code |= c4 << (8 * i); nbits |= n4 << (4 * i); bad |= b4 << (4 * i); }
                 // a byte outside A/C/G/T/N: it equals nothing in RfqCodec::overlap (k_overlap's byte-wise path)
                 if (bad) rflag[m.gi] = 1;
+                // (every byte here is a base of the read or a blanked 'A')
+                if (CHK && (m.gi & 1u)) { if (ctl_flags4(w[0]) | ctl_flags4(w[1]) | ctl_flags4(w[2]) | ctl_flags4(w[3])) *s_bad = 1u; }
             }
         } else {
             lds_get16(s_text, tail ? m.ssrc : m.ssrc + m.len - 16u * gi - 16u, w);   // the 16 file bases that END at len - 16 gi
             if (nv0 < 16u && !tail) blank(0u, 16u - nv0);
             if (pack16_fast(w, code)) code = ~g2_rev2x16(code);             // reverse complement in 2-bit space: the fields back to front, G 0 <-> C 3, A 1 <-> T 2
             else {
+                // (two files whose mates pair up are stored like an interleaved chunk: stream 1's reads come this way in phase 1)
+                if (CHK && (m.gi & 1u)) { if (ctl_flags4(w[0]) | ctl_flags4(w[1]) | ctl_flags4(w[2]) | ctl_flags4(w[3])) *s_bad = 1u; }
                 const uint32_t x0 = bswap32(w[3]), x1 = bswap32(w[2]), x2 = bswap32(w[1]), x3 = bswap32(w[0]); w[0] = x0; w[1] = x1; w[2] = x2; w[3] = x3; code = 0;
 #pragma unroll
                 for (int i = 0; i < 4; i++) { uint32_t c4, n4; pack4_codes_rc(w[i], c4, n4); code |= c4 << (8 * i); nbits |= n4 << (4 * i); }
@@ -174,7 +199,7 @@ __device__ __forceinline__ void g2_compose(const uint8_t* s_text, const G2Read& 
             }
         } else for (uint32_t i = part; i < n; i += P) { const uint8_t q = s_text[rc ? m.qsrc + n - 1u - i : m.qsrc + i]; o[i] = q; qc(m.qpos + i, q); }
     }
-    g2_bases(s_text, m, part, P, lpk, lnb, rflag, rn);
+    g2_bases(s_text, m, part, P, lpk, lnb, rflag, rn, nullptr);
 }
 // FastqMeta::parse + RfqCodec::encodeChunk's pass 1 (src/fastqmeta.cpp:22-80, src/rfqcodec.cpp:220-263) for the reads of the tile k_gather2 has staged:
 // the name line is in LDS already, so the text is not fetched a third time for the names (the separate read-table pass cost 8.1 GB / 1.9 ms
@@ -352,14 +377,17 @@ __device__ __forceinline__ void g2_parse(const Text& T, const ReadTab& R, const 
 }
 // two files, one line table (see g2_ctl_count): a lane per read of the tile - the four line ends of a stream-1 record must be line feeds (the last one may be the
 // virtual terminator behind an unterminated text).  The parsing wave runs it behind g2_parse, on its own registers.
-__device__ __forceinline__ void g2_mirror_ends(const Text& T, const uint8_t* tx, const G2Geo& g, uint32_t cur, uint32_t cnt, uint32_t* mirror_err) {
+// same_len (the lanes' form of the control-byte test, g2_ctl_line): the quality lanes look at as many bytes as the sequence line has, so a record whose table entry has a
+// quality line of another length is not taken on trust either (such a text is broken in stream 0 already; the repeat decides as it would without the mirror)
+__device__ __forceinline__ void g2_mirror_ends(const Text& T, const uint8_t* tx, const G2Geo& g, uint32_t cur, uint32_t cnt, uint32_t* mirror_err, bool same_len = false) {
     const uint32_t l = (uint32_t)lane_id(); bool bad = false;
     if (l < cnt) {
         int s_; uint32_t r_; read_loc(T, cur + l, s_, r_);
         if (s_ == 1) {
             const uint32_t* const p = t_lo(T, 1) + 4 * (size_t)r_; const uint32_t o = g.base1 - g.a01, n = T.n[1];
             const uint32_t e1 = p[1], e2 = p[2], e3 = p[3], e4 = p[4];
-            bad = tx[o + e1 - 1u] != '\n' || tx[o + e2 - 1u] != '\n' || tx[o + e3 - 1u] != '\n' || (e4 - 1u < n && tx[o + e4 - 1u] != '\n');
+            bad = tx[o + e1 - 1u] != '\n' || tx[o + e2 - 1u] != '\n' || tx[o + e3 - 1u] != '\n' || (e4 - 1u < n && tx[o + e4 - 1u] != '\n') ||
+                  (same_len && e4 - e3 != e2 - e1);
         }
     }
     if (__any(bad)) { if (l == 0u) atomicOr(mirror_err, (uint32_t)DE_MIRROR_FAIL); }      // (wave-uniform; only where something is wrong)
@@ -384,10 +412,29 @@ __device__ __forceinline__ void g2_mirror_ends(const Text& T, const uint8_t* tx,
 struct G2Planes { uint32_t* planes; uint64_t pstride; uint32_t pw, nd; uint32_t* rare; uint32_t* mirror_err; };
 // ---- two files, one line table: what the gather proves about stream 1 as it goes (the host acts on DE_MIRROR_FAIL, rfq_encode.hip).  Every record a tile owns must hold
 // exactly four '\n', at its four line ends, and no '\r'.  In two parts: the parsing wave looks at the four line-end bytes of each of its stream-1 records (g2_mirror_ends), and
-// every thread counts the bytes below 0x10 in its share of the tile's staged stream-1 span; the workgroup's count must be its number of line ends.  Line ends that are all
-// '\n' and no control byte more than there are line ends: the line feeds are those, and there is no '\r'.  (The test also fires on the other bytes below 0x10 and - through
-// a borrow - on a 0x10 right behind one of them: it can only count too many, and a false alarm costs the repeat, nothing else.  Four instructions per four bytes.)
-__device__ __forceinline__ uint32_t ctl_flags4(uint32_t w) { return (w - 0x10101010u) & ~w & 0x80808080u; }
+// no line of the record may hold a byte below 0x10 (the test also fires on the other control bytes: a false alarm costs the repeat, nothing else).
+// The second part, match-mask form (k_gather2<true, 1, true>): in the lanes that hold the bytes anyway -
+//   * base line: a group with a byte outside A/C/G/T leaves pack16_fast for the exact path, one group in a few hundred: the test sits there (g2_bases<true>);
+//   * quality line: a byte that is neither the major value nor a dense one is taken out of its group one by one (g2_quals_masks' `rest` loop): the test sits there; the
+//     major and the dense values themselves come from chunk 0, read through the table that is still unproven - one of them below 0x10 fails the kernel at its start;
+//   * name and '+' line: g2_ctl_line, the read's P lanes over the lines' 16-byte groups in LDS, right behind the tile's first barrier.
+// The verdict is one word of LDS that only a lane that found something writes (the word the count's sum uses), read once at the kernel's end: a flag kept per thread
+// through the tile loop put four VGPRs into scratch, an atomicOr on the status word where the byte is found six (profiles/r13_gather_isa_stats.txt).
+// Byte-stream form (<false, -1>: its quality bytes have no rare path): every thread counts the bytes below 0x10 in its share of the tile's staged stream-1 span; the
+// workgroup's count must be its number of line ends (g2_ctl_count).
+// bytes [a, a + n) of the staged text, the share of lane `part` of the line's P lanes: a byte below 0x10 among them?  16 bytes per step; the last group of a line of >= 16 bytes
+// is moved back to end at the line's end, a shorter line goes byte by byte: nothing outside the line is read
+__device__ __forceinline__ uint32_t g2_ctl_line(const uint8_t* tx, uint32_t a, uint32_t n, uint32_t part, uint32_t P) {
+    uint32_t f = 0;
+    if (n >= 16u) {
+        const uint32_t ng = (n + 15u) >> 4;
+        for (uint32_t gi = part; gi < ng; gi += P) {
+            uint32_t p0 = 16u * gi; if (p0 + 16u > n) p0 = n - 16u;
+            uint32_t w[4]; lds_get16(tx, a + p0, w); f |= ctl_flags4(w[0]) | ctl_flags4(w[1]) | ctl_flags4(w[2]) | ctl_flags4(w[3]);
+        }
+    } else for (uint32_t i = part; i < n; i += P) if (tx[a + i] < 0x10u) f = 1u;
+    return f;
+}
 __device__ __forceinline__ uint32_t ctl_count16(const uint4& q) {       // flagged bytes of a 16-byte group
     return (uint32_t)__popc(ctl_flags4(q.x)) + (uint32_t)__popc(ctl_flags4(q.y)) + (uint32_t)__popc(ctl_flags4(q.z)) + (uint32_t)__popc(ctl_flags4(q.w));
 }
@@ -408,9 +455,9 @@ __device__ __forceinline__ void g2_rare_or(uint32_t* __restrict__ gpl, uint64_t 
     // the word's first bit: remember the word
     if (old == 0u) { const uint32_t k = atomicAdd(rare_c, 1u); if (k < G2_RARE_LIST) rare_c[1u + k] = (plane << 28) | (pos >> 5); }
 }
-__device__ __forceinline__ void g2_quals_masks(const uint8_t* tx, const G2Read& m, uint32_t part, uint32_t P, uint32_t* pl, uint32_t pw, uint32_t wbase, uint32_t nd,
+template <bool CHK = false> __device__ __forceinline__ void g2_quals_masks(const uint8_t* tx, const G2Read& m, uint32_t part, uint32_t P, uint32_t* pl, uint32_t pw, uint32_t wbase, uint32_t nd,
                                                uint32_t pat0, uint32_t pat1, uint32_t pat2, uint32_t patm, const DevHeader* __restrict__ D, uint8_t* qd, uint32_t* __restrict__ gpl, uint64_t pstride,
-                                               uint32_t* __restrict__ segm_c, int* __restrict__ segc_c, uint32_t n_seg, uint32_t* __restrict__ rare_c) {
+                                               uint32_t* __restrict__ segm_c, int* __restrict__ segc_c, uint32_t n_seg, uint32_t* __restrict__ rare_c, uint32_t* s_bad) {
     if (!m.on) return;
     const uint32_t n = m.len, ng = (n + 15u) >> 4; const bool rc = m.rc;
     for (uint32_t gi = part; gi < ng; gi += P) {
@@ -436,6 +483,7 @@ __device__ __forceinline__ void g2_quals_masks(const uint8_t* tx, const G2Read& 
         while (rest) {
             const uint32_t k = (uint32_t)__ffs((int)rest) - 1u; rest &= rest - 1u;
             const uint32_t ww = k < 8u ? (k < 4u ? w[0] : w[1]) : (k < 12u ? w[2] : w[3]), pos = m.qpos + p0 + k, b = (ww >> (8u * (k & 3u))) & 0xFFu;
+            if (CHK && b < 0x10u && (m.gi & 1u)) *s_bad = 1u;               // (two files, one line table: a control byte in stream 1's quality line)
             const uint32_t j = D->stream_of[b];
             if (j < 4u && j < D->n_normal) { const size_t si = (size_t)j * n_seg + pos / PC_SEG_POS; g2_rare_or(gpl, pstride, rare_c, j, pos); atomicAdd(&segm_c[si], 1u);
                     atomicMax(&segc_c[si], (int)pos); }
@@ -489,12 +537,16 @@ __global__ void k_mask_bounds(const uint32_t* __restrict__ pq, const uint32_t* _
 // PE = false: single-end input - no second stream, no mates, nothing stored back to front: the instantiation drops those paths and the values they keep alive
 // PAIRED = 0 / 1 / 2: the input's pairing (RFQ_SE / RFQ_PE_TWO_FILES / RFQ_PE_INTERLEAVED) as a compile-time constant - every read_loc, every "which stream" select and, for
 // single-end input, the mates' whole path fold away; -1: taken from the argument
-template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6) k_gather2(Text T_, ReadTab R, const uint32_t* __restrict__ first, const uint64_t* __restrict__ qbase,
+// MIRROR (<true, 1, true> only): stream 1 is read through stream 0's line table - T.lo[1] IS T.lo[0], T.n[1] == T.n[0] (enc_index) - as a compile-time fact: one boundary and
+// one geometry per tile, one staging loop, and the proof of it (above g2_ctl_line) in the lanes that hold the bytes.  <true, 1> is two files with a table each: no check.
+template <bool MASKS, int PAIRED = -1, bool MIRROR = false> __global__ void __launch_bounds__(256, 6) k_gather2(Text T_, ReadTab R, const uint32_t* __restrict__ first, const uint64_t* __restrict__ qbase,
                                                  const DevHeader* __restrict__ D, uint8_t* __restrict__ qcat, uint32_t* __restrict__ lpk, uint16_t* __restrict__ lnb, uint8_t* __restrict__ rflag,
                                                  uint8_t* __restrict__ rn, uint32_t* __restrict__ segm, int* __restrict__ segc, uint32_t n_seg, uint32_t kshift,
                                                  uint32_t* __restrict__ cbits, uint32_t* __restrict__ cfail, const uint32_t* __restrict__ only, uint32_t text4, G2Planes M) {
+    static_assert(!MIRROR || (MASKS && PAIRED == 1), "the shared-table form is the match-mask form of two files");
     Text T = T_; if (PAIRED >= 0) T.paired = PAIRED;
-    constexpr bool PE = PAIRED != 0;
+    if (MIRROR) { T.lo[1] = T.lo[0]; T.n[1] = T.n[0]; }
+    constexpr bool PE = PAIRED != 0, SH = MIRROR, LANES = MIRROR;          // (the fold of the second table; the proof in the lanes)
     RFQ_DYN_SHARED(uint4, g2_lds);
     __shared__ uint32_t sh[MASKS ? 1 : G2_CNT]; __shared__ int sh_last[MASKS ? 1 : G2_CNT]; __shared__ uint8_t s_slot[MASKS ? 16 : 256];
             __shared__ uint32_t s_r0[8], s_carry[4], s_mctl;
@@ -537,8 +589,15 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
     const bool parse = !redo && gs < ge;                                    // block-uniform
     // two files through one line table (phase 1 proves it; phase 2 repeats chunks it has seen): my count of stream 1's control bytes, the line ends my workgroup owns
     // (the instantiations that take two files: <MASKS, 1> and the generic byte-stream form; the generic match-mask form is interleaved input's and stays as it was)
-    const bool mirror = (PAIRED == 1 || (PAIRED == -1 && !MASKS)) && two && !redo && M.mirror_err != nullptr;
+    const bool mirror = PAIRED == -1 && !MASKS && two && !redo && M.mirror_err != nullptr;     // (the byte-stream form's count)
     uint32_t mwant = 0;
+    // (the lanes' tests are not gated on !redo as the count is: phase 2 repeats a few chunks phase 1 has proven, the same bytes give the same verdict, and a
+    // block-uniform flag kept through the tile loop for them is a live SGPR more in a kernel that spills 173)
+    if (LANES) {
+        // a control value that chunk 0 made the major or a dense one would pass as "known": not through this table
+        const bool tb = (patm & 0xF0u) == 0u || (nd > 0u && (pat0 & 0xF0u) == 0u) || (nd > 1u && (pat1 & 0xF0u) == 0u) || (nd > 2u && (pat2 & 0xF0u) == 0u);
+        if (tb && tid == 0) atomicOr(M.mirror_err, (uint32_t)DE_MIRROR_FAIL);
+    }
     if (parse) {
         // read 0 of the chunk: the first bytes of its name and strand lines into LDS, its name parsed by one lane
         uint32_t r_; read_loc(T, f, r0.s, r_); const uint32_t* p = t_lo(T, r0.s) + 4 * (size_t)r_;
@@ -559,26 +618,29 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
     // boundaries b0 .. b2 of tiles t, t + 1, t + 2 are here, b3 is requested; my read's lines in tile t are in `mr` (requested a tile ago)
     const uint32_t ntile = gs < ge ? (ge - gs + K - 1u) >> kshift : 0u;
     auto tile_at = [&](uint32_t t_) -> uint32_t { const uint32_t x = gs + (t_ << kshift); return x < ge ? x : ge; };
-    G2Bound b0 = g2_bound(T, two, pq, tile_at(0)), b1 = g2_bound(T, two, pq, tile_at(1)), b2 = g2_bound(T, two, pq, tile_at(2));
+    G2Bound b0 = g2_bound<SH>(T, two, pq, tile_at(0)), b1 = g2_bound<SH>(T, two, pq, tile_at(1)), b2 = g2_bound<SH>(T, two, pq, tile_at(2));
     G2MRaw mr = g2_mraw(T, pq, gs, j, ntile ? tile_at(1) - gs : 0u);
-    if (ntile) g2_stage(T, two, g2_geo(b0, b1, two), buf4, tid);
+    if (ntile) g2_stage<SH>(T, two, g2_geo<SH>(b0, b1, two), buf4, tid);
     for (uint32_t t = 0; t < ntile; t++, tix++) {                          // block-uniform
         const uint32_t cur = tile_at(t), cnt = tile_at(t + 1u) - cur;
-        const G2Geo g = g2_geo(b0, b1, two);                                // (its text was requested before the previous tile's flush)
+        const G2Geo g = g2_geo<SH>(b0, b1, two);                                // (its text was requested before the previous tile's flush)
         const G2Read m = g2_read(T, mr, g, f, pq0, il, cur, j, cnt);
         const uint32_t qbeg = b0.q - pq0, qend = b1.q - pq0;               // the tile's quality positions (chunk-relative)
         { const uint32_t ncur = tile_at(t + 1u); mr = g2_mraw(T, pq, ncur, j, tile_at(t + 2u) - ncur); }
-        const G2Bound b3 = g2_bound(T, two, pq, tile_at(t + 3u));
+        const G2Bound b3 = g2_bound<SH>(T, two, pq, tile_at(t + 3u));
         __syncthreads();                                                    // (drains the LDS-DMA)
+        // (stream 1's name and '+' line: [nsrc, ssrc - 1) and [ssrc + len + 1, qsrc - 1); the even reads' waves pass by)
+        if (LANES) { if (m.on && (m.gi & 1u)) { const uint32_t ts = m.ssrc + m.len + 1u;
+                if (g2_ctl_line(tx, m.nsrc, m.ssrc - 1u - m.nsrc, part, P) | g2_ctl_line(tx, ts, m.qsrc - 1u - ts, part, P)) s_mctl = 1u; } }
         qc.seg0 = qbeg / PC_SEG_POS;
         // (wave-uniform: this tile's parsing wave)
         if (parse && (uint32_t)wave_id() == (tix & 3u)) { g2_parse(T, R, tx, REFN, REFS, g, r0, f, cur, cnt, can0, dpos, dch, acc);
-                if (mirror) g2_mirror_ends(T, tx, g, cur, cnt, M.mirror_err); }
+                if (mirror || LANES) g2_mirror_ends(T, tx, g, cur, cnt, M.mirror_err, LANES); }
         if (MASKS) {
             if (tid < nd && s_carry[tid]) atomicOr(&pl[tid * M.pw], s_carry[tid]);       // the word the tile in front left unfinished
-            g2_quals_masks(tx, m, part, P, pl, M.pw, qbeg & ~31u, nd, pat0, pat1, pat2, patm, D, qd, gpl, M.pstride, segm + (size_t)c * MAX_STREAMS * n_seg,
-                    segc + (size_t)c * MAX_STREAMS * n_seg, n_seg, M.rare + (size_t)c * (1u + G2_RARE_LIST));
-            g2_bases(tx, m, part, P, lpk, lnb, rflag, rn);
+            g2_quals_masks<LANES>(tx, m, part, P, pl, M.pw, qbeg & ~31u, nd, pat0, pat1, pat2, patm, D, qd, gpl, M.pstride, segm + (size_t)c * MAX_STREAMS * n_seg,
+                    segc + (size_t)c * MAX_STREAMS * n_seg, n_seg, M.rare + (size_t)c * (1u + G2_RARE_LIST), &s_mctl);
+            g2_bases<LANES>(tx, m, part, P, lpk, lnb, rflag, rn, &s_mctl);
         } else g2_compose(tx, m, part, P, qd, lpk, lnb, rflag, rn, qc);
         if (mirror) {                                                       // (block-uniform) stream 1's staged span, up to the text's end: two line ends per read of the tile
             const uint32_t end1 = g.end1 < T.n[1] ? g.end1 : T.n[1];
@@ -587,7 +649,7 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
             mwant += 2u * cnt - (g.end1 > T.n[1] ? 1u : 0u);
         }
         __syncthreads();                                                    // the text is free for the next tile; the tile's counts / planes are complete
-        if (t + 1u < ntile) g2_stage(T, two, g2_geo(b1, b2, two), buf4, tid);  // the next tile's text is on its way while the planes / counters of this one leave
+        if (t + 1u < ntile) g2_stage<SH>(T, two, g2_geo<SH>(b1, b2, two), buf4, tid);  // the next tile's text is on its way while the planes / counters of this one leave
         if (MASKS) {
             const uint32_t gw0 = qbeg >> 5, nw = ((qend + 31u) >> 5) - gw0; const bool last_tile = cur + cnt >= ge;
             g2_flush_masks(pl, M.pw, nd, dense3, s_carry, gpl, M.pstride, gw0, nw, !last_tile && (qend & 31u) != 0u, cur == gs && gs > f && (qbeg & 31u) != 0u,
@@ -604,6 +666,7 @@ template <bool MASKS, int PAIRED = -1> __global__ void __launch_bounds__(256, 6)
         __syncthreads();
         if (tid == 0 && s_mctl != mwant) atomicOr(M.mirror_err, (uint32_t)DE_MIRROR_FAIL);
     }
+    if (LANES) { __syncthreads(); if (tid == 0 && s_mctl) atomicOr(M.mirror_err, (uint32_t)DE_MIRROR_FAIL); }      // (s_mctl: here the lanes' flag, not a count)
 }
 // phase 2 of the gather re-counts the qualities of the chunks it repeats: their per-(stream, segment) entries back to "nothing seen"
 __device__ __forceinline__ uint32_t dense_mask_of(const DevHeader* __restrict__ D, uint32_t nd) { uint32_t m = 0;

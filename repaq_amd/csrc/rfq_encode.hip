@@ -520,6 +520,8 @@ static int enc_gather_tiles(rfq_ctx* ctx, const EncBatch& b, const EncCut& cut, 
         // (single-end input with match masks: the instantiation without mates - 132 spilled SGPRs instead of 182, no VGPR in scratch; the byte-stream form of it
         // spills 64 VGPRs instead and is not used)
         if (f.masks && !b.is_pe && G2_SE_OK) hipLaunchKernelGGL((k_gather2<true, 0>), dim3(bx, cut.n_chunks), dim3(256), dyn, S, RFQ_G2_ARGS);
+        // (two files: through one line table - the fact is the instantiation's, with its proof - or with a table each)
+        else if (f.masks && b.a->paired == RFQ_PE_TWO_FILES && G2_SE_OK && b.mirrored) hipLaunchKernelGGL((k_gather2<true, 1, true>), dim3(bx, cut.n_chunks), dim3(256), dyn, S, RFQ_G2_ARGS);
         else if (f.masks && b.a->paired == RFQ_PE_TWO_FILES && G2_SE_OK) hipLaunchKernelGGL((k_gather2<true, 1>), dim3(bx, cut.n_chunks), dim3(256), dyn, S, RFQ_G2_ARGS);
         else if (f.masks) hipLaunchKernelGGL(k_gather2<true>, dim3(bx, cut.n_chunks), dim3(256), dyn, S, RFQ_G2_ARGS);
         else hipLaunchKernelGGL(k_gather2<false>, dim3(bx, cut.n_chunks), dim3(256), dyn, S, RFQ_G2_ARGS);
