@@ -342,6 +342,68 @@ typedef struct {
 } rfq_select_rows_result;
 RFQ_API int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_select_rows_args* args, rfq_select_rows_result* res);
 
+/* The step that DECIDES, in front of rfq_select_rows: rows -> per row a keep byte, a window (start, len), a reason byte and four metrics - exactly the d_keep /
+ * d_start / d_len arrays rfq_select_rows takes - and one QC summary of the batch.  Quality trimming and filtering by integer rules of this project's own
+ * (a sliding window in the manner of Trimmomatic, filters in the manner of fastp; no parity with either is claimed).  No float anywhere, products in 64 bits.
+ * A quality row byte IS the score (rows hold "quality character minus qual_offset"; rows->qual_offset is not looked at).  rows->base_mode says what a base
+ * byte is: N is code 4 or 'N' / 'n', G is code 2 or 'G' / 'g'.  Names are not looked at (d_names / d_name_off may be NULL).
+ * Per row with l = lens[i], bases b, scores q and S(p, w) = q[p] + ... + q[p + w - 1], in this order; a step that is off, or whose window [a, e) is already
+ * empty, is skipped:
+ *   a = min(trim_front, l);  e = max(a, l - min(trim_tail, l))
+ *   poly_g > 0:      r = length of the run of G that ends at e - 1 inside [a, e);  r >= poly_g: e -= r
+ *   RFQ_CUT_FRONT:   w = min(cut_window, e - a);  p = the smallest p in [a, e - w] with S(p, w) >= cut_mean_q * w;  none: e = a;  else a = p
+ *   RFQ_CUT_RIGHT:   w = min(cut_window, e - a);  p = the smallest p in [a, e - w] with S(p, w) <  cut_mean_q * w;  found: e = p
+ *   RFQ_CUT_TAIL:    w = min(cut_window, e - a);  p = the largest  p in [a, e - w] with S(p, w) >= cut_mean_q * w;  none: e = a;  else e = p + w
+ *   max_len > 0:     e = min(e, a + max_len)
+ *   start = a;  len = n = e - a
+ * Metrics of the final window: qsum = S(a, n); n_cnt = its N; lowq = its q < qual_q (0 with qual_q == 0); trans = the j in [a, e - 1) with b[j] != b[j + 1]
+ * (a byte compare).  All reasons are evaluated and ORed into why; keep = (why == 0):
+ *   RFQ_WHY_SHORT    n < min_len                        RFQ_WHY_N        max_n >= 0 && n_cnt > max_n
+ *   RFQ_WHY_MEANQ    qsum < min_mean_q * n              RFQ_WHY_LOWQ     qual_q > 0 && lowq * 100 > max_lowq_pct * n
+ *   RFQ_WHY_COMPLEX  n > 1 && trans * 100 < min_complexity_pct * (n - 1)
+ * The pair rule is rfq_select_rows's (pairs = 1): this call judges each row on its own.
+ * Every output is [n_rows] entries (d_metrics [n_rows][4]: qsum, n_cnt, lowq, trans); an output that is NULL is not produced; the result is filled also when all
+ * five are NULL.  The *_in fields are taken over the whole reads [0, l), the *_out fields over the windows of the kept rows; q20 / q30: scores >= 20 / >= 30.
+ * RFQ_E_ARG, judged on the host: unknown cut_flags bits, a cut flag with cut_window outside 1 .. 1000, a percentage above 100, a bad base_mode, row_len == 0 with
+ * rows, d_quals == NULL with a quality criterion set (a cut flag, min_mean_q, qual_q), d_bases == NULL with poly_g, max_n >= 0 or min_complexity_pct set, a d_lens /
+ * d_start / d_len / d_metrics that is not 4-byte aligned, an output that overlaps an input.  RFQ_E_ARG, judged on the device, the message names the first such
+ * row: lens[i] < 0 or > row_len - what the outputs hold is then unspecified; nothing outside the row buffers is read for such a row.  After any refusal the context
+ * stays usable.
+ * The row buffers may have any alignment: with row_len % 16 == 0 and 16-byte alignment they are loaded in whole 16-byte groups, otherwise at their own alignment -
+ * never a byte outside [d_x, d_x + n_rows * row_len).  n_rows * row_len may exceed 4 GiB (n_rows < 2^31).  Every sum is an integer: the same call gives the same
+ * bytes.  Synchronous on the context's stream; stage time through rfq_last_timings (judge:rows). */
+#define RFQ_CUT_FRONT   1u
+#define RFQ_CUT_RIGHT   2u
+#define RFQ_CUT_TAIL    4u
+#define RFQ_WHY_SHORT   1u
+#define RFQ_WHY_N       2u
+#define RFQ_WHY_MEANQ   4u
+#define RFQ_WHY_LOWQ    8u
+#define RFQ_WHY_COMPLEX 16u
+typedef struct {
+    uint32_t trim_front, trim_tail;       /* bases taken off either end first                                           */
+    uint32_t poly_g;                      /* > 0: a trailing run of at least that many G is cut                         */
+    uint32_t cut_flags;                   /* RFQ_CUT_FRONT | RFQ_CUT_RIGHT | RFQ_CUT_TAIL                               */
+    uint32_t cut_window, cut_mean_q;      /* 1 .. 1000 with a cut flag; a window is good when its sum >= cut_mean_q * w */
+    uint32_t max_len;                     /* > 0: the window is cut to that many bases                                  */
+    uint32_t min_len;
+    int32_t  max_n;                       /* < 0: off                                                                   */
+    uint32_t min_mean_q, qual_q, max_lowq_pct, min_complexity_pct;
+    uint32_t reserved;
+    uint8_t*  d_keep;                     /* [n_rows] 1 / 0, or NULL                                                    */
+    int32_t*  d_start;                    /* [n_rows] or NULL                                                           */
+    int32_t*  d_len;                      /* [n_rows] or NULL                                                           */
+    uint8_t*  d_why;                      /* [n_rows] RFQ_WHY_* bits, or NULL                                           */
+    uint32_t* d_metrics;                  /* [n_rows][4] qsum, n_cnt, lowq, trans, or NULL                              */
+} rfq_judge_rows_args;
+typedef struct {
+    uint64_t n_rows, n_kept;
+    uint64_t why_short, why_n, why_meanq, why_lowq, why_complex;   /* rows with that bit set                            */
+    uint64_t bases_in, qsum_in, q20_in, q30_in;                    /* over the whole reads                              */
+    uint64_t bases_out, qsum_out, q20_out, q30_out;                /* over the windows of the kept rows                 */
+} rfq_judge_rows_result;
+RFQ_API int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_judge_rows_args* args, rfq_judge_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -375,7 +437,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

@@ -116,6 +116,22 @@ class SelectRowsResult(C.Structure):
                 ("n_in", C.c_uint64), ("dropped_mask", C.c_uint64), ("dropped_short", C.c_uint64), ("dropped_mate", C.c_uint64)]
 
 
+CUT_FRONT, CUT_RIGHT, CUT_TAIL = 1, 2, 4
+WHY_SHORT, WHY_N, WHY_MEANQ, WHY_LOWQ, WHY_COMPLEX = 1, 2, 4, 8, 16
+
+
+class JudgeRowsArgs(C.Structure):
+    _fields_ = [("trim_front", C.c_uint32), ("trim_tail", C.c_uint32), ("poly_g", C.c_uint32), ("cut_flags", C.c_uint32), ("cut_window", C.c_uint32),
+                ("cut_mean_q", C.c_uint32), ("max_len", C.c_uint32), ("min_len", C.c_uint32), ("max_n", C.c_int32), ("min_mean_q", C.c_uint32),
+                ("qual_q", C.c_uint32), ("max_lowq_pct", C.c_uint32), ("min_complexity_pct", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_keep", C.c_void_p), ("d_start", C.c_void_p), ("d_len", C.c_void_p), ("d_why", C.c_void_p), ("d_metrics", C.c_void_p)]
+
+
+class JudgeRowsResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_rows", "n_kept", "why_short", "why_n", "why_meanq", "why_lowq", "why_complex", "bases_in", "qsum_in", "q20_in",
+                                          "q30_in", "bases_out", "qsum_out", "q20_out", "q30_out")]
+
+
 _libs = {}
 
 
@@ -150,6 +166,7 @@ def load(path=None):
     L.rfq_encode_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(EncodeArgs), C.POINTER(EncodeResult)]
     L.rfq_text_rows.argtypes = [C.c_void_p, C.POINTER(TextRowsArgs), C.POINTER(TextRowsResult)]
     L.rfq_select_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(SelectRowsArgs), C.POINTER(SelectRowsResult)]
+    L.rfq_judge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(JudgeRowsArgs), C.POINTER(JudgeRowsResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -173,6 +190,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

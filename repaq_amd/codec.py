@@ -317,6 +317,25 @@ class RfqCodec:
         self._check(self._L.rfq_select_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
+    # --- the step that decides: rows -> keep, window, reason and metrics per row (rfq_judge_rows)
+    def judge_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, codes=False, trim_front=0, trim_tail=0, poly_g=0, cut_front=False, cut_right=False,
+                   cut_tail=False, cut_flags=None, cut_window=0, cut_mean_q=0, max_len=0, min_len=0, max_n=-1, min_mean_q=0, qual_q=0, max_lowq_pct=0,
+                   min_complexity_pct=0, d_keep=None, d_start=None, d_len=None, d_why=None, d_metrics=None, base_mode=None):
+        """rfq_judge_rows: the rows as rows_to_text takes them (names are not looked at; a quality byte is the score) and the criteria of include/rfq_hip.h:
+        trim_front / trim_tail, poly_g, cut_front / cut_right / cut_tail (or cut_flags as bits) with cut_window and cut_mean_q, max_len; then min_len, max_n
+        (< 0: off), min_mean_q, qual_q + max_lowq_pct, min_complexity_pct.  d_keep / d_why: n_rows bytes, d_start / d_len: n_rows int32 - what select_rows
+        takes -, d_metrics: n_rows x 4 uint32 (qsum, n_cnt, lowq, trans); an output that is None is not produced.  Returns JudgeRowsResult (n_rows, n_kept,
+        why_short, why_n, why_meanq, why_lowq, why_complex, bases / qsum / q20 / q30 _in and _out)."""
+        rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, codes, 0)
+        if base_mode is not None:
+            rows.base_mode = base_mode                                       # (as it stands, for callers that keep the C constants)
+        flags = cut_flags if cut_flags is not None else (A.CUT_FRONT if cut_front else 0) | (A.CUT_RIGHT if cut_right else 0) | (A.CUT_TAIL if cut_tail else 0)
+        a = A.JudgeRowsArgs(trim_front, trim_tail, poly_g, flags, cut_window, cut_mean_q, max_len, min_len, max_n, min_mean_q, qual_q, max_lowq_pct,
+                            min_complexity_pct, 0, d_keep, d_start, d_len, d_why, d_metrics)
+        r = A.JudgeRowsResult()
+        self._check(self._L.rfq_judge_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

@@ -1326,3 +1326,68 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     ctx->timer.collect();
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- rows -> keep, window, reason and metrics per row, one QC summary: rfq_judge_rows of include/rfq_hip.h
+// One kernel and one read-back (the verdict block with the sums).  Which kernel is the row length's to say: up to 256 bytes a DPP row of 16 lanes holds a row,
+// up to 1024 a wave, beyond that (or with RFQ_JUDGE=general, in tiles of 64) a wave walks it in tiles (enc/rows_judge.h).
+extern "C" int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_judge_rows_args* a, rfq_judge_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows;
+    if (a->cut_flags & ~(RFQ_CUT_FRONT | RFQ_CUT_RIGHT | RFQ_CUT_TAIL)) return rfq_fail(ctx, RFQ_E_ARG, "unknown cut_flags bits (0x%x)", a->cut_flags);
+    if (a->cut_flags && (a->cut_window < 1u || a->cut_window > 1000u)) return rfq_fail(ctx, RFQ_E_ARG, "cut_window must be 1 .. 1000 with a cut flag (got %u)", a->cut_window);
+    if (a->max_lowq_pct > 100u || a->min_complexity_pct > 100u) return rfq_fail(ctx, RFQ_E_ARG, "a percentage is 0 .. 100 (max_lowq_pct %u, min_complexity_pct %u)", a->max_lowq_pct, a->min_complexity_pct);
+    if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode);
+    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    if (n && !in->d_lens) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens");
+    const bool need_q = a->cut_flags || a->min_mean_q || a->qual_q, need_b = a->poly_g || a->max_n >= 0 || a->min_complexity_pct;
+    if (n && need_q && !in->d_quals) return rfq_fail(ctx, RFQ_E_ARG, "a quality criterion (a cut flag, min_mean_q, qual_q) needs rows->d_quals");
+    if (n && need_b && !in->d_bases) return rfq_fail(ctx, RFQ_E_ARG, "a base criterion (poly_g, max_n, min_complexity_pct) needs rows->d_bases");
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_start | (uintptr_t)a->d_len | (uintptr_t)a->d_metrics) & 3u)
+        return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_start, d_len and d_metrics must be 4-byte aligned");
+    {
+        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
+        const struct { const void* p; unsigned long long n; const char* what; } ins[] = {
+            { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" } };
+        const struct { const void* p; unsigned long long n; const char* what; } outs[] = {
+            { a->d_keep, n, "d_keep" }, { a->d_start, n * 4ull, "d_start" }, { a->d_len, n * 4ull, "d_len" }, { a->d_why, n, "d_why" }, { a->d_metrics, n * 16ull, "d_metrics" } };
+        for (const auto& o : outs) for (const auto& i : ins)
+            if (sel_overlap(o.p, o.n, i.p, i.n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the input %s", o.what, i.what);
+    }
+    res->n_rows = n;
+    if (!n) return RFQ_OK;
+    hipStream_t S = ctx->stream;
+    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    JudgeIn ji; memset(&ji, 0, sizeof ji);
+    ji.b = in->d_bases; ji.q = in->d_quals; ji.lens = in->d_lens; ji.total = n * in->row_len; ji.n_rows = (uint32_t)n; ji.row_len = in->row_len;
+    ji.vec_in = (in->row_len % 16u == 0 && !(((uintptr_t)in->d_bases | (uintptr_t)in->d_quals) & 15u)) ? 1u : 0u;
+    ji.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u;
+    ji.trim_front = a->trim_front; ji.trim_tail = a->trim_tail; ji.poly_g = a->poly_g; ji.cut_flags = a->cut_flags; ji.cut_window = a->cut_window; ji.cut_mean_q = a->cut_mean_q;
+    ji.max_len = a->max_len; ji.min_len = a->min_len; ji.max_n = a->max_n; ji.min_mean_q = a->min_mean_q; ji.qual_q = a->qual_q; ji.max_lowq_pct = a->max_lowq_pct;
+    ji.min_complexity_pct = a->min_complexity_pct;
+    ji.keep = a->d_keep; ji.start = a->d_start; ji.len = a->d_len; ji.why = a->d_why; ji.metrics = a->d_metrics;
+    const bool general = ctx->opt.judge_general || in->row_len > 1024u;
+    ji.tile = ctx->opt.judge_general ? 64u : 1024u;
+    ctx->timer.begin("judge:rows", S);
+    HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(JudgeStat)));
+    JudgeStat* dst = ctx->rows_stat.as<JudgeStat>();
+    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(JudgeStat), S));
+    HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+    if (general) hipLaunchKernelGGL(k_judge_rows_long, dim3((uint32_t)n), dim3(64), 0, S, ji, dst);
+    else if (in->row_len <= 256u) hipLaunchKernelGGL(k_judge_rows<16>, dim3((uint32_t)((n + 16u * JR_ITER - 1u) / (16u * JR_ITER))), dim3(256), 0, S, ji, dst);
+    else hipLaunchKernelGGL(k_judge_rows<64>, dim3((uint32_t)((n + 4u * JR_ITER - 1u) / (4u * JR_ITER))), dim3(256), 0, S, ji, dst);
+    KCHK(ctx, "k_judge_rows");
+    ctx->timer.end(S);
+    JudgeStat hs; memset(&hs, 0, sizeof hs);
+    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    ctx->timer.collect();
+    if (hs.err & JR_ERR_LEN)
+        return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, (unsigned long long)hs.bad_row);
+    res->n_kept = hs.c[0]; res->why_short = hs.c[1]; res->why_n = hs.c[2]; res->why_meanq = hs.c[3]; res->why_lowq = hs.c[4]; res->why_complex = hs.c[5];
+    res->bases_in = hs.c[6]; res->qsum_in = hs.c[7]; res->q20_in = hs.c[8]; res->q30_in = hs.c[9];
+    res->bases_out = hs.c[10]; res->qsum_out = hs.c[11]; res->q20_out = hs.c[12]; res->q30_out = hs.c[13];
+    return RFQ_OK;
+}

@@ -24,3 +24,4 @@
 #include "enc/rows_text.h"                    // rows -> FASTQ text in front of the encoder (rfq_rows_to_text, rfq_encode_rows)
 #include "enc/text_rows.h"                    // FASTQ text -> rows, lengths and names from the line index (rfq_text_rows)
 #include "enc/rows_select.h"                  // rows -> the kept rows, trimmed, with their names (rfq_select_rows)
+#include "enc/rows_judge.h"                   // rows -> keep, window, reason and metrics per row + a QC summary (rfq_judge_rows)

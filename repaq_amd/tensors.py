@@ -26,6 +26,15 @@ keeps bases [start, start + length) of it, a read trimmed below min_len is dropp
     t = fastq_to_tensors(codec, fq)                                                   # "bases", "quals", "lens", "names", "name_off", "consumed"
     s = select_rows(codec, t, start=torch.full_like(t["lens"], 5), length=t["lens"] - 10, min_len=30)
 
+fastq -> judge -> select -> encode, four calls and nothing on the host: rfq_judge_rows looks at the bases and the scores - it trims by quality (a sliding window
+from either end), cuts poly-G tails, counts N, low scores and base changes - and leaves the keep mask and the window per row that select_rows takes, with a QC
+summary of the batch (reads, bases, Q20 / Q30 before and after, rows per reason); filter_rows is the two in one:
+
+    t = fastq_to_tensors(codec, fq1, fq2, paired=PE_TWO_FILES)
+    j = judge_rows(codec, t, cut_tail=True, cut_window=4, cut_mean_q=20, poly_g=10, max_n=5, min_mean_q=20, qual_q=15, max_lowq_pct=40)
+    s = select_rows(codec, t, keep=j["keep"], start=j["start"], length=j["length"], pairs=True, min_len=36)       # or: s = filter_rows(codec, t, pairs=True, min_len=36, ...)
+    image = encode_tensors(codec, s["bases"], s["quals"], s["lens"], s["names"], s["name_off"], paired=PE_TWO_FILES)
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -137,6 +146,44 @@ def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_l
     out = {"bases": ob, "quals": oq, "lens": ol, "dropped": {"mask": int(q.dropped_mask), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}}
     if named:
         out["names"], out["name_off"] = blob, off
+    return out
+
+
+SUMMARY_FIELDS = ("n_rows", "n_kept", "why_short", "why_n", "why_meanq", "why_lowq", "why_complex", "bases_in", "qsum_in", "q20_in", "q30_in", "bases_out", "qsum_out",
+                  "q20_out", "q30_out")
+
+
+def judge_rows(codec, t, codes=True, metrics=False, **criteria):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "quals", "lens"; codes: what they were made with) and the criteria of rfq_judge_rows
+    (RfqCodec.judge_rows: trim_front, trim_tail, poly_g, cut_front / cut_right / cut_tail with cut_window and cut_mean_q, max_len, min_len, max_n, min_mean_q,
+    qual_q + max_lowq_pct, min_complexity_pct) -> {"keep": [n] uint8, "start": [n] int32, "length": [n] int32, "why": [n] uint8 (the WHY_* bits of the reasons a
+    row fails for), "summary": dict of the batch's counts} and, with metrics=True, "metrics": [n, 4] int32 (qsum, n_cnt, lowq, trans of the window).  keep, start
+    and length are what select_rows takes.  "quals" must hold the scores (qual_offset taken off, as decode_tensors and fastq_to_tensors leave them).  One call,
+    ordered with torch's current stream; the context goes back to its own stream afterwards."""
+    bases, quals, lens = t["bases"], t["quals"], t["lens"]
+    n, L, p_b, p_q, p_l = _rows_args(bases, quals, lens, bases.new_empty((0,)), torch.zeros((int(bases.shape[0]) + 1,), dtype=torch.int64, device=bases.device))[:5]
+    dev = bases.device
+    keep = torch.empty((n,), dtype=torch.uint8, device=dev); why = torch.empty((n,), dtype=torch.uint8, device=dev)
+    start = torch.empty((n,), dtype=torch.int32, device=dev); length = torch.empty((n,), dtype=torch.int32, device=dev)
+    met = torch.empty((n, 4), dtype=torch.int32, device=dev) if metrics else None
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        r = codec.judge_rows(n, L, p_b, p_q, p_l, codes=codes, d_keep=keep.data_ptr(), d_start=start.data_ptr(), d_len=length.data_ptr(), d_why=why.data_ptr(),
+                             d_metrics=met.data_ptr() if metrics else None, **criteria)
+    finally:
+        codec.set_stream(None)
+    out = {"keep": keep, "start": start, "length": length, "why": why, "summary": {f: int(getattr(r, f)) for f in SUMMARY_FIELDS}}
+    if metrics:
+        out["metrics"] = met
+    return out
+
+
+def filter_rows(codec, t, pairs=False, codes=True, min_len=1, row_len=None, pad=255, **criteria):
+    """judge_rows with the criteria, then select_rows with its keep mask and windows and the same min_len: the dict of select_rows (the kept rows, trimmed and
+    compacted, with their names) plus "summary" (the judge's: every row on its own, before the pair rule)."""
+    j = judge_rows(codec, t, codes=codes, min_len=min_len, **criteria)
+    out = select_rows(codec, t, keep=j["keep"], start=j["start"], length=j["length"], pairs=pairs, min_len=min_len, row_len=row_len, pad=pad)
+    out["summary"] = j["summary"]
     return out
 
 
