@@ -13,8 +13,6 @@ struct RowsOut {
 };
 // A C G T N -> 0 1 2 3 4: bits 1-3 of the ASCII byte (A 0, C 1, T 2, G 3, N 7) index an 8-entry table, four bytes in one v_perm_b32
 __device__ __forceinline__ uint32_t code4_acgtn(uint32_t w) { return __builtin_amdgcn_perm(0x04000000u, 0x02030100u, (w >> 1) & 0x07070707u); }
-// x - y in each byte, mod 256
-__device__ __forceinline__ uint32_t sub_bytes(uint32_t x, uint32_t y) { return ((x | 0x80808080u) - (y & 0x7F7F7F7Fu)) ^ ((x ^ ~y) & 0x80808080u); }
 // 16 bytes at any alignment: five aligned words and a funnel shift (reads up to 3 bytes in front of p and 4 behind p + 16: both inside the
 // 256-byte-aligned qdec / sdec allocations, whose last chunk is followed by >= 256 bytes of slack)
 __device__ __forceinline__ void ld16_any(const uint8_t* p, uint32_t (&w)[4]) {
@@ -26,8 +24,7 @@ __device__ __forceinline__ void ld16_any(const uint8_t* p, uint32_t (&w)[4]) {
     for (int i = 0; i < 4; i++) w[i] = (uint32_t)((((uint64_t)v[i + 1] << 32) | v[i]) >> sh);
 }
 // grid (bx, n_chunks), 256 threads.  A workgroup owns a run of a chunk's reads; a thread owns one 16-byte group [k0, k0 + 16) of one row at a
-// time - consecutive threads take consecutive groups of consecutive rows, so with row_len % 16 == 0 a wave's stores are one contiguous span
-// of whole 16-byte groups (no row shares a group with another: no partly written 64-byte sector between two waves).
+// time, in GroupWalk's order (rfq_common.h), and stores it once (store_group16).
 __global__ void __launch_bounds__(256) k_dec_rows(const DChunk* __restrict__ CH, const DevHeader* __restrict__ D, DReadTab R,
                                                   const uint64_t* __restrict__ qbase, const uint64_t* __restrict__ sbase,
                                                   const uint8_t* __restrict__ qdec, const uint8_t* __restrict__ sdec, RowsOut o) {
@@ -38,11 +35,8 @@ __global__ void __launch_bounds__(256) k_dec_rows(const DChunk* __restrict__ CH,
     const uint8_t* const qc = qdec + qbase[c]; const uint8_t* const sc = sdec + sbase[c];
     const uint32_t per = (d.reads + gridDim.x - 1) / gridDim.x;
     const uint32_t rs = blockIdx.x * per < d.reads ? blockIdx.x * per : d.reads, nr = (rs + per < d.reads ? rs + per : d.reads) - rs;
-    const uint32_t G = (uint32_t)((o.row_len + 15u) / 16u);                  // groups per row
-    const uint32_t sj = blockDim.x / G, sk = blockDim.x % G;                 // one step of blockDim.x groups: sj rows and sk groups further
-    uint32_t j = threadIdx.x / G, k = threadIdx.x % G;
-    while (j < nr) {
-        const uint32_t r = rs + j, g = f + r; const uint64_t row = (uint64_t)d.rbase_abs + r;
+    for (GroupWalk w(o.row_len, blockDim.x); w.j < nr; w.step()) {
+        const uint32_t k = w.k, r = rs + w.j, g = f + r; const uint64_t row = (uint64_t)d.rbase_abs + r;
         if (row >= o.n_rows) break;                                          // (the walk's read count bounds the rows: never past the caller's buffers)
         const uint32_t len = R.len[g]; const int ov = R.ov[g]; const bool rc = il && (r & 1u);
         const uint32_t k0 = 16u * k;
@@ -93,17 +87,6 @@ __global__ void __launch_bounds__(256) k_dec_rows(const DChunk* __restrict__ CH,
                 }
             }
         }
-        const uint64_t at = row * o.row_len + k0;
-        if (o.vec) {
-            if (o.bases) *(uint4*)(o.bases + at) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-            if (o.quals) *(uint4*)(o.quals + at) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
-        } else {
-            const uint32_t n = o.row_len - k0 < 16u ? (uint32_t)(o.row_len - k0) : 16u;
-            for (uint32_t i = 0; i < n; i++) {
-                if (o.bases) o.bases[at + i] = (uint8_t)(wb[i >> 2] >> (8u * (i & 3u)));
-                if (o.quals) o.quals[at + i] = (uint8_t)(wq[i >> 2] >> (8u * (i & 3u)));
-            }
-        }
-        j += sj; k += sk; if (k >= G) { k -= G; j++; }
+        store_group16(o.bases, o.quals, row * o.row_len + k0, o.row_len, k0, o.vec, wb, wq);
     }
 }

@@ -116,7 +116,7 @@ __device__ __forceinline__ void jr_ld(const JudgeIn& in, const uint8_t* buf, uin
         for (uint32_t i = 0; i < have; i++) w[i >> 2] |= (uint32_t)buf[p + i] << (8u * (i & 3u));
     }
 #pragma unroll
-    for (int i = 0; i < 4; i++) w[i] &= tr_low_bytes((int)have - 4 * i);
+    for (int i = 0; i < 4; i++) w[i] &= low_bytes((int)have - 4 * i);
 }
 // E[i] lives at word i + i / 16: the lanes of a group read and write 16 positions apart - 17 words, another bank each
 __device__ __forceinline__ uint32_t jr_ix(uint32_t i) { return i + (i >> 4); }
@@ -338,7 +338,7 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
         if (on && a > p0) {                                                  // (the qualities in front of the window do not count)
             const uint32_t f = a - p0 < 16u ? a - p0 : 16u;
 #pragma unroll
-            for (int i = 0; i < 4; i++) q[i] &= ~tr_low_bytes((int)f - 4 * i);
+            for (int i = 0; i < 4; i++) q[i] &= ~low_bytes((int)f - 4 * i);
         }
         uint32_t prev = wave_shr1(b[3] >> 24, 0u);
         if (threadIdx.x == 0u && in.b && p0 > a) prev = in.b[rowbase + p0 - 1u];      // (the tile in front holds it: a byte of the row, inside the window)

@@ -35,15 +35,15 @@ __device__ __forceinline__ uint32_t sel_window(const SelIn& in, uint32_t i, uint
     return len < in.min_len ? 2u : 0u;
 }
 
-// grid ceil(n_rows / SJ_ROWS) x 256 threads, a thread per row and SJ_ITER rows per thread (k_text_rows_sizes' shape: a workgroup ends in a handful of atomics on the
-// same words, eight times fewer of them than with a workgroup per 256 rows).  The mate of row g is row g ^ 1: its mask byte and window are read again rather than
+// grid ceil(n_rows / SJ_ROWS) x 256 threads, a thread per row and SJ_ITER rows per thread; the workgroup ends in rows_sizes_reduce (enc/text_rows.h) with the three
+// drop counts beside it: the same barrier, three more atomics of thread 0.  The mate of row g is row g ^ 1: its mask byte and window are read again rather than
 // shuffled (the same cache lines; no rendezvous inside the loop a short last workgroup leaves early).  flag[g] = 1 for a kept row, nsz[g] = bytes of its name (0
-// for a dropped row; 64-bit: scanned in place to the output offsets; null for rows without names).  All rows are judged, kept or not; only where a row is at
-// fault: one atomicOr of the error bits per wave and one atomicMin of the row per offending thread.
+// for a dropped row; 64-bit: scanned in place to the output offsets; null for rows without names).  All rows are judged, kept or not; an offending thread leaves
+// its row with one atomicMin.
 #define SJ_ITER 8u
 #define SJ_ROWS (256u * SJ_ITER)
 __global__ void __launch_bounds__(256) k_sel_judge(SelIn in, uint32_t* __restrict__ flag, uint64_t* __restrict__ nsz, SelStat* __restrict__ st) {
-    __shared__ uint32_t s_ml[4], s_mn[4], s_dm[4], s_ds[4], s_dt[4]; __shared__ unsigned long long s_nb[4];
+    __shared__ uint32_t s_dm[4], s_ds[4], s_dt[4];
     uint32_t ml = 0, mn = 0, err = 0, dm = 0, ds = 0, dt = 0; unsigned long long nb = 0;
     for (uint32_t it = 0; it < SJ_ITER; it++) {
         const uint64_t g64 = (uint64_t)blockIdx.x * SJ_ROWS + it * 256u + threadIdx.x;
@@ -66,15 +66,12 @@ __global__ void __launch_bounds__(256) k_sel_judge(SelIn in, uint32_t* __restric
             if (w > ml) ml = w; if (n32 > mn) mn = n32; nb += w;
         }
     }
-    ml = wave_max(ml); mn = wave_max(mn); dm = wave_sum(dm); ds = wave_sum(ds); dt = wave_sum(dt); const uint32_t e = wave_or(err); nb = wave_sum<unsigned long long>(nb);
-    if (lane_id() == 0) { const int w = wave_id(); s_ml[w] = ml; s_mn[w] = mn; s_dm[w] = dm; s_ds[w] = ds; s_dt[w] = dt; s_nb[w] = nb; if (e) atomicOr(&st->err, e); }
-    __syncthreads();
+    dm = wave_sum(dm); ds = wave_sum(ds); dt = wave_sum(dt);
+    if (lane_id() == 0) { const int w = wave_id(); s_dm[w] = dm; s_ds[w] = ds; s_dt[w] = dt; }
+    rows_sizes_reduce(ml, mn, nb, err, st);                                  // (its barrier stands between the three stores above and thread 0's loads below)
     if (threadIdx.x == 0) {
-        uint32_t a = s_ml[0], b = s_mn[0]; unsigned long long c = s_nb[0], x = s_dm[0], y = s_ds[0], z = s_dt[0];
-        for (uint32_t i = 1; i < 4u; i++) { if (s_ml[i] > a) a = s_ml[i]; if (s_mn[i] > b) b = s_mn[i]; c += s_nb[i]; x += s_dm[i]; y += s_ds[i]; z += s_dt[i]; }
-        if (a) atomicMax(&st->max_len, a);
-        if (b) atomicMax(&st->max_name, b);
-        if (c) atomicAdd(&st->n_bases, c);
+        unsigned long long x = s_dm[0], y = s_ds[0], z = s_dt[0];
+        for (uint32_t i = 1; i < 4u; i++) { x += s_dm[i]; y += s_ds[i]; z += s_dt[i]; }
         if (x) atomicAdd(&st->d_mask, x);
         if (y) atomicAdd(&st->d_short, y);
         if (z) atomicAdd(&st->d_mate, z);
@@ -107,24 +104,21 @@ struct SelRowsOut {
     uint32_t vec;                                     // row_len % 16 == 0 and both output buffers 16-byte aligned: one 16-byte store per group
     uint32_t per;                                     // output rows of a workgroup
 };
-// grid ceil(n_out / per) x 256 threads.  The work follows the OUTPUT, in k_text_rows' order: a workgroup owns `per` consecutive output rows, a thread one 16-byte
-// group [k0, k0 + 16) of one row at a time, consecutive threads consecutive groups of consecutive rows.  A group that holds bases is ONE load of 16 source bytes at
+// grid ceil(n_out / per) x 256 threads.  The work follows the OUTPUT: a workgroup owns `per` consecutive output rows, a thread one 16-byte group [k0, k0 + 16) of
+// one row at a time, in GroupWalk's order (rfq_common.h).  A group that holds bases is ONE load of 16 source bytes at
 // the source's own alignment (the window start makes most of them unaligned also for aligned rows): from the one or two aligned groups of the source row that hold
 // them where both lie inside that row (rt_ld16's groups form), else one 16-byte load wherever 16 bytes from there still lie inside the input buffer; only behind that,
-// at the very end of the buffer, byte by byte.  What lies behind the window is masked off in registers and replaced by the pad, so every group of the output is
-// stored once.  No LDS.
+// at the very end of the buffer, byte by byte.  What lies behind the window is masked off in registers and replaced by the pad (low_bytes), and the group is stored
+// once (store_group16).  No LDS.
 __global__ void __launch_bounds__(256) k_sel_rows(SelRowsOut o, const SelRow* __restrict__ tab) {
     const uint32_t rs = blockIdx.x * o.per;
     if (rs >= o.n_out) return;
     const uint32_t nr = (o.n_out - rs < o.per) ? o.n_out - rs : o.per;
-    const uint32_t G = (uint32_t)((o.row_len + 15u) / 16u);                  // groups per output row
-    const uint32_t sj = 256u / G, sk = 256u % G;                             // one step of 256 groups: sj rows and sk groups further
-    uint32_t j = threadIdx.x / G, k = threadIdx.x % G;
-    while (j < nr) {
-        const uint32_t g = rs + j;
+    for (GroupWalk w(o.row_len, 256u); w.j < nr; w.step()) {
+        const uint32_t g = rs + w.j;
         const uint4 t = *(const uint4*)(tab + g);                            // (source row, window start, window length)
         const uint32_t len = t.z;
-        const uint64_t k0 = 16ull * k;
+        const uint64_t k0 = 16ull * w.k;
         uint32_t wb[4] = { o.pad_b4, o.pad_b4, o.pad_b4, o.pad_b4 }, wq[4] = { o.pad_q4, o.pad_q4, o.pad_q4, o.pad_q4 };
         if (k0 < len) {
             const uint32_t at = (uint32_t)k0, have = len - at < 16u ? len - at : 16u;        // bytes of the window in this group
@@ -145,89 +139,23 @@ __global__ void __launch_bounds__(256) k_sel_rows(SelRowsOut o, const SelRow* __
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const uint32_t m = tr_low_bytes((int)have - 4 * i);
+                const uint32_t m = low_bytes((int)have - 4 * i);
                 wb[i] = (b[i] & m) | (o.pad_b4 & ~m);
                 wq[i] = (q[i] & m) | (o.pad_q4 & ~m);
             }
         }
-        const uint64_t dst = (uint64_t)g * o.row_len + k0;
-        if (o.vec) {
-            if (o.bases) *(uint4*)(o.bases + dst) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-            if (o.quals) *(uint4*)(o.quals + dst) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
-        } else {
-            const uint32_t cnt = o.row_len - k0 < 16u ? (uint32_t)(o.row_len - k0) : 16u;
-            for (uint32_t i = 0; i < cnt; i++) {
-                if (o.bases) o.bases[dst + i] = (uint8_t)(wb[i >> 2] >> (8u * (i & 3u)));
-                if (o.quals) o.quals[dst + i] = (uint8_t)(wq[i >> 2] >> (8u * (i & 3u)));
-            }
-        }
-        j += sj; k += sk; if (k >= G) { k -= G; j++; }
+        store_group16(o.bases, o.quals, (uint64_t)g * o.row_len + k0, o.row_len, k0, o.vec, wb, wq);
     }
 }
 
-// ---- names: the whole name of every kept row, back to back
-// grid ceil((names_len + shift) / TN_TILE) x 256 threads: k_text_names over the OUTPUT blob - positions count from the 16-byte boundary at or below it (shift =
-// blob & 15), a workgroup owns TN_TILE of them and a thread one aligned 16-byte group; thread 0 finds the name the tile starts in by binary search in off[] (the
-// output offsets, off[n_out] = names_len), the starts of the names behind it go to LDS and every thread finds its group's name there.  Output name g is input name
-// tab[g].src: its bytes are names + in_off[tab[g].src] + p.  A group inside one name is one 16-byte load at the source's own alignment and one aligned store; a
-// group that holds a boundary is put together byte by byte in registers; the blob's first and last group, where they are not whole, are stored byte by byte.
-// Unlike a line of text a name may have no bytes here (the encoder refuses it later, this call does not): equal offsets are searched to the LAST of them, the name
-// that holds the byte, and a tile in which more names start than the LDS table holds searches off[] itself.
-__device__ __forceinline__ const uint8_t* sn_name(const uint8_t* names, const uint64_t* in_off, const SelRow* tab, uint32_t g) { return names + in_off[tab[g].src]; }
+// ---- names: the whole name of every kept row, back to back (name_blob_write, enc/text_rows.h, over the OUTPUT blob: off[] are the output offsets, off[n_out] =
+// names_len).  Output name g is input name tab[g].src: its bytes start at names + in_off[tab[g].src].  A name may have no bytes here (the encoder refuses it later,
+// this call does not).
+struct SelNameSrc {
+    const uint8_t* names; const uint64_t* in_off; const SelRow* tab;
+    __device__ __forceinline__ const uint8_t* operator()(uint32_t g) const { return names + in_off[tab[g].src]; }
+};
 __global__ void __launch_bounds__(TN_TPB) k_sel_names(const uint8_t* __restrict__ names, const uint64_t* __restrict__ in_off, const SelRow* __restrict__ tab,
                                                       const uint64_t* __restrict__ off, uint32_t n_out, uint8_t* __restrict__ blob, uint64_t names_len) {
-    __shared__ uint32_t s_rel[TN_RECS + 1]; __shared__ uint32_t s_r0, s_hi;
-    const uint32_t shift = (uint32_t)((uintptr_t)blob & 15u); uint8_t* const nb = blob - shift;
-    const uint64_t A0 = (uint64_t)blockIdx.x * TN_TILE;                      // (position from nb)
-    const uint64_t q0 = A0 > shift ? A0 - shift : 0ull;                      // the tile's first blob byte
-    if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = n_out;                                          // off[lo] <= q0 < off[hi]
-        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] <= q0) lo = mid; else hi = mid; }
-        s_r0 = lo;
-        const uint64_t qt = A0 + TN_TILE - shift;                             // the first name that starts at or behind the tile's end (n_out: none does)
-        uint32_t hi2 = n_out;                                                 // off[lo] < qt <= off[hi2], or hi2 = n_out
-        while (hi2 - lo > 1) { const uint32_t mid = lo + (hi2 - lo) / 2; if (off[mid] < qt) lo = mid; else hi2 = mid; }
-        s_hi = hi2;
-    }
-    __syncthreads();
-    const uint32_t r0 = s_r0, span = s_hi - r0; const bool in_lds = span <= TN_RECS; const uint32_t cnt = in_lds ? span : 0u;
-    // s_rel[k]: start of name r0 + k, in blob bytes from q0 (name r0 itself starts at or before q0: 0); beyond the tile or the rows: ~0
-    if (in_lds) for (uint32_t k = threadIdx.x; k <= cnt; k += TN_TPB) {
-        uint32_t v = 0xFFFFFFFFu;
-        if (k == 0) v = 0;
-        else if ((uint64_t)r0 + k <= n_out) { const uint64_t d = off[r0 + k] - q0; if (d < 0xFFFFFFFFull) v = (uint32_t)d; }
-        s_rel[k] = v;
-    }
-    __syncthreads();
-    const uint64_t A = A0 + 16ull * threadIdx.x;
-    if (A >= names_len + shift) return;
-    const uint64_t qa = A > shift ? A - shift : 0ull, qe = (A + 16u - shift < names_len) ? A + 16u - shift : names_len;   // this group's blob bytes [qa, qe)
-    uint32_t g;
-    if (in_lds) {
-        const uint32_t rel = (uint32_t)(qa - q0);
-        uint32_t lo = 0, hi = cnt;                                            // s_rel[lo] <= rel < s_rel[hi]: name r0 + cnt starts at or behind the tile's end
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s_rel[mid] <= rel) lo = mid; else hi = mid; }
-        g = r0 + lo;
-    } else {
-        uint32_t lo = r0, hi = s_hi;                                          // off[lo] <= qa < off[hi] (hi = n_out: off[n_out] = names_len)
-        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] <= qa) lo = mid; else hi = mid; }
-        g = lo;
-    }
-    uint64_t beg = off[g], end = off[g + 1];
-    const bool whole = qe - qa == 16u;
-    if (whole && qe <= end) {
-        uint32_t w[4]; rt_ld16(sn_name(names, in_off, tab, g) + (qa - beg), false, w);
-        *(uint4*)(nb + A) = make_uint4(w[0], w[1], w[2], w[3]);
-        return;
-    }
-    unsigned long long h0 = 0, h1 = 0; const uint32_t nby = (uint32_t)(qe - qa);
-    const uint8_t* src = sn_name(names, in_off, tab, g);
-    for (uint32_t i = 0; i < nby; i++) {
-        const uint64_t q = qa + i;
-        while (q >= end) { g++; beg = end; end = off[g + 1]; src = sn_name(names, in_off, tab, g); }
-        const unsigned long long c = src[q - beg];
-        if (i < 8u) h0 |= c << (8u * i); else h1 |= c << (8u * (i - 8u));
-    }
-    if (whole) *(uint4*)(nb + A) = make_uint4((uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32));
-    else for (uint32_t i = 0; i < nby; i++) blob[qa + i] = (uint8_t)(i < 8u ? h0 >> (8u * i) : h1 >> (8u * (i - 8u)));
+    name_blob_write(SelNameSrc{ names, in_off, tab }, off, n_out, blob, names_len);
 }

@@ -11,14 +11,28 @@
 // what the host reads back: zeroed per pass, first_empty = bad_row = ~0
 struct TextRowsStat { uint32_t err, max_len, max_name, first_empty; unsigned long long bad_row, n_bases; };
 
-// grid ceil(n_rows / TS_ROWS) x 256 threads, a thread per row and TS_ITER rows per thread.  A workgroup ends in three atomics on the same three words (longest
-// read, longest name, bases) - eight times fewer of them than with a workgroup per 256 rows - and, only where a row is at fault, one atomicOr of the error bits
-// per wave and one atomicMin of the row per offending thread (rare: both end the call or the rows).  lens[g] = bases of row g, nsz[g] = bytes of its name line
-// (64-bit: scanned in place to the offsets).
+// How a sizes kernel of 256 threads (k_text_rows_sizes, k_sel_judge) ends: every thread's longest read, longest name, bases and error bits into the verdict block
+// (Stat: max_len, max_name, n_bases, err).  Wave reduce, four LDS slots, and thread 0's three atomics on the same three words - with several rows per thread, that
+// many times fewer of them than with a workgroup per 256 rows - and, only where a row is at fault, one atomicOr of the error bits per wave (rare: it ends the call
+// or the rows).  Every thread of the workgroup calls it; what a caller's lanes 0 wrote to LDS before the call, its thread 0 may read after it.
+template <class Stat> __device__ __forceinline__ void rows_sizes_reduce(uint32_t ml, uint32_t mn, unsigned long long nb, uint32_t err, Stat* __restrict__ st) {
+    __shared__ uint32_t s_ml[4], s_mn[4]; __shared__ unsigned long long s_nb[4];
+    ml = wave_max(ml); mn = wave_max(mn); const uint32_t e = wave_or(err); nb = wave_sum<unsigned long long>(nb);
+    if (lane_id() == 0) { s_ml[wave_id()] = ml; s_mn[wave_id()] = mn; s_nb[wave_id()] = nb; if (e) atomicOr(&st->err, e); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t a = s_ml[0], b = s_mn[0]; unsigned long long c = s_nb[0];
+        for (uint32_t i = 1; i < 4u; i++) { if (s_ml[i] > a) a = s_ml[i]; if (s_mn[i] > b) b = s_mn[i]; c += s_nb[i]; }
+        if (a) atomicMax(&st->max_len, a);
+        if (b) atomicMax(&st->max_name, b);
+        if (c) atomicAdd(&st->n_bases, c);
+    }
+}
+// grid ceil(n_rows / TS_ROWS) x 256 threads, a thread per row and TS_ITER rows per thread; the workgroup ends in rows_sizes_reduce, and an offending thread leaves
+// its row with one atomicMin.  lens[g] = bases of row g, nsz[g] = bytes of its name line (64-bit: scanned in place to the offsets).
 #define TS_ITER 8u
 #define TS_ROWS (256u * TS_ITER)
 __global__ void __launch_bounds__(256) k_text_rows_sizes(Text T, uint32_t n_rows, int32_t* __restrict__ lens, uint64_t* __restrict__ nsz, TextRowsStat* __restrict__ st) {
-    __shared__ uint32_t s_ml[4], s_mn[4]; __shared__ unsigned long long s_nb[4];
     uint32_t ml = 0, mn = 0, err = 0; unsigned long long nb = 0;
     for (uint32_t it = 0; it < TS_ITER; it++) {
         const uint64_t g64 = (uint64_t)blockIdx.x * TS_ROWS + it * 256u + threadIdx.x;
@@ -32,16 +46,7 @@ __global__ void __launch_bounds__(256) k_text_rows_sizes(Text T, uint32_t n_rows
         lens[g] = (int32_t)sl; nsz[g] = nl;
         if (sl > ml) ml = sl; if (nl > mn) mn = nl; nb += sl;
     }
-    ml = wave_max(ml); mn = wave_max(mn); const uint32_t e = wave_or(err); nb = wave_sum<unsigned long long>(nb);
-    if (lane_id() == 0) { s_ml[wave_id()] = ml; s_mn[wave_id()] = mn; s_nb[wave_id()] = nb; if (e) atomicOr(&st->err, e); }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = s_ml[0], b = s_mn[0]; unsigned long long c = s_nb[0];
-        for (uint32_t i = 1; i < 4u; i++) { if (s_ml[i] > a) a = s_ml[i]; if (s_mn[i] > b) b = s_mn[i]; c += s_nb[i]; }
-        if (a) atomicMax(&st->max_len, a);
-        if (b) atomicMax(&st->max_name, b);
-        if (c) atomicAdd(&st->n_bases, c);
-    }
+    rows_sizes_reduce(ml, mn, nb, err, st);
 }
 
 struct TextRowsOut {
@@ -52,8 +57,6 @@ struct TextRowsOut {
     uint32_t vec;                                     // row_len % 16 == 0 and both row buffers 16-byte aligned: one 16-byte store per group
     uint32_t per;                                     // rows of a workgroup
 };
-// x - y in each byte, mod 256 (dec/rows.h sub_bytes, which this translation unit does not see)
-__device__ __forceinline__ uint32_t tr_sub_bytes(uint32_t x, uint32_t y) { return ((x | 0x80808080u) - (y & 0x7F7F7F7Fu)) ^ ((x ^ ~y) & 0x80808080u); }
 // A C G T N -> 0 1 2 3 4 and the test in one go: bits 1-3 of the byte (A 0, C 1, T 2, G 3, N 7) index an 8-entry table whose other entries are 7; the code
 // looked up in the table of ascii4_of_code (7 -> 0x00) gives the byte back exactly when it was one of the five.  bad: non-zero bytes = not A C G T N
 __device__ __forceinline__ uint32_t tr_code4(uint32_t w, uint32_t& bad) {
@@ -61,27 +64,21 @@ __device__ __forceinline__ uint32_t tr_code4(uint32_t w, uint32_t& bad) {
     bad |= ascii4_of_code(c) ^ w;
     return c;
 }
-// the low n bytes (n <= 4 counts as all) of a word as a mask
-__device__ __forceinline__ uint32_t tr_low_bytes(int n) { return n >= 4 ? 0xFFFFFFFFu : (n <= 0 ? 0u : (1u << (8 * n)) - 1u); }
 // grid ceil(n_rows / per) x 256 threads.  The work follows the OUTPUT: a workgroup owns `per` consecutive rows, a thread one 16-byte group [k0, k0 + 16) of one
-// row at a time, consecutive threads consecutive groups of consecutive rows (k_dec_rows' order: with row_len % 16 == 0 a wave's stores are one contiguous span of
-// whole groups).  A group that holds bases is ONE 16-byte load from the text at the text's own alignment per source - also the read's last, partial group wherever
-// 16 bytes from there still lie inside the stream (what follows the line is masked off in registers); only at the very end of a stream is it read byte by byte.
-// The tail of a read and the pad are merged in registers, so every group of the output is stored once.  No LDS.
+// row at a time, in GroupWalk's order (rfq_common.h).  A group that holds bases is ONE 16-byte load from the text at the text's own alignment per source - also the
+// read's last, partial group wherever 16 bytes from there still lie inside the stream (what follows the line is masked off in registers); only at the very end of a
+// stream is it read byte by byte.  The tail of a read and the pad are merged in registers (low_bytes) and the group is stored once (store_group16).  No LDS.
 __global__ void __launch_bounds__(256) k_text_rows(Text T, TextRowsOut o, TextRowsStat* __restrict__ st) {
     const uint32_t rs = blockIdx.x * o.per;
     if (rs >= o.n_rows) return;
     const uint32_t nr = (o.n_rows - rs < o.per) ? o.n_rows - rs : o.per;
-    const uint32_t G = (uint32_t)((o.row_len + 15u) / 16u);                  // groups per row
-    const uint32_t sj = 256u / G, sk = 256u % G;                             // one step of 256 groups: sj rows and sk groups further
-    uint32_t j = threadIdx.x / G, k = threadIdx.x % G;
     uint32_t bad = 0; unsigned long long bad_row = ~0ull;
-    while (j < nr) {
-        const uint32_t g = rs + j; int s; uint32_t r; read_loc(T, g, s, r);
+    for (GroupWalk w(o.row_len, 256u); w.j < nr; w.step()) {
+        const uint32_t g = rs + w.j; int s; uint32_t r; read_loc(T, g, s, r);
         const uint32_t* p = t_lo(T, s) + 4 * (size_t)r;
         const uint32_t p1 = p[1], p2 = p[2], p3 = p[3], len = p2 - 1 - p1, n = t_n(T, s);
         const uint8_t* const fq = s ? T.fq[1] : T.fq[0];
-        const uint64_t k0 = 16ull * k;
+        const uint64_t k0 = 16ull * w.k;
         uint32_t wb[4] = { o.pad_b4, o.pad_b4, o.pad_b4, o.pad_b4 }, wq[4] = { o.pad_q4, o.pad_q4, o.pad_q4, o.pad_q4 };
         if (k0 < len) {
             const uint32_t at = (uint32_t)k0, have = len - at < 16u ? len - at : 16u;        // bytes of the read in this group
@@ -100,90 +97,96 @@ __global__ void __launch_bounds__(256) k_text_rows(Text T, TextRowsOut o, TextRo
             uint32_t bb = 0;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const uint32_t m = tr_low_bytes((int)have - 4 * i);
+                const uint32_t m = low_bytes((int)have - 4 * i);
                 uint32_t x = b[i];
                 if (o.codes) x = tr_code4((x & m) | (0x41414141u & ~m), bb);                     // (bytes behind the read count as 'A': never an offender)
                 wb[i] = (x & m) | (o.pad_b4 & ~m);
-                wq[i] = (tr_sub_bytes(q[i], o.qoff4) & m) | (o.pad_q4 & ~m);
+                wq[i] = (sub_bytes(q[i], o.qoff4) & m) | (o.pad_q4 & ~m);
             }
             if (bb && o.bases) { bad |= TR_ERR_BASE; if (bad_row == ~0ull) bad_row = g; }
         }
-        const uint64_t dst = (uint64_t)g * o.row_len + k0;
-        if (o.vec) {
-            if (o.bases) *(uint4*)(o.bases + dst) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-            if (o.quals) *(uint4*)(o.quals + dst) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
-        } else {
-            const uint32_t cnt = o.row_len - k0 < 16u ? (uint32_t)(o.row_len - k0) : 16u;
-            for (uint32_t i = 0; i < cnt; i++) {
-                if (o.bases) o.bases[dst + i] = (uint8_t)(wb[i >> 2] >> (8u * (i & 3u)));
-                if (o.quals) o.quals[dst + i] = (uint8_t)(wq[i >> 2] >> (8u * (i & 3u)));
-            }
-        }
-        j += sj; k += sk; if (k >= G) { k -= G; j++; }
+        store_group16(o.bases, o.quals, (uint64_t)g * o.row_len + k0, o.row_len, k0, o.vec, wb, wq);
     }
     if (bad) { atomicOr(&st->err, bad); atomicMin(&st->bad_row, bad_row); }
 }
 
-// ---- names: the first line of every row, back to back
+// ---- a name blob: names back to back, name g's bytes wherever its source keeps them (k_text_names, k_sel_names)
 #define TN_TPB 256
 #define TN_TILE (TN_TPB * 16u)                // blob bytes of a workgroup: 4 KiB
-#define TN_RECS (TN_TILE + 1u)                // a name has a byte or more (an empty line ends the rows): those that start inside a tile, the end of the last
-__device__ __forceinline__ const uint8_t* tn_name(const Text& T, uint32_t g) {
-    int s; uint32_t r; read_loc(T, g, s, r);
-    return (s ? T.fq[1] : T.fq[0]) + t_lo(T, s)[4 * (size_t)r];
-}
-// grid ceil((names_len + shift) / TN_TILE) x 256 threads.  The work follows the BLOB: positions count from the 16-byte boundary at or below it (shift = blob & 15),
-// a workgroup owns TN_TILE of them and a thread one aligned 16-byte group.  Thread 0 finds the name the tile starts in (binary search in off[], the exclusive scan
-// of the name sizes, off[n_rows] = names_len); where the names behind it start, relative to the tile, goes to LDS and every thread finds its group's name there.  A group inside
-// one name is one 16-byte load at the text's own alignment and one aligned store; a group that holds a boundary is put together byte by byte in registers; the
-// blob's first and last group, where they are not whole, are stored byte by byte.
-__global__ void __launch_bounds__(TN_TPB) k_text_names(Text T, const uint64_t* __restrict__ off, uint32_t n_rows, uint8_t* __restrict__ blob, uint64_t names_len) {
-    __shared__ uint32_t s_rel[TN_RECS + 1]; __shared__ uint32_t s_r0, s_cnt;
+// the LDS table of a tile: the names that start inside it - TN_TILE at most where every name has a byte - and one entry more, the end of the last of them (the start
+// of the first name at or behind the tile's end), which closes the search from above
+#define TN_RECS (TN_TILE + 1u)
+// grid ceil((names_len + shift) / TN_TILE) x TN_TPB threads; src(g): the address of name g's first byte.  The work follows the BLOB: positions count from the
+// 16-byte boundary at or below it (shift = blob & 15), a workgroup owns TN_TILE of them and a thread one aligned 16-byte group.  Thread 0 finds the name the tile
+// starts in and the first name that starts at or behind the tile's end (binary searches in off[], the exclusive scan of the name sizes, off[n] = names_len); where
+// the names in between start, relative to the tile, goes to LDS and every thread finds its group's name there.  A name may have no bytes (rfq_select_rows passes
+// them through; a line of text always has one): equal offsets are searched to the LAST of them, the name that holds the byte, and a tile in which more names start
+// than the LDS table holds searches off[] itself.  A group inside one name is one 16-byte load at the source's own alignment and one aligned store; a group that
+// holds a boundary is put together byte by byte in registers; the blob's first and last group, where they are not whole, are stored byte by byte.
+template <class Src> __device__ __forceinline__ void name_blob_write(const Src& src, const uint64_t* __restrict__ off, uint32_t n, uint8_t* __restrict__ blob, uint64_t names_len) {
+    __shared__ uint32_t s_rel[TN_RECS + 1]; __shared__ uint32_t s_r0, s_hi;
     const uint32_t shift = (uint32_t)((uintptr_t)blob & 15u); uint8_t* const nb = blob - shift;
     const uint64_t A0 = (uint64_t)blockIdx.x * TN_TILE;                      // (position from nb)
     const uint64_t q0 = A0 > shift ? A0 - shift : 0ull;                      // the tile's first blob byte
     if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = n_rows;                                         // off[lo] <= q0 < off[hi]
+        uint32_t lo = 0, hi = n;                                              // off[lo] <= q0 < off[hi]
         while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] <= q0) lo = mid; else hi = mid; }
         s_r0 = lo;
-        // ... and the first name that starts at or behind the tile's end (n_rows: none does - off[n_rows] = names_len ends the last one): the entries in between are
-        // all a group of this tile can ask for (names of 53 bytes: 80 of the 4,098 entries)
+        // ... and the first name that starts at or behind the tile's end (n: none does - off[n] = names_len ends the last one): the entries in between are all a
+        // group of this tile can ask for (names of 53 bytes: 80 of the 4,098 entries)
         const uint64_t qt = A0 + TN_TILE - shift;
-        uint32_t hi2 = n_rows;                                                // off[lo] < qt <= off[hi2], or hi2 = n_rows
+        uint32_t hi2 = n;                                                     // off[lo] < qt <= off[hi2], or hi2 = n
         while (hi2 - lo > 1) { const uint32_t mid = lo + (hi2 - lo) / 2; if (off[mid] < qt) lo = mid; else hi2 = mid; }
-        s_cnt = hi2 - s_r0 < TN_RECS ? hi2 - s_r0 : TN_RECS;
+        s_hi = hi2;
     }
     __syncthreads();
-    const uint32_t r0 = s_r0, cnt = s_cnt;
-    // s_rel[k]: start of name r0 + k, in blob bytes from q0 (name r0 itself starts at or before q0: 0); beyond the tile or the rows: ~0
-    for (uint32_t k = threadIdx.x; k <= cnt; k += TN_TPB) {
+    const uint32_t r0 = s_r0, span = s_hi - r0; const bool in_lds = span <= TN_RECS; const uint32_t cnt = in_lds ? span : 0u;
+    // s_rel[k]: start of name r0 + k, in blob bytes from q0 (name r0 itself starts at or before q0: 0); beyond the tile or the names: ~0
+    if (in_lds) for (uint32_t k = threadIdx.x; k <= cnt; k += TN_TPB) {
         uint32_t v = 0xFFFFFFFFu;
         if (k == 0) v = 0;
-        else if ((uint64_t)r0 + k <= n_rows) { const uint64_t d = off[r0 + k] - q0; if (d < 0xFFFFFFFFull) v = (uint32_t)d; }
+        else if ((uint64_t)r0 + k <= n) { const uint64_t d = off[r0 + k] - q0; if (d < 0xFFFFFFFFull) v = (uint32_t)d; }
         s_rel[k] = v;
     }
     __syncthreads();
     const uint64_t A = A0 + 16ull * threadIdx.x;
     if (A >= names_len + shift) return;
     const uint64_t qa = A > shift ? A - shift : 0ull, qe = (A + 16u - shift < names_len) ? A + 16u - shift : names_len;   // this group's blob bytes [qa, qe)
-    const uint32_t rel = (uint32_t)(qa - q0);
-    uint32_t lo = 0, hi = cnt;                                                // s_rel[lo] <= rel < s_rel[hi]: name r0 + cnt starts at or behind the tile's end
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s_rel[mid] <= rel) lo = mid; else hi = mid; }
-    uint32_t g = r0 + lo; uint64_t beg = off[g], end = off[g + 1];
+    uint32_t g;
+    if (in_lds) {
+        const uint32_t rel = (uint32_t)(qa - q0);
+        uint32_t lo = 0, hi = cnt;                                            // s_rel[lo] <= rel < s_rel[hi]: name r0 + cnt starts at or behind the tile's end
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s_rel[mid] <= rel) lo = mid; else hi = mid; }
+        g = r0 + lo;
+    } else {
+        uint32_t lo = r0, hi = s_hi;                                          // off[lo] <= qa < off[hi] (hi = n: off[n] = names_len)
+        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] <= qa) lo = mid; else hi = mid; }
+        g = lo;
+    }
+    uint64_t beg = off[g], end = off[g + 1];
     const bool whole = qe - qa == 16u;
     if (whole && qe <= end) {
-        uint32_t w[4]; rt_ld16(tn_name(T, g) + (qa - beg), false, w);
+        uint32_t w[4]; rt_ld16(src(g) + (qa - beg), false, w);
         *(uint4*)(nb + A) = make_uint4(w[0], w[1], w[2], w[3]);
         return;
     }
     unsigned long long h0 = 0, h1 = 0; const uint32_t nby = (uint32_t)(qe - qa);
-    const uint8_t* src = tn_name(T, g);
+    const uint8_t* p = src(g);
     for (uint32_t i = 0; i < nby; i++) {
         const uint64_t q = qa + i;
-        while (q >= end) { g++; beg = end; end = off[g + 1]; src = tn_name(T, g); }
-        const unsigned long long c = src[q - beg];
+        while (q >= end) { g++; beg = end; end = off[g + 1]; p = src(g); }
+        const unsigned long long c = p[q - beg];
         if (i < 8u) h0 |= c << (8u * i); else h1 |= c << (8u * (i - 8u));
     }
     if (whole) *(uint4*)(nb + A) = make_uint4((uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32));
     else for (uint32_t i = 0; i < nby; i++) blob[qa + i] = (uint8_t)(i < 8u ? h0 >> (8u * i) : h1 >> (8u * (i - 8u)));
+}
+
+// ---- names: the first line of every row, back to back (name_blob_write over the rows' name lines)
+struct TextNameSrc {
+    const Text& T;
+    __device__ __forceinline__ const uint8_t* operator()(uint32_t g) const { int s; uint32_t r; read_loc(T, g, s, r); return (s ? T.fq[1] : T.fq[0]) + t_lo(T, s)[4 * (size_t)r]; }
+};
+__global__ void __launch_bounds__(TN_TPB) k_text_names(Text T, const uint64_t* __restrict__ off, uint32_t n_rows, uint8_t* __restrict__ blob, uint64_t names_len) {
+    name_blob_write(TextNameSrc{ T }, off, n_rows, blob, names_len);
 }

@@ -309,3 +309,35 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// ---------------------------------------------------------------- fixed-stride rows, written in 16-byte groups (k_dec_rows, k_text_rows, k_sel_rows)
+// x - y in each byte, mod 256
+__device__ __forceinline__ uint32_t sub_bytes(uint32_t x, uint32_t y) { return ((x | 0x80808080u) - (y & 0x7F7F7F7Fu)) ^ ((x ^ ~y) & 0x80808080u); }
+// the low n bytes (n <= 4 counts as all) of a word as a mask: word i of a group that holds `have` bytes of a read keeps low_bytes(have - 4 * i) of them, the pad
+// takes the rest - merged in registers, so that the read's tail and the pad behind it are one store
+__device__ __forceinline__ uint32_t low_bytes(int n) { return n >= 4 ? 0xFFFFFFFFu : (n <= 0 ? 0u : (1u << (8 * n)) - 1u); }
+// The walk of a workgroup of `tpb` threads over the groups of its rows, G = ceil(row_len / 16) to a row: thread t starts at group k = t % G of row j = t / G, and a
+// step takes it tpb groups further.  Consecutive threads hold consecutive groups of consecutive rows, so with row_len % 16 == 0 a wave's stores are one contiguous
+// span of whole groups (no row shares a group with another: no partly written 64-byte sector between two waves).
+struct GroupWalk {
+    uint32_t G, sj, sk;                                                      // groups per row; one step: sj rows and sk groups further
+    uint32_t j, k;                                                           // the row (counted from the workgroup's first) and the group in it
+    __device__ __forceinline__ GroupWalk(uint64_t row_len, uint32_t tpb) : G((uint32_t)((row_len + 15u) / 16u)) { sj = tpb / G; sk = tpb % G; j = threadIdx.x / G; k = threadIdx.x % G; }
+    __device__ __forceinline__ void step() { j += sj; k += sk; if (k >= G) { k -= G; j++; } }
+};
+// The group [k0, k0 + 16) of the row that starts at byte `at - k0` of each buffer (null: not wanted), from its words wb / wq.  Every group is stored ONCE, pad
+// included - no second pass over the rows, no byte written twice: one 16-byte store per buffer where vec says that every group is whole and aligned (row_len % 16
+// == 0 and both buffers 16-byte aligned), else the row's bytes of the group one by one (the last group of a row ends with the row).
+__device__ __forceinline__ void store_group16(uint8_t* bases, uint8_t* quals, uint64_t at, uint64_t row_len, uint64_t k0, uint32_t vec, const uint32_t (&wb)[4],
+                                              const uint32_t (&wq)[4]) {
+    if (vec) {
+        if (bases) *(uint4*)(bases + at) = make_uint4(wb[0], wb[1], wb[2], wb[3]);
+        if (quals) *(uint4*)(quals + at) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
+    } else {
+        const uint32_t cnt = row_len - k0 < 16u ? (uint32_t)(row_len - k0) : 16u;
+        for (uint32_t i = 0; i < cnt; i++) {
+            if (bases) bases[at + i] = (uint8_t)(wb[i >> 2] >> (8u * (i & 3u)));
+            if (quals) quals[at + i] = (uint8_t)(wq[i >> 2] >> (8u * (i & 3u)));
+        }
+    }
+}

@@ -187,6 +187,9 @@ static inline int rfq_fail(rfq_ctx* c, int code, const char* fmt, ...) {
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return rfq_fail(ctx, RFQ_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 #define KCHK(ctx, what) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return rfq_fail(ctx, RFQ_E_HIP, "launch of %s failed: %s", what, hipGetErrorString(e_)); } while (0)
 
+// rows of stride row_len in the buffers p and q (either may be null) consist of whole, aligned 16-byte groups: the row kernels load / store them 16 bytes at a time
+static inline uint32_t rows_vec(uint64_t row_len, const void* p, const void* q) { return (row_len % 16u == 0 && !(((uintptr_t)p | (uintptr_t)q) & 15u)) ? 1u : 0u; }
+
 // ---------------------------------------------------------------- multi-block exclusive scan (3 launches)
 #define SCAN_TPB 256
 #define SCAN_ITEMS 8

@@ -650,7 +650,7 @@ extern "C" int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* ra, rfq
     o.bases = ra->d_bases; o.quals = ra->d_quals; o.lens = ra->d_lens; o.row_len = L; o.n_rows = n_rows;
     o.codes = ra->base_mode == RFQ_ROWS_CODE ? 1u : 0u;
     o.qoff4 = ra->qual_offset * 0x01010101u; o.pad_b4 = ra->pad_base * 0x01010101u; o.pad_q4 = ra->pad_qual * 0x01010101u;
-    o.vec = (L % 16u == 0 && !((uintptr_t)ra->d_bases & 15u) && !((uintptr_t)ra->d_quals & 15u)) ? 1u : 0u;
+    o.vec = rows_vec(L, ra->d_bases, ra->d_quals);
     DChunk* CHm = ctx->b[DB_CHUNKS].as<DChunk>();
     // the text path's ranges: bases and qualities of a pass are placed by 32-bit prefix sums (RFQ_SLICE_BASES forces ranges on small images)
     const uint64_t slice_env = ctx->opt.slice_bases;

@@ -2,6 +2,7 @@
 // Replaces, per batch: Repaq::compress / compressPE chunking (src/repaq.cpp:530-762), RfqCodec::makeHeader
 // (src/rfqcodec.cpp:20-145), RfqCodec::encodeChunk (:147-586) and RfqChunk::write (src/rfqchunk.cpp:230-311).
 #include "rfq_ctx.h"
+#include <type_traits>
 #include "rfq_encode_kernels.h"
 #include <algorithm>
 #include <cstring>
@@ -953,6 +954,60 @@ extern "C" int rfq_scan_batch(rfq_ctx* ctx, const rfq_encode_args* a, rfq_scan_r
     out->h_end2 = (r.n_chunks && a->paired == RFQ_PE_TWO_FILES) ? ctx->scan_end[1].data() : nullptr;
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- steps the rows entry points below share
+// a call begins: no stage timed, nothing waiting in the read-back block, the context's device current
+static int rows_begin(rfq_ctx* ctx) {
+    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return RFQ_OK;
+}
+// the context's verdict block as a fresh Stat: all zero, bad_row (and the text's first_empty) all ones - "no such row" under the kernels' atomicMin
+template <class Stat> static int rows_stat_fresh(rfq_ctx* ctx, hipStream_t S, Stat** dst) {
+    HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(Stat)));
+    Stat* const d = *dst = ctx->rows_stat.as<Stat>();
+    HIPCHK(ctx, hipMemsetAsync(d, 0, sizeof(Stat), S));
+    if constexpr (std::is_same<Stat, TextRowsStat>::value) HIPCHK(ctx, hipMemsetAsync(&d->first_empty, 0xFF, sizeof d->first_empty, S));
+    HIPCHK(ctx, hipMemsetAsync(&d->bad_row, 0xFF, sizeof d->bad_row, S));
+    return RFQ_OK;
+}
+// output rows of a workgroup of k_text_rows / k_sel_rows: about four 16-byte groups per thread
+static uint32_t rows_per(uint32_t row_len) { const uint32_t G = (row_len + 15u) / 16u; return std::max(1u, 1024u / G); }
+// workgroups of a names writer (name_blob_write): tiles of TN_TILE bytes, counted from the 16-byte boundary at or below the blob
+static int name_blob_blocks(rfq_ctx* ctx, const uint8_t* dst, uint64_t names_len, uint32_t* blocks) {
+    const uint64_t span = names_len + ((uintptr_t)dst & 15u), nb = (span + TN_TILE - 1) / TN_TILE;
+    if (nb > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "a name blob of %llu bytes is too large for one call", (unsigned long long)names_len);
+    *blocks = (uint32_t)nb;
+    return RFQ_OK;
+}
+// room for everything asked for, or nothing is written (A: rfq_text_rows_args, rfq_select_rows_args - the same output fields)
+template <class A> static int rows_room(rfq_ctx* ctx, const A* a, uint64_t n_rows, uint64_t names_len, uint32_t max_len) {
+    const unsigned long long rowb = (unsigned long long)n_rows * a->row_len;
+    if ((n_rows && a->row_len < max_len) || (a->d_bases && a->bases_cap < rowb) || (a->d_quals && a->quals_cap < rowb) || (a->d_lens && a->lens_cap < n_rows) ||
+        (a->d_names && a->names_cap < names_len) || (a->d_name_off && a->off_cap < n_rows + 1))
+        return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need row_len >= %u, %llu bytes per row buffer (at that row_len: %llu), %llu lens, %llu name bytes, %llu offsets",
+                        max_len, rowb, (unsigned long long)n_rows * std::max(a->row_len, max_len), (unsigned long long)n_rows, (unsigned long long)names_len,
+                        (unsigned long long)n_rows + 1);
+    return RFQ_OK;
+}
+// a call that leaves no rows: the offsets of no names are one zero
+static int rows_none(rfq_ctx* ctx, uint64_t* d_name_off) {
+    if (d_name_off) HIPCHK(ctx, hipMemsetAsync(d_name_off, 0, 8, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); ctx->timer.collect();
+    return RFQ_OK;
+}
+// no output may lie on an input: the bytes a call can write against the bytes it reads (tail: what the message ends in)
+struct Span { const void* p; unsigned long long n; const char* what; };
+static bool sel_overlap(const void* a, unsigned long long an, const void* b, unsigned long long bn) {
+    if (!a || !b || !an || !bn) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    const uintptr_t a1 = an > UINTPTR_MAX - a0 ? UINTPTR_MAX : a0 + (uintptr_t)an, b1 = bn > UINTPTR_MAX - b0 ? UINTPTR_MAX : b0 + (uintptr_t)bn;
+    return a0 < b1 && b0 < a1;
+}
+template <size_t NO, size_t NI> static int rows_apart(rfq_ctx* ctx, const Span (&outs)[NO], const Span (&ins)[NI], const char* tail) {
+    for (const Span& o : outs) for (const Span& i : ins)
+        if (sel_overlap(o.p, o.n, i.p, i.n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the input %s%s", o.what, i.what, tail);
+    return RFQ_OK;
+}
 // ---------------------------------------------------------------- rows -> FASTQ text (-> image): rfq_rows_to_text, rfq_encode_rows of include/rfq_hip.h
 // The judged part (k_rows_sizes + one scan per text) ends in ONE read-back - the texts' sizes, the bases, the error bits - and the writer (k_rows_text)
 // runs only on rows that passed; what the writer itself finds in the bytes comes back with a second look at the same block.
@@ -970,22 +1025,19 @@ static int rows_text_impl(rfq_ctx* ctx, const rfq_rows_in* in, int32_t paired, u
     if (((uintptr_t)in->d_lens & 3u) || ((uintptr_t)in->d_name_off & 7u)) return rfq_fail(ctx, RFQ_E_ARG, "d_lens must be 4-byte and d_name_off 8-byte aligned");
     if ((((uintptr_t)d_out1) | ((uintptr_t)d_out2)) & 15u) return rfq_fail(ctx, RFQ_E_ARG, "output buffers must be 16-byte aligned");
     if (!size_only && two && (d_out1 == nullptr) != (d_out2 == nullptr)) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_PE_TWO_FILES: give both output buffers or none");
-    hipStream_t S = ctx->stream;
-    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t S = ctx->stream; int rc;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
     if (n == 0) { ctx->timer.collect(); return RFQ_OK; }
     const uint64_t nrec[2] = { two ? n / 2 : n, two ? n / 2 : 0 };
     RowsIn ri; memset(&ri, 0, sizeof ri);
     ri.bases = in->d_bases; ri.quals = in->d_quals; ri.lens = in->d_lens; ri.names = in->d_names; ri.name_off = in->d_name_off;
     ri.n_rows = n; ri.names_len = in->names_len; ri.row_len = in->row_len; ri.codes = in->base_mode == RFQ_ROWS_CODE ? 1u : 0u;
     ri.qoff = in->qual_offset; ri.qoff4 = in->qual_offset * 0x01010101u;
-    ri.vec = (in->row_len % 16u == 0 && !(((uintptr_t)in->d_bases | (uintptr_t)in->d_quals) & 15u)) ? 1u : 0u;
+    ri.vec = rows_vec(in->row_len, in->d_bases, in->d_quals);
 
     ctx->timer.begin("rows_sizes", S);
-    HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(RowsStat)));
-    RowsStat* dst = ctx->rows_stat.as<RowsStat>();
-    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(RowsStat), S));
-    HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+    RowsStat* dst = nullptr;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
     for (int t = 0; t < nt; t++) HIPCHK(ctx, ctx->rows_off[t].ensure((size_t)(nrec[t] + 2) * 8));
     HIPCHK(ctx, ctx->b[B_SCANTMP].ensure(std::max<size_t>(1024, (size_t)(nrec[0] / SCAN_TILE + 2) * 16)));
     uint64_t* off[2] = { ctx->rows_off[0].as<uint64_t>(), two ? ctx->rows_off[1].as<uint64_t>() : nullptr };
@@ -1080,8 +1132,7 @@ static int text_rows_impl(rfq_ctx* ctx, const rfq_text_rows_args* a, const rfq_e
         if (b.nbytes[s] && !b.fq[s]) return rfq_fail(ctx, RFQ_E_ARG, "null FASTQ pointer");
         if (b.nbytes[s] && (((uintptr_t)b.fq[s]) & 15u)) return rfq_fail(ctx, RFQ_E_HIP, "internal: FASTQ stream not rounded down to 16 bytes");
     }
-    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
     // (a marker, not a phase: the text has '\r' line ends or blank lines and was rewritten by the normaliser - tests look for it)
     if (nm) { ctx->timer.begin("normalise", S); ctx->timer.end(S); }
     HIPCHK(ctx, table(ctx->d_status, sizeof(DevStatus), b.dst));
@@ -1091,8 +1142,7 @@ static int text_rows_impl(rfq_ctx* ctx, const rfq_text_rows_args* a, const rfq_e
     uint32_t n_units = ea->paired == RFQ_SE ? cut.nrec[0] : (ea->paired == RFQ_PE_TWO_FILES ? std::min(cut.nrec[0], cut.nrec[1]) : cut.nrec[0] / 2);
     memset(out, 0, sizeof *out);
     TextRowsStat hs; memset(&hs, 0, sizeof hs); uint64_t names_len = 0; uint32_t cons[2] = { 0, 0 };
-    HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(TextRowsStat)));
-    TextRowsStat* dst = ctx->rows_stat.as<TextRowsStat>();
+    TextRowsStat* dst = nullptr;
     int32_t* lens = nullptr; uint64_t* off = nullptr;
     for (;;) {
         const uint32_t n_rows = n_units * b.T.upr; b.T.n_reads = n_rows;
@@ -1100,8 +1150,7 @@ static int text_rows_impl(rfq_ctx* ctx, const rfq_text_rows_args* a, const rfq_e
         ctx->timer.begin("text_rows:sizes", S);
         HIPCHK(ctx, table(B[B_LEN], ((size_t)n_rows + 2) * 4, lens)); HIPCHK(ctx, table(B[B_P], ((size_t)n_rows + 2) * 8, off));
         HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)n_rows / SCAN_TILE + 2) * 16)));
-        HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(TextRowsStat), S));
-        HIPCHK(ctx, hipMemsetAsync(&dst->first_empty, 0xFF, sizeof dst->first_empty, S)); HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+        if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
         hipLaunchKernelGGL(k_text_rows_sizes, dim3((n_rows + TS_ROWS - 1u) / TS_ROWS), dim3(256), 0, S, b.T, n_rows, lens, off, dst);
         KCHK(ctx, "k_text_rows_sizes");
         scan_exclusive<uint64_t>(S, off, off, n_rows, B[B_SCANTMP].as<uint64_t>(), 1);
@@ -1127,28 +1176,15 @@ static int text_rows_impl(rfq_ctx* ctx, const rfq_text_rows_args* a, const rfq_e
     out->n_rows = n_rows; out->n_bases = hs.n_bases; out->names_len = names_len; out->max_len = hs.max_len; out->max_name = hs.max_name;
     for (int s = 0; s < nstreams; s++) out->consumed[s] = n_rows ? (size_t)consumed_of(b, s, cons[s]) : 0;
     if (size_query) { ctx->timer.collect(); return RFQ_OK; }
-    {   // room for everything asked for, or nothing is written
-        const unsigned long long rowb = (unsigned long long)n_rows * a->row_len;
-        if ((n_rows && a->row_len < hs.max_len) || (a->d_bases && a->bases_cap < rowb) || (a->d_quals && a->quals_cap < rowb) || (a->d_lens && a->lens_cap < n_rows) ||
-            (a->d_names && a->names_cap < names_len) || (a->d_name_off && a->off_cap < n_rows + 1))
-            return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need row_len >= %u, %llu bytes per row buffer (at that row_len: %llu), %llu lens, %llu name bytes, %llu offsets",
-                            hs.max_len, rowb, (unsigned long long)n_rows * std::max(a->row_len, hs.max_len), (unsigned long long)n_rows, (unsigned long long)names_len,
-                            (unsigned long long)n_rows + 1);
-    }
-    if (n_rows == 0) {
-        if (a->d_name_off) HIPCHK(ctx, hipMemsetAsync(a->d_name_off, 0, 8, S));
-        HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect();
-        return RFQ_OK;
-    }
+    if ((rc = rows_room(ctx, a, n_rows, names_len, hs.max_len)) != RFQ_OK) return rc;
+    if (n_rows == 0) return rows_none(ctx, a->d_name_off);
     ctx->timer.begin("text_rows:rows", S);
     if (a->d_lens) HIPCHK(ctx, hipMemcpyAsync(a->d_lens, lens, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, S));
     if (a->d_bases || a->d_quals) {
         TextRowsOut o; memset(&o, 0, sizeof o);
         o.bases = a->d_bases; o.quals = a->d_quals; o.row_len = a->row_len; o.n_rows = (uint32_t)n_rows; o.codes = a->base_mode == RFQ_ROWS_CODE ? 1u : 0u;
         o.qoff4 = a->qual_offset * 0x01010101u; o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
-        o.vec = (a->row_len % 16u == 0 && !(((uintptr_t)a->d_bases | (uintptr_t)a->d_quals) & 15u)) ? 1u : 0u;
-        const uint32_t G = (a->row_len + 15u) / 16u;
-        o.per = std::max(1u, 1024u / G);                                    // about four groups per thread
+        o.vec = rows_vec(a->row_len, a->d_bases, a->d_quals); o.per = rows_per(a->row_len);
         hipLaunchKernelGGL(k_text_rows, dim3((uint32_t)((n_rows + o.per - 1) / o.per)), dim3(256), 0, S, b.T, o, dst);
         KCHK(ctx, "k_text_rows");
     }
@@ -1156,9 +1192,9 @@ static int text_rows_impl(rfq_ctx* ctx, const rfq_text_rows_args* a, const rfq_e
     ctx->timer.begin("text_rows:names", S);
     if (a->d_name_off) HIPCHK(ctx, hipMemcpyAsync(a->d_name_off, off, (size_t)(n_rows + 1) * 8, hipMemcpyDeviceToDevice, S));
     if (a->d_names && names_len) {
-        const uint64_t span = names_len + ((uintptr_t)a->d_names & 15u), blocks = (span + TN_TILE - 1) / TN_TILE;
-        if (blocks > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "a name blob of %llu bytes is too large for one call", (unsigned long long)names_len);
-        hipLaunchKernelGGL(k_text_names, dim3((uint32_t)blocks), dim3(TN_TPB), 0, S, b.T, (const uint64_t*)off, (uint32_t)n_rows, a->d_names, names_len);
+        uint32_t blocks = 0;
+        if ((rc = name_blob_blocks(ctx, a->d_names, names_len, &blocks)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_text_names, dim3(blocks), dim3(TN_TPB), 0, S, b.T, (const uint64_t*)off, (uint32_t)n_rows, a->d_names, names_len);
         KCHK(ctx, "k_text_names");
     }
     ctx->timer.end(S);
@@ -1206,12 +1242,6 @@ extern "C" int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* a, rfq_text
 // The judging pass (k_sel_judge), TWO scans - the kept flags to output row indices (32-bit), the kept name sizes to output name offsets (64-bit: a blob may exceed
 // 4 GiB, and the block scan's wave primitives take 4- and 8-byte values, not a two-field struct) - and ONE read-back: the verdict block and the two totals.  The host
 // refuses or goes on; k_sel_tables makes the per-output-row tables (and the caller's lens / name_off), k_sel_rows and k_sel_names follow them.
-static bool sel_overlap(const void* a, unsigned long long an, const void* b, unsigned long long bn) {
-    if (!a || !b || !an || !bn) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    const uintptr_t a1 = an > UINTPTR_MAX - a0 ? UINTPTR_MAX : a0 + (uintptr_t)an, b1 = bn > UINTPTR_MAX - b0 ? UINTPTR_MAX : b0 + (uintptr_t)bn;
-    return a0 < b1 && b0 < a1;
-}
 extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_select_rows_args* a, rfq_select_rows_result* res) {
     if (!ctx || !in || !a || !res) return RFQ_E_ARG;
     memset(res, 0, sizeof *res);
@@ -1229,22 +1259,21 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     if (((uintptr_t)in->d_lens | (uintptr_t)a->d_lens | (uintptr_t)a->d_start | (uintptr_t)a->d_len) & 3u)
         return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_start and d_len must be 4-byte aligned");
     if (((uintptr_t)in->d_name_off | (uintptr_t)a->d_name_off) & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
-    {   // no output may lie on an input: the bytes a call can write (its cap, and never more than n_rows rows of row_len) against the bytes it reads
+    int rc;
+    {   // the bytes a call can write (its cap, and never more than n_rows rows of row_len) against the bytes it reads
         const unsigned long long rows_in = (unsigned long long)n * in->row_len, rows_out = (unsigned long long)n * a->row_len;
-        const struct { const void* p; unsigned long long n; const char* what; } ins[] = {
+        const Span ins[] = {
             { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" },
             { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }, { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" },
             { a->d_keep, n, "d_keep" }, { a->d_start, n * 4ull, "d_start" }, { a->d_len, n * 4ull, "d_len" } };
-        const struct { const void* p; unsigned long long n; const char* what; } outs[] = {
+        const Span outs[] = {
             { a->d_bases, std::min<unsigned long long>(a->bases_cap, rows_out), "d_bases" }, { a->d_quals, std::min<unsigned long long>(a->quals_cap, rows_out), "d_quals" },
             { a->d_lens, std::min<unsigned long long>(a->lens_cap, n) * 4ull, "d_lens" }, { a->d_names, std::min<unsigned long long>(a->names_cap, in->names_len), "d_names" },
             { a->d_name_off, std::min<unsigned long long>(a->off_cap, n + 1) * 8ull, "d_name_off" } };
-        for (const auto& o : outs) for (const auto& i : ins)
-            if (sel_overlap(o.p, o.n, i.p, i.n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the input %s: selection in place is not offered", o.what, i.what);
+        if ((rc = rows_apart(ctx, outs, ins, ": selection in place is not offered")) != RFQ_OK) return rc;
     }
     hipStream_t S = ctx->stream; DBuf* B = ctx->b;
-    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
     res->n_in = n;
     SelStat hs; memset(&hs, 0, sizeof hs); uint32_t n_out = 0; uint64_t names_len = 0;
     SelIn si; memset(&si, 0, sizeof si);
@@ -1253,13 +1282,11 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     uint32_t* pos = nullptr; uint64_t* noff = nullptr;
     if (n) {
         ctx->timer.begin("select:judge", S);
-        HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(SelStat)));
-        SelStat* dst = ctx->rows_stat.as<SelStat>();
+        SelStat* dst = nullptr;
         HIPCHK(ctx, table(B[B_LEN], ((size_t)n + 2) * 4, pos));
         if (named) HIPCHK(ctx, table(B[B_P], ((size_t)n + 2) * 8, noff));
         HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)n / SCAN_TILE + 2) * 16)));
-        HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(SelStat), S));
-        HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+        if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
         hipLaunchKernelGGL(k_sel_judge, dim3((uint32_t)((n + SJ_ROWS - 1u) / SJ_ROWS)), dim3(256), 0, S, si, pos, noff, dst);
         KCHK(ctx, "k_sel_judge");
         scan_exclusive<uint32_t>(S, pos, pos, n, B[B_SCANTMP].as<uint32_t>(), 1);
@@ -1278,21 +1305,8 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     res->n_rows = n_out; res->n_bases = hs.n_bases; res->names_len = names_len; res->max_len = hs.max_len; res->max_name = hs.max_name;
     res->dropped_mask = hs.d_mask; res->dropped_short = hs.d_short; res->dropped_mate = hs.d_mate;
     if (size_query) { ctx->timer.collect(); return RFQ_OK; }
-    {   // room for everything asked for, or nothing is written
-        const unsigned long long rowb = (unsigned long long)n_out * a->row_len;
-        if ((n_out && a->row_len < hs.max_len) || (a->d_bases && a->bases_cap < rowb) || (a->d_quals && a->quals_cap < rowb) || (a->d_lens && a->lens_cap < n_out) ||
-            (a->d_names && a->names_cap < names_len) || (a->d_name_off && a->off_cap < (size_t)n_out + 1)) {
-            const unsigned long long at = (unsigned long long)n_out * std::max(a->row_len, hs.max_len);
-            memset(res, 0, sizeof *res);
-            return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need row_len >= %u, %llu bytes per row buffer (at that row_len: %llu), %llu lens, %llu name bytes, %llu offsets",
-                            hs.max_len, rowb, at, (unsigned long long)n_out, (unsigned long long)names_len, (unsigned long long)n_out + 1);
-        }
-    }
-    if (n_out == 0) {
-        if (a->d_name_off) HIPCHK(ctx, hipMemsetAsync(a->d_name_off, 0, 8, S));
-        HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect();
-        return RFQ_OK;
-    }
+    if ((rc = rows_room(ctx, a, n_out, names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    if (n_out == 0) return rows_none(ctx, a->d_name_off);
     ctx->timer.begin("select:tables", S);
     SelRow* tab = nullptr; uint64_t* ooff = nullptr;
     HIPCHK(ctx, table(B[B_X], (size_t)n_out * sizeof(SelRow), tab));
@@ -1306,19 +1320,17 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
         o.sb = in->d_bases; o.sq = in->d_quals; o.bases = a->d_bases; o.quals = a->d_quals;
         o.row_len_in = in->row_len; o.total_in = n * in->row_len; o.row_len = a->row_len; o.n_out = n_out;
         o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
-        o.vec_in = (in->row_len % 16u == 0 && !(((a->d_bases ? (uintptr_t)in->d_bases : 0) | (a->d_quals ? (uintptr_t)in->d_quals : 0)) & 15u)) ? 1u : 0u;
-        o.vec = (a->row_len % 16u == 0 && !(((uintptr_t)a->d_bases | (uintptr_t)a->d_quals) & 15u)) ? 1u : 0u;
-        const uint32_t G = (a->row_len + 15u) / 16u;
-        o.per = std::max(1u, 1024u / G);                                    // about four groups per thread
+        o.vec_in = rows_vec(in->row_len, a->d_bases ? in->d_bases : nullptr, a->d_quals ? in->d_quals : nullptr);      // (of the buffers that are read)
+        o.vec = rows_vec(a->row_len, a->d_bases, a->d_quals); o.per = rows_per(a->row_len);
         hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)n_out + o.per - 1) / o.per)), dim3(256), 0, S, o, (const SelRow*)tab);
         KCHK(ctx, "k_sel_rows");
     }
     ctx->timer.end(S);
     ctx->timer.begin("select:names", S);
     if (a->d_names && names_len) {
-        const uint64_t span = names_len + ((uintptr_t)a->d_names & 15u), blocks = (span + TN_TILE - 1) / TN_TILE;
-        if (blocks > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "a name blob of %llu bytes is too large for one call", (unsigned long long)names_len);
-        hipLaunchKernelGGL(k_sel_names, dim3((uint32_t)blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, names_len);
+        uint32_t blocks = 0;
+        if ((rc = name_blob_blocks(ctx, a->d_names, names_len, &blocks)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_sel_names, dim3(blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, names_len);
         KCHK(ctx, "k_sel_names");
     }
     ctx->timer.end(S);
@@ -1346,23 +1358,21 @@ extern "C" int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_jud
     if (n && need_b && !in->d_bases) return rfq_fail(ctx, RFQ_E_ARG, "a base criterion (poly_g, max_n, min_complexity_pct) needs rows->d_bases");
     if (((uintptr_t)in->d_lens | (uintptr_t)a->d_start | (uintptr_t)a->d_len | (uintptr_t)a->d_metrics) & 3u)
         return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_start, d_len and d_metrics must be 4-byte aligned");
+    int rc;
     {
         const unsigned long long rows_in = (unsigned long long)n * in->row_len;
-        const struct { const void* p; unsigned long long n; const char* what; } ins[] = {
-            { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" } };
-        const struct { const void* p; unsigned long long n; const char* what; } outs[] = {
+        const Span ins[] = { { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" } };
+        const Span outs[] = {
             { a->d_keep, n, "d_keep" }, { a->d_start, n * 4ull, "d_start" }, { a->d_len, n * 4ull, "d_len" }, { a->d_why, n, "d_why" }, { a->d_metrics, n * 16ull, "d_metrics" } };
-        for (const auto& o : outs) for (const auto& i : ins)
-            if (sel_overlap(o.p, o.n, i.p, i.n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the input %s", o.what, i.what);
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
     }
     res->n_rows = n;
     if (!n) return RFQ_OK;
     hipStream_t S = ctx->stream;
-    ctx->timer.reset(); ctx->pend.clear(); ctx->pin_used = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
     JudgeIn ji; memset(&ji, 0, sizeof ji);
     ji.b = in->d_bases; ji.q = in->d_quals; ji.lens = in->d_lens; ji.total = n * in->row_len; ji.n_rows = (uint32_t)n; ji.row_len = in->row_len;
-    ji.vec_in = (in->row_len % 16u == 0 && !(((uintptr_t)in->d_bases | (uintptr_t)in->d_quals) & 15u)) ? 1u : 0u;
+    ji.vec_in = rows_vec(in->row_len, in->d_bases, in->d_quals);
     ji.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u;
     ji.trim_front = a->trim_front; ji.trim_tail = a->trim_tail; ji.poly_g = a->poly_g; ji.cut_flags = a->cut_flags; ji.cut_window = a->cut_window; ji.cut_mean_q = a->cut_mean_q;
     ji.max_len = a->max_len; ji.min_len = a->min_len; ji.max_n = a->max_n; ji.min_mean_q = a->min_mean_q; ji.qual_q = a->qual_q; ji.max_lowq_pct = a->max_lowq_pct;
@@ -1371,10 +1381,8 @@ extern "C" int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_jud
     const bool general = ctx->opt.judge_general || in->row_len > 1024u;
     ji.tile = ctx->opt.judge_general ? 64u : 1024u;
     ctx->timer.begin("judge:rows", S);
-    HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(JudgeStat)));
-    JudgeStat* dst = ctx->rows_stat.as<JudgeStat>();
-    HIPCHK(ctx, hipMemsetAsync(dst, 0, sizeof(JudgeStat), S));
-    HIPCHK(ctx, hipMemsetAsync(&dst->bad_row, 0xFF, sizeof dst->bad_row, S));
+    JudgeStat* dst = nullptr;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
     if (general) hipLaunchKernelGGL(k_judge_rows_long, dim3((uint32_t)n), dim3(64), 0, S, ji, dst);
     else if (in->row_len <= 256u) hipLaunchKernelGGL(k_judge_rows<16>, dim3((uint32_t)((n + 16u * JR_ITER - 1u) / (16u * JR_ITER))), dim3(256), 0, S, ji, dst);
     else hipLaunchKernelGGL(k_judge_rows<64>, dim3((uint32_t)((n + 4u * JR_ITER - 1u) / (4u * JR_ITER))), dim3(256), 0, S, ji, dst);

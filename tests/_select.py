@@ -268,6 +268,13 @@ def check_name_residues(codec):
     for i in range(100, 140):
         empty[i] = b""                                                       # names of no bytes pass through (the encoder refuses them later)
     call(codec, B, Q, lens, empty, keep=keep, out_shift=3)
+    # more names start in the only tile than the writer's LDS table holds (4097): it searches the offsets themselves
+    n = 6000
+    B, Q, lens, _ = small_rows(n, 8, seed=9)
+    sparse = [bytes(((i * 31 + k) % 94) + 33 for k in range(1 + i % 23)) if i in (0, 1500, 4200, 4300, 5999) else b"" for i in range(n)]
+    keep = np.ones(n, np.uint8); keep[7] = 0
+    call(codec, B, Q, lens, sparse, keep=keep, out_shift=3)
+    call(codec, B, Q, lens, sparse, keep=keep, in_shift=5)
 
 
 def check_long_name(codec):
