@@ -404,6 +404,60 @@ typedef struct {
 } rfq_judge_rows_result;
 RFQ_API int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_judge_rows_args* args, rfq_judge_rows_result* res);
 
+/* Adapter removal, in front of rfq_judge_rows: rows -> per row the length that is left and the detector that cut it, per pair the insert size and the mismatch
+ * count of the overlap found, per batch a summary and an insert-size histogram.  Like rfq_judge_rows it DECIDES and moves no bytes: d_len is what rfq_select_rows
+ * takes as d_len (start 0) and, never greater than lens[i] and possibly 0, also valid as the d_lens of a later rfq_judge_rows - adapter -> judge on the shortened
+ * lengths -> select, all on the GPU.  Integer rules of this project's own (in the manner of fastp's overlap analysis and adapter match; no parity with fastp is
+ * claimed).  No float anywhere, products in 64 bits; the same call gives the same bytes.  Quality rows and names are not looked at (d_quals, d_names, d_name_off
+ * may be NULL).
+ * Base classes.  rows->base_mode says what a base byte is: in code mode 0 1 2 3 are A C G T, in ASCII mode 'A' 'C' 'G' 'T' in either case; every other byte (code 4
+ * and above, N, IUPAC letters) is OTHER.  The complement swaps A with T and C with G and leaves other as other.  Two positions AGREE when both are in A C G T and
+ * equal; a position that is other never agrees.  Only positions < lens[i] of a row are data: what lies behind a read never influences a result.
+ * Pair overlap (pairs = 1; rows 2k / 2k + 1 are R1 / R2 of pair k).  x = R1, l1 bases; y = the reverse complement of R2, l2 bases: y[j] = comp(r2[l2 - 1 - j]).
+ * A shift d aligns y[j] with x[j + d]; the compared positions are j in [max(0, -d), min(l2, l1 - d)), ov(d) is their number and diff(d) the number of them that do
+ * not agree.  d is ACCEPTABLE when ov(d) >= min_overlap, diff(d) <= max_diff and diff(d) * 100 <= max_diff_pct * ov(d).  Shifts are tried in this order: first
+ * d = 0, 1, ..., l1 - min_overlap, then d = -1, -2, ..., -(l2 - min_overlap) (a range whose end lies below its start is empty); the first acceptable shift wins - no
+ * shift is skipped by an early-exit heuristic, the full count decides.  Found: insert = d + l2, diff = diff(d), cut_o(R1) = min(l1, insert), cut_o(R2) =
+ * min(l2, insert).  Not found: insert = -1, diff = 0, cut_o = the row's length.
+ * Adapter match, per row: without pairs every row uses adapter 1, with pairs even rows adapter 1 and odd rows adapter 2; either may be off.  For a row of l bases
+ * and an adapter A of m bases, p in [0, l): c = min(m, l - p), diff_a(p) = the number of j < c for which row[p + j] does not agree with A[j]; p is acceptable when
+ * c >= adapter_min and either adapter_mm_per == 0 and diff_a(p) == 0, or adapter_mm_per > 0 and diff_a(p) * adapter_mm_per <= c.  cut_a = the smallest acceptable p,
+ * or l.  The match runs over the whole read, independent of the overlap's verdict.
+ * Per row: len = min(cut_o, cut_a); how has RFQ_CUT_BY_OVERLAP set when cut_o < l and RFQ_CUT_BY_ADAPTER when cut_a < l (both may be set).
+ * The histogram is zeroed, then filled: bin b < hist_len - 1 counts the found pairs with insert == b, the last bin those with insert >= hist_len - 1; pairs without
+ * an overlap are not counted.  An output that is NULL is not produced; the result is filled also when every output is NULL.  rows_cut: rows with len < l.
+ * RFQ_E_ARG, judged on the host: an odd n_rows with pairs; with pairs min_overlap == 0 or max_diff_pct > 100; an adapter longer than 64 bases or with a byte other
+ * than ACGTacgt; h_adapter2, d_insert, d_diff or d_insert_hist without pairs; adapter_min outside 1 .. 64 with an adapter; hist_len == 0 with a histogram pointer or
+ * hist_len > 65536; d_bases == NULL or row_len == 0 with rows; a bad base_mode; a d_lens / d_len / d_insert / d_diff that is not 4-byte or a d_insert_hist that is
+ * not 8-byte aligned; an output that overlaps an input (byte ranges are compared).  Neither pairs nor an adapter is NOT an error: every row keeps its length.
+ * RFQ_E_ARG, judged on the device, the message names the first such row: lens[i] < 0 or > row_len - what the outputs hold is then unspecified; nothing outside the
+ * row buffers is read for such a row.  After any refusal the context stays usable.
+ * The row buffer may have any alignment, on rfq_judge_rows' terms - never a byte outside [d_bases, d_bases + n_rows * row_len).  n_rows * row_len may exceed 4 GiB
+ * (n_rows < 2^31).  Rows of up to 1024 bytes are searched as bit planes (64 positions per word); longer ones (and every one with RFQ_ADAPTER=general) byte by byte,
+ * a lane per shift: the search is quadratic in the read length, and slow on very long rows.  Synchronous on the context's stream; stage time through
+ * rfq_last_timings (adapter:rows). */
+#define RFQ_CUT_BY_OVERLAP 1u
+#define RFQ_CUT_BY_ADAPTER 2u
+typedef struct {
+    int32_t  pairs;                       /* 1: overlap search on, n_rows must be even                                  */
+    uint32_t min_overlap, max_diff, max_diff_pct;      /* pairs: min_overlap >= 1, max_diff_pct <= 100                  */
+    const uint8_t* h_adapter1; uint32_t adapter1_len;  /* HOST bytes, A C G T in either case, 1 .. 64; NULL / 0 = off   */
+    const uint8_t* h_adapter2; uint32_t adapter2_len;  /* pairs only (odd rows)                                         */
+    uint32_t adapter_min, adapter_mm_per; /* with an adapter: adapter_min in 1 .. 64                                    */
+    uint32_t hist_len;                    /* entries of d_insert_hist, <= 65536                                         */
+    int32_t*  d_len;                      /* [n_rows] or NULL                                                           */
+    uint8_t*  d_how;                      /* [n_rows] RFQ_CUT_BY_* bits, or NULL                                        */
+    int32_t*  d_insert;                   /* [n_rows / 2] insert or -1, or NULL; pairs only                             */
+    int32_t*  d_diff;                     /* [n_rows / 2], or NULL; pairs only                                          */
+    uint64_t* d_insert_hist;              /* [hist_len], 8-byte aligned, or NULL; pairs only                            */
+} rfq_adapter_rows_args;
+typedef struct {
+    uint64_t n_rows, n_pairs, pairs_found;
+    uint64_t rows_cut, rows_cut_overlap, rows_cut_adapter;   /* len < l; the how bits                                   */
+    uint64_t bases_in, bases_out;
+} rfq_adapter_rows_result;
+RFQ_API int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_adapter_rows_args* args, rfq_adapter_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -437,7 +491,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

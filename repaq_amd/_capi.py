@@ -132,6 +132,20 @@ class JudgeRowsResult(C.Structure):
                                           "q30_in", "bases_out", "qsum_out", "q20_out", "q30_out")]
 
 
+CUT_BY_OVERLAP, CUT_BY_ADAPTER = 1, 2
+
+
+class AdapterRowsArgs(C.Structure):
+    _fields_ = [("pairs", C.c_int32), ("min_overlap", C.c_uint32), ("max_diff", C.c_uint32), ("max_diff_pct", C.c_uint32),
+                ("h_adapter1", C.c_char_p), ("adapter1_len", C.c_uint32), ("h_adapter2", C.c_char_p), ("adapter2_len", C.c_uint32),
+                ("adapter_min", C.c_uint32), ("adapter_mm_per", C.c_uint32), ("hist_len", C.c_uint32),
+                ("d_len", C.c_void_p), ("d_how", C.c_void_p), ("d_insert", C.c_void_p), ("d_diff", C.c_void_p), ("d_insert_hist", C.c_void_p)]
+
+
+class AdapterRowsResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_rows", "n_pairs", "pairs_found", "rows_cut", "rows_cut_overlap", "rows_cut_adapter", "bases_in", "bases_out")]
+
+
 _libs = {}
 
 
@@ -167,6 +181,7 @@ def load(path=None):
     L.rfq_text_rows.argtypes = [C.c_void_p, C.POINTER(TextRowsArgs), C.POINTER(TextRowsResult)]
     L.rfq_select_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(SelectRowsArgs), C.POINTER(SelectRowsResult)]
     L.rfq_judge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(JudgeRowsArgs), C.POINTER(JudgeRowsResult)]
+    L.rfq_adapter_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(AdapterRowsArgs), C.POINTER(AdapterRowsResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -190,6 +205,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

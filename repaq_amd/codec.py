@@ -336,6 +336,24 @@ class RfqCodec:
         self._check(self._L.rfq_judge_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
+    # --- adapter removal, in front of the judge: rows -> the length that is left, the detector, insert sizes (rfq_adapter_rows)
+    def adapter_rows(self, n_rows, row_len, d_bases, d_lens, codes=False, pairs=False, min_overlap=0, max_diff=0, max_diff_pct=0, adapter1=None, adapter2=None,
+                     adapter_min=0, adapter_mm_per=0, hist_len=0, d_len=None, d_how=None, d_insert=None, d_diff=None, d_insert_hist=None, base_mode=None):
+        """rfq_adapter_rows: base rows and lengths (qualities and names are not looked at) and the rules of include/rfq_hip.h: pairs (rows 2k / 2k + 1: the
+        overlap search with min_overlap, max_diff, max_diff_pct), adapter1 / adapter2 (bytes of ACGT, at most 64; None: off; adapter2 is the odd rows' with pairs)
+        with adapter_min and adapter_mm_per.  d_len: n_rows int32 - what select_rows takes as d_len and a later judge_rows as d_lens -, d_how: n_rows bytes
+        (CUT_BY_OVERLAP | CUT_BY_ADAPTER), d_insert / d_diff: n_rows / 2 int32, d_insert_hist: hist_len uint64; an output that is None is not produced.
+        Returns AdapterRowsResult (n_rows, n_pairs, pairs_found, rows_cut, rows_cut_overlap, rows_cut_adapter, bases_in, bases_out)."""
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
+        if base_mode is not None:
+            rows.base_mode = base_mode
+        a1 = bytes(adapter1) if adapter1 is not None else None; a2 = bytes(adapter2) if adapter2 is not None else None
+        a = A.AdapterRowsArgs(1 if pairs else 0, min_overlap, max_diff, max_diff_pct, a1, len(a1) if a1 else 0, a2, len(a2) if a2 else 0, adapter_min, adapter_mm_per,
+                              hist_len, d_len, d_how, d_insert, d_diff, d_insert_hist)
+        r = A.AdapterRowsResult()
+        self._check(self._L.rfq_adapter_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

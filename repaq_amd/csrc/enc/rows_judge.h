@@ -107,16 +107,19 @@ __device__ __forceinline__ uint32_t jr_sum16(const uint32_t (&q)[4]) { return ud
 // Bytes [off, off + 16) of the row that starts at byte `rowbase` of buf (off a multiple of 16, off < lim <= row_len): bytes at positions >= lim come back 0.
 // Never a byte outside the buffer: whole aligned groups lie inside their row; else 16 bytes at the row's own alignment wherever they still lie inside the
 // buffer; only at the buffer's very end byte by byte.
-__device__ __forceinline__ void jr_ld(const JudgeIn& in, const uint8_t* buf, uint64_t rowbase, uint32_t off, uint32_t lim, uint32_t (&w)[4]) {
+__device__ __forceinline__ void rows_ld16(const uint8_t* buf, uint32_t vec_in, uint64_t total, uint64_t rowbase, uint32_t off, uint32_t lim, uint32_t (&w)[4]) {
     const uint64_t p = rowbase + off; const uint32_t have = lim - off < 16u ? lim - off : 16u;
-    if (in.vec_in) rt_ld16(buf + p, true, w);
-    else if (p + 16u <= in.total) rt_ld16(buf + p, false, w);
+    if (vec_in) rt_ld16(buf + p, true, w);
+    else if (p + 16u <= total) rt_ld16(buf + p, false, w);
     else {
         w[0] = w[1] = w[2] = w[3] = 0u;
         for (uint32_t i = 0; i < have; i++) w[i >> 2] |= (uint32_t)buf[p + i] << (8u * (i & 3u));
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) w[i] &= low_bytes((int)have - 4 * i);
+}
+__device__ __forceinline__ void jr_ld(const JudgeIn& in, const uint8_t* buf, uint64_t rowbase, uint32_t off, uint32_t lim, uint32_t (&w)[4]) {
+    rows_ld16(buf, in.vec_in, in.total, rowbase, off, lim, w);
 }
 // E[i] lives at word i + i / 16: the lanes of a group read and write 16 positions apart - 17 words, another bank each
 __device__ __forceinline__ uint32_t jr_ix(uint32_t i) { return i + (i >> 4); }

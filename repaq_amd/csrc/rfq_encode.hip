@@ -1399,3 +1399,80 @@ extern "C" int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_jud
     res->bases_out = hs.c[10]; res->qsum_out = hs.c[11]; res->q20_out = hs.c[12]; res->q30_out = hs.c[13];
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- rows -> the length adapter removal leaves, insert sizes, a summary: rfq_adapter_rows of include/rfq_hip.h
+// One kernel and one read-back, like rfq_judge_rows.  The adapters come as host bytes and travel as two class planes of 64 bits in the kernel arguments.  Which
+// kernel is the row length's to say: up to 256 bytes a DPP row of 16 lanes holds a pair, up to 1024 a wave, beyond that (or with RFQ_ADAPTER=general) a wave
+// compares a pair byte by byte (enc/rows_adapter.h).
+static int adapter_planes(rfq_ctx* ctx, const uint8_t* h, uint32_t m, const char* what, unsigned long long* H, unsigned long long* L, uint32_t* len) {
+    *H = *L = 0ull; *len = 0u;
+    if (!h || !m) return RFQ_OK;
+    if (m > 64u) return rfq_fail(ctx, RFQ_E_ARG, "%s has %u bases: an adapter has at most 64", what, m);
+    for (uint32_t j = 0; j < m; j++) {
+        unsigned long long c;
+        switch (h[j] & 0xDFu) { case 'A': c = 0; break; case 'C': c = 1; break; case 'G': c = 2; break; case 'T': c = 3; break;
+        default: return rfq_fail(ctx, RFQ_E_ARG, "%s holds a byte that is not one of ACGTacgt (0x%02x at %u)", what, h[j], j); }
+        *H |= (c >> 1) << j; *L |= (c & 1ull) << j;
+    }
+    *len = m;
+    return RFQ_OK;
+}
+extern "C" int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_adapter_rows_args* a, rfq_adapter_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows;
+    if (a->pairs != 0 && a->pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
+    if (a->pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    if (a->pairs && (a->min_overlap == 0u || a->max_diff_pct > 100u)) return rfq_fail(ctx, RFQ_E_ARG, "with pairs min_overlap is >= 1 and max_diff_pct 0 .. 100 (got %u, %u)", a->min_overlap, a->max_diff_pct);
+    if (!a->pairs && ((a->h_adapter2 && a->adapter2_len) || a->d_insert || a->d_diff || a->d_insert_hist))
+        return rfq_fail(ctx, RFQ_E_ARG, "h_adapter2, d_insert, d_diff and d_insert_hist are for pairs");
+    AdapterIn ai; memset(&ai, 0, sizeof ai);
+    int rc;
+    if ((rc = adapter_planes(ctx, a->h_adapter1, a->adapter1_len, "adapter 1", &ai.a_h[0], &ai.a_l[0], &ai.a_m[0])) != RFQ_OK) return rc;
+    if ((rc = adapter_planes(ctx, a->h_adapter2, a->adapter2_len, "adapter 2", &ai.a_h[1], &ai.a_l[1], &ai.a_m[1])) != RFQ_OK) return rc;
+    if ((ai.a_m[0] || ai.a_m[1]) && (a->adapter_min < 1u || a->adapter_min > 64u)) return rfq_fail(ctx, RFQ_E_ARG, "adapter_min must be 1 .. 64 with an adapter (got %u)", a->adapter_min);
+    if (a->hist_len > 65536u || (a->d_insert_hist && a->hist_len == 0u)) return rfq_fail(ctx, RFQ_E_ARG, "hist_len must be 1 .. 65536 with d_insert_hist, at most 65536 without (got %u)", a->hist_len);
+    if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode);
+    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    if (n && (!in->d_lens || !in->d_bases)) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens / d_bases");
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_len | (uintptr_t)a->d_insert | (uintptr_t)a->d_diff) & 3u)
+        return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_len, d_insert and d_diff must be 4-byte aligned");
+    if ((uintptr_t)a->d_insert_hist & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_insert_hist must be 8-byte aligned");
+    const uint64_t units = a->pairs ? n / 2 : n;
+    {
+        const Span ins[] = { { in->d_bases, (unsigned long long)n * in->row_len, "rows->d_bases" }, { in->d_lens, n * 4ull, "rows->d_lens" } };
+        const Span outs[] = { { a->d_len, n * 4ull, "d_len" }, { a->d_how, n, "d_how" }, { a->d_insert, units * 4ull, "d_insert" }, { a->d_diff, units * 4ull, "d_diff" },
+                              { a->d_insert_hist, a->hist_len * 8ull, "d_insert_hist" } };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+    }
+    res->n_rows = n; res->n_pairs = a->pairs ? units : 0;
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    if (a->d_insert_hist) HIPCHK(ctx, hipMemsetAsync(a->d_insert_hist, 0, (size_t)a->hist_len * 8, S));
+    if (!n) { HIPCHK(ctx, hipStreamSynchronize(S)); return RFQ_OK; }
+    ai.b = in->d_bases; ai.lens = in->d_lens; ai.total = n * in->row_len; ai.n_rows = (uint32_t)n; ai.n_units = (uint32_t)units; ai.row_len = in->row_len;
+    ai.vec_in = rows_vec(in->row_len, in->d_bases, nullptr);
+    ai.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u; ai.pairs = a->pairs ? 1u : 0u;
+    ai.min_overlap = a->min_overlap; ai.max_diff = a->max_diff; ai.max_diff_pct = a->max_diff_pct;
+    if (!a->pairs) { ai.a_h[1] = ai.a_l[1] = 0ull; ai.a_m[1] = 0u; }
+    ai.adapter_min = a->adapter_min; ai.adapter_mm_per = a->adapter_mm_per; ai.hist_len = a->hist_len;
+    ai.len = a->d_len; ai.how = a->d_how; ai.insert = a->d_insert; ai.diff = a->d_diff; ai.hist = (unsigned long long*)a->d_insert_hist;
+    const bool general = ctx->opt.adapter_general || in->row_len > 1024u;
+    ctx->timer.begin("adapter:rows", S);
+    AdapterStat* dst = nullptr;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if (general) hipLaunchKernelGGL(k_adapter_rows_any, dim3((uint32_t)units), dim3(64), 0, S, ai, dst);
+    else if (in->row_len <= 256u) hipLaunchKernelGGL(k_adapter_rows<16>, dim3((uint32_t)((units + 16u * AR_ITER - 1u) / (16u * AR_ITER))), dim3(256), 0, S, ai, dst);
+    else hipLaunchKernelGGL(k_adapter_rows<64>, dim3((uint32_t)((units + 4u * AR_ITER - 1u) / (4u * AR_ITER))), dim3(256), 0, S, ai, dst);
+    KCHK(ctx, "k_adapter_rows");
+    ctx->timer.end(S);
+    AdapterStat hs; memset(&hs, 0, sizeof hs);
+    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    ctx->timer.collect();
+    if (hs.err & AR_ERR_LEN)
+        return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, (unsigned long long)hs.bad_row);
+    res->pairs_found = hs.c[0]; res->rows_cut = hs.c[1]; res->rows_cut_overlap = hs.c[2]; res->rows_cut_adapter = hs.c[3]; res->bases_in = hs.c[4]; res->bases_out = hs.c[5];
+    return RFQ_OK;
+}

@@ -25,3 +25,4 @@
 #include "enc/text_rows.h"                    // FASTQ text -> rows, lengths and names from the line index (rfq_text_rows)
 #include "enc/rows_select.h"                  // rows -> the kept rows, trimmed, with their names (rfq_select_rows)
 #include "enc/rows_judge.h"                   // rows -> keep, window, reason and metrics per row + a QC summary (rfq_judge_rows)
+#include "enc/rows_adapter.h"                 // rows -> the length adapter removal leaves, insert sizes of the pairs + a summary (rfq_adapter_rows)

@@ -35,6 +35,14 @@ summary of the batch (reads, bases, Q20 / Q30 before and after, rows per reason)
     s = select_rows(codec, t, keep=j["keep"], start=j["start"], length=j["length"], pairs=True, min_len=36)       # or: s = filter_rows(codec, t, pairs=True, min_len=36, ...)
     image = encode_tensors(codec, s["bases"], s["quals"], s["lens"], s["names"], s["name_off"], paired=PE_TWO_FILES)
 
+adapter -> judge -> select: rfq_adapter_rows cuts adapters first - a pair whose insert is shorter than its reads is found by the overlap of R1 with the reverse
+complement of R2, a known adapter sequence by a match at every position - and leaves the shortened lengths; the judge then trims and filters what is left, and
+select_rows moves the bytes once:
+
+    a = trim_adapters(codec, t, pairs=True, adapter1=b"AGATCGGAAGAGC", adapter2=b"AGATCGGAAGAGC")
+    j = judge_rows(codec, dict(t, lens=a["length"]), cut_tail=True, cut_window=4, cut_mean_q=20, min_mean_q=20)
+    s = select_rows(codec, t, keep=j["keep"], start=j["start"], length=j["length"], pairs=True, min_len=36)
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -175,6 +183,46 @@ def judge_rows(codec, t, codes=True, metrics=False, **criteria):
     out = {"keep": keep, "start": start, "length": length, "why": why, "summary": {f: int(getattr(r, f)) for f in SUMMARY_FIELDS}}
     if metrics:
         out["metrics"] = met
+    return out
+
+
+ADAPTER_FIELDS = ("n_rows", "n_pairs", "pairs_found", "rows_cut", "rows_cut_overlap", "rows_cut_adapter", "bases_in", "bases_out")
+
+
+def trim_adapters(codec, t, pairs=False, codes=True, adapter1=None, adapter2=None, min_overlap=30, max_diff=5, max_diff_pct=20, adapter_min=4, adapter_mm_per=8,
+                  hist_len=0):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "lens"; codes: what they were made with) -> {"length": [n] int32 - what is left of each row
+    after adapter removal (rfq_adapter_rows) -, "how": [n] uint8 (CUT_BY_OVERLAP | CUT_BY_ADAPTER), "summary": dict of the batch's counts}.  pairs: rows 2k /
+    2k + 1 are R1 / R2; their overlap is searched (min_overlap, max_diff, max_diff_pct) and "insert" and "diff", [n / 2] int32 (insert -1: no overlap), are
+    returned too.  adapter1 / adapter2: bytes of ACGT, at most 64 (None: off; with pairs adapter2 is the odd rows'), matched with adapter_min and adapter_mm_per
+    (one mismatch per that many compared bases; 0: exact).  hist_len > 0 (pairs): "insert_hist", [hist_len] int64, the last bin holds every longer insert.
+    "length" is select_rows' length (start 0) and, as "lens", what a later judge_rows takes.  One call, ordered with torch's current stream; the context goes
+    back to its own stream afterwards."""
+    bases, lens = t["bases"], t["lens"]
+    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == bases.device, "lens: [n] int32 on the rows' device"
+    assert not hist_len or pairs, "the insert-size histogram is for pairs"
+    dev = bases.device
+    length = torch.empty((n,), dtype=torch.int32, device=dev); how = torch.empty((n,), dtype=torch.uint8, device=dev)
+    insert = torch.empty((n // 2,), dtype=torch.int32, device=dev) if pairs else None
+    diff = torch.empty((n // 2,), dtype=torch.int32, device=dev) if pairs else None
+    hist = torch.empty((hist_len,), dtype=torch.int64, device=dev) if hist_len else None
+    crit = dict(min_overlap=min_overlap, max_diff=max_diff, max_diff_pct=max_diff_pct) if pairs else {}
+    if adapter1 is not None or adapter2 is not None:
+        crit.update(adapter_min=adapter_min, adapter_mm_per=adapter_mm_per)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        r = codec.adapter_rows(n, L, bases.data_ptr(), lens.data_ptr(), codes=codes, pairs=pairs, adapter1=adapter1, adapter2=adapter2, hist_len=hist_len,
+                               d_len=length.data_ptr(), d_how=how.data_ptr(), d_insert=insert.data_ptr() if pairs else None, d_diff=diff.data_ptr() if pairs else None,
+                               d_insert_hist=hist.data_ptr() if hist_len else None, **crit)
+    finally:
+        codec.set_stream(None)
+    out = {"length": length, "how": how, "summary": {f: int(getattr(r, f)) for f in ADAPTER_FIELDS}}
+    if pairs:
+        out["insert"], out["diff"] = insert, diff
+    if hist_len:
+        out["insert_hist"] = hist
     return out
 
 
