@@ -6,14 +6,17 @@
 // u32 per coded position, in stream order, all streams of all chunks in one arena (a position belongs to at most one stream, so a list is a
 // few percent of the bases).  The emitter prefills a tile's qualities with the major value in LDS, scatters the list entries that fall into
 // the tile, unpacks the tile's bases LDS -> LDS from the packed bytes and scatters the N list: no qdec / sdec, no prefill, unpack or
-// one-line-per-token scatter kernels.  Three light passes build the lists, one wave per POS2_SEG-byte segment of a stream (256-byte steps):
-//   k_dec_pos_sum2   per segment and entry state of the token automaton: exit state, positions advanced, positions emitted
+// one-line-per-token scatter kernels.  Three light passes build the lists, one wave per segment of segb bytes of a stream:
+//   k_dec_pos_sum2   per segment and entry state of the token automaton: exit state, positions advanced, positions emitted.  On the WIDE front (dec/pos_streams.h):
+//                    1024-byte steps, 16 bytes per lane - it needs all four entry states of every lane, which the lane's backward chain gives with one decode per byte
+//                    (0.74 -> 0.42 ms on configs[2], profiles/r17_lists_kernel_stats_{before,after}.txt)
 //   k_dec_pos_link2  per stream, a wave scan over those summaries: entry state / entry position / entry list index of every segment
 //   k_dec_pos_list   decodes every segment from its now-known entry and writes its positions; records for every POS2_CELL positions the
-//                    index of the first list entry at or beyond the cell (the emitter starts there)
-// bytes of a stream per wave (segb / 256 steps of 4 bytes per lane): the host takes POS2_SEG_BIG for files whose largest stream is 32 KB or more - a NovaSeq-binned file's three streams of
-// 40 - 70 KB per chunk: half the waves, each setting up once for eight steps, dec:streams 1.30 -> 1.22 ms on configs[2] - and POS2_SEG for many short streams (forty quality values: the
-// configs[4] shape is 6 % slower with the larger segments; 512 and 4096 lose on both - profiles/r06_ze_pos2seg.txt)
+//                    index of the first list entry at or beyond the cell (the emitter starts there).  256-byte steps, 4 bytes per lane (pos_front).
+// sum2 and list take the quality streams and the N-position stream in ONE launch each (the grid's last row).
+// bytes of a stream per wave (segb, a multiple of 1024): the host takes POS2_SEG_BIG for files whose largest stream is 32 KB or more - a NovaSeq-binned file's three streams of
+// 40 - 70 KB per chunk - and POS2_SEG for many short streams (forty quality values).  RFQ_POS_SEG forces 1024, 2048 or 4096; the sweep on both shapes with these kernels:
+// profiles/r17_lists_pos_seg_sweep.txt (round 6's: profiles/r06_ze_pos2seg.txt)
 #define POS2_SEG 1024u
 #define POS2_SEG_BIG 2048u
 #define POS2_CELL 1024u
@@ -37,84 +40,48 @@ __device__ __forceinline__ PosSrc pos_src_of(const uint8_t* __restrict__ img, co
     s.sp = qp + off; s.slen = sl; s.q = D->normal[jj];
     return s;
 }
-// tokens that START in the lane's 4 bytes when the automaton enters them in state st: positions advanced (adv) and positions emitted (cnt:
-// one per gap token, the run length per run token)
-__device__ __forceinline__ void pos_lane_adv_cnt(const PosFront& f, uint32_t slen, uint32_t i0, uint32_t st, int& adv, int& cnt) {
-    adv = 0; cnt = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t b0 = f.bt[k]; const bool valid = i0 + (uint32_t)k < slen;
-        const uint32_t b1 = (uint32_t)(f.v >> (8 * (k + 1))) & 0xFFu, b2 = (uint32_t)(f.v >> (8 * (k + 2))) & 0xFFu, b3 = (uint32_t)(f.v >> (8 * (k + 3))) & 0xFFu;
-        if (valid && st == 0) {
-            if ((b0 & 0x80u) == 0) { adv += (int)b0 + 1; cnt++; }
-            else if ((b0 & 0x40u) == 0) { adv += (int)(((b0 & 0x3Fu) << 8) | b1) + 1; cnt++; }
-            else if ((b0 & 0x20u) == 0) { adv += (int)(b0 & 0x1Fu) + 1; cnt += (int)(b0 & 0x1Fu) + 1; }
-            else { adv += (int)(((b0 & 0x1Fu) << 24) | (b1 << 16) | (b2 << 8) | b3) + 1; cnt++; }
-        }
-        if (valid) st = fn_apply(f.fn[k], st);
-    }
-}
 __device__ __forceinline__ int sel4(const int (&v)[4], uint32_t t) { return t == 0 ? v[0] : (t == 1 ? v[1] : (t == 2 ? v[2] : v[3])); }
-// The same for ALL four entry states at once: the tokens that start at each of the lane's bytes are decoded once, a backward pass chains them
-// (a token that starts at byte k is followed by the one at k + its length), and entry state s - s bytes to skip - reads the chain at byte s.
-// (pos_lane_adv_cnt four times over was 60 % of the summary kernel's instructions.)
-__device__ __forceinline__ void pos_lane_adv_cnt4(const PosFront& f, uint32_t slen, uint32_t i0, int (&adv)[4], int (&cnt)[4]) {
-    const uint32_t nv = i0 >= slen ? 0u : (slen - i0 < 4u ? slen - i0 : 4u);   // the lane's valid bytes
-    int ca[4], cc[4]; uint32_t tl[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t b0 = f.bt[k];
-        const uint32_t b1 = (uint32_t)(f.v >> (8 * (k + 1))) & 0xFFu, b2 = (uint32_t)(f.v >> (8 * (k + 2))) & 0xFFu, b3 = (uint32_t)(f.v >> (8 * (k + 3))) & 0xFFu;
-        if ((b0 & 0x80u) == 0) { ca[k] = (int)b0 + 1; cc[k] = 1; tl[k] = 1; }
-        else if ((b0 & 0x40u) == 0) { ca[k] = (int)(((b0 & 0x3Fu) << 8) | b1) + 1; cc[k] = 1; tl[k] = 2; }
-        else if ((b0 & 0x20u) == 0) { ca[k] = (int)(b0 & 0x1Fu) + 1; cc[k] = ca[k]; tl[k] = 1; }
-        else { ca[k] = (int)(((b0 & 0x1Fu) << 24) | (b1 << 16) | (b2 << 8) | b3) + 1; cc[k] = 1; tl[k] = 4; }
-    }
-#pragma unroll
-    for (int k = 2; k >= 0; k--) {                                           // chain: byte k's token, then whatever starts behind it inside the lane
-        const uint32_t nx = (uint32_t)k + tl[k];
-        if (nx < nv) { const int a_ = nx == 1u ? ca[1] : (nx == 2u ? ca[2] : ca[3]), c_ = nx == 1u ? cc[1] : (nx == 2u ? cc[2] : cc[3]); ca[k] += a_; cc[k] += c_; }
-    }
-#pragma unroll
-    for (int s = 0; s < 4; s++) { const bool on = (uint32_t)s < nv; adv[s] = on ? ca[s] : 0; cnt[s] = on ? cc[s] : 0; }
-}
 #define POS_ADV_MAX 0x3FFFFFFFull   // advances are summed saturating at this value (two saturated terms still fit an int)
 __device__ __forceinline__ int pos_adv_sat(int v) { return v > (int)POS_ADV_MAX ? (int)POS_ADV_MAX : v; }
-// grid (ceil(maxseg / 4), streams, n_chunks) x 256 threads: one wave per segment; index arrays are [chunk][nstr][maxseg]; segA[8 * idx + s] =
-// positions advanced, segA[8 * idx + 4 + s] = positions emitted for entry state s
+// grid (ceil(maxseg / 4), nq + (1 with N positions), n_chunks) x 256 threads: one wave per segment; row y < nq of the grid is quality stream y, the row behind them the
+// N-position stream (one launch for both: waves past a stream's end leave).  Index arrays are [chunk][nstr][maxseg]; segA[8 * idx + s] = positions advanced,
+// segA[8 * idx + 4 + s] = positions emitted for entry state s
 __global__ void k_dec_pos_sum2(const uint8_t* __restrict__ img, const DChunk* __restrict__ CH, const DevHeader* __restrict__ D,
-                               uint8_t* __restrict__ segF, int* __restrict__ segA, uint32_t* __restrict__ segN, uint32_t maxseg, DecStatus* st, uint64_t img_bytes, uint32_t jj0, uint32_t nstr,
+                               uint8_t* __restrict__ segF, int* __restrict__ segA, uint32_t* __restrict__ segN, uint32_t maxseg, DecStatus* st, uint64_t img_bytes, uint32_t nq, uint32_t nstr,
                                uint32_t segb) {
-    const uint32_t g = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_id(), jj = jj0 + blockIdx.y, c = blockIdx.z; const int l = lane_id();
+    const uint32_t g = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_id(), jj = blockIdx.y < nq ? blockIdx.y : D->n_normal, c = blockIdx.z; const int l = lane_id();
             const uint8_t* lim = img + img_bytes;
     const DChunk d = CH[c];
     const PosSrc s = pos_src_of(img, d, D, jj, g == 0 ? st : nullptr);
     if (g == 0 && l == 0) segN[(size_t)c * nstr + jj] = (s.slen + segb - 1) / segb;
     const uint32_t b0 = g * segb; if (b0 >= s.slen) return;
     const uint32_t b1 = b0 + segb < s.slen ? b0 + segb : s.slen;
-    uint32_t Fcum = POS_ID; int a[4] = { 0, 0, 0, 0 }, n[4] = { 0, 0, 0, 0 };
-    PosStep nxt = pos_fetch(s.sp, s.slen, b0 + 4u * (uint32_t)l, lim);
-    for (uint32_t base = b0; base < b1; base += 256u) {                    // (wave-uniform)
-        const uint32_t i0 = base + 4u * (uint32_t)l;
-        const PosStep w = nxt;
-        if (base + 256u < b1) nxt = pos_fetch(s.sp, s.slen, i0 + 256u, lim);
-        const PosFront f = pos_front(w, s.sp, s.slen, i0, l);
-        const uint32_t Fex = wave_shr1(f.Fin, POS_ID);
+    uint32_t Fcum = POS_ID; uint32_t a[4] = { 0, 0, 0, 0 }; int n[4] = { 0, 0, 0, 0 };
+    PosStep16 nxt = pos_fetch16(s.sp, s.slen, b0 + 16u * (uint32_t)l, lim);
+    for (uint32_t base = b0; base < b1; base += 1024u) {                   // (wave-uniform)
+        const uint32_t i0 = base + 16u * (uint32_t)l;
+        const PosStep16 w = nxt;
+        if (base + 1024u < b1) nxt = pos_fetch16(s.sp, s.slen, i0 + 1024u, lim);
+        const PosLane t = pos_lane16(pos_bytes16(w, s.sp, s.slen, i0));     // the lane's tokens for each state in front of its bytes
+        const uint32_t Fin = wave_scan_compose(t.F);
+        const uint32_t Fex = wave_shr1(Fin, POS_ID);
         const uint32_t G = fn_compose(Fcum, Fex);                          // segment entry state -> state in front of my bytes
-        int la[4], lc[4]; pos_lane_adv_cnt4(f, s.slen, i0, la, lc);         // the lane's tokens for each state in front of its bytes
+        // (a lane's step advances up to 2^31 positions - four 4-byte gaps of a corrupt stream -: every term and the running sum SATURATE at POS_ADV_MAX, so nothing wraps)
 #pragma unroll
-        for (int e = 0; e < 4; e++) { const uint32_t t_ = fn_apply(G, e); a[e] += sel4(la, t_); n[e] += sel4(lc, t_); }
-        Fcum = fn_compose(Fcum, wave_last(f.Fin));
+        for (int e = 0; e < 4; e++) { const uint32_t t_ = fn_apply(G, e); const uint32_t x = (uint32_t)pos_pick(t.adv, t_);
+                a[e] += x > (uint32_t)POS_ADV_MAX ? (uint32_t)POS_ADV_MAX : x; if (a[e] > (uint32_t)POS_ADV_MAX) a[e] = (uint32_t)POS_ADV_MAX; n[e] += pos_pick(t.cnt, t_); }
+        Fcum = fn_compose(Fcum, wave_last(Fin));
     }
-    // (a lane's four steps advance less than 4 x 2^30 positions: no wrap as 32 bits; the wave's sum is taken in 64 bits and SATURATED at POS_ADV_MAX - a corrupt
-    // stream advances up to 2^29 per token, a wrapped sum went negative, slipped through k_dec_pos_link2's "beyond the chunk" test and aliased 16-bit list entries:
-    // ADVICE r5.  Saturated sums stay sums for every position a chunk the fused path takes can hold - rfq_decode.hip sends larger chunks to the expanded path.)
+    // (the wave's sum is taken in 64 bits and SATURATED at POS_ADV_MAX - a corrupt stream advances up to 2^29 per token, a wrapped sum went negative, slipped through
+    // k_dec_pos_link2's "beyond the chunk" test and aliased 16-bit list entries: ADVICE r5.  Saturated sums stay sums for every position a chunk the fused path takes
+    // can hold - rfq_decode.hip sends larger chunks to the expanded path.)
+    int as[4];
 #pragma unroll
-    for (int e = 0; e < 4; e++) { const unsigned long long w64 = wave_sum<unsigned long long>((unsigned long long)(uint32_t)a[e]); a[e] = (int)(w64 > POS_ADV_MAX ? POS_ADV_MAX : w64);
+    for (int e = 0; e < 4; e++) { const unsigned long long w64 = wave_sum<unsigned long long>((unsigned long long)a[e]); as[e] = (int)(w64 > POS_ADV_MAX ? POS_ADV_MAX : w64);
             n[e] = wave_sum(n[e]); }
     if (l == 0) { const size_t idx = ((size_t)c * nstr + jj) * maxseg + g; segF[idx] = (uint8_t)fn_pack8(Fcum);
 #pragma unroll
-                  for (int e = 0; e < 4; e++) { segA[8 * idx + e] = a[e]; segA[8 * idx + 4 + e] = n[e]; } }
+                  for (int e = 0; e < 4; e++) { segA[8 * idx + e] = as[e]; segA[8 * idx + 4 + e] = n[e]; } }
 }
 // one wave per (chunk, stream): entry state / position / list index of every segment by a scan over (transition table, advance and count
 // per entry state): x then y is (y.F o x.F, s -> x.a[s] + y.a[x.F[s]]); also the stream's number of list entries
@@ -179,13 +146,16 @@ __global__ void k_dec_pos_off(const uint32_t* __restrict__ nent, unsigned long l
     if (threadIdx.x == 0) st->list_need = tot;
 }
 // decodeSingleQualByCol (src/rfqcodec.cpp:957-1007) for one segment from its entry (state, last covered position, list index): the positions
-// it codes go to plist[loff + k ...] in stream order; cellidx[cell] = index (within the stream's list) of the first entry >= cell * POS2_CELL
+// it codes go to plist[loff + k ...] in stream order; cellidx[cell] = index (within the stream's list) of the first entry >= cell * POS2_CELL.
+// Grid as k_dec_pos_sum2's.  This pass stays on pos_front, 4 bytes per lane and 256 per step: it knows its entry state, so a lane decodes its tokens once and walks them;
+// on the wide front it needs the lane's chain for the scan AND a second decode for the walk, and its stores spread over four times the cache lines
+// (measured: 0.66 -> 0.81 ms, profiles/r17_lists_kernel_stats_after.txt).
 __global__ void k_dec_pos_list(const uint8_t* __restrict__ img, const DChunk* __restrict__ CH, const DevHeader* __restrict__ D,
                                const uint8_t* __restrict__ segS, const int* __restrict__ segP, const uint32_t* __restrict__ segK, const unsigned long long* __restrict__ loff,
-                               plist_t* __restrict__ plist, unsigned long long cap, uint32_t* __restrict__ cellidx, uint32_t maxseg, uint32_t ncell, uint64_t img_bytes, uint32_t jj0, uint32_t nstr, const DecStatus* st,
+                               plist_t* __restrict__ plist, unsigned long long cap, uint32_t* __restrict__ cellidx, uint32_t maxseg, uint32_t ncell, uint64_t img_bytes, uint32_t nq, uint32_t nstr, const DecStatus* st,
                                uint32_t segb) {
     if (st->list_need > cap) return;                                      // (uniform) the arena is too small: the host repeats the pass
-    const uint32_t g = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_id(), jj = jj0 + blockIdx.y, c = blockIdx.z; const int l = lane_id();
+    const uint32_t g = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_id(), jj = blockIdx.y < nq ? blockIdx.y : D->n_normal, c = blockIdx.z; const int l = lane_id();
             const uint8_t* lim = img + img_bytes;
     const DChunk d = CH[c];
     const PosSrc s = pos_src_of(img, d, D, jj, nullptr);

@@ -80,6 +80,94 @@ __device__ __forceinline__ PosFront pos_front(const PosStep& w, const uint8_t* _
     f.Fin = wave_scan_compose(F);
     return f;
 }
+// ---- the WIDE front of the position-list summary pass (k_dec_pos_sum2, dec/pos_lists.h): one step = 1024 stream bytes, 16 consecutive bytes per lane.  What a step costs whatever it decodes - address
+// alignment, guarded loads, funnel, the wave scan of the tables, the sum scans - is paid once per 16 bytes of a lane, not once per 4: a 2 KB segment is two dependent scan round
+// trips, not eight.  The expanded path above (k_dec_pos_sum, k_dec_pos_emit, wave_pos_decode) and k_dec_pos_list stay on pos_front.
+// The six aligned words that hold the 19 stream bytes from i0 on (the lane's 16 + the three a token's tail can run over) at any alignment of the stream; all 0 past the stream.
+// No byte at or past `lim` is read: words that lie wholly inside the image are loaded as they are, the one that straddles it byte by byte.
+struct PosStep16 { uint32_t w[6]; };
+__device__ __forceinline__ PosStep16 pos_fetch16(const uint8_t* __restrict__ sp, uint32_t slen, uint32_t i0, const uint8_t* lim) {
+    PosStep16 r;
+#pragma unroll
+    for (int k = 0; k < 6; k++) r.w[k] = 0;
+    if (i0 < slen) {
+        const uint8_t* p = (const uint8_t*)((uintptr_t)(sp + i0) & ~(uintptr_t)3);
+        if (p + 24 <= lim) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) r.w[k] = ((const uint32_t*)p)[k];
+        } else {                                                            // (the image ends inside the six words: at most one of them straddles `lim` - its bytes one by one)
+            const uint8_t* e = (const uint8_t*)((uintptr_t)lim & ~(uintptr_t)3); uint32_t tail = 0;
+            if (e < lim) tail = e[0];
+            if (e + 1 < lim) tail |= (uint32_t)e[1] << 8;
+            if (e + 2 < lim) tail |= (uint32_t)e[2] << 16;
+#pragma unroll
+            for (int k = 0; k < 6; k++) { const uint8_t* q = p + 4 * k; if (q + 4 <= lim) r.w[k] = *(const uint32_t*)q; else if (q == e) r.w[k] = tail; }
+        }
+    }
+    return r;
+}
+// b[0..3]: the lane's 16 bytes, b[4]: the four behind them; bytes at or past the stream's end read as 0.  on[j]: 0x01 in every byte of b[j] that is a byte of the stream.
+struct PosWide { uint32_t b[5], on[4]; };
+__device__ __forceinline__ uint32_t pos_low_bytes(uint32_t n) { return n >= 4u ? 0xFFFFFFFFu : (1u << (8u * n)) - 1u; }
+__device__ __forceinline__ PosWide pos_bytes16(const PosStep16& r, const uint8_t* __restrict__ sp, uint32_t slen, uint32_t i0) {
+    PosWide f; const uint32_t left = i0 < slen ? slen - i0 : 0u;             // stream bytes from i0 on
+    const uint32_t sh = (uint32_t)((uintptr_t)(sp + i0) & 3u) * 8u;
+#pragma unroll
+    for (int j = 0; j < 5; j++) f.b[j] = (uint32_t)((((unsigned long long)r.w[j + 1] << 32) | r.w[j]) >> sh);
+#pragma unroll
+    for (int j = 0; j < 4; j++) f.on[j] = 0x01010101u;
+    if (left < 20u) {
+#pragma unroll
+        for (int j = 0; j < 5; j++) { const uint32_t m = left > 4u * (uint32_t)j ? pos_low_bytes(left - 4u * (uint32_t)j) : 0u; f.b[j] &= m; if (j < 4) f.on[j] &= m; }
+    }
+    return f;
+}
+// the token whose first byte is byte q (0 .. 3) of word lo (hi: the word behind it), as b0 << 24 | b1 << 16 | b2 << 8 | b3: one v_perm_b32
+__device__ __forceinline__ uint32_t pos_be4(uint32_t lo, uint32_t hi, int q) {
+    return __builtin_amdgcn_perm(hi, lo, (uint32_t)((q + 3) | ((q + 2) << 8) | ((q + 1) << 16) | (q << 24)));
+}
+// What the top three bits of a token's first byte say, for the four bytes of a stream word at once (four v_perm_b32 table look-ups; 0xxxxxxx gap of one byte, 10xxxxxx gap of
+// two, 110xxxxx run, 111xxxxx gap of four): the token's bytes - 1, its flag bits (lz), 32 - its value bits (sh), and 0x1F where it is a run.  No branch decodes a token.
+struct PosTab { uint32_t lm1, lz, sh, run; };
+__device__ __forceinline__ PosTab pos_tab(uint32_t w) {
+    const uint32_t idx = (w >> 5) & 0x07070707u; PosTab t;
+    t.lm1 = __builtin_amdgcn_perm(0x03000101u, 0x00000000u, idx); t.lz = __builtin_amdgcn_perm(0x03030202u, 0x00000000u, idx);
+    t.sh = __builtin_amdgcn_perm(0x031B1212u, 0x18181818u, idx); t.run = __builtin_amdgcn_perm(0x001F0000u, 0x00000000u, idx);
+    return t;
+}
+// the token at byte q of the word `tab` was made from (be = pos_be4 there): positions advanced, positions emitted (one per gap token, the run length per run token), bytes.
+// on = pos_bytes16's flags of that word: a byte past the stream's end (it reads as 0) gives a one-byte token that advances and emits nothing.
+struct PosTok { uint32_t adv, cnt, len; };
+__device__ __forceinline__ PosTok pos_tok(uint32_t be, const PosTab& tab, uint32_t on, int q) {
+    const uint32_t rm = (tab.run >> (8 * q)) & 0xFFu, v = (be << ((tab.lz >> (8 * q)) & 0xFFu)) >> ((tab.sh >> (8 * q)) & 0xFFu);      // the token's value: positions - 1
+    const uint32_t one = (on >> (8 * q)) & 0xFFu;
+    PosTok t; t.adv = v + one; t.cnt = (v & rm) + one; t.len = ((tab.lm1 >> (8 * q)) & 0xFFu) + 1u;
+    return t;
+}
+// The lane's 16 bytes for ALL four entry states at once.  Every byte's token is decoded once; a backward pass chains them - the token at byte k is followed by the one at
+// k + 1, k + 2 or k + 4, so only the chain values of the four bytes behind k are live: no register arrays.  Entry state s - s bytes to skip - reads the chain at byte s:
+// adv[s] / cnt[s] = positions advanced / emitted by the tokens that start in the lane, F = the lane's transition table (byte s = the state the lane is left in).
+// Bytes past the stream's end are one-byte tokens that code nothing (pos_tok; the state behind the end of a stream is looked at by nobody).
+// (a lane's 16 bytes hold at most four 4-byte gaps of 2^29 positions and sixteen runs of 32: adv < 2^32 as 32 bits, cnt <= 512 - the exit state rides in bits 16+ of the count)
+struct PosLane { uint32_t F; int adv[4], cnt[4]; };
+__device__ __forceinline__ int pos_pick(const int (&v)[4], uint32_t t) { const int lo = (t & 1u) ? v[1] : v[0], hi = (t & 1u) ? v[3] : v[2]; return (t & 2u) ? hi : lo; }   // v[t], three selects
+__device__ __forceinline__ PosLane pos_lane16(const PosWide& f) {
+    uint32_t a1 = 0, a2 = 0, a3 = 0, a4 = 0, c1 = 0u << 16, c2 = 1u << 16, c3 = 2u << 16, c4 = 3u << 16;        // bytes 16 .. 19: the states 0 .. 3 behind the lane
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+        const PosTab tab = pos_tab(f.b[j]);
+#pragma unroll
+        for (int q = 3; q >= 0; q--) {
+            const PosTok t = pos_tok(pos_be4(f.b[j], f.b[j + 1], q), tab, f.on[j], q);
+            const uint32_t a0 = t.adv + (t.len == 1u ? a1 : (t.len == 2u ? a2 : a4)), c0 = t.cnt + (t.len == 1u ? c1 : (t.len == 2u ? c2 : c4));
+            a4 = a3; a3 = a2; a2 = a1; a1 = a0; c4 = c3; c3 = c2; c2 = c1; c1 = c0;
+        }
+    }
+    PosLane r; r.F = (c1 >> 16) | ((c2 >> 16) << 8) | ((c3 >> 16) << 16) | ((c4 >> 16) << 24);
+    r.adv[0] = (int)a1; r.adv[1] = (int)a2; r.adv[2] = (int)a3; r.adv[3] = (int)a4;
+    r.cnt[0] = (int)(c1 & 0xFFFFu); r.cnt[1] = (int)(c2 & 0xFFFFu); r.cnt[2] = (int)(c3 & 0xFFFFu); r.cnt[3] = (int)(c4 & 0xFFFFu);
+    return r;
+}
 // positions covered by the tokens that START in the lane's 4 bytes when the automaton enters them in state st
 __device__ __forceinline__ int pos_lane_adv(const PosFront& f, uint32_t slen, uint32_t i0, uint32_t st) {
     int a = 0;

@@ -43,7 +43,7 @@ extern "C" int rfq_set_option(rfq_ctx* c, const char* name, const char* value) {
     else if (n == "RFQ_TRACE") { if (set && v != "0" && v != "1") return rfq_fail(c, RFQ_E_ARG, "RFQ_TRACE is 0 or 1"); c->opt.trace = v == "1"; }
     else if (n == "RFQ_G2_PAD") { RFQ_OPT_NUM(0, 150000, "0 .. 150000 bytes of LDS") c->opt.g2_pad = set ? (uint32_t)num : 0u; }
     else if (n == "RFQ_SP_PAD") { RFQ_OPT_NUM(0, 150000, "0 .. 150000 bytes of LDS") c->opt.sp_pad = set ? (uint32_t)num : d.sp_pad; }
-    else if (n == "RFQ_POS_SEG") { if (set && v != "1024" && v != "2048") return rfq_fail(c, RFQ_E_ARG, "RFQ_POS_SEG is 1024 or 2048"); c->opt.pos_seg = set ? atoi(v.c_str()) : 0; }
+    else if (n == "RFQ_POS_SEG") { if (set && v != "1024" && v != "2048" && v != "4096") return rfq_fail(c, RFQ_E_ARG, "RFQ_POS_SEG is 1024, 2048 or 4096"); c->opt.pos_seg = set ? atoi(v.c_str()) : 0; }
     else if (n == "RFQ_SPEC") { if (set && v != "0" && v != "1") return rfq_fail(c, RFQ_E_ARG, "RFQ_SPEC is 0 or 1"); c->opt.no_spec = v == "0"; }
     else if (n == "RFQ_MIRROR") { if (set && v != "0" && v != "1") return rfq_fail(c, RFQ_E_ARG, "RFQ_MIRROR is 0 or 1"); c->opt.no_mirror = v == "0"; }
     else if (n == "RFQ_JUDGE") { if (set && v != "general" && v != "staged") return rfq_fail(c, RFQ_E_ARG, "RFQ_JUDGE is staged or general"); c->opt.judge_general = v == "general"; }

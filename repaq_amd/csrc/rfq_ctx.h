@@ -97,7 +97,7 @@ struct RfqOpts {
     // RFQ_SP_PAD         bytes of unused dynamic LDS added to k_seqpack: caps its resident workgroups so that the position coder beside it keeps its share
     uint32_t sp_pad = 0;
     bool no_spec = false;             // RFQ_SPEC=0         decode: the emitter only behind the host's look at the status (default: launched ahead of it where the caller gave the output buffers)
-    int  pos_seg = 0;                 // RFQ_POS_SEG=1024|2048   decode, list chain: bytes of a position stream per wave (default: by the largest stream, dec/pos_lists.h)
+    int  pos_seg = 0;                 // RFQ_POS_SEG=1024|2048|4096  decode, list chain: bytes of a position stream per wave (default: by the largest stream, dec/pos_lists.h)
     bool judge_general = false;       // RFQ_JUDGE=general  rfq_judge_rows: the any-length kernel for every row length, in tiles of 64 window starts (default: rows of up to 1024 bytes are held whole)
     bool adapter_general = false;     // RFQ_ADAPTER=general  rfq_adapter_rows: the any-length kernel (a lane per shift, byte by byte) for every row length (default: rows of up to 1024 bytes as bit planes in LDS)
     bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)

@@ -135,18 +135,19 @@ static FusedPlan plan_fused(const rfq_ctx* ctx, const DecRange& g, bool force_ex
 }
 // what the position-list chain of a range left behind: the shape of its tables (B[DB_SEG*], B[DB_CELL], B[DB_NENT], B[DB_LOFF]), whether lists were built at
 // all (a file without quality streams and N positions has none), and the stream the emitter has to wait for (join: the chain ran beside the main stream)
-struct ListChain { uint32_t maxseg = 1, ncell = 1, nstr = 1, mq = 0, mn = 0, nn = 0, segb = POS2_SEG; bool hasn = false, built = false, join = false; hipStream_t aux = nullptr; };
+struct ListChain { uint32_t maxseg = 1, ncell = 1, nstr = 1, mq = 0, mn = 0, nn = 0, segb = POS2_SEG; bool hasn = false, built = false, join = false; hipStream_t aux = nullptr;
+    // the grid of k_dec_pos_sum2 / k_dec_pos_list: the quality streams and, in the row behind them, the N-position stream in ONE launch - x for the longer of the two
+    dim3 grid(uint32_t n_chunks) const { return dim3((maxseg + 3) / 4, nn + (hasn ? 1u : 0u), n_chunks); } };
 // (an early return must not leave the chain running over buffers the next call reuses)
 struct AuxJoin { rfq_ctx* c; bool armed; ~AuxJoin() { if (armed) (void)hipStreamSynchronize(c->aux); } };
 
-// k_dec_pos_list for the quality streams and the N-position stream (the arena is whatever B[DB_PLIST] holds)
+// k_dec_pos_list for the quality streams and the N-position stream, one launch (the arena is whatever B[DB_PLIST] holds)
 static void launch_pos_list(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const ListChain& L, hipStream_t LS) {
     DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>(); const DecStatus* dst = B[DB_STATUS].as<DecStatus>();
     const unsigned long long cap = B[DB_PLIST].cap / sizeof(plist_t);
 #define RFQ_LIST_ARGS a->d_rfq, g.CH, D, (const uint8_t*)B[DB_SEGS].as<uint8_t>(), (const int*)B[DB_SEGP].as<int>(), (const uint32_t*)B[DB_SEGK].as<uint32_t>(), \
                       (const unsigned long long*)B[DB_LOFF].as<unsigned long long>(), B[DB_PLIST].as<plist_t>(), cap, B[DB_CELL].as<uint32_t>(), L.maxseg, L.ncell, (uint64_t)a->n
-    if (L.nn) hipLaunchKernelGGL(k_dec_pos_list, dim3((L.mq + 3) / 4, L.nn, g.n_chunks), dim3(256), 0, LS, RFQ_LIST_ARGS, 0u, L.nstr, dst, L.segb);
-    if (L.hasn) hipLaunchKernelGGL(k_dec_pos_list, dim3((L.mn + 3) / 4, 1, g.n_chunks), dim3(256), 0, LS, RFQ_LIST_ARGS, ctx->h_hdr.n_normal, L.nstr, dst, L.segb);
+    hipLaunchKernelGGL(k_dec_pos_list, L.grid(g.n_chunks), dim3(256), 0, LS, RFQ_LIST_ARGS, L.nn, L.nstr, dst, L.segb);
 #undef RFQ_LIST_ARGS
 }
 // The lists need nothing but the chunk table, so their chain (stream summaries, link, offsets, lists + cell index) starts at the top of a range on the second
@@ -176,8 +177,7 @@ static int dec_list_chain(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange
             HIPCHK(ctx, B[DB_PLIST].ensure((size_t)(g.bases / 32 + 1024) * sizeof(plist_t))); }
     { ClearList z; memset(&z, 0, sizeof z); z.add(B[DB_SEGN].p, nst * 4, 0u); z.add(B[DB_NENT].p, nst * 4, 0u); z.add(B[DB_CELL].p, ncl * 4, 0xFFFFFFFFu); clear_list(A, z); }
 #define RFQ_SUM2_ARGS a->d_rfq, CH, D, B[DB_SEGF].as<uint8_t>(), B[DB_SEGA].as<int>(), B[DB_SEGN].as<uint32_t>(), L->maxseg, dst, (uint64_t)a->n
-    if (L->nn) hipLaunchKernelGGL(k_dec_pos_sum2, dim3((L->mq + 3) / 4, L->nn, n_chunks), dim3(256), 0, A, RFQ_SUM2_ARGS, 0u, L->nstr, L->segb);
-    if (L->hasn) hipLaunchKernelGGL(k_dec_pos_sum2, dim3((L->mn + 3) / 4, 1, n_chunks), dim3(256), 0, A, RFQ_SUM2_ARGS, HH.n_normal, L->nstr, L->segb);
+    hipLaunchKernelGGL(k_dec_pos_sum2, L->grid(n_chunks), dim3(256), 0, A, RFQ_SUM2_ARGS, L->nn, L->nstr, L->segb);
 #undef RFQ_SUM2_ARGS
     hipLaunchKernelGGL(k_dec_pos_link2, dim3((uint32_t)((nst + 3) / 4)), dim3(256), 0, A, (const uint8_t*)B[DB_SEGF].as<uint8_t>(), (const int*)B[DB_SEGA].as<int>(),
                        (const uint32_t*)B[DB_SEGN].as<uint32_t>(), B[DB_SEGS].as<uint8_t>(), B[DB_SEGP].as<int>(), B[DB_SEGK].as<uint32_t>(), B[DB_NENT].as<uint32_t>(),
