@@ -458,6 +458,53 @@ typedef struct {
 } rfq_adapter_rows_result;
 RFQ_API int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_adapter_rows_args* args, rfq_adapter_rows_result* res);
 
+/* Merging, behind rfq_adapter_rows: every pair with an insert size becomes ONE row of `insert` bases - the fragment both mates were read from, R1 from its front, the
+ * reverse complement of R2 from its back, the consensus of the two where they overlap - under R1's name (in the manner of fastp --merge, PEAR, BBMerge).  Like
+ * rfq_select_rows it moves bytes and takes no decision about the alignment: d_insert says which pairs merge and at which shift.  Integer rules of this project's own;
+ * no parity with any tool is claimed.  No float anywhere; the same call gives the same bytes.  A quality row byte IS the score (rows->qual_offset is not looked at).
+ * Inputs.  Rows 2k / 2k + 1 are R1 / R2 of pair k, l1 / l2 their lengths, r1, q1, r2, q2 their bases and scores; ins = d_insert[k].  A pair is merged when ins >= 0
+ * (rfq_adapter_rows leaves -1 for a pair without an overlap; a caller narrows further by writing -1 itself).  Output row j is the j-th merged pair, in input order:
+ * its length is ins, its name the whole name of row 2k (R2's name is dropped); name_off[0] = 0 and name_off[n_out] = names_len.
+ * Fragment coordinates, p in [0, ins).  R1 covers p < min(l1, ins) with (r1[p], q1[p]).  R2 covers p >= ins - l2 with (comp(r2[i]), q2[i]), i = ins - 1 - p.  comp is
+ * rfq_adapter_rows' complement as a byte map: in code mode it swaps 0 with 3 and 1 with 2, in ASCII mode A with T, C with G, a with t and c with g; every other
+ * byte is itself.  This is rfq_adapter_rows' alignment with d = ins - l2: y[j] = comp(r2[l2 - 1 - j]) lies at x[j + d].  The same insert stays valid for lengths cut
+ * to min(l, insert): of a mate longer than the insert only its first insert bases are looked at (R1's tail is left out; R2's index i = ins - 1 - p is below ins), so
+ * the merged row is the same.  It does NOT stay valid for lengths cut further by the adapter match (rfq_adapter_rows' d_len where RFQ_CUT_BY_ADAPTER is set): merge
+ * with the lengths the insert was found on, or with min(l, insert).
+ * A position one mate covers takes that mate's base and score.  A position both cover - classes and AGREE are rfq_adapter_rows' definitions, b2 = comp(r2[i]):
+ *   1. they agree:                                   the base is r1[p] (R1's byte, in its case), the score max(q1, q2)
+ *   2. exactly one of them is in A C G T:            that one wins, with its own score
+ *   3. otherwise (two different A C G T, two others): q1 >= q2: r1[p] with score q1 - q2; else b2 with score q2 - q1
+ * Positions >= ins of an output row hold pad_base / pad_qual.
+ * Sizes.  All five outputs NULL = a size query: the whole result is filled, nothing is written.  An output that is NULL is not produced.  RFQ_E_NOSPACE with a
+ * "need ..." message, and nothing written, when row_len < max_len or a cap is too small.  Rows without names: rows->d_name_off == NULL, and then d_names /
+ * d_name_off must be NULL.  Either row output needs BOTH rows->d_bases and rows->d_quals: the rule looks at the bases and the scores.
+ * RFQ_E_ARG, judged on the host: an odd n_rows; d_insert == NULL with rows; a d_insert, d_lens or rows->d_lens that is not 4-byte aligned; a d_name_off that is not
+ * 8-byte aligned; row_len == 0 on a call that writes; a bad base_mode; rows->d_bases or rows->d_quals NULL with a row output wanted; an output that overlaps an
+ * input (byte ranges, as rfq_select_rows compares them).  RFQ_E_ARG, judged on the device before anything is written, the message names the first such row or pair
+ * - ALL pairs are judged, merged or not: lens[i] < 0 or > rows->row_len; for a pair with ins >= 0: l1 == 0, l2 == 0, ins == 0 or ins > l1 + l2 - 1, that is, no
+ * position that both mates cover; name offsets that decrease or end past names_len.  After any refusal the context stays usable.
+ * The row buffers may have any alignment on either side - never a byte outside [d_x, d_x + n * row_len).  n_rows * row_len may exceed 4 GiB.  The default kernel
+ * takes a 16-byte group of an output row per lane (R2's bytes in one load, reversed and complemented in registers, the rule as byte masks); RFQ_MERGE=general takes
+ * a lane per output byte with the rule as plain branches - the same bytes.  Synchronous on the context's stream; stage times through rfq_last_timings (merge:judge,
+ * merge:tables, merge:rows, merge:names). */
+typedef struct {
+    const int32_t* d_insert;              /* [n_rows / 2]: the pair's insert size (rfq_adapter_rows' d_insert); < 0 = the pair is not merged */
+    uint32_t row_len;                     /* OUTPUT stride (>= 1, >= the longest merged read; may exceed rows->row_len: up to 2 * row_len - 1) */
+    uint8_t  pad_base, pad_qual, reserved[2];
+    uint8_t* d_bases; size_t bases_cap;   /* [n_out][row_len] or NULL                                                   */
+    uint8_t* d_quals; size_t quals_cap;   /* [n_out][row_len] or NULL                                                   */
+    int32_t* d_lens;  size_t lens_cap;    /* [n_out] (entries) or NULL                                                  */
+    uint8_t* d_names; size_t names_cap;   /* blob, any alignment, or NULL                                               */
+    uint64_t* d_name_off; size_t off_cap; /* [n_out + 1] (entries), 8-byte aligned, or NULL                             */
+} rfq_merge_rows_args;
+typedef struct {
+    uint64_t n_rows, n_bases, names_len;  /* of the OUTPUT: n_rows = merged pairs                                       */
+    uint32_t max_len, max_name;
+    uint64_t n_pairs, overlap_bases;      /* pairs in; sum over merged pairs of the positions both mates cover          */
+} rfq_merge_rows_result;
+RFQ_API int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_merge_rows_args* args, rfq_merge_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -491,7 +538,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

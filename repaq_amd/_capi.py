@@ -146,6 +146,18 @@ class AdapterRowsResult(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("n_rows", "n_pairs", "pairs_found", "rows_cut", "rows_cut_overlap", "rows_cut_adapter", "bases_in", "bases_out")]
 
 
+class MergeRowsArgs(C.Structure):
+    _fields_ = [("d_insert", C.c_void_p), ("row_len", C.c_uint32), ("pad_base", C.c_uint8), ("pad_qual", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("d_bases", C.c_void_p), ("bases_cap", C.c_size_t), ("d_quals", C.c_void_p), ("quals_cap", C.c_size_t),
+                ("d_lens", C.c_void_p), ("lens_cap", C.c_size_t), ("d_names", C.c_void_p), ("names_cap", C.c_size_t),
+                ("d_name_off", C.c_void_p), ("off_cap", C.c_size_t)]
+
+
+class MergeRowsResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_bases", C.c_uint64), ("names_len", C.c_uint64), ("max_len", C.c_uint32), ("max_name", C.c_uint32),
+                ("n_pairs", C.c_uint64), ("overlap_bases", C.c_uint64)]
+
+
 _libs = {}
 
 
@@ -182,6 +194,7 @@ def load(path=None):
     L.rfq_select_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(SelectRowsArgs), C.POINTER(SelectRowsResult)]
     L.rfq_judge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(JudgeRowsArgs), C.POINTER(JudgeRowsResult)]
     L.rfq_adapter_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(AdapterRowsArgs), C.POINTER(AdapterRowsResult)]
+    L.rfq_merge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(MergeRowsArgs), C.POINTER(MergeRowsResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -205,6 +218,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

@@ -354,6 +354,24 @@ class RfqCodec:
         self._check(self._L.rfq_adapter_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
+    # --- behind the adapter step: every pair with an insert size -> one row, the consensus of both mates (rfq_merge_rows)
+    def merge_rows(self, n_rows, row_len_in, d_bases, d_quals, d_lens, d_names=None, names_len=0, d_name_off=None, d_insert=None, codes=False, row_len=0,
+                   pad_base=255, pad_qual=255, out_bases=None, bases_cap=0, out_quals=None, quals_cap=0, out_lens=None, lens_cap=0, out_names=None, names_cap=0,
+                   out_name_off=None, off_cap=0, base_mode=None):
+        """rfq_merge_rows: the first eight arguments are the rows as rows_to_text / encode_rows take them (rows 2k / 2k + 1: R1 / R2; d_name_off None: rows without
+        names; a quality byte is the score), d_insert n_rows / 2 int32 - adapter_rows' d_insert: a pair with insert >= 0 becomes one row of insert bases, R1 from the
+        front, the reverse complement of R2 from the back, the consensus of include/rfq_hip.h where both cover a position, under R1's name.  out_*: the merged rows at
+        stride row_len (up to 2 * row_len_in - 1), their lengths, name lines and n_out + 1 uint64 offsets; no output pointer at all = a size query, an output that
+        is None is not produced.  Returns MergeRowsResult (n_rows, n_bases, names_len, max_len, max_name, n_pairs, overlap_bases)."""
+        rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, 0)
+        if base_mode is not None:
+            rows.base_mode = base_mode
+        a = A.MergeRowsArgs(d_insert, row_len, pad_base, pad_qual, (C.c_uint8 * 2)(), out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap,
+                            out_name_off, off_cap)
+        r = A.MergeRowsResult()
+        self._check(self._L.rfq_merge_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

@@ -100,6 +100,7 @@ struct RfqOpts {
     int  pos_seg = 0;                 // RFQ_POS_SEG=1024|2048|4096  decode, list chain: bytes of a position stream per wave (default: by the largest stream, dec/pos_lists.h)
     bool judge_general = false;       // RFQ_JUDGE=general  rfq_judge_rows: the any-length kernel for every row length, in tiles of 64 window starts (default: rows of up to 1024 bytes are held whole)
     bool adapter_general = false;     // RFQ_ADAPTER=general  rfq_adapter_rows: the any-length kernel (a lane per shift, byte by byte) for every row length (default: rows of up to 1024 bytes as bit planes in LDS)
+    bool merge_general = false;       // RFQ_MERGE=general  rfq_merge_rows: the lane-per-byte kernel with the rule as plain branches (default: a lane per 16-byte group, the rule as byte masks in registers)
     bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)
 };
 struct rfq_ctx {

@@ -1338,6 +1338,114 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     ctx->timer.collect();
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- pairs -> one row per overlapping pair, under R1's name: rfq_merge_rows of include/rfq_hip.h
+// rfq_select_rows' shape over PAIRS: the judging pass (k_merge_judge), the two scans, ONE read-back, the tables (k_merge_tables), two writers - k_merge_rows
+// (RFQ_MERGE=general: k_merge_rows_any) and k_sel_names as it is, over a table that keeps the source row where it reads it (enc/rows_merge.h).
+extern "C" int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_merge_rows_args* a, rfq_merge_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows, np = n / 2; const bool named = in->d_name_off != nullptr;
+    const bool size_query = !a->d_bases && !a->d_quals && !a->d_lens && !a->d_names && !a->d_name_off;
+    if (n & 1u) return rfq_fail(ctx, RFQ_E_ARG, "merging takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    if (!size_query && a->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be >= 1");
+    if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode);
+    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if (n >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    if (!named && (a->d_names || a->d_name_off)) return rfq_fail(ctx, RFQ_E_ARG, "rows without names (d_name_off == NULL) have no name outputs: d_names / d_name_off must be NULL");
+    if (n && !a->d_insert) return rfq_fail(ctx, RFQ_E_ARG, "null d_insert");
+    if (n && (!in->d_lens || (a->d_names && in->names_len && !in->d_names))) return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
+    if (n && (a->d_bases || a->d_quals) && (!in->d_bases || !in->d_quals))
+        return rfq_fail(ctx, RFQ_E_ARG, "a row output needs rows->d_bases and rows->d_quals, both: the rule looks at the bases and the scores");
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_lens | (uintptr_t)a->d_insert) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens and d_insert must be 4-byte aligned");
+    if (((uintptr_t)in->d_name_off | (uintptr_t)a->d_name_off) & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
+    int rc;
+    {   // the bytes a call can write (its cap, and never more than n_rows / 2 rows of row_len) against the bytes it reads
+        const unsigned long long rows_in = (unsigned long long)n * in->row_len, rows_out = (unsigned long long)np * a->row_len;
+        const Span ins[] = {
+            { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" },
+            { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }, { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" },
+            { a->d_insert, np * 4ull, "d_insert" } };
+        const Span outs[] = {
+            { a->d_bases, std::min<unsigned long long>(a->bases_cap, rows_out), "d_bases" }, { a->d_quals, std::min<unsigned long long>(a->quals_cap, rows_out), "d_quals" },
+            { a->d_lens, std::min<unsigned long long>(a->lens_cap, np) * 4ull, "d_lens" }, { a->d_names, std::min<unsigned long long>(a->names_cap, in->names_len), "d_names" },
+            { a->d_name_off, std::min<unsigned long long>(a->off_cap, np + 1) * 8ull, "d_name_off" } };
+        if ((rc = rows_apart(ctx, outs, ins, ": merging in place is not offered")) != RFQ_OK) return rc;
+    }
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    res->n_pairs = np;
+    MergeStat hs; memset(&hs, 0, sizeof hs); uint32_t n_out = 0; uint64_t names_len = 0;
+    MergeIn mi; memset(&mi, 0, sizeof mi);
+    mi.lens = in->d_lens; mi.insert = a->d_insert; mi.name_off = in->d_name_off; mi.names_len = in->names_len;
+    mi.n_rows = (uint32_t)n; mi.n_pairs = (uint32_t)np; mi.row_len = in->row_len;
+    uint32_t* pos = nullptr; uint64_t* noff = nullptr;
+    if (np) {
+        ctx->timer.begin("merge:judge", S);
+        MergeStat* dst = nullptr;
+        HIPCHK(ctx, table(B[B_LEN], ((size_t)np + 2) * 4, pos));
+        if (named) HIPCHK(ctx, table(B[B_P], ((size_t)np + 2) * 8, noff));
+        HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)np / SCAN_TILE + 2) * 16)));
+        if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_merge_judge, dim3((uint32_t)((np + MJ_PAIRS - 1u) / MJ_PAIRS)), dim3(256), 0, S, mi, pos, noff, dst);
+        KCHK(ctx, "k_merge_judge");
+        scan_exclusive<uint32_t>(S, pos, pos, np, B[B_SCANTMP].as<uint32_t>(), 1);
+        if (named) scan_exclusive<uint64_t>(S, noff, noff, np, B[B_SCANTMP].as<uint64_t>(), 1);
+        KCHK(ctx, "scan_exclusive");
+        ctx->timer.end(S);
+        HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+        HIPCHK(ctx, ctx->fetch(&n_out, pos + np, 4, S));
+        if (named) HIPCHK(ctx, ctx->fetch(&names_len, noff + np, 8, S));
+        HIPCHK(ctx, ctx->fetch_sync(S));
+        if (hs.err) {                                                        // the first offender's key says which rule it broke (enc/rows_merge.h)
+            const unsigned long long row = hs.bad_row >> 2;
+            switch ((uint32_t)(hs.bad_row & 3u)) {
+            case MG_ERR_LEN: return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, row);
+            case MG_ERR_INS: return rfq_fail(ctx, RFQ_E_ARG, "a pair with insert >= 0 has no position that both mates cover: an empty mate, insert == 0 or insert > l1 + l2 - 1 (first such pair: %llu)", row / 2);
+            default: return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, row);
+            }
+        }
+    }
+    res->n_rows = n_out; res->n_bases = hs.n_bases; res->names_len = names_len; res->max_len = hs.max_len; res->max_name = hs.max_name; res->overlap_bases = hs.overlap;
+    if (size_query) { ctx->timer.collect(); return RFQ_OK; }
+    if ((rc = rows_room(ctx, a, n_out, names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    if (n_out == 0) return rows_none(ctx, a->d_name_off);
+    ctx->timer.begin("merge:tables", S);
+    SelRow* tab = nullptr; uint64_t* ooff = nullptr;
+    HIPCHK(ctx, table(B[B_X], (size_t)n_out * sizeof(SelRow), tab));
+    if (named) HIPCHK(ctx, table(B[B_Y], ((size_t)n_out + 1) * 8, ooff));
+    hipLaunchKernelGGL(k_merge_tables, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, S, mi, (const uint32_t*)pos, (const uint64_t*)noff, tab, ooff, a->d_lens, a->d_name_off);
+    KCHK(ctx, "k_merge_tables");
+    ctx->timer.end(S);
+    ctx->timer.begin("merge:rows", S);
+    if (a->d_bases || a->d_quals) {
+        MergeRowsOut o; memset(&o, 0, sizeof o);
+        o.sb = in->d_bases; o.sq = in->d_quals; o.bases = a->d_bases; o.quals = a->d_quals;
+        o.row_len_in = in->row_len; o.total_in = n * in->row_len; o.row_len = a->row_len; o.n_out = n_out;
+        o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
+        o.vec_in = rows_vec(in->row_len, in->d_bases, in->d_quals);
+        o.vec = rows_vec(a->row_len, a->d_bases, a->d_quals); o.per = rows_per(a->row_len);
+        o.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u;
+        if (ctx->opt.merge_general) {
+            const unsigned long long nb = ((unsigned long long)n_out * a->row_len + 255ull) / 256ull;
+            if (nb > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_MERGE=general: %llu output bytes are too many for one call", (unsigned long long)n_out * a->row_len);
+            hipLaunchKernelGGL(k_merge_rows_any, dim3((uint32_t)nb), dim3(256), 0, S, o, (const SelRow*)tab);
+        } else hipLaunchKernelGGL(k_merge_rows, dim3((uint32_t)(((uint64_t)n_out + o.per - 1) / o.per)), dim3(256), 0, S, o, (const SelRow*)tab);
+        KCHK(ctx, "k_merge_rows");
+    }
+    ctx->timer.end(S);
+    ctx->timer.begin("merge:names", S);
+    if (a->d_names && names_len) {
+        uint32_t blocks = 0;
+        if ((rc = name_blob_blocks(ctx, a->d_names, names_len, &blocks)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_sel_names, dim3(blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, names_len);
+        KCHK(ctx, "k_sel_names");
+    }
+    ctx->timer.end(S);
+    HIPCHK(ctx, hipStreamSynchronize(S));
+    ctx->timer.collect();
+    return RFQ_OK;
+}
 // ---------------------------------------------------------------- rows -> keep, window, reason and metrics per row, one QC summary: rfq_judge_rows of include/rfq_hip.h
 // One kernel and one read-back (the verdict block with the sums).  Which kernel is the row length's to say: up to 256 bytes a DPP row of 16 lanes holds a row,
 // up to 1024 a wave, beyond that (or with RFQ_JUDGE=general, in tiles of 64) a wave walks it in tiles (enc/rows_judge.h).

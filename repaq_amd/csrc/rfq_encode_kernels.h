@@ -26,3 +26,4 @@
 #include "enc/rows_select.h"                  // rows -> the kept rows, trimmed, with their names (rfq_select_rows)
 #include "enc/rows_judge.h"                   // rows -> keep, window, reason and metrics per row + a QC summary (rfq_judge_rows)
 #include "enc/rows_adapter.h"                 // rows -> the length adapter removal leaves, insert sizes of the pairs + a summary (rfq_adapter_rows)
+#include "enc/rows_merge.h"                   // pairs -> one read per overlapping pair, the consensus of both mates, with R1's names (rfq_merge_rows)

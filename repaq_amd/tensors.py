@@ -43,6 +43,13 @@ select_rows moves the bytes once:
     j = judge_rows(codec, dict(t, lens=a["length"]), cut_tail=True, cut_window=4, cut_mean_q=20, min_mean_q=20)
     s = select_rows(codec, t, keep=j["keep"], start=j["start"], length=j["length"], pairs=True, min_len=36)
 
+adapter -> merge: the insert size trim_adapters finds for a pair is the length of the fragment both mates were read from; rfq_merge_rows collapses every such pair
+into one read of that length - R1 from the front, the reverse complement of R2 from the back, a consensus by the scores where they overlap - under R1's name, and
+the pairs without an overlap come back as they are:
+
+    a = trim_adapters(codec, t, pairs=True); m = merge_pairs(codec, t, a["insert"])
+    image = encode_tensors(codec, *(m["merged"][k] for k in ("bases", "quals", "lens", "names", "name_off")))          # SE; m["unmerged"]: the other pairs, PE
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -223,6 +230,50 @@ def trim_adapters(codec, t, pairs=False, codes=True, adapter1=None, adapter2=Non
         out["insert"], out["diff"] = insert, diff
     if hist_len:
         out["insert_hist"] = hist
+    return out
+
+
+MERGE_FIELDS = ("n_rows", "n_bases", "names_len", "max_len", "max_name", "n_pairs", "overlap_bases")
+
+
+def merge_pairs(codec, t, insert, row_len=None, pad=255, unmerged=True, codes=True):
+    """The paired rows of decode_tensors / fastq_to_tensors (`t`: "bases", "quals", "lens", optionally "names" + "name_off"; rows 2k / 2k + 1 are R1 / R2; codes:
+    what they were made with) and trim_adapters' "insert" ([n / 2] int32, -1: no overlap) -> {"merged": a rows dict ("bases", "quals", "lens" and, when `t` has
+    them, "names" + "name_off") with ONE row per pair whose insert is >= 0 - the fragment of insert bases: R1 from the front, the reverse complement of R2 from
+    the back, the consensus of rfq_merge_rows where both cover a position, under R1's name -, "unmerged": select_rows of the other pairs, both mates (left out
+    with unmerged=False), "summary": dict of the call's counts}.  `t` holds the lengths the insert was found on (not lengths cut further by an adapter match);
+    narrow the choice with torch.where(cond, insert, -1).  Rows are padded with `pad` to row_len (None: the longest merged read).  "quals" must hold the scores.
+    A size query and one call, both ordered with torch's current stream; the context goes back to its own stream afterwards."""
+    bases, quals, lens = t["bases"], t["quals"], t["lens"]
+    named = t.get("name_off") is not None
+    names, name_off = (t["names"], t["name_off"]) if named else (bases.new_empty((0,)), torch.zeros((int(bases.shape[0]) + 1,), dtype=torch.int64, device=bases.device))
+    n, L_in, p_b, p_q, p_l, p_n, nl_in, p_o = _rows_args(bases, quals, lens, names, name_off)
+    dev = bases.device
+    assert n % 2 == 0 and insert.dtype == torch.int32 and insert.is_contiguous() and insert.numel() == n // 2 and insert.device == dev, \
+        "rows in pairs, insert: [n / 2] int32 on the rows' device"
+    rows = (n, L_in, p_b, p_q, p_l, p_n if named else None, nl_in if named else 0, p_o if named else None)
+    kw = dict(d_insert=insert.data_ptr(), codes=codes)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        q = codec.merge_rows(*rows, **kw)
+        L = max(int(q.max_len), 1) if row_len is None else int(row_len)
+        m, nl = int(q.n_rows), int(q.names_len)
+        ob = torch.empty((m, L), dtype=torch.uint8, device=dev); oq = torch.empty((m, L), dtype=torch.uint8, device=dev)
+        ol = torch.empty((m,), dtype=torch.int32, device=dev)
+        blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if named else None
+        off = torch.zeros((m + 1,), dtype=name_off.dtype, device=dev) if named else None
+        if m:
+            q = codec.merge_rows(*rows, row_len=L, pad_base=pad, pad_qual=pad, out_bases=ob.data_ptr(), bases_cap=m * L, out_quals=oq.data_ptr(), quals_cap=m * L,
+                                 out_lens=ol.data_ptr(), lens_cap=m, out_names=blob.data_ptr() if (named and nl) else None, names_cap=nl if named else 0,
+                                 out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **kw)
+    finally:
+        codec.set_stream(None)
+    merged = {"bases": ob, "quals": oq, "lens": ol}
+    if named:
+        merged["names"], merged["name_off"] = blob, off
+    out = {"merged": merged, "summary": {f: int(getattr(q, f)) for f in MERGE_FIELDS}}
+    if unmerged:
+        out["unmerged"] = select_rows(codec, t, keep=(insert < 0).repeat_interleave(2), pairs=True)
     return out
 
 
