@@ -348,6 +348,9 @@ def _marker_ok(codec, marker):
         assert (marker[1:] not in names) if marker.startswith("!") else (marker in names), (marker, sorted(names))
 
 
+Options, marker_ok = _Options, _marker_ok                                  # (for the tests that run a formulation's switches around calls of their own)
+
+
 def check_encode_formulation(codec, form, fq1, fq2, paired, chunk_bases, want_md5=None, want_len=None, want=None):
     """one input through rfq_encode_batch with the switches of ENC_FORMS[form]: the image equals the golden (md5 + size) or the expected bytes"""
     opts, marker = ENC_FORMS[form]
