@@ -1,7 +1,7 @@
 // enc/rows_merge.h - pairs of rows -> one row per overlapping pair: the fragment both mates were read from, `insert` bases long, the consensus of the two where they
 // overlap, under R1's name (rfq_merge_rows): what consumes the insert sizes rfq_adapter_rows leaves.  It moves bytes and decides nothing about the alignment.
-// Part of rfq_encode_kernels.h (included from there, last: it uses rows_select.h's table entry and names kernel, rows_judge.h's 16-byte pieces and
-// rows_adapter.h's base classes; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, last: it uses rows_select.h's table entry, tables body (rows_tables), writers' arguments (RowsOut) and names
+// kernel, rows_judge.h's 16-byte pieces and rows_adapter.h's base classes; not a stand-alone header).
 #pragma once
 // The shape is rfq_select_rows': k_merge_judge validates EVERY pair and leaves a merged flag and the merged name size per pair (scanned by the host's scan_exclusive
 // to the output row index and the output name offset) with the maxima and sums; after ONE read-back the host decides; k_merge_tables turns the two scans into a table
@@ -75,20 +75,15 @@ __global__ void __launch_bounds__(256) k_merge_judge(MergeIn in, uint32_t* __res
     if (threadIdx.x == 0) { const unsigned long long x = s_ov[0] + s_ov[1] + s_ov[2] + s_ov[3]; if (x) atomicAdd(&st->overlap, x); }
 }
 
-// grid ceil(n_pairs / 256) x 256 threads, a thread per INPUT pair: pos[] / noff[] are the exclusive scans of the merged flags / merged name sizes with their totals
-// behind them, as k_sel_tables takes them.  The entry of output row j is a SelRow (enc/rows_select.h) read as (src = row 2k, start = l1, len = ins, pad = l2): src
-// stands where k_sel_names reads it.  d_lens / d_name_off: the caller's, where asked for.
+// grid ceil(n_pairs / 256) x 256 threads, a thread per INPUT pair: rows_tables (enc/rows_select.h) over pairs.  The entry of output row j is a SelRow read as
+// (src = row 2k, start = l1, len = ins, pad = l2): src stands where k_sel_names reads it.
+struct MergeEntry {
+    const MergeIn& in;
+    __device__ __forceinline__ uint4 operator()(uint32_t k, int32_t& len) const { const MgPair p = mg_pair(in, k); len = p.ins; return make_uint4(2u * k, p.l1, (uint32_t)p.ins, p.l2); }
+};
 __global__ void __launch_bounds__(256) k_merge_tables(MergeIn in, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ noff, SelRow* __restrict__ tab,
                                                       uint64_t* __restrict__ ooff, int32_t* __restrict__ d_lens, uint64_t* __restrict__ d_name_off) {
-    const uint64_t k64 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (k64 >= in.n_pairs) return;
-    const uint32_t k = (uint32_t)k64, j = pos[k];
-    if (k == 0 && noff) { const uint32_t n_out = pos[in.n_pairs]; const uint64_t t = noff[in.n_pairs]; ooff[n_out] = t; if (d_name_off) d_name_off[n_out] = t; }
-    if (pos[k + 1] == j) return;
-    const MgPair p = mg_pair(in, k);
-    *(uint4*)(tab + j) = make_uint4(2u * k, p.l1, (uint32_t)p.ins, p.l2);
-    if (d_lens) d_lens[j] = p.ins;
-    if (noff) { const uint64_t t = noff[k]; ooff[j] = t; if (d_name_off) d_name_off[j] = t; }
+    rows_tables(MergeEntry{ in }, in.n_pairs, pos, noff, tab, ooff, d_lens, d_name_off);
 }
 
 // ---- four bytes at a time
@@ -126,17 +121,6 @@ __device__ __forceinline__ void mg_consensus(uint32_t ascii, uint32_t b1, uint32
     oq = (q1 & s1) | (q2 & s2) | (hi & both & agree) | (sub_bytes(hi, lo) & both & rest);
 }
 
-struct MergeRowsOut {
-    const uint8_t* sb; const uint8_t* sq;             // the input rows [n_in][row_len_in]: both, whichever output is wanted (the rule looks at the bases AND the scores)
-    uint8_t* bases; uint8_t* quals;                   // [n_out][row_len]; null = not wanted
-    uint64_t row_len_in, total_in;                    // input stride; bytes of an input row buffer (n_in * row_len_in)
-    uint64_t row_len; uint32_t n_out;
-    uint32_t pad_b4, pad_q4;                          // pad bytes, repeated in the four bytes of a word
-    uint32_t vec_in;                                  // row_len_in % 16 == 0 and both input buffers 16-byte aligned: R1's groups may be loaded whole
-    uint32_t vec;                                     // row_len % 16 == 0 and both output buffers 16-byte aligned: one 16-byte store per group
-    uint32_t per;                                     // output rows of a workgroup
-    uint32_t ascii;
-};
 // 16 bytes of buf that END in front of byte `end` of the row that starts at rowbase, in reverse order: w holds source bytes end - 1, end - 2, ..., end - 16.  Only
 // bytes j in [f, t) of w are wanted (source bytes end - 1 - j: the caller sees to it that they lie inside the row); the others come back as whatever the load found
 // inside the buffer, or 0.  One 16-byte load at the bytes' own alignment wherever all 16 lie inside the buffer, byte by byte only at the buffer's two ends.
@@ -155,7 +139,7 @@ __device__ __forceinline__ void mg_ld16_rev(const uint8_t* buf, uint64_t total, 
 // aligned rows the aligned load).  R2's part is source bytes [ins - 16 - k0, ins - k0) of row 2k + 1: one load at their own alignment (mg_ld16_rev), reversed in
 // registers (the four words swapped, v_perm_b32 in each) and complemented by SWAR; the quality group takes the same load and the same reversal.  The rule is byte
 // masks and selects (mg_consensus); what lies behind the read is the pad (low_bytes), and the group is stored once (store_group16).  No LDS, no atomics.
-__global__ void __launch_bounds__(256) k_merge_rows(MergeRowsOut o, const SelRow* __restrict__ tab) {
+__global__ void __launch_bounds__(256) k_merge_rows(RowsOut o, const SelRow* __restrict__ tab) {
     const uint32_t rs = blockIdx.x * o.per;
     if (rs >= o.n_out) return;
     const uint32_t nr = (o.n_out - rs < o.per) ? o.n_out - rs : o.per;
@@ -194,7 +178,7 @@ __device__ __forceinline__ uint8_t mg_comp_byte(uint32_t ascii, uint8_t c) {
 }
 // grid ceil(n_out * row_len / 256) x 256 threads: thread t writes byte t % row_len of output row t / row_len, in each buffer that is wanted.  Only bytes in front of
 // a read's length are read, so never a byte outside the rows.
-__global__ void __launch_bounds__(256) k_merge_rows_any(MergeRowsOut o, const SelRow* __restrict__ tab) {
+__global__ void __launch_bounds__(256) k_merge_rows_any(RowsOut o, const SelRow* __restrict__ tab) {
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (t >= (uint64_t)o.n_out * o.row_len) return;
     const uint64_t g = t / o.row_len, p = t % o.row_len;

@@ -1,6 +1,7 @@
 // enc/rows_select.h - rows -> the kept rows, trimmed to a window each, with their lengths, names and name offsets (rfq_select_rows): the step between
 // rfq_decode_rows / rfq_text_rows and rfq_encode_rows / rfq_rows_to_text
-// Part of rfq_encode_kernels.h (included from there, last; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, last; not a stand-alone header).  The pieces of a compacting call that rfq_merge_rows (enc/rows_merge.h) takes
+// from here as they are: the table entry (SelRow), the tables body (rows_tables), the row writers' arguments (RowsOut) and the names kernel (k_sel_names).
 #pragma once
 // k_sel_judge resolves every row's window, validates it and decides who stays (mask, min_len, the pair rule); it leaves a kept flag and the kept name size per
 // row (scanned by the host's scan_exclusive to the output row index and the output name offset), the maxima, sums and drop counts.  After ONE read-back the host
@@ -78,31 +79,43 @@ __global__ void __launch_bounds__(256) k_sel_judge(SelIn in, uint32_t* __restric
     }
 }
 
-// grid ceil(n_rows / 256) x 256 threads, a thread per INPUT row: pos[] / noff[] are the exclusive scans of the kept flags / kept name sizes with their totals behind
-// them (pos[n_rows] = n_out), so row i was kept exactly when pos[i + 1] != pos[i], and is output row pos[i].  tab / ooff: the context's tables the writers search;
-// d_lens / d_name_off: the caller's, where asked for (the same values: no copy behind this).  noff null: rows without names.
-__global__ void __launch_bounds__(256) k_sel_tables(SelIn in, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ noff, SelRow* __restrict__ tab,
-                                                    uint64_t* __restrict__ ooff, int32_t* __restrict__ d_lens, uint64_t* __restrict__ d_name_off) {
+// The tables of a compacting call, a thread per INPUT unit (select: a row, merge: a pair): pos[] / noff[] are the exclusive scans of the kept flags / kept name sizes
+// with their totals behind them (pos[n] = n_out), so unit i was kept exactly when pos[i + 1] != pos[i], and is output row pos[i].  entry(i, len) yields the SelRow of
+// a kept unit as a uint4 and the output row's length.  tab / ooff: the context's tables the writers search; d_lens / d_name_off: the caller's, where asked for (the
+// same values: no copy behind this).  noff null: rows without names.
+template <class Entry> __device__ __forceinline__ void rows_tables(const Entry& entry, uint32_t n, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ noff,
+        SelRow* __restrict__ tab, uint64_t* __restrict__ ooff, int32_t* __restrict__ d_lens, uint64_t* __restrict__ d_name_off) {
     const uint64_t i64 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i64 >= in.n_rows) return;
+    if (i64 >= n) return;
     const uint32_t i = (uint32_t)i64, j = pos[i];
-    if (i == 0 && noff) { const uint32_t n_out = pos[in.n_rows]; const uint64_t t = noff[in.n_rows]; ooff[n_out] = t; if (d_name_off) d_name_off[n_out] = t; }
+    if (i == 0 && noff) { const uint32_t n_out = pos[n]; const uint64_t t = noff[n]; ooff[n_out] = t; if (d_name_off) d_name_off[n_out] = t; }
     if (pos[i + 1] == j) return;
-    uint32_t s0, w, e; (void)sel_window(in, i, s0, w, e);
-    *(uint4*)(tab + j) = make_uint4(i, s0, w, 0u);
-    if (d_lens) d_lens[j] = (int32_t)w;
+    int32_t len; const uint4 e = entry(i, len);
+    *(uint4*)(tab + j) = e;
+    if (d_lens) d_lens[j] = len;
     if (noff) { const uint64_t t = noff[i]; ooff[j] = t; if (d_name_off) d_name_off[j] = t; }
 }
+// grid ceil(n_rows / 256) x 256 threads: the entry of a kept row is (the row, its window's start, its window's length, 0)
+struct SelEntry {
+    const SelIn& in;
+    __device__ __forceinline__ uint4 operator()(uint32_t i, int32_t& len) const { uint32_t s0, w, e; (void)sel_window(in, i, s0, w, e); len = (int32_t)w; return make_uint4(i, s0, w, 0u); }
+};
+__global__ void __launch_bounds__(256) k_sel_tables(SelIn in, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ noff, SelRow* __restrict__ tab,
+                                                    uint64_t* __restrict__ ooff, int32_t* __restrict__ d_lens, uint64_t* __restrict__ d_name_off) {
+    rows_tables(SelEntry{ in }, in.n_rows, pos, noff, tab, ooff, d_lens, d_name_off);
+}
 
-struct SelRowsOut {
-    const uint8_t* sb; const uint8_t* sq;             // the input rows [n_in][row_len_in]; null with its output
+// what a row writer of a compacting call takes (k_sel_rows; k_merge_rows and k_merge_rows_any of enc/rows_merge.h)
+struct RowsOut {
+    const uint8_t* sb; const uint8_t* sq;             // the input rows [n_in][row_len_in]; select: null with its output; merge: both, whichever output is wanted
     uint8_t* bases; uint8_t* quals;                   // [n_out][row_len]; null = not wanted
     uint64_t row_len_in, total_in;                    // input stride; bytes of an input row buffer (n_in * row_len_in)
     uint64_t row_len; uint32_t n_out;
     uint32_t pad_b4, pad_q4;                          // pad bytes, repeated in the four bytes of a word
-    uint32_t vec_in;                                  // row_len_in % 16 == 0 and both input buffers 16-byte aligned: the aligned groups of a row may be loaded whole
+    uint32_t vec_in;                                  // row_len_in % 16 == 0 and the input buffers that are read 16-byte aligned: the aligned groups of a row may be loaded whole
     uint32_t vec;                                     // row_len % 16 == 0 and both output buffers 16-byte aligned: one 16-byte store per group
     uint32_t per;                                     // output rows of a workgroup
+    uint32_t ascii;                                   // merge: the bases are letters, not codes (select leaves it 0 and never reads it)
 };
 // grid ceil(n_out / per) x 256 threads.  The work follows the OUTPUT: a workgroup owns `per` consecutive output rows, a thread one 16-byte group [k0, k0 + 16) of
 // one row at a time, in GroupWalk's order (rfq_common.h).  A group that holds bases is ONE load of 16 source bytes at
@@ -110,7 +123,7 @@ struct SelRowsOut {
 // them where both lie inside that row (rt_ld16's groups form), else one 16-byte load wherever 16 bytes from there still lie inside the input buffer; only behind that,
 // at the very end of the buffer, byte by byte.  What lies behind the window is masked off in registers and replaced by the pad (low_bytes), and the group is stored
 // once (store_group16).  No LDS.
-__global__ void __launch_bounds__(256) k_sel_rows(SelRowsOut o, const SelRow* __restrict__ tab) {
+__global__ void __launch_bounds__(256) k_sel_rows(RowsOut o, const SelRow* __restrict__ tab) {
     const uint32_t rs = blockIdx.x * o.per;
     if (rs >= o.n_out) return;
     const uint32_t nr = (o.n_out - rs < o.per) ? o.n_out - rs : o.per;

@@ -1008,6 +1008,89 @@ template <size_t NO, size_t NI> static int rows_apart(rfq_ctx* ctx, const Span (
         if (sel_overlap(o.p, o.n, i.p, i.n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the input %s%s", o.what, i.what, tail);
     return RFQ_OK;
 }
+// ---- the plan of a compacting call (rfq_select_rows over rows, rfq_merge_rows over pairs): judge, two scans, ONE read-back; the caller refuses or goes on; tables,
+// row writer, names writer.  A caller supplies its unit count, its stage names and three launches - the judge, the tables kernel, the row writer - and keeps its own
+// argument checks (in its own order: the first refusal met is the one reported), its verdict on the Stat and its result fields.
+struct RowsStages { const char* judge; const char* tables; const char* rows; const char* names; };
+// A below: rfq_select_rows_args, rfq_merge_rows_args - they end in the same output block (row_len, pad_*, d_bases / bases_cap .. d_name_off / off_cap), as rows_room takes it
+template <class A> static bool rows_size_query(const A* o) { return !o->d_bases && !o->d_quals && !o->d_lens && !o->d_names && !o->d_name_off; }
+template <class A> static int rows_dst_len(rfq_ctx* ctx, const A* o) { return !rows_size_query(o) && o->row_len == 0 ? rfq_fail(ctx, RFQ_E_ARG, "row_len must be >= 1") : (int)RFQ_OK; }
+template <class A> static int rows_dst_named(rfq_ctx* ctx, const A* o, bool named) {
+    if (named || (!o->d_names && !o->d_name_off)) return RFQ_OK;
+    return rfq_fail(ctx, RFQ_E_ARG, "rows without names (d_name_off == NULL) have no name outputs: d_names / d_name_off must be NULL");
+}
+// (others4 / what4: the caller's further 4-byte inputs, ORed, and what the message calls them all)
+template <class A> static int rows_dst_aligned(rfq_ctx* ctx, const rfq_rows_in* in, const A* o, uintptr_t others4, const char* what4) {
+    if (((uintptr_t)in->d_lens | (uintptr_t)o->d_lens | others4) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "%s must be 4-byte aligned", what4);
+    if (((uintptr_t)in->d_name_off | (uintptr_t)o->d_name_off) & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
+    return RFQ_OK;
+}
+// the bytes a call can write: its cap, and never more than `units` rows of row_len or the names there are
+template <class A> static void rows_dst_spans(const A* o, uint64_t units, uint64_t names_len, Span (&outs)[5]) {
+    const unsigned long long rows_out = (unsigned long long)units * o->row_len;
+    outs[0] = { o->d_bases, std::min<unsigned long long>(o->bases_cap, rows_out), "d_bases" }; outs[1] = { o->d_quals, std::min<unsigned long long>(o->quals_cap, rows_out), "d_quals" };
+    outs[2] = { o->d_lens, std::min<unsigned long long>(o->lens_cap, units) * 4ull, "d_lens" }; outs[3] = { o->d_names, std::min<unsigned long long>(o->names_cap, names_len), "d_names" };
+    outs[4] = { o->d_name_off, std::min<unsigned long long>(o->off_cap, units + 1) * 8ull, "d_name_off" };
+}
+// what the callables handed to rows_judge / rows_write end in, behind their hipLaunchKernelGGL: the launch's error, if it left one
+static int launched(rfq_ctx* ctx, const char* what) { KCHK(ctx, what); return RFQ_OK; }
+// judge(pos, noff, dst) launches the judging kernel: a kept flag per unit in pos[], the kept name size in noff[] (null: rows without names), the verdict in *dst.
+// Both are scanned in place, their totals behind them; *hs, n_out and names_len come back in ONE read-back.  No units: nothing runs, *hs stays zero.
+struct RowsJudged { uint32_t* pos = nullptr; uint64_t* noff = nullptr; uint32_t n_out = 0; uint64_t names_len = 0; };
+template <class Stat, class Judge> static int rows_judge(rfq_ctx* ctx, uint64_t units, bool named, const char* stage, Judge judge, Stat* hs, RowsJudged* j) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; int rc;
+    memset(hs, 0, sizeof *hs);
+    if (!units) return RFQ_OK;
+    ctx->timer.begin(stage, S);
+    Stat* dst = nullptr;
+    HIPCHK(ctx, table(B[B_LEN], ((size_t)units + 2) * 4, j->pos));
+    if (named) HIPCHK(ctx, table(B[B_P], ((size_t)units + 2) * 8, j->noff));
+    HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)units / SCAN_TILE + 2) * 16)));
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if ((rc = judge(j->pos, j->noff, dst)) != RFQ_OK) return rc;
+    scan_exclusive<uint32_t>(S, j->pos, j->pos, units, B[B_SCANTMP].as<uint32_t>(), 1);
+    if (named) scan_exclusive<uint64_t>(S, j->noff, j->noff, units, B[B_SCANTMP].as<uint64_t>(), 1);
+    KCHK(ctx, "scan_exclusive");
+    ctx->timer.end(S);
+    HIPCHK(ctx, ctx->fetch(hs, dst, sizeof *hs, S));
+    HIPCHK(ctx, ctx->fetch(&j->n_out, j->pos + units, 4, S));
+    if (named) HIPCHK(ctx, ctx->fetch(&j->names_len, j->noff + units, 8, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    return RFQ_OK;
+}
+// tables(pos, noff, tab, ooff) launches the tables kernel (a rows_tables), rows(o, tab) completes o - vec_in and what else is its own - and launches the row writer;
+// k_sel_names follows the same table.  Ends the call: synchronised, the stage times collected.
+template <class A, class Tables, class Rows> static int rows_write(rfq_ctx* ctx, const rfq_rows_in* in, const A* a, const RowsJudged& j, const RowsStages& st, Tables tables, Rows rows) {
+    hipStream_t S = ctx->stream; DBuf* B = ctx->b; int rc;
+    const uint32_t n_out = j.n_out;
+    ctx->timer.begin(st.tables, S);
+    SelRow* tab = nullptr; uint64_t* ooff = nullptr;
+    HIPCHK(ctx, table(B[B_X], (size_t)n_out * sizeof(SelRow), tab));
+    if (j.noff) HIPCHK(ctx, table(B[B_Y], ((size_t)n_out + 1) * 8, ooff));
+    if ((rc = tables((const uint32_t*)j.pos, (const uint64_t*)j.noff, tab, ooff)) != RFQ_OK) return rc;
+    ctx->timer.end(S);
+    ctx->timer.begin(st.rows, S);
+    if (a->d_bases || a->d_quals) {
+        RowsOut o; memset(&o, 0, sizeof o);
+        o.sb = in->d_bases; o.sq = in->d_quals; o.bases = a->d_bases; o.quals = a->d_quals;
+        o.row_len_in = in->row_len; o.total_in = in->n_rows * in->row_len; o.row_len = a->row_len; o.n_out = n_out;
+        o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
+        o.vec = rows_vec(a->row_len, a->d_bases, a->d_quals); o.per = rows_per(a->row_len);
+        if ((rc = rows(o, (const SelRow*)tab)) != RFQ_OK) return rc;
+    }
+    ctx->timer.end(S);
+    ctx->timer.begin(st.names, S);
+    if (a->d_names && j.names_len) {
+        uint32_t blocks = 0;
+        if ((rc = name_blob_blocks(ctx, a->d_names, j.names_len, &blocks)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_sel_names, dim3(blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, j.names_len);
+        KCHK(ctx, "k_sel_names");
+    }
+    ctx->timer.end(S);
+    HIPCHK(ctx, hipStreamSynchronize(S));
+    ctx->timer.collect();
+    return RFQ_OK;
+}
 // ---------------------------------------------------------------- rows -> FASTQ text (-> image): rfq_rows_to_text, rfq_encode_rows of include/rfq_hip.h
 // The judged part (k_rows_sizes + one scan per text) ends in ONE read-back - the texts' sizes, the bases, the error bits - and the writer (k_rows_text)
 // runs only on rows that passed; what the writer itself finds in the bytes comes back with a second look at the same block.
@@ -1239,212 +1322,134 @@ extern "C" int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* a, rfq_text
     return RFQ_OK;
 }
 // ---------------------------------------------------------------- rows -> kept, trimmed rows with their names: rfq_select_rows of include/rfq_hip.h
-// The judging pass (k_sel_judge), TWO scans - the kept flags to output row indices (32-bit), the kept name sizes to output name offsets (64-bit: a blob may exceed
-// 4 GiB, and the block scan's wave primitives take 4- and 8-byte values, not a two-field struct) - and ONE read-back: the verdict block and the two totals.  The host
-// refuses or goes on; k_sel_tables makes the per-output-row tables (and the caller's lens / name_off), k_sel_rows and k_sel_names follow them.
+// A compacting call over ROWS (the plan: rows_judge / rows_write above).  The judging pass (k_sel_judge), TWO scans - the kept flags to output row indices (32-bit),
+// the kept name sizes to output name offsets (64-bit: a blob may exceed 4 GiB, and the block scan's wave primitives take 4- and 8-byte values, not a two-field
+// struct) - and ONE read-back: the verdict block and the two totals.  The host refuses or goes on; k_sel_tables makes the per-output-row tables (and the caller's
+// lens / name_off), k_sel_rows and k_sel_names follow them.
+static const RowsStages SELECT_STAGES = { "select:judge", "select:tables", "select:rows", "select:names" };
 extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_select_rows_args* a, rfq_select_rows_result* res) {
     if (!ctx || !in || !a || !res) return RFQ_E_ARG;
     memset(res, 0, sizeof *res);
     ctx->err.clear();
     const uint64_t n = in->n_rows; const bool named = in->d_name_off != nullptr;
-    const bool size_query = !a->d_bases && !a->d_quals && !a->d_lens && !a->d_names && !a->d_name_off;
+    int rc;
     if (a->pairs != 0 && a->pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
     if (a->pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
-    if (!size_query && a->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be >= 1");
+    if ((rc = rows_dst_len(ctx, a)) != RFQ_OK) return rc;
     if (in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
     if (n >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
-    if (!named && (a->d_names || a->d_name_off)) return rfq_fail(ctx, RFQ_E_ARG, "rows without names (d_name_off == NULL) have no name outputs: d_names / d_name_off must be NULL");
+    if ((rc = rows_dst_named(ctx, a, named)) != RFQ_OK) return rc;
     if (n && (!in->d_lens || (a->d_bases && !in->d_bases) || (a->d_quals && !in->d_quals) || (a->d_names && in->names_len && !in->d_names)))
         return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
-    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_lens | (uintptr_t)a->d_start | (uintptr_t)a->d_len) & 3u)
-        return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_start and d_len must be 4-byte aligned");
-    if (((uintptr_t)in->d_name_off | (uintptr_t)a->d_name_off) & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
-    int rc;
+    if ((rc = rows_dst_aligned(ctx, in, a, (uintptr_t)a->d_start | (uintptr_t)a->d_len, "d_lens, d_start and d_len")) != RFQ_OK) return rc;
     {   // the bytes a call can write (its cap, and never more than n_rows rows of row_len) against the bytes it reads
-        const unsigned long long rows_in = (unsigned long long)n * in->row_len, rows_out = (unsigned long long)n * a->row_len;
+        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
         const Span ins[] = {
             { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" },
             { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }, { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" },
             { a->d_keep, n, "d_keep" }, { a->d_start, n * 4ull, "d_start" }, { a->d_len, n * 4ull, "d_len" } };
-        const Span outs[] = {
-            { a->d_bases, std::min<unsigned long long>(a->bases_cap, rows_out), "d_bases" }, { a->d_quals, std::min<unsigned long long>(a->quals_cap, rows_out), "d_quals" },
-            { a->d_lens, std::min<unsigned long long>(a->lens_cap, n) * 4ull, "d_lens" }, { a->d_names, std::min<unsigned long long>(a->names_cap, in->names_len), "d_names" },
-            { a->d_name_off, std::min<unsigned long long>(a->off_cap, n + 1) * 8ull, "d_name_off" } };
+        Span outs[5]; rows_dst_spans(a, n, in->names_len, outs);
         if ((rc = rows_apart(ctx, outs, ins, ": selection in place is not offered")) != RFQ_OK) return rc;
     }
-    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
     if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
     res->n_in = n;
-    SelStat hs; memset(&hs, 0, sizeof hs); uint32_t n_out = 0; uint64_t names_len = 0;
     SelIn si; memset(&si, 0, sizeof si);
     si.lens = in->d_lens; si.name_off = in->d_name_off; si.keep = a->d_keep; si.start = a->d_start; si.len = a->d_len;
     si.names_len = in->names_len; si.n_rows = (uint32_t)n; si.row_len = in->row_len; si.pairs = a->pairs ? 1u : 0u; si.min_len = a->min_len;
-    uint32_t* pos = nullptr; uint64_t* noff = nullptr;
-    if (n) {
-        ctx->timer.begin("select:judge", S);
-        SelStat* dst = nullptr;
-        HIPCHK(ctx, table(B[B_LEN], ((size_t)n + 2) * 4, pos));
-        if (named) HIPCHK(ctx, table(B[B_P], ((size_t)n + 2) * 8, noff));
-        HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)n / SCAN_TILE + 2) * 16)));
-        if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
-        hipLaunchKernelGGL(k_sel_judge, dim3((uint32_t)((n + SJ_ROWS - 1u) / SJ_ROWS)), dim3(256), 0, S, si, pos, noff, dst);
-        KCHK(ctx, "k_sel_judge");
-        scan_exclusive<uint32_t>(S, pos, pos, n, B[B_SCANTMP].as<uint32_t>(), 1);
-        if (named) scan_exclusive<uint64_t>(S, noff, noff, n, B[B_SCANTMP].as<uint64_t>(), 1);
-        KCHK(ctx, "scan_exclusive");
-        ctx->timer.end(S);
-        HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
-        HIPCHK(ctx, ctx->fetch(&n_out, pos + n, 4, S));
-        if (named) HIPCHK(ctx, ctx->fetch(&names_len, noff + n, 8, S));
-        HIPCHK(ctx, ctx->fetch_sync(S));
-        const unsigned long long br = hs.bad_row;
-        if (hs.err & SL_ERR_LEN) return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, br);
-        if (hs.err & SL_ERR_WIN) return rfq_fail(ctx, RFQ_E_ARG, "a window starts below 0, has a negative length or ends behind its read (first such row: %llu)", br);
-        if (hs.err & SL_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
-    }
-    res->n_rows = n_out; res->n_bases = hs.n_bases; res->names_len = names_len; res->max_len = hs.max_len; res->max_name = hs.max_name;
+    SelStat hs; RowsJudged j;
+    rc = rows_judge(ctx, n, named, SELECT_STAGES.judge, [&](uint32_t* flag, uint64_t* nsz, SelStat* dst) -> int {
+        hipLaunchKernelGGL(k_sel_judge, dim3((uint32_t)((n + SJ_ROWS - 1u) / SJ_ROWS)), dim3(256), 0, ctx->stream, si, flag, nsz, dst);
+        return launched(ctx, "k_sel_judge");
+    }, &hs, &j);
+    if (rc != RFQ_OK) return rc;
+    const unsigned long long br = hs.bad_row;
+    if (hs.err & SL_ERR_LEN) return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, br);
+    if (hs.err & SL_ERR_WIN) return rfq_fail(ctx, RFQ_E_ARG, "a window starts below 0, has a negative length or ends behind its read (first such row: %llu)", br);
+    if (hs.err & SL_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
+    res->n_rows = j.n_out; res->n_bases = hs.n_bases; res->names_len = j.names_len; res->max_len = hs.max_len; res->max_name = hs.max_name;
     res->dropped_mask = hs.d_mask; res->dropped_short = hs.d_short; res->dropped_mate = hs.d_mate;
-    if (size_query) { ctx->timer.collect(); return RFQ_OK; }
-    if ((rc = rows_room(ctx, a, n_out, names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
-    if (n_out == 0) return rows_none(ctx, a->d_name_off);
-    ctx->timer.begin("select:tables", S);
-    SelRow* tab = nullptr; uint64_t* ooff = nullptr;
-    HIPCHK(ctx, table(B[B_X], (size_t)n_out * sizeof(SelRow), tab));
-    if (named) HIPCHK(ctx, table(B[B_Y], ((size_t)n_out + 1) * 8, ooff));
-    hipLaunchKernelGGL(k_sel_tables, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, S, si, (const uint32_t*)pos, (const uint64_t*)noff, tab, ooff, a->d_lens, a->d_name_off);
-    KCHK(ctx, "k_sel_tables");
-    ctx->timer.end(S);
-    ctx->timer.begin("select:rows", S);
-    if (a->d_bases || a->d_quals) {
-        SelRowsOut o; memset(&o, 0, sizeof o);
-        o.sb = in->d_bases; o.sq = in->d_quals; o.bases = a->d_bases; o.quals = a->d_quals;
-        o.row_len_in = in->row_len; o.total_in = n * in->row_len; o.row_len = a->row_len; o.n_out = n_out;
-        o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
-        o.vec_in = rows_vec(in->row_len, a->d_bases ? in->d_bases : nullptr, a->d_quals ? in->d_quals : nullptr);      // (of the buffers that are read)
-        o.vec = rows_vec(a->row_len, a->d_bases, a->d_quals); o.per = rows_per(a->row_len);
-        hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)n_out + o.per - 1) / o.per)), dim3(256), 0, S, o, (const SelRow*)tab);
-        KCHK(ctx, "k_sel_rows");
-    }
-    ctx->timer.end(S);
-    ctx->timer.begin("select:names", S);
-    if (a->d_names && names_len) {
-        uint32_t blocks = 0;
-        if ((rc = name_blob_blocks(ctx, a->d_names, names_len, &blocks)) != RFQ_OK) return rc;
-        hipLaunchKernelGGL(k_sel_names, dim3(blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, names_len);
-        KCHK(ctx, "k_sel_names");
-    }
-    ctx->timer.end(S);
-    HIPCHK(ctx, hipStreamSynchronize(S));
-    ctx->timer.collect();
-    return RFQ_OK;
+    if (rows_size_query(a)) { ctx->timer.collect(); return RFQ_OK; }
+    if ((rc = rows_room(ctx, a, j.n_out, j.names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    if (j.n_out == 0) return rows_none(ctx, a->d_name_off);
+    return rows_write(ctx, in, a, j, SELECT_STAGES,
+        [&](const uint32_t* pos, const uint64_t* noff, SelRow* tab, uint64_t* ooff) -> int {
+            hipLaunchKernelGGL(k_sel_tables, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, si, pos, noff, tab, ooff, a->d_lens, a->d_name_off);
+            return launched(ctx, "k_sel_tables");
+        },
+        [&](RowsOut& r, const SelRow* tab) -> int {
+            r.vec_in = rows_vec(in->row_len, a->d_bases ? in->d_bases : nullptr, a->d_quals ? in->d_quals : nullptr);      // (of the buffers that are read)
+            hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)r.n_out + r.per - 1) / r.per)), dim3(256), 0, ctx->stream, r, tab);
+            return launched(ctx, "k_sel_rows");
+        });
 }
 // ---------------------------------------------------------------- pairs -> one row per overlapping pair, under R1's name: rfq_merge_rows of include/rfq_hip.h
-// rfq_select_rows' shape over PAIRS: the judging pass (k_merge_judge), the two scans, ONE read-back, the tables (k_merge_tables), two writers - k_merge_rows
-// (RFQ_MERGE=general: k_merge_rows_any) and k_sel_names as it is, over a table that keeps the source row where it reads it (enc/rows_merge.h).
+// A compacting call over PAIRS: the judging pass (k_merge_judge), the tables (k_merge_tables), two row writers - k_merge_rows (RFQ_MERGE=general: k_merge_rows_any) -
+// and k_sel_names as it is, over a table that keeps the source row where it reads it (enc/rows_merge.h).
+static const RowsStages MERGE_STAGES = { "merge:judge", "merge:tables", "merge:rows", "merge:names" };
 extern "C" int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_merge_rows_args* a, rfq_merge_rows_result* res) {
     if (!ctx || !in || !a || !res) return RFQ_E_ARG;
     memset(res, 0, sizeof *res);
     ctx->err.clear();
     const uint64_t n = in->n_rows, np = n / 2; const bool named = in->d_name_off != nullptr;
-    const bool size_query = !a->d_bases && !a->d_quals && !a->d_lens && !a->d_names && !a->d_name_off;
+    int rc;
     if (n & 1u) return rfq_fail(ctx, RFQ_E_ARG, "merging takes rows in pairs (got %llu rows)", (unsigned long long)n);
-    if (!size_query && a->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be >= 1");
+    if ((rc = rows_dst_len(ctx, a)) != RFQ_OK) return rc;
     if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode);
     if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
     if (n >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
-    if (!named && (a->d_names || a->d_name_off)) return rfq_fail(ctx, RFQ_E_ARG, "rows without names (d_name_off == NULL) have no name outputs: d_names / d_name_off must be NULL");
+    if ((rc = rows_dst_named(ctx, a, named)) != RFQ_OK) return rc;
     if (n && !a->d_insert) return rfq_fail(ctx, RFQ_E_ARG, "null d_insert");
     if (n && (!in->d_lens || (a->d_names && in->names_len && !in->d_names))) return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
     if (n && (a->d_bases || a->d_quals) && (!in->d_bases || !in->d_quals))
         return rfq_fail(ctx, RFQ_E_ARG, "a row output needs rows->d_bases and rows->d_quals, both: the rule looks at the bases and the scores");
-    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_lens | (uintptr_t)a->d_insert) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens and d_insert must be 4-byte aligned");
-    if (((uintptr_t)in->d_name_off | (uintptr_t)a->d_name_off) & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
-    int rc;
+    if ((rc = rows_dst_aligned(ctx, in, a, (uintptr_t)a->d_insert, "d_lens and d_insert")) != RFQ_OK) return rc;
     {   // the bytes a call can write (its cap, and never more than n_rows / 2 rows of row_len) against the bytes it reads
-        const unsigned long long rows_in = (unsigned long long)n * in->row_len, rows_out = (unsigned long long)np * a->row_len;
+        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
         const Span ins[] = {
             { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" },
             { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }, { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" },
             { a->d_insert, np * 4ull, "d_insert" } };
-        const Span outs[] = {
-            { a->d_bases, std::min<unsigned long long>(a->bases_cap, rows_out), "d_bases" }, { a->d_quals, std::min<unsigned long long>(a->quals_cap, rows_out), "d_quals" },
-            { a->d_lens, std::min<unsigned long long>(a->lens_cap, np) * 4ull, "d_lens" }, { a->d_names, std::min<unsigned long long>(a->names_cap, in->names_len), "d_names" },
-            { a->d_name_off, std::min<unsigned long long>(a->off_cap, np + 1) * 8ull, "d_name_off" } };
+        Span outs[5]; rows_dst_spans(a, np, in->names_len, outs);
         if ((rc = rows_apart(ctx, outs, ins, ": merging in place is not offered")) != RFQ_OK) return rc;
     }
-    hipStream_t S = ctx->stream; DBuf* B = ctx->b;
     if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
     res->n_pairs = np;
-    MergeStat hs; memset(&hs, 0, sizeof hs); uint32_t n_out = 0; uint64_t names_len = 0;
     MergeIn mi; memset(&mi, 0, sizeof mi);
     mi.lens = in->d_lens; mi.insert = a->d_insert; mi.name_off = in->d_name_off; mi.names_len = in->names_len;
     mi.n_rows = (uint32_t)n; mi.n_pairs = (uint32_t)np; mi.row_len = in->row_len;
-    uint32_t* pos = nullptr; uint64_t* noff = nullptr;
-    if (np) {
-        ctx->timer.begin("merge:judge", S);
-        MergeStat* dst = nullptr;
-        HIPCHK(ctx, table(B[B_LEN], ((size_t)np + 2) * 4, pos));
-        if (named) HIPCHK(ctx, table(B[B_P], ((size_t)np + 2) * 8, noff));
-        HIPCHK(ctx, B[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)np / SCAN_TILE + 2) * 16)));
-        if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
-        hipLaunchKernelGGL(k_merge_judge, dim3((uint32_t)((np + MJ_PAIRS - 1u) / MJ_PAIRS)), dim3(256), 0, S, mi, pos, noff, dst);
-        KCHK(ctx, "k_merge_judge");
-        scan_exclusive<uint32_t>(S, pos, pos, np, B[B_SCANTMP].as<uint32_t>(), 1);
-        if (named) scan_exclusive<uint64_t>(S, noff, noff, np, B[B_SCANTMP].as<uint64_t>(), 1);
-        KCHK(ctx, "scan_exclusive");
-        ctx->timer.end(S);
-        HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
-        HIPCHK(ctx, ctx->fetch(&n_out, pos + np, 4, S));
-        if (named) HIPCHK(ctx, ctx->fetch(&names_len, noff + np, 8, S));
-        HIPCHK(ctx, ctx->fetch_sync(S));
-        if (hs.err) {                                                        // the first offender's key says which rule it broke (enc/rows_merge.h)
-            const unsigned long long row = hs.bad_row >> 2;
-            switch ((uint32_t)(hs.bad_row & 3u)) {
-            case MG_ERR_LEN: return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, row);
-            case MG_ERR_INS: return rfq_fail(ctx, RFQ_E_ARG, "a pair with insert >= 0 has no position that both mates cover: an empty mate, insert == 0 or insert > l1 + l2 - 1 (first such pair: %llu)", row / 2);
-            default: return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, row);
-            }
+    MergeStat hs; RowsJudged j;
+    rc = rows_judge(ctx, np, named, MERGE_STAGES.judge, [&](uint32_t* flag, uint64_t* nsz, MergeStat* dst) -> int {
+        hipLaunchKernelGGL(k_merge_judge, dim3((uint32_t)((np + MJ_PAIRS - 1u) / MJ_PAIRS)), dim3(256), 0, ctx->stream, mi, flag, nsz, dst);
+        return launched(ctx, "k_merge_judge");
+    }, &hs, &j);
+    if (rc != RFQ_OK) return rc;
+    if (hs.err) {                                                            // the first offender's key says which rule it broke (enc/rows_merge.h)
+        const unsigned long long row = hs.bad_row >> 2;
+        switch ((uint32_t)(hs.bad_row & 3u)) {
+        case MG_ERR_LEN: return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, row);
+        case MG_ERR_INS: return rfq_fail(ctx, RFQ_E_ARG, "a pair with insert >= 0 has no position that both mates cover: an empty mate, insert == 0 or insert > l1 + l2 - 1 (first such pair: %llu)", row / 2);
+        default: return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, row);
         }
     }
-    res->n_rows = n_out; res->n_bases = hs.n_bases; res->names_len = names_len; res->max_len = hs.max_len; res->max_name = hs.max_name; res->overlap_bases = hs.overlap;
-    if (size_query) { ctx->timer.collect(); return RFQ_OK; }
-    if ((rc = rows_room(ctx, a, n_out, names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
-    if (n_out == 0) return rows_none(ctx, a->d_name_off);
-    ctx->timer.begin("merge:tables", S);
-    SelRow* tab = nullptr; uint64_t* ooff = nullptr;
-    HIPCHK(ctx, table(B[B_X], (size_t)n_out * sizeof(SelRow), tab));
-    if (named) HIPCHK(ctx, table(B[B_Y], ((size_t)n_out + 1) * 8, ooff));
-    hipLaunchKernelGGL(k_merge_tables, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, S, mi, (const uint32_t*)pos, (const uint64_t*)noff, tab, ooff, a->d_lens, a->d_name_off);
-    KCHK(ctx, "k_merge_tables");
-    ctx->timer.end(S);
-    ctx->timer.begin("merge:rows", S);
-    if (a->d_bases || a->d_quals) {
-        MergeRowsOut o; memset(&o, 0, sizeof o);
-        o.sb = in->d_bases; o.sq = in->d_quals; o.bases = a->d_bases; o.quals = a->d_quals;
-        o.row_len_in = in->row_len; o.total_in = n * in->row_len; o.row_len = a->row_len; o.n_out = n_out;
-        o.pad_b4 = a->pad_base * 0x01010101u; o.pad_q4 = a->pad_qual * 0x01010101u;
-        o.vec_in = rows_vec(in->row_len, in->d_bases, in->d_quals);
-        o.vec = rows_vec(a->row_len, a->d_bases, a->d_quals); o.per = rows_per(a->row_len);
-        o.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u;
-        if (ctx->opt.merge_general) {
-            const unsigned long long nb = ((unsigned long long)n_out * a->row_len + 255ull) / 256ull;
-            if (nb > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_MERGE=general: %llu output bytes are too many for one call", (unsigned long long)n_out * a->row_len);
-            hipLaunchKernelGGL(k_merge_rows_any, dim3((uint32_t)nb), dim3(256), 0, S, o, (const SelRow*)tab);
-        } else hipLaunchKernelGGL(k_merge_rows, dim3((uint32_t)(((uint64_t)n_out + o.per - 1) / o.per)), dim3(256), 0, S, o, (const SelRow*)tab);
-        KCHK(ctx, "k_merge_rows");
-    }
-    ctx->timer.end(S);
-    ctx->timer.begin("merge:names", S);
-    if (a->d_names && names_len) {
-        uint32_t blocks = 0;
-        if ((rc = name_blob_blocks(ctx, a->d_names, names_len, &blocks)) != RFQ_OK) return rc;
-        hipLaunchKernelGGL(k_sel_names, dim3(blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, names_len);
-        KCHK(ctx, "k_sel_names");
-    }
-    ctx->timer.end(S);
-    HIPCHK(ctx, hipStreamSynchronize(S));
-    ctx->timer.collect();
-    return RFQ_OK;
+    res->n_rows = j.n_out; res->n_bases = hs.n_bases; res->names_len = j.names_len; res->max_len = hs.max_len; res->max_name = hs.max_name; res->overlap_bases = hs.overlap;
+    if (rows_size_query(a)) { ctx->timer.collect(); return RFQ_OK; }
+    if ((rc = rows_room(ctx, a, j.n_out, j.names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    if (j.n_out == 0) return rows_none(ctx, a->d_name_off);
+    return rows_write(ctx, in, a, j, MERGE_STAGES,
+        [&](const uint32_t* pos, const uint64_t* noff, SelRow* tab, uint64_t* ooff) -> int {
+            hipLaunchKernelGGL(k_merge_tables, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, ctx->stream, mi, pos, noff, tab, ooff, a->d_lens, a->d_name_off);
+            return launched(ctx, "k_merge_tables");
+        },
+        [&](RowsOut& r, const SelRow* tab) -> int {
+            r.vec_in = rows_vec(in->row_len, in->d_bases, in->d_quals);
+            r.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u;
+            if (ctx->opt.merge_general) {
+                const unsigned long long nb = ((unsigned long long)r.n_out * a->row_len + 255ull) / 256ull;
+                if (nb > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_MERGE=general: %llu output bytes are too many for one call", (unsigned long long)r.n_out * a->row_len);
+                hipLaunchKernelGGL(k_merge_rows_any, dim3((uint32_t)nb), dim3(256), 0, ctx->stream, r, tab);
+            } else hipLaunchKernelGGL(k_merge_rows, dim3((uint32_t)(((uint64_t)r.n_out + r.per - 1) / r.per)), dim3(256), 0, ctx->stream, r, tab);
+            return launched(ctx, "k_merge_rows");
+        });
 }
 // ---------------------------------------------------------------- rows -> keep, window, reason and metrics per row, one QC summary: rfq_judge_rows of include/rfq_hip.h
 // One kernel and one read-back (the verdict block with the sums).  Which kernel is the row length's to say: up to 256 bytes a DPP row of 16 lanes holds a row,

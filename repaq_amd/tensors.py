@@ -124,28 +124,20 @@ def fastq_to_tensors(codec, fq1: torch.Tensor, fq2: torch.Tensor = None, paired=
     return out
 
 
-def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_len=1, row_len=None, pad=255):
-    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "quals", "lens", optionally "names" + "name_off") -> a new dict with the same keys for the
-    rows that are KEPT, each TRIMMED to bases [start, start + length) (rfq_select_rows), plus "dropped": {"mask", "short", "mate"}.  keep: [n] bool or uint8,
-    non-zero = keep (None: every row); start / length: [n] int32 (None: 0 / to the end of the read); pairs: rows 2k / 2k + 1 stand or fall together; a row
-    whose window is shorter than min_len is dropped (and with pairs its mate); rows are padded with `pad` to row_len (None: the longest kept window).  The
-    bytes are the rows' own, names are kept whole.  A size query and one call, both ordered with torch's current stream; the context goes back to its own
-    stream afterwards."""
+def _compact(codec, t, call, kw_of, row_len, pad):
+    """What select_rows and merge_pairs share: `call` (RfqCodec.select_rows / merge_rows) as a size query, then once more into five new tensors of exactly the
+    reported sizes, both ordered with torch's current stream.  kw_of(n, dev) checks the caller's own inputs and returns the arguments they become.  -> the last
+    result struct, the rows dict ("bases", "quals", "lens" and, when `t` has them, "names" + "name_off")."""
     bases, quals, lens = t["bases"], t["quals"], t["lens"]
     named = t.get("name_off") is not None
     names, name_off = (t["names"], t["name_off"]) if named else (bases.new_empty((0,)), torch.zeros((int(bases.shape[0]) + 1,), dtype=torch.int64, device=bases.device))
     n, L_in, p_b, p_q, p_l, p_n, nl_in, p_o = _rows_args(bases, quals, lens, names, name_off)
     dev = bases.device
-    sel = {}
-    for key, v, dts in (("d_keep", keep, (torch.bool, torch.uint8)), ("d_start", start, (torch.int32,)), ("d_len", length, (torch.int32,))):
-        if v is not None:
-            assert v.dtype in dts and v.is_contiguous() and v.numel() == n and v.device == dev, "keep: [n] bool / uint8, start / length: [n] int32, on the rows' device"
-            sel[key] = v.data_ptr()
+    kw = kw_of(n, dev)
     rows = (n, L_in, p_b, p_q, p_l, p_n if named else None, nl_in if named else 0, p_o if named else None)
-    kw = dict(pairs=pairs, min_len=min_len, **sel)
     codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     try:
-        q = codec.select_rows(*rows, **kw)
+        q = call(*rows, **kw)
         L = max(int(q.max_len), 1) if row_len is None else int(row_len)
         m, nl = int(q.n_rows), int(q.names_len)
         ob = torch.empty((m, L), dtype=torch.uint8, device=dev); oq = torch.empty((m, L), dtype=torch.uint8, device=dev)
@@ -153,14 +145,33 @@ def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_l
         blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if named else None
         off = torch.zeros((m + 1,), dtype=name_off.dtype, device=dev) if named else None
         if m:
-            codec.select_rows(*rows, row_len=L, pad_base=pad, pad_qual=pad, out_bases=ob.data_ptr(), bases_cap=m * L, out_quals=oq.data_ptr(), quals_cap=m * L,
-                              out_lens=ol.data_ptr(), lens_cap=m, out_names=blob.data_ptr() if (named and nl) else None, names_cap=nl if named else 0,
-                              out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **kw)
+            q = call(*rows, row_len=L, pad_base=pad, pad_qual=pad, out_bases=ob.data_ptr(), bases_cap=m * L, out_quals=oq.data_ptr(), quals_cap=m * L,
+                     out_lens=ol.data_ptr(), lens_cap=m, out_names=blob.data_ptr() if (named and nl) else None, names_cap=nl if named else 0,
+                     out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **kw)
     finally:
         codec.set_stream(None)
-    out = {"bases": ob, "quals": oq, "lens": ol, "dropped": {"mask": int(q.dropped_mask), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}}
+    out = {"bases": ob, "quals": oq, "lens": ol}
     if named:
         out["names"], out["name_off"] = blob, off
+    return q, out
+
+
+def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_len=1, row_len=None, pad=255):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "quals", "lens", optionally "names" + "name_off") -> a new dict with the same keys for the
+    rows that are KEPT, each TRIMMED to bases [start, start + length) (rfq_select_rows), plus "dropped": {"mask", "short", "mate"}.  keep: [n] bool or uint8,
+    non-zero = keep (None: every row); start / length: [n] int32 (None: 0 / to the end of the read); pairs: rows 2k / 2k + 1 stand or fall together; a row
+    whose window is shorter than min_len is dropped (and with pairs its mate); rows are padded with `pad` to row_len (None: the longest kept window).  The
+    bytes are the rows' own, names are kept whole.  A size query and one call, both ordered with torch's current stream; the context goes back to its own
+    stream afterwards."""
+    def kw_of(n, dev):
+        sel = {}
+        for key, v, dts in (("d_keep", keep, (torch.bool, torch.uint8)), ("d_start", start, (torch.int32,)), ("d_len", length, (torch.int32,))):
+            if v is not None:
+                assert v.dtype in dts and v.is_contiguous() and v.numel() == n and v.device == dev, "keep: [n] bool / uint8, start / length: [n] int32, on the rows' device"
+                sel[key] = v.data_ptr()
+        return dict(pairs=pairs, min_len=min_len, **sel)
+    q, out = _compact(codec, t, codec.select_rows, kw_of, row_len, pad)
+    out["dropped"] = {"mask": int(q.dropped_mask), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}
     return out
 
 
@@ -244,33 +255,11 @@ def merge_pairs(codec, t, insert, row_len=None, pad=255, unmerged=True, codes=Tr
     with unmerged=False), "summary": dict of the call's counts}.  `t` holds the lengths the insert was found on (not lengths cut further by an adapter match);
     narrow the choice with torch.where(cond, insert, -1).  Rows are padded with `pad` to row_len (None: the longest merged read).  "quals" must hold the scores.
     A size query and one call, both ordered with torch's current stream; the context goes back to its own stream afterwards."""
-    bases, quals, lens = t["bases"], t["quals"], t["lens"]
-    named = t.get("name_off") is not None
-    names, name_off = (t["names"], t["name_off"]) if named else (bases.new_empty((0,)), torch.zeros((int(bases.shape[0]) + 1,), dtype=torch.int64, device=bases.device))
-    n, L_in, p_b, p_q, p_l, p_n, nl_in, p_o = _rows_args(bases, quals, lens, names, name_off)
-    dev = bases.device
-    assert n % 2 == 0 and insert.dtype == torch.int32 and insert.is_contiguous() and insert.numel() == n // 2 and insert.device == dev, \
-        "rows in pairs, insert: [n / 2] int32 on the rows' device"
-    rows = (n, L_in, p_b, p_q, p_l, p_n if named else None, nl_in if named else 0, p_o if named else None)
-    kw = dict(d_insert=insert.data_ptr(), codes=codes)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        q = codec.merge_rows(*rows, **kw)
-        L = max(int(q.max_len), 1) if row_len is None else int(row_len)
-        m, nl = int(q.n_rows), int(q.names_len)
-        ob = torch.empty((m, L), dtype=torch.uint8, device=dev); oq = torch.empty((m, L), dtype=torch.uint8, device=dev)
-        ol = torch.empty((m,), dtype=torch.int32, device=dev)
-        blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if named else None
-        off = torch.zeros((m + 1,), dtype=name_off.dtype, device=dev) if named else None
-        if m:
-            q = codec.merge_rows(*rows, row_len=L, pad_base=pad, pad_qual=pad, out_bases=ob.data_ptr(), bases_cap=m * L, out_quals=oq.data_ptr(), quals_cap=m * L,
-                                 out_lens=ol.data_ptr(), lens_cap=m, out_names=blob.data_ptr() if (named and nl) else None, names_cap=nl if named else 0,
-                                 out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **kw)
-    finally:
-        codec.set_stream(None)
-    merged = {"bases": ob, "quals": oq, "lens": ol}
-    if named:
-        merged["names"], merged["name_off"] = blob, off
+    def kw_of(n, dev):
+        assert n % 2 == 0 and insert.dtype == torch.int32 and insert.is_contiguous() and insert.numel() == n // 2 and insert.device == dev, \
+            "rows in pairs, insert: [n / 2] int32 on the rows' device"
+        return dict(d_insert=insert.data_ptr(), codes=codes)
+    q, merged = _compact(codec, t, codec.merge_rows, kw_of, row_len, pad)
     out = {"merged": merged, "summary": {f: int(getattr(q, f)) for f in MERGE_FIELDS}}
     if unmerged:
         out["unmerged"] = select_rows(codec, t, keep=(insert < 0).repeat_interleave(2), pairs=True)

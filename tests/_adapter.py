@@ -97,25 +97,6 @@ def expected(B, lens, c, codes):
     return dict(length=length, how=how, insert=insert, diff=diff, hist=hist, summary=s)
 
 
-class DevRows:
-    """base rows and lengths in device memory; shift: bytes by which the row buffer is moved off its 256-byte aligned start"""
-    def __init__(self, codec, B, lens, shift=0):
-        self.codec = codec; self.n, self.L = B.shape; self.raw = []
-
-        def put(data, sh=0):
-            r = codec.dev_put(b"\xEE" * sh + data); self.raw.append(r)
-            return C.c_void_p(r.value + sh)
-        self.bases = put(np.ascontiguousarray(B, np.uint8).tobytes(), shift)
-        self.lens = put(np.ascontiguousarray(lens, np.int32).tobytes())
-
-    def args(self):
-        return (self.n, self.L, self.bases, self.lens)
-
-    def free(self):
-        for r in self.raw:
-            self.codec.dev_free(r)
-
-
 OUT_ARGS = dict(l="d_len", h="d_how", i="d_insert", d="d_diff", H="d_insert_hist")
 OUT_NAMES = dict(l="length", h="how", i="insert", d="diff", H="hist")
 OUT_TYPES = dict(l=np.int32, h=np.uint8, i=np.int32, d=np.int32, H=np.uint64)
@@ -136,7 +117,7 @@ def run(codec, dev, c, codes, outputs=None):
     size = dict(l=4 * n, h=n, i=4 * (n // 2), d=4 * (n // 2), H=8 * c["hist_len"])
     g = {o: W.Guarded(codec, size[o]) for o in outputs}
     try:
-        r = codec.adapter_rows(*dev.args(), codes=codes, **c, **{OUT_ARGS[o]: g[o].ptr for o in outputs})
+        r = codec.adapter_rows(*dev.adapter_args(), codes=codes, **c, **{OUT_ARGS[o]: g[o].ptr for o in outputs})
         assert all(x.guards_intact() for x in g.values()), "a guard around an output buffer was written"
         raw = {o: x.body() for o, x in g.items()}
         return {o: np.frombuffer(raw[o], OUT_TYPES[o]) for o in outputs}, summary_of(r), raw
@@ -158,7 +139,7 @@ def check(codec, B, lens, c, codes, shifts=(0,), paths=PATHS, e=None, outputs=No
     """the call equals the reference, at every shift and on both paths; returns the reference"""
     e = e or expected(B, lens, c, codes)
     for shift in shifts:
-        dev = DevRows(codec, B, lens, shift)
+        dev = W.DevRows(codec, B, None, lens, shift=shift)
         try:
             for path in paths:
                 codec.set_option("RFQ_ADAPTER", path)
@@ -547,7 +528,7 @@ def check_outputs(codec):
     e = expected(B, lens, c, False)
     assert 10 < e["summary"]["pairs_found"] < 120 and all(e["summary"][f] > 0 for f in FIELDS), e["summary"]
     eh_by = {hl: expected(B, lens, dict(c, hist_len=hl), False) for hl in (1, 2, 151, 400, 65536)}
-    dev = DevRows(codec, B, lens, 3)
+    dev = W.DevRows(codec, B, None, lens, shift=3)
     try:
         for path in PATHS:
             codec.set_option("RFQ_ADAPTER", path)
@@ -580,10 +561,10 @@ def check_host_refusals(codec):
     from repaq_amd import RfqError
     n, L = 40, 32
     B, lens = random_pairs(n // 2, L, 10, codes=False)
-    dev = DevRows(codec, B, lens)
+    dev = W.DevRows(codec, B, None, lens)
     buf = codec.dev_put(b"\0" * 8192); b = buf.value
     try:
-        rows = dev.args()
+        rows = dev.adapter_args()
 
         def at(p, k):
             return C.c_void_p(p.value + k)
@@ -643,7 +624,7 @@ def check_device_refusal(codec, label):
         row = dict(first=0, middle=n // 2 + 1, last=n - 1)[where]
         lens[row] = -1 if value == "negative" else L + 1
         lens[row ^ 1] = L                                                   # (a good row beside it)
-        dev = DevRows(codec, B, lens, shift=1)
+        dev = W.DevRows(codec, B, None, lens, shift=1)
         c = shape_criteria(L)[2][1]
         try:
             for path in PATHS:
@@ -712,7 +693,7 @@ def check_composition(codec):
     assert 100 < kept < 290 and e["summary"]["rows_cut"] > 100, (kept, e["summary"])
     _, B, Q, lens, names = codec.text_rows_bytes(fq1, fq2, paired=PE_TWO_FILES, row_len=160, qual_offset=33)
     n = len(lens)
-    dev = S.DevSel(codec, B, Q, lens, names)
+    dev = W.DevRows(codec, B, Q, lens, names)
     ga, gk, gs, gl = W.Guarded(codec, 4 * n), W.Guarded(codec, n), W.Guarded(codec, 4 * n), W.Guarded(codec, 4 * n)
     bufs = []
     try:

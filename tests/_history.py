@@ -430,7 +430,7 @@ class Calls:
         return tuple(self.mod["S"].call(c, *self.rows, row_len="x16", **self.sel)[5])
 
     def judge_rows(self, c):
-        J = self.mod["J"]; dev = J.DevRows(c, *self.j_rows)
+        J, W = self.mod["J"], self.mod["W"]; dev = W.DevRows(c, *self.j_rows)
         try:
             out, summ, raw = J.run(c, dev, self.j_crit, False)
         finally:
@@ -439,7 +439,7 @@ class Calls:
         return tuple(sorted(raw.items())), tuple(sorted(summ.items()))
 
     def adapter_rows(self, c):
-        A = self.mod["A"]; dev = A.DevRows(c, *self.a_rows)
+        A, W = self.mod["A"], self.mod["W"]; B, lens = self.a_rows; dev = W.DevRows(c, B, None, lens)
         try:
             out, summ, raw = A.run(c, dev, self.a_crit, True)
         finally:

@@ -102,26 +102,6 @@ def expected(B, Q, lens, c, codes):
     return dict(keep=keep, start=start, length=length, why=why, metrics=met, summary=s)
 
 
-class DevRows:
-    """base / quality rows and lengths in device memory; shift: bytes by which the row buffers are moved off their 256-byte aligned start.  The row buffers end
-    where the allocation's payload ends, so a read behind the last row shows under the sanitizer build."""
-    def __init__(self, codec, B, Q, lens, shift=0):
-        self.codec = codec; self.n, self.L = B.shape; self.raw = []
-
-        def put(data, sh=0):
-            r = codec.dev_put(b"\xEE" * sh + data); self.raw.append(r)
-            return C.c_void_p(r.value + sh)
-        self.bases = put(np.ascontiguousarray(B, np.uint8).tobytes(), shift); self.quals = put(np.ascontiguousarray(Q, np.uint8).tobytes(), shift)
-        self.lens = put(np.ascontiguousarray(lens, np.int32).tobytes())
-
-    def args(self):
-        return (self.n, self.L, self.bases, self.quals, self.lens)
-
-    def free(self):
-        for r in self.raw:
-            self.codec.dev_free(r)
-
-
 OUT_SIZES = dict(k=1, s=4, l=4, w=1, m=16)
 OUT_ARGS = dict(k="d_keep", s="d_start", l="d_len", w="d_why", m="d_metrics")
 
@@ -135,7 +115,7 @@ def run(codec, dev, c, codes, outputs="kslwm"):
     n = dev.n
     g = {o: W.Guarded(codec, OUT_SIZES[o] * n) for o in outputs}
     try:
-        r = codec.judge_rows(*dev.args(), codes=codes, **c, **{OUT_ARGS[o]: g[o].ptr for o in outputs})
+        r = codec.judge_rows(*dev.judge_args(), codes=codes, **c, **{OUT_ARGS[o]: g[o].ptr for o in outputs})
         assert all(x.guards_intact() for x in g.values()), "a guard around an output buffer was written"
         raw = {o: x.body() for o, x in g.items()}
         dt = dict(k=np.uint8, s=np.int32, l=np.int32, w=np.uint8, m=np.uint32)
@@ -166,7 +146,7 @@ def check(codec, B, Q, lens, c, codes, shifts=(0,), paths=(None, "general"), e=N
     """the call equals the reference, at every shift and on both paths; returns the reference"""
     e = e or expected(B, Q, lens, c, codes)
     for shift in shifts:
-        dev = DevRows(codec, B, Q, lens, shift)
+        dev = W.DevRows(codec, B, Q, lens, shift=shift)
         try:
             for path in paths:
                 codec.set_option("RFQ_JUDGE", path)
@@ -373,7 +353,7 @@ def check_outputs_and_summary(codec):
     c = STEPS[-1][1]
     e = expected(B, Q, lens, c, False)
     assert 0 < e["summary"]["n_kept"] < 700 and all(e["summary"][f] > 0 for f in FIELDS), e["summary"]
-    dev = DevRows(codec, B, Q, lens, 3)
+    dev = W.DevRows(codec, B, Q, lens, shift=3)
     try:
         for path in (None, "general"):
             codec.set_option("RFQ_JUDGE", path)
@@ -386,7 +366,7 @@ def check_outputs_and_summary(codec):
         codec.set_option("RFQ_JUDGE", None)
         dev.free()
     # rows without bases or without qualities, where no criterion needs them: their counts are 0
-    dev = DevRows(codec, B, Q, lens)
+    dev = W.DevRows(codec, B, Q, lens)
     try:
         zb = np.zeros_like(B)
         for c2, args, ref in ((crit(min_len=50, min_mean_q=20, qual_q=10, max_lowq_pct=50), (dev.n, dev.L, None, dev.quals, dev.lens), (zb, Q)),
@@ -415,10 +395,10 @@ def check_host_refusals(codec):
     from repaq_amd import RfqError
     n, L = 40, 32
     B, Q, lens = random_rows(n, L, 10, codes=False)
-    dev = DevRows(codec, B, Q, lens)
+    dev = W.DevRows(codec, B, Q, lens)
     buf = codec.dev_put(b"\0" * 4096); b = buf.value
     try:
-        rows = dev.args()
+        rows = dev.judge_args()
 
         def at(p, k):
             return C.c_void_p(p.value + k)
@@ -469,7 +449,7 @@ def check_device_refusal(codec, label):
         row = dict(first=0, middle=n // 2, last=n - 1)[where]
         lens[row] = -1 if value == "negative" else L + 1
         lens[(row + 1) % n] = L                                              # (a good row beside it)
-        dev = DevRows(codec, B, Q, lens, shift=1)
+        dev = W.DevRows(codec, B, Q, lens, shift=1)
         try:
             for path in (None, "general"):
                 codec.set_option("RFQ_JUDGE", path)
@@ -531,7 +511,7 @@ def check_composition(codec):
     _, B, Q, lens, names = codec.text_rows_bytes(fq1, fq2, paired=PE_TWO_FILES, row_len=160, qual_offset=33)
     n = len(lens)
     assert n == 1200
-    dev = S.DevSel(codec, B, Q, lens, names)
+    dev = W.DevRows(codec, B, Q, lens, names)
     gk, gs, gl = W.Guarded(codec, n), W.Guarded(codec, 4 * n), W.Guarded(codec, 4 * n)
     bufs = []
     try:

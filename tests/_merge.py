@@ -10,7 +10,6 @@ import numpy as np
 import _adapter as A
 import _rows as W
 import _rows_enc as R
-import _select as S
 
 PAD_B, PAD_Q = 0xA7, 0x51
 PATHS = (None, "general")
@@ -85,12 +84,9 @@ def expected(B, Q, lens, names, insert, codes):
 
 
 # ---------------------------------------------------------------- calling
-class DevMerge(S.DevSel):
-    """rows, names (_select.DevSel) and the pairs' insert sizes in device memory"""
-    def __init__(self, codec, B, Q, lens, names, insert, shift=0, name_off=None):
-        super().__init__(codec, B, Q, lens, names, shift=shift, name_off=name_off)
-        r = codec.dev_put(np.ascontiguousarray(insert, np.int32).tobytes()); self.raw.append(r)
-        self.insert = r
+def dev_merge(codec, B, Q, lens, names, insert, shift=0, name_off=None):
+    """_rows.DevRows with the pairs' insert sizes as its extra input: dev.insert"""
+    return W.DevRows(codec, B, Q, lens, names, shift=shift, name_off=name_off, insert=(insert, np.int32))
 
 
 def out_len(ml, rule):
@@ -104,67 +100,36 @@ def result_of(r):
     return tuple(int(getattr(r, f)) for f in FIELDS)
 
 
-def call(codec, B, Q, lens, names, insert, codes, row_len=None, in_shift=0, out_shift=0, outputs="bqlno", dev=None, paths=PATHS, e=None):
-    """Per path one size query and one rfq_merge_rows into Guarded buffers of exactly the reported sizes, compared with expected(); both paths must write the
-    same bytes.  Returns (expected dict, bases, quals, raw bytes of every output body) of the last path."""
+def call(codec, B, Q, lens, names, insert, codes, row_len=None, in_shift=0, out_shift=0, outputs="bqlno", paths=PATHS, e=None):
+    """Per path one size query and one rfq_merge_rows into Guarded buffers of exactly the reported sizes (_rows.compact_into_guarded), compared with expected();
+    both paths must write the same bytes.  Returns (expected dict, bases, quals, raw bytes of every output body) of the last path."""
     e = e or expected(B, Q, lens, names, insert, codes)
-    own = dev is None
-    if own:
-        dev = DevMerge(codec, B, Q, lens, names, insert, shift=in_shift)
+    dev = dev_merge(codec, B, Q, lens, names, insert, shift=in_shift)
     if names is None:
         outputs = outputs.replace("n", "").replace("o", "")
     kw = dict(d_insert=dev.insert, codes=codes)
+    n = len(e["idx"])
+
+    def rows_differ(kind, g, wantr, bad):
+        j = int(bad[0]); k = int(e["idx"][j]); at = int(np.nonzero(g[j] != wantr[j])[0][0])
+        return "%s rows differ: %d of %d, first %d (pair %d: l1 %d, l2 %d, insert %d) at position %d: got %r, want %r" % (
+            kind, len(bad), n, j, k, lens[2 * k], lens[2 * k + 1], insert[k], at, bytes(g[j][at:at + 8]), bytes(wantr[j][at:at + 8]))
     raws = []
     try:
         for path in paths:
             codec.set_option("RFQ_MERGE", path)
-            what = "path %s:" % (path or "default")
-            gs = []
-            try:
-                q = codec.merge_rows(*dev.args(), **kw)
-                assert result_of(q) == e["result"], (what, result_of(q), e["result"])
-                n = len(e["idx"]); L = out_len(e["max_len"], row_len); nl = e["names_len"]
-                gb = W.Guarded(codec, n * L, shift=out_shift) if "b" in outputs else None
-                gq = W.Guarded(codec, n * L, shift=out_shift) if "q" in outputs else None
-                gl = W.Guarded(codec, 4 * n) if "l" in outputs else None
-                gn = W.Guarded(codec, nl, shift=out_shift) if "n" in outputs else None
-                go = W.Guarded(codec, 8 * (n + 1)) if "o" in outputs else None
-                gs = [g for g in (gb, gq, gl, gn, go) if g is not None]
-
-                def p(g):
-                    return g.ptr if g is not None else None
-                r = codec.merge_rows(*dev.args(), row_len=L, pad_base=PAD_B, pad_qual=PAD_Q, out_bases=p(gb), bases_cap=n * L if gb else 0, out_quals=p(gq),
-                                     quals_cap=n * L if gq else 0, out_lens=p(gl), lens_cap=n if gl else 0, out_names=p(gn), names_cap=nl if gn else 0,
-                                     out_name_off=p(go), off_cap=n + 1 if go else 0, **kw)
-                assert result_of(r) == e["result"], (what, result_of(r), e["result"])
-                assert all(g.guards_intact() for g in gs), what + " a guard around an output buffer was written"
-                raws.append([g.body() for g in gs])
-                gB = np.frombuffer(gb.body(), np.uint8).reshape(n, L) if gb else None
-                gQ = np.frombuffer(gq.body(), np.uint8).reshape(n, L) if gq else None
-                if gl:
-                    assert np.array_equal(np.frombuffer(gl.body(), np.int32), e["lens"]), what + " lens differ"
-                if go:
-                    want = np.concatenate([[0], np.cumsum([len(x) for x in e["names"]])]).astype(np.uint64)
-                    assert np.array_equal(np.frombuffer(go.body(), np.uint64), want), what + " name offsets differ"
-                if gn:
-                    assert gn.body() == b"".join(e["names"]), what + " the name blob differs"
-                for g, rows, pad, kind in ((gB, e["bases"], PAD_B, "base"), (gQ, e["quals"], PAD_Q, "quality")):
-                    if g is not None and n:
-                        wantr = S.padded(rows, L, pad)
-                        bad = np.nonzero((g != wantr).any(axis=1))[0]
-                        if len(bad):
-                            j = int(bad[0]); k = int(e["idx"][j]); at = int(np.nonzero(g[j] != wantr[j])[0][0])
-                            raise AssertionError("%s %s rows differ: %d of %d, first %d (pair %d: l1 %d, l2 %d, insert %d) at position %d: got %r, want %r" % (
-                                what, kind, len(bad), n, j, k, lens[2 * k], lens[2 * k + 1], insert[k], at, bytes(g[j][at:at + 8]), bytes(wantr[j][at:at + 8])))
-            finally:
-                for g in gs:
-                    g.free()
+            what = "path %s: " % (path or "default")
+            q = codec.merge_rows(*dev.args(), **kw)
+            assert result_of(q) == e["result"], (what, result_of(q), e["result"])
+            r, gB, gQ, _, raw = W.compact_into_guarded(codec, lambda **out: codec.merge_rows(*dev.args(), **out, **kw), e, out_len(e["max_len"], row_len),
+                                                       PAD_B, PAD_Q, outputs, out_shift, what, rows_differ)
+            assert result_of(r) == e["result"], (what, result_of(r), e["result"])
+            raws.append(raw)
         assert all(x == raws[0] for x in raws), "the two formulations wrote different bytes"
         return e, gB, gQ, raws[-1]
     finally:
         codec.set_option("RFQ_MERGE", None)
-        if own:
-            dev.free()
+        dev.free()
 
 
 # ---------------------------------------------------------------- making pairs
@@ -336,10 +301,10 @@ def check_fragments_result(F, insert, diff, e, gB):
 def check_fragments(codec):
     B, Q, lens, names, F = fragments()
     n = len(lens)
-    dev = A.DevRows(codec, B, lens)
+    dev = W.DevRows(codec, B, None, lens)
     gi, gd = W.Guarded(codec, 2 * n), W.Guarded(codec, 2 * n)
     try:
-        codec.adapter_rows(*dev.args(), codes=True, d_insert=gi.ptr, d_diff=gd.ptr, **FRAG_CRIT)
+        codec.adapter_rows(*dev.adapter_args(), codes=True, d_insert=gi.ptr, d_diff=gd.ptr, **FRAG_CRIT)
         insert = np.frombuffer(gi.body(), np.int32).copy(); diff = np.frombuffer(gd.body(), np.int32).copy()
     finally:
         dev.free(); gi.free(); gd.free()
@@ -379,7 +344,7 @@ def check_names(codec):
     e = call(codec, B, Q, lens, None, insert, False)[0]                                         # rows without names
     assert e["result"][2] == e["result"][4] == 0
     from repaq_amd import RfqError
-    dev = DevMerge(codec, B, Q, lens, None, insert)
+    dev = dev_merge(codec, B, Q, lens, None, insert)
     g = W.Guarded(codec, 4096)
     try:
         for kw in (dict(out_names=g.ptr, names_cap=4096), dict(out_name_off=g.ptr, off_cap=512)):
@@ -406,7 +371,7 @@ def check_outputs(codec):
         got = call(codec, B, Q, lens, names, insert, False, outputs=o, row_len="x16" if o in "bq" else None, e=e)[3]
         assert o in "bq" or got == [raw[k]], o                               # (the rows at another stride: compared inside call())
     n, nl, L = len(e["idx"]), e["names_len"], e["max_len"]
-    dev = DevMerge(codec, B, Q, lens, names, insert)
+    dev = dev_merge(codec, B, Q, lens, names, insert)
     g = dict(b=W.Guarded(codec, n * L), q=W.Guarded(codec, n * L), l=W.Guarded(codec, 4 * n), n=W.Guarded(codec, nl), o=W.Guarded(codec, 8 * (n + 1)))
     try:
         caps = dict(bases_cap=n * L, quals_cap=n * L, lens_cap=n, names_cap=nl, off_cap=n + 1)
@@ -436,7 +401,7 @@ def check_host_refusals(codec):
     from repaq_amd import RfqError
     npairs, L = 20, 16; n = 2 * npairs
     B, Q, lens, names, insert = random_pairs(npairs, L, 12, True)
-    dev = DevMerge(codec, B, Q, lens, names, insert)
+    dev = dev_merge(codec, B, Q, lens, names, insert)
     buf = codec.dev_put(b"\0" * (1 << 16)); b = buf.value
     try:
         M = codec.merge_rows; rows = dev.args(); ins = dict(d_insert=dev.insert)
@@ -502,7 +467,7 @@ def check_device_refusal(codec, label):
     else:
         assert insert[5] == -1
         lens[11] = L + 7; needle = "first such row: 11)"
-    dev = DevMerge(codec, B, Q, lens, names, insert, name_off=name_off)
+    dev = dev_merge(codec, B, Q, lens, names, insert, name_off=name_off)
     g = [W.Guarded(codec, npairs * 2 * L), W.Guarded(codec, npairs * 2 * L), W.Guarded(codec, 4 * npairs), W.Guarded(codec, dev.names_len), W.Guarded(codec, 8 * (npairs + 1))]
     try:
         args = list(dev.args()); args[6] += nl_delta
@@ -569,7 +534,7 @@ def check_composition(codec):
     merged, w1, w2, m, ea = compose_expected(t1, t2)
     _, B, Q, lens, names = codec.text_rows_bytes(b"".join(t1), b"".join(t2), paired=PE_TWO_FILES, row_len=160, qual_offset=33)
     n = len(lens)
-    dev = S.DevSel(codec, B, Q, lens, names)
+    dev = W.DevRows(codec, B, Q, lens, names)
     gi = W.Guarded(codec, 2 * n)
     bufs = []
     try:

@@ -83,6 +83,95 @@ class Guarded:
         self.codec.dev_free(self.raw)
 
 
+class DevRows:
+    """Rows in device memory as the rows calls take them: base rows, optionally quality rows (Q None: NULL), lengths, optionally names (None: rows without names;
+    name_off: other offsets than the names' own).  shift: bytes by which the row buffers and the name blob are moved off their 256-byte aligned start.  Every
+    buffer ends where its allocation's payload ends, so a read behind the last row shows under the sanitizer build.  extra: further inputs of the call, name =
+    (array or None, dtype) - each becomes the attribute `name`, a device pointer or None for a NULL argument (_select.dev_sel: keep, start, length; _merge.dev_merge:
+    insert).  put(): one more buffer, freed with the rest."""
+    def __init__(self, codec, B, Q, lens, names=None, shift=0, name_off=None, **extra):
+        self.codec = codec; self.n, self.L = B.shape; self.raw = []
+        self.bases = self.put(np.ascontiguousarray(B, np.uint8).tobytes(), shift)
+        self.quals = self.put(np.ascontiguousarray(Q, np.uint8).tobytes(), shift) if Q is not None else None
+        self.lens = self.put(np.ascontiguousarray(lens, np.int32).tobytes())
+        self.names = self.name_off = None; self.names_len = 0
+        if names is not None:
+            off = np.zeros(self.n + 1, np.uint64)
+            if self.n:
+                off[1:] = np.cumsum([len(x) for x in names])
+            if name_off is not None:
+                off = np.asarray(name_off, np.uint64)
+            blob = b"".join(names); self.names_len = len(blob)
+            self.names = self.put(blob, shift); self.name_off = self.put(off.tobytes())
+        for name, (v, dtype) in extra.items():
+            setattr(self, name, self.put(np.ascontiguousarray(v, dtype).tobytes()) if v is not None else None)
+
+    def put(self, data, shift=0):
+        r = self.codec.dev_put(b"\xEE" * shift + data); self.raw.append(r)
+        return C.c_void_p(r.value + shift)
+
+    def args(self):
+        """rfq_rows_in: what rfq_select_rows, rfq_merge_rows, rfq_rows_to_text and rfq_encode_rows take"""
+        return (self.n, self.L, self.bases, self.quals, self.lens, self.names, self.names_len, self.name_off)
+
+    def judge_args(self):
+        return (self.n, self.L, self.bases, self.quals, self.lens)
+
+    def adapter_args(self):
+        return (self.n, self.L, self.bases, self.lens)
+
+    def free(self):
+        for r in self.raw:
+            self.codec.dev_free(r)
+
+
+def padded(rows, L, pad):
+    out = np.full((len(rows), L), pad, np.uint8)
+    for j, r in enumerate(rows):
+        out[j, :len(r)] = np.frombuffer(r, np.uint8)
+    return out
+
+
+def compact_into_guarded(codec, call, e, L, pad_base, pad_qual, outputs="bqlno", out_shift=0, what="", rows_differ=None):
+    """The second call of a compacting call (rfq_select_rows, rfq_merge_rows) after its size query: call(**outputs and caps) writes into Guarded buffers of exactly
+    the sizes `e` (the caller's expected dict: idx, lens, bases, quals, names, names_len) gives at stride L; the guards, lens, name offsets, name blob and padded
+    rows are compared with `e`.  what: prefix of the failure messages; rows_differ(kind, got, want, bad rows) words the caller's own for rows.  Returns
+    (result, bases, quals, lens, raw) - an output not in `outputs` is not asked for and comes back as None; raw: the bytes of every output body."""
+    n, nl = len(e["idx"]), e["names_len"]
+    size = dict(b=n * L, q=n * L, l=4 * n, n=nl, o=8 * (n + 1))
+    g = {o: Guarded(codec, size[o], shift=out_shift if o in "bqn" else 0) for o in "bqlno" if o in outputs}
+
+    def p(o):
+        return g[o].ptr if o in g else None
+
+    def cap(o, entries):
+        return entries if o in g else 0
+    try:
+        r = call(row_len=L, pad_base=pad_base, pad_qual=pad_qual, out_bases=p("b"), bases_cap=cap("b", n * L), out_quals=p("q"), quals_cap=cap("q", n * L),
+                 out_lens=p("l"), lens_cap=cap("l", n), out_names=p("n"), names_cap=cap("n", nl), out_name_off=p("o"), off_cap=cap("o", n + 1))
+        assert all(x.guards_intact() for x in g.values()), what + "a guard around an output buffer was written"
+        body = {o: x.body() for o, x in g.items()}
+        gB = np.frombuffer(body["b"], np.uint8).reshape(n, L) if "b" in g else None
+        gQ = np.frombuffer(body["q"], np.uint8).reshape(n, L) if "q" in g else None
+        gL = np.frombuffer(body["l"], np.int32) if "l" in g else None
+        if gL is not None:
+            assert np.array_equal(gL, e["lens"]), what + "lens differ"
+        if "o" in g:
+            want = np.concatenate([[0], np.cumsum([len(x) for x in e["names"]])]).astype(np.uint64)
+            assert np.array_equal(np.frombuffer(body["o"], np.uint64), want), what + "name offsets differ"
+        if "n" in g:
+            assert body["n"] == b"".join(e["names"]), what + "the name blob differs"
+        for got, rows, pad, kind in ((gB, e["bases"], pad_base, "base"), (gQ, e["quals"], pad_qual, "quality")):
+            if got is not None and n:
+                want = padded(rows, L, pad)
+                bad = np.nonzero((got != want).any(axis=1))[0]
+                assert not len(bad), what + rows_differ(kind, got, want, bad)
+        return r, gB, gQ, gL, list(body.values())
+    finally:
+        for x in g.values():
+            x.free()
+
+
 def decode_rows_in_slices(codec, rfq: bytes, step: int, row_len: int, codes=False):
     """the streaming contract: `step` bytes at a time (has_header on the first call, final on the last, the unconsumed tail carried over);
     returns the concatenated (bases, quals, lens)"""

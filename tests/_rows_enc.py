@@ -76,36 +76,16 @@ def rows_of(fq1: bytes, fq2: bytes = b"", paired=O.SE, row_len=None, extra=0, co
     return B, Q, lens, [r[0] for r in recs]
 
 
-class DevRows:
-    """rows and names in device memory; shift: bytes by which the row buffers and the name blob are moved off their 256-byte aligned start"""
-    def __init__(self, codec, B, Q, lens, names, shift=0, name_off=None):
-        self.codec = codec; n, L = B.shape
-        off = np.zeros(n + 1, np.uint64)
-        if n:
-            off[1:] = np.cumsum([len(x) for x in names])
-        if name_off is not None:
-            off = np.asarray(name_off, np.uint64)
-        blob = b"".join(names)
-        lens = np.ascontiguousarray(lens, np.int32)
-        self.raw = [codec.dev_put(b"\xEE" * shift + x) for x in (B.tobytes(), Q.tobytes(), blob)] + [codec.dev_put(lens.tobytes()), codec.dev_put(off.tobytes())]
-        p = [C.c_void_p(r.value + shift) for r in self.raw[:3]]
-        self.args = (n, L, p[0], p[1], self.raw[3], p[2], len(blob), self.raw[4])
-
-    def free(self):
-        for r in self.raw:
-            self.codec.dev_free(r)
-
-
-def text_of(codec, dev: DevRows, paired, want1: bytes, want2: bytes = b"", **kw):
+def text_of(codec, dev, paired, want1: bytes, want2: bytes = b"", **kw):
     """rfq_rows_to_text into guarded caller buffers of exactly the texts' sizes: the size query, the texts, the guards"""
     two = paired == O.PE_TWO_FILES
-    q = codec.rows_to_text(*dev.args, paired=paired, size_only=True, **kw)
+    q = codec.rows_to_text(*dev.args(), paired=paired, size_only=True, **kw)
     assert (q.n1, q.n2) == (len(want1), len(want2) if two else 0), ((q.n1, q.n2), (len(want1), len(want2)))
-    assert q.n_reads == dev.args[0]
+    assert q.n_reads == dev.args()[0]
     g1 = W.Guarded(codec, len(want1)); g2 = W.Guarded(codec, len(want2)) if two else None
     try:
         assert g1.ptr.value % 16 == 0
-        r = codec.rows_to_text(*dev.args, paired=paired, d_out1=g1.ptr, cap1=len(want1), d_out2=g2.ptr if two else None, cap2=len(want2) if two else 0, **kw)
+        r = codec.rows_to_text(*dev.args(), paired=paired, d_out1=g1.ptr, cap1=len(want1), d_out2=g2.ptr if two else None, cap2=len(want2) if two else 0, **kw)
         assert (r.n1, r.n2) == (q.n1, q.n2) and r.n_bases == q.n_bases
         got1 = g1.body(); got2 = g2.body() if two else b""
         assert got1 == want1, "text 1 differs at byte %d of %d" % (next((i for i, (a, b) in enumerate(zip(got1, want1)) if a != b), -1), len(want1))
@@ -130,7 +110,7 @@ def check_text_variants(codec, label):
         rows = rows_of(fq1, fq2, paired, extra=extra, codes=codes, qual_offset=qoff, pad=(0xA7 + ran) & 0xFF)
         if rows is None:
             continue
-        dev = DevRows(codec, *rows, shift=shift)
+        dev = W.DevRows(codec, *rows, shift=shift)
         try:
             text_of(codec, dev, paired, fq1, fq2, codes=codes, qual_offset=qoff)
         finally:
@@ -187,7 +167,7 @@ def long_read():
 def check_shape(codec, text, chunk_bases=20000):
     """a handmade SE text: rows -> the text (both base modes, both load paths) and -> the oracle's image"""
     for codes, extra, shift in ((False, 0, 0), (True, "x16", 0), (True, 1, 1)):
-        dev = DevRows(codec, *rows_of(text, codes=codes, extra=extra), shift=shift)
+        dev = W.DevRows(codec, *rows_of(text, codes=codes, extra=extra), shift=shift)
         try:
             text_of(codec, dev, O.SE, text, codes=codes)
         finally:
@@ -213,17 +193,17 @@ def check_sizes_and_short_caps(codec, label):
     from repaq_amd import RfqError
     _, fq1, fq2, paired, _ = BY_LABEL[label]
     two = paired == O.PE_TWO_FILES
-    dev = DevRows(codec, *rows_of(fq1, fq2, paired))
+    dev = W.DevRows(codec, *rows_of(fq1, fq2, paired))
     g1 = W.Guarded(codec, len(fq1)); g2 = W.Guarded(codec, max(len(fq2), 1))
     try:
-        q = codec.rows_to_text(*dev.args, paired=paired, size_only=True)
+        q = codec.rows_to_text(*dev.args(), paired=paired, size_only=True)
         assert (q.n1, q.n2) == (len(fq1), len(fq2)) and q.d_fq1 is None
         assert q.n_bases == sum(len(x) for t in (fq1, fq2) for x in lines_of(t)[1::4])
         before = (g1.body(), g2.body())
         shorts = [(len(fq1) - 1, len(fq2))] + ([(len(fq1), len(fq2) - 1)] if two else [])
         for cap1, cap2 in shorts:
             with pytest_raises(RfqError) as ei:
-                codec.rows_to_text(*dev.args, paired=paired, d_out1=g1.ptr, cap1=cap1, d_out2=g2.ptr if two else None, cap2=cap2 if two else 0)
+                codec.rows_to_text(*dev.args(), paired=paired, d_out1=g1.ptr, cap1=cap1, d_out2=g2.ptr if two else None, cap2=cap2 if two else 0)
             assert ei.value.code == -8 and "need %d" % len(fq1) in ei.value.message, ei.value
             assert (g1.body(), g2.body()) == before and g1.guards_intact() and g2.guards_intact()
         text_of(codec, dev, paired, fq1, fq2)
@@ -286,9 +266,9 @@ def check_refusal(codec, label, through_encoder):
     name_off = None
     if off == "swap":
         name_off = np.concatenate([[0], np.cumsum([len(x) for x in mn])]).astype(np.uint64); name_off[[4, 5]] = name_off[[5, 4]]
-    bad = DevRows(codec, mB, mQ, ml, mn, name_off=name_off); good = DevRows(codec, B, Q, lens, names)
+    bad = W.DevRows(codec, mB, mQ, ml, mn, name_off=name_off); good = W.DevRows(codec, B, Q, lens, names)
     try:
-        args = list(bad.args); args[6] += dlen
+        args = list(bad.args()); args[6] += dlen
         with pytest_raises(RfqError) as ei:
             if through_encoder:
                 codec.clearHeader(); codec.encode_rows(*args, codes=codes)
@@ -305,14 +285,14 @@ def check_refusal(codec, label, through_encoder):
 def check_argument_refusals(codec):
     from repaq_amd import RfqError
     text, (B, Q, lens, names) = _base_rows(False)
-    odd = DevRows(codec, B[:39], Q[:39], lens[:39], names[:39]); good = DevRows(codec, B, Q, lens, names)
+    odd = W.DevRows(codec, B[:39], Q[:39], lens[:39], names[:39]); good = W.DevRows(codec, B, Q, lens, names)
     try:
-        for what, call in (("odd rows, two files", lambda: codec.rows_to_text(*odd.args, paired=O.PE_TWO_FILES)),
-                           ("odd rows, two files, encoder", lambda: codec.encode_rows(*odd.args, paired=O.PE_TWO_FILES)),
-                           ("neither final nor flush_all", lambda: codec.encode_rows(*good.args, final=False, flush_all=False)),
-                           ("a text pointer in enc", lambda: codec.encode_rows(*good.args, d_fq1=good.args[2])),
-                           ("row_len 0", lambda: codec.rows_to_text(good.args[0], 0, *good.args[2:])),
-                           ("misaligned output", lambda: codec.rows_to_text(*good.args, d_out1=C.c_void_p(good.raw[0].value + 8), cap1=1 << 20))):
+        for what, call in (("odd rows, two files", lambda: codec.rows_to_text(*odd.args(), paired=O.PE_TWO_FILES)),
+                           ("odd rows, two files, encoder", lambda: codec.encode_rows(*odd.args(), paired=O.PE_TWO_FILES)),
+                           ("neither final nor flush_all", lambda: codec.encode_rows(*good.args(), final=False, flush_all=False)),
+                           ("a text pointer in enc", lambda: codec.encode_rows(*good.args(), d_fq1=good.args()[2])),
+                           ("row_len 0", lambda: codec.rows_to_text(good.args()[0], 0, *good.args()[2:])),
+                           ("misaligned output", lambda: codec.rows_to_text(*good.args(), d_out1=C.c_void_p(good.bases.value + 8), cap1=1 << 20))):
             codec.clearHeader()
             with pytest_raises(RfqError) as ei:
                 call()

@@ -36,46 +36,14 @@ def expected(B, Q, lens, names, keep=None, start=None, length=None, pairs=False,
     return e
 
 
-def padded(rows, L, pad):
-    out = np.full((len(rows), L), pad, np.uint8)
-    for j, r in enumerate(rows):
-        out[j, :len(r)] = np.frombuffer(r, np.uint8)
-    return out
+def dev_sel(codec, B, Q, lens, names, keep=None, start=None, length=None, shift=0, name_off=None):
+    """_rows.DevRows with a selection as its extra inputs: dev.keep / dev.start / dev.length (None: the pointer is NULL)"""
+    return W.DevRows(codec, B, Q, lens, names, shift=shift, name_off=name_off, keep=(keep, np.uint8), start=(start, np.int32), length=(length, np.int32))
 
 
-class DevSel:
-    """rows, names and a selection in device memory; shift: bytes by which the row buffers and the name blob are moved off their 256-byte aligned start"""
-    def __init__(self, codec, B, Q, lens, names, keep=None, start=None, length=None, shift=0, name_off=None):
-        self.codec = codec; n, L = B.shape; self.n, self.L = n, L
-        self.raw = []
-
-        def put(data, sh=0):
-            r = codec.dev_put(b"\xEE" * sh + data); self.raw.append(r)
-            return C.c_void_p(r.value + sh)
-        self.bases = put(np.ascontiguousarray(B, np.uint8).tobytes(), shift); self.quals = put(np.ascontiguousarray(Q, np.uint8).tobytes(), shift)
-        self.lens = put(np.ascontiguousarray(lens, np.int32).tobytes())
-        self.names = self.name_off = None; self.names_len = 0
-        if names is not None:
-            off = np.zeros(n + 1, np.uint64)
-            if n:
-                off[1:] = np.cumsum([len(x) for x in names])
-            if name_off is not None:
-                off = np.asarray(name_off, np.uint64)
-            blob = b"".join(names); self.names_len = len(blob)
-            self.names = put(blob, shift); self.name_off = put(off.tobytes())
-        self.keep = put(np.ascontiguousarray(keep, np.uint8).tobytes()) if keep is not None else None
-        self.start = put(np.ascontiguousarray(start, np.int32).tobytes()) if start is not None else None
-        self.length = put(np.ascontiguousarray(length, np.int32).tobytes()) if length is not None else None
-
-    def args(self):
-        return (self.n, self.L, self.bases, self.quals, self.lens, self.names, self.names_len, self.name_off)
-
-    def sel(self):
-        return dict(d_keep=self.keep, d_start=self.start, d_len=self.length)
-
-    def free(self):
-        for r in self.raw:
-            self.codec.dev_free(r)
+def sel_of(dev):
+    """the selection of a dev_sel() as select_rows takes it"""
+    return dict(d_keep=dev.keep, d_start=dev.start, d_len=dev.length)
 
 
 def out_len(ml, rule):
@@ -88,64 +56,32 @@ def out_len(ml, rule):
 
 
 def call(codec, B, Q, lens, names, keep=None, start=None, length=None, pairs=False, min_len=1, row_len=None, pad_base=PAD_B, pad_qual=PAD_Q,
-         in_shift=0, out_shift=0, outputs="bqlno", dev=None):
-    """One size query and one rfq_select_rows into Guarded buffers of exactly the reported sizes, compared with expected().  Returns
+         in_shift=0, out_shift=0, outputs="bqlno"):
+    """One size query and one rfq_select_rows into Guarded buffers of exactly the reported sizes (_rows.compact_into_guarded), compared with expected().  Returns
     (result, bases, quals, lens, names, raw) - an output not in `outputs` is not asked for and comes back as None; raw: the bytes of every output body."""
     e = expected(B, Q, lens, names, keep, start, length, pairs, min_len)
-    own = dev is None
-    if own:
-        dev = DevSel(codec, B, Q, lens, names, keep, start, length, shift=in_shift)
+    dev = dev_sel(codec, B, Q, lens, names, keep, start, length, shift=in_shift)
     if names is None:
         outputs = outputs.replace("n", "").replace("o", "")
-    gs = []
     try:
-        kw = dict(pairs=pairs, min_len=min_len, **dev.sel())
+        kw = dict(pairs=pairs, min_len=min_len, **sel_of(dev))
         q = codec.select_rows(*dev.args(), **kw)
         n = len(e["idx"])
         got = (q.n_rows, q.n_bases, q.names_len, q.max_len, q.max_name, q.n_in, q.dropped_mask, q.dropped_short, q.dropped_mate)
         want = (n, e["n_bases"], e["names_len"], e["max_len"], e["max_name"], e["n_in"], e["mask"], e["short"], e["mate"])
         assert got == want, (got, want)
         assert q.n_in == q.n_rows + q.dropped_mask + q.dropped_short + q.dropped_mate
-        L = out_len(e["max_len"], row_len); nl = e["names_len"]
-        gb = W.Guarded(codec, n * L, shift=out_shift) if "b" in outputs else None
-        gq = W.Guarded(codec, n * L, shift=out_shift) if "q" in outputs else None
-        gl = W.Guarded(codec, 4 * n) if "l" in outputs else None
-        gn = W.Guarded(codec, nl, shift=out_shift) if "n" in outputs else None
-        go = W.Guarded(codec, 8 * (n + 1)) if "o" in outputs else None
-        gs = [g for g in (gb, gq, gl, gn, go) if g is not None]
 
-        def p(g):
-            return g.ptr if g is not None else None
-        r = codec.select_rows(*dev.args(), row_len=L, pad_base=pad_base, pad_qual=pad_qual, out_bases=p(gb), bases_cap=n * L if gb else 0,
-                              out_quals=p(gq), quals_cap=n * L if gq else 0, out_lens=p(gl), lens_cap=n if gl else 0, out_names=p(gn), names_cap=nl if gn else 0,
-                              out_name_off=p(go), off_cap=n + 1 if go else 0, **kw)
+        def rows_differ(kind, g, wantr, bad):
+            return "%s rows differ: %d of %d, first %d (input row %d): %r / %r" % (kind, len(bad), n, bad[0], e["idx"][bad[0]], bytes(g[bad[0]][:48]),
+                                                                                   bytes(wantr[bad[0]][:48]))
+        r, gB, gQ, gL, raw = W.compact_into_guarded(codec, lambda **out: codec.select_rows(*dev.args(), **out, **kw), e, out_len(e["max_len"], row_len),
+                                                    pad_base, pad_qual, outputs, out_shift, rows_differ=rows_differ)
         for f in ("n_rows", "n_bases", "names_len", "max_len", "max_name", "n_in", "dropped_mask", "dropped_short", "dropped_mate"):
             assert getattr(r, f) == getattr(q, f), (f, getattr(r, f), getattr(q, f))
-        assert all(g.guards_intact() for g in gs), "a guard around an output buffer was written"
-        raw = [g.body() for g in gs]
-        gB = np.frombuffer(gb.body(), np.uint8).reshape(n, L) if gb else None
-        gQ = np.frombuffer(gq.body(), np.uint8).reshape(n, L) if gq else None
-        gL = np.frombuffer(gl.body(), np.int32) if gl else None
-        off = np.frombuffer(go.body(), np.uint64) if go else None
-        blob = gn.body() if gn else None
-        if gL is not None:
-            assert np.array_equal(gL, e["lens"])
-        if off is not None:
-            assert np.array_equal(off, np.concatenate([[0], np.cumsum([len(x) for x in e["names"]])]).astype(np.uint64))
-        if blob is not None:
-            assert blob == b"".join(e["names"]), "the name blob differs"
-        for g, rows, pad, what in ((gB, e["bases"], pad_base, "base"), (gQ, e["quals"], pad_qual, "quality")):
-            if g is not None and n:
-                wantr = padded(rows, L, pad)
-                bad = np.nonzero((g != wantr).any(axis=1))[0]
-                assert not len(bad), "%s rows differ: %d of %d, first %d (input row %d): %r / %r" % (what, len(bad), n, bad[0], e["idx"][bad[0]], bytes(g[bad[0]][:48]),
-                                                                                                 bytes(wantr[bad[0]][:48]))
         return r, gB, gQ, gL, e["names"], raw
     finally:
-        if own:
-            dev.free()
-        for g in gs:
-            g.free()
+        dev.free()
 
 
 def small_rows(n, L, seed, name_lens=(1, 2, 3), full=False):
@@ -295,7 +231,7 @@ def check_no_names_and_each_output_alone(codec):
     for o in "bqlno":
         call(codec, B, Q, lens, names, keep=keep, start=start, outputs=o, row_len="x16")
     from repaq_amd import RfqError
-    dev = DevSel(codec, B, Q, lens, None)
+    dev = dev_sel(codec, B, Q, lens, None)
     g = W.Guarded(codec, 4096)
     try:
         for kw in (dict(out_names=g.ptr, names_cap=4096), dict(out_name_off=g.ptr, off_cap=512)):
@@ -320,7 +256,7 @@ def check_short_caps(codec):
     e = expected(B, Q, lens, names, keep)
     n, nl, L = len(e["idx"]), e["names_len"], e["max_len"]
     assert L == 37
-    dev = DevSel(codec, B, Q, lens, names, keep)
+    dev = dev_sel(codec, B, Q, lens, names, keep)
     g = dict(b=W.Guarded(codec, n * L), q=W.Guarded(codec, n * L), l=W.Guarded(codec, 4 * n), n=W.Guarded(codec, nl), o=W.Guarded(codec, 8 * (n + 1)))
     try:
         caps = dict(bases_cap=n * L, quals_cap=n * L, lens_cap=n, names_cap=nl, off_cap=n + 1)
@@ -329,11 +265,11 @@ def check_short_caps(codec):
         for short in list(caps) + ["row_len"]:
             kw = dict(caps, row_len=L); kw[short] -= 1
             with R.pytest_raises(RfqError) as ei:
-                codec.select_rows(*dev.args(), **dev.sel(), **ptrs, **kw)
+                codec.select_rows(*dev.args(), **sel_of(dev), **ptrs, **kw)
             assert ei.value.code == -8 and "need" in ei.value.message, (short, ei.value)
             assert all(v.body() == before[k] and v.guards_intact() for k, v in g.items()), short
             _good(codec)
-        r = codec.select_rows(*dev.args(), **dev.sel(), **ptrs, row_len=L, **caps)
+        r = codec.select_rows(*dev.args(), **sel_of(dev), **ptrs, row_len=L, **caps)
         assert r.n_rows == n and g["n"].body() == b"".join(e["names"]) and all(v.guards_intact() for v in g.values())
     finally:
         dev.free()
@@ -379,7 +315,7 @@ def check_device_refusal(codec, label):
         name_off = np.concatenate([[0], np.cumsum([len(x) for x in names])]).astype(np.uint64); name_off[[12, 13]] = name_off[[13, 12]]
     if m.get("name_off") == "past":
         nl_delta = -1
-    dev = DevSel(codec, B, Q, lens, names, keep, start, None if ("length" in m and m["length"] is None) else length, name_off=name_off)
+    dev = dev_sel(codec, B, Q, lens, names, keep, start, None if ("length" in m and m["length"] is None) else length, name_off=name_off)
     g = [W.Guarded(codec, n * L), W.Guarded(codec, n * L), W.Guarded(codec, 4 * n), W.Guarded(codec, dev.names_len), W.Guarded(codec, 8 * (n + 1))]
     try:
         args = list(dev.args()); args[6] += nl_delta
@@ -388,7 +324,7 @@ def check_device_refusal(codec, label):
             out = {} if query else dict(row_len=L, out_bases=g[0].ptr, bases_cap=n * L, out_quals=g[1].ptr, quals_cap=n * L, out_lens=g[2].ptr, lens_cap=n,
                                         out_names=g[3].ptr, names_cap=dev.names_len, out_name_off=g[4].ptr, off_cap=n + 1)
             with R.pytest_raises(RfqError) as ei:
-                codec.select_rows(*args, **dev.sel(), **out)
+                codec.select_rows(*args, **sel_of(dev), **out)
             assert ei.value.code == -3 and "first such row: %d)" % row in ei.value.message, (label, ei.value)
             assert [x.body() for x in g] == before and all(x.guards_intact() for x in g)
         _good(codec)
@@ -402,8 +338,8 @@ def check_host_refusals(codec):
     from repaq_amd import RfqError
     n, L = 40, 16
     B, Q, lens, names = small_rows(n, L, seed=12)
-    dev = DevSel(codec, B, Q, lens, names, start=np.zeros(n, np.int32), length=lens)
-    odd = DevSel(codec, B[:39], Q[:39], lens[:39], names[:39])
+    dev = dev_sel(codec, B, Q, lens, names, start=np.zeros(n, np.int32), length=lens)
+    odd = dev_sel(codec, B[:39], Q[:39], lens[:39], names[:39])
     buf = codec.dev_put(b"\0" * (1 << 16)); b = buf.value
     try:
         full = dict(row_len=L, out_bases=C.c_void_p(b), bases_cap=n * L)

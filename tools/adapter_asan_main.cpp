@@ -4,16 +4,10 @@
 //   0 / 1 / 7 / 15, both base modes, the default path and RFQ_ADAPTER=general, each output alone and none - with rows in allocations that end where the rows end
 //   and outputs of exactly their size, compared with a host loop written from include/rfq_hip.h; then every refusal, each followed by a good call.
 //   Anything unexpected is an error (exit 1).
-#include "../include/rfq_hip.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+#include "asan_common.h"
 #include <algorithm>
 #include <string>
 #include <vector>
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 16); }
 
 static const char AD1[] = "AGATCGGAAGAGC", AD2[] = "CTGTCTCTTATAC";
 struct Rows { uint32_t n = 0, L = 1; int codes = 0; std::vector<uint8_t> B; std::vector<int32_t> lens; };
@@ -47,14 +41,6 @@ static Rows make_rows(uint32_t pairs, uint32_t L, int codes) {
     }
     return r;
 }
-// a device buffer holding `data` `shift` bytes into its allocation, which ends with the data
-struct Dev { rfq_ctx* c; void* raw = nullptr; uint8_t* p = nullptr;
-    Dev(rfq_ctx* ctx, const void* data, size_t n, size_t shift = 0) : c(ctx) {
-        if (rfq_dev_malloc(c, &raw, n + shift)) { fprintf(stderr, "rfq_dev_malloc failed\n"); exit(1); }
-        p = (uint8_t*)raw + shift; if (n && data) rfq_copy_h2d(c, p, data, n); }
-    ~Dev() { rfq_dev_free(c, raw); } };
-
-static int fail(const char* what, const char* why) { fprintf(stderr, "%s: %s\n", what, why); return 1; }
 
 struct Ref { std::vector<int32_t> len, insert, diff; std::vector<uint8_t> how; std::vector<uint64_t> hist; rfq_adapter_rows_result s; };
 // the rules of include/rfq_hip.h as plain loops
@@ -112,8 +98,7 @@ static int run(rfq_ctx* ctx, const char* what, const Rows& r, rfq_adapter_rows_a
     if (!c.hist_len) outs &= ~16;
     Dev db(ctx, r.B.data(), r.B.size(), shift), dl(ctx, r.lens.data(), n * 4ull);
     Dev ol(ctx, nullptr, n * 4ull), oh(ctx, nullptr, n), oi(ctx, nullptr, np * 4ull), od(ctx, nullptr, np * 4ull), oH(ctx, nullptr, c.hist_len * 8ull);
-    rfq_rows_in in; memset(&in, 0, sizeof in);
-    in.n_rows = n; in.row_len = r.L; in.base_mode = r.codes ? RFQ_ROWS_CODE : RFQ_ROWS_ASCII; in.d_bases = db.p; in.d_lens = (const int32_t*)dl.p;
+    const rfq_rows_in in = rows_in(n, r.L, r.codes, db, nullptr, dl);
     c.d_len = (outs & 1) ? (int32_t*)ol.p : nullptr; c.d_how = (outs & 2) ? oh.p : nullptr; c.d_insert = (outs & 4) ? (int32_t*)oi.p : nullptr;
     c.d_diff = (outs & 8) ? (int32_t*)od.p : nullptr; c.d_insert_hist = (outs & 16) ? (uint64_t*)oH.p : nullptr;
     rfq_adapter_rows_result g;
@@ -162,7 +147,7 @@ int main() {
         const Rows r = make_rows(20, 32, 0);
         std::vector<int32_t> lp = r.lens; lp.push_back(0);                   // (a word more: the misaligned d_lens stays inside it)
         Dev db(ctx, r.B.data(), r.B.size()), dl(ctx, lp.data(), 160 + 4), out(ctx, nullptr, 8192);
-        rfq_rows_in in; memset(&in, 0, sizeof in); in.n_rows = 40; in.row_len = 32; in.d_bases = db.p; in.d_lens = (const int32_t*)dl.p;
+        const rfq_rows_in in = rows_in(40, 32, 0, db, nullptr, dl);
         const rfq_adapter_rows_args both = crit(2, 32); rfq_adapter_rows_args single = crit(1, 32), c; rfq_rows_in x;
         const std::string long_ad(65, 'A');
 #define REFUSED(WHAT, IN, C, NEEDLE) { bad |= refused(ctx, WHAT, IN, C, NEEDLE); host_refusals++; }

@@ -4,15 +4,9 @@
 //   shifts 0 / 1 / 7 / 15, both base modes, the default path and RFQ_JUDGE=general, each output alone and none - with rows in allocations that end where the rows
 //   end and outputs of exactly n_rows entries, compared with a host reference written from include/rfq_hip.h; then every refusal, each followed by a good call.
 //   Anything unexpected is an error (exit 1).
-#include "../include/rfq_hip.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+#include "asan_common.h"
 #include <algorithm>
 #include <vector>
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 16); }
 
 struct Rows { uint32_t n = 0, L = 1; int codes = 0; std::vector<uint8_t> B, Q; std::vector<int32_t> lens; };
 // lengths 0 .. L, bases ACGTN (either case in ASCII mode) with G tails, scores that rise towards the middle of a read; noise behind the reads
@@ -34,14 +28,6 @@ static Rows make_rows(uint32_t n, uint32_t L, int codes) {
     }
     return r;
 }
-// a device buffer holding `data` `shift` bytes into its allocation, which ends with the data
-struct Dev { rfq_ctx* c; void* raw = nullptr; uint8_t* p = nullptr;
-    Dev(rfq_ctx* ctx, const void* data, size_t n, size_t shift = 0) : c(ctx) {
-        if (rfq_dev_malloc(c, &raw, n + shift)) { fprintf(stderr, "rfq_dev_malloc failed\n"); exit(1); }
-        p = (uint8_t*)raw + shift; if (n && data) rfq_copy_h2d(c, p, data, n); }
-    ~Dev() { rfq_dev_free(c, raw); } };
-
-static int fail(const char* what, const char* why) { fprintf(stderr, "%s: %s\n", what, why); return 1; }
 
 struct Ref { std::vector<uint8_t> keep, why; std::vector<int32_t> start, len; std::vector<uint32_t> met; rfq_judge_rows_result s; };
 static Ref reference(const Rows& r, const rfq_judge_rows_args& c) {
@@ -96,8 +82,7 @@ static int run(rfq_ctx* ctx, const char* what, const Rows& r, rfq_judge_rows_arg
     const uint32_t n = r.n; const Ref e = reference(r, c);
     Dev db(ctx, r.B.data(), r.B.size(), shift), dq(ctx, r.Q.data(), r.Q.size(), shift), dl(ctx, r.lens.data(), n * 4ull);
     Dev ok(ctx, nullptr, n), os(ctx, nullptr, n * 4ull), ol(ctx, nullptr, n * 4ull), ow(ctx, nullptr, n), om(ctx, nullptr, n * 16ull);
-    rfq_rows_in in; memset(&in, 0, sizeof in);
-    in.n_rows = n; in.row_len = r.L; in.base_mode = r.codes ? RFQ_ROWS_CODE : RFQ_ROWS_ASCII; in.d_bases = db.p; in.d_quals = dq.p; in.d_lens = (const int32_t*)dl.p;
+    const rfq_rows_in in = rows_in(n, r.L, r.codes, db, &dq, dl);
     c.d_keep = (outs & 1) ? ok.p : nullptr; c.d_start = (outs & 2) ? (int32_t*)os.p : nullptr; c.d_len = (outs & 4) ? (int32_t*)ol.p : nullptr;
     c.d_why = (outs & 8) ? ow.p : nullptr; c.d_metrics = (outs & 16) ? (uint32_t*)om.p : nullptr;
     rfq_judge_rows_result g;
@@ -150,7 +135,7 @@ int main() {
         const Rows r = make_rows(40, 32, 0);
         std::vector<int32_t> lp = r.lens; lp.push_back(0);                   // (a word more: the misaligned d_lens stays inside it)
         Dev db(ctx, r.B.data(), r.B.size()), dq(ctx, r.Q.data(), r.Q.size()), dl(ctx, lp.data(), 160 + 4), out(ctx, nullptr, 4096);
-        rfq_rows_in in; memset(&in, 0, sizeof in); in.n_rows = 40; in.row_len = 32; in.d_bases = db.p; in.d_quals = dq.p; in.d_lens = (const int32_t*)dl.p;
+        const rfq_rows_in in = rows_in(40, 32, 0, db, &dq, dl);
         rfq_judge_rows_args c; rfq_rows_in x;
         c = crit(); c.cut_flags = 8; c.cut_window = 4; bad |= refused(ctx, "unknown cut_flags bits", in, c, "cut_flags");
         c = crit(); c.cut_flags = 1; bad |= refused(ctx, "cut_window 0", in, c, "cut_window");

@@ -4,16 +4,10 @@
 //   strides, the default path and RFQ_MERGE=general - and every insert of its seven (l1, l2), with rows in allocations that end where the rows end and outputs of
 //   exactly their size, compared with a host loop written from include/rfq_hip.h; then every refusal, each followed by a good call.
 //   Anything unexpected is an error (exit 1).
-#include "../include/rfq_hip.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+#include "asan_common.h"
 #include <algorithm>
 #include <string>
 #include <vector>
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 16); }
 
 struct Rows { uint32_t n = 0, L = 1; int codes = 0; std::vector<uint8_t> B, Q, names; std::vector<int32_t> lens, insert; std::vector<uint64_t> off; };
 static uint32_t cls_of(uint8_t b, int codes) {
@@ -49,14 +43,6 @@ static Rows make_rows(uint32_t pairs, uint32_t L, int codes, uint32_t l1 = 0, ui
     }
     return r;
 }
-// a device buffer holding `data` `shift` bytes into its allocation, which ends with the data
-struct Dev { rfq_ctx* c; void* raw = nullptr; uint8_t* p = nullptr;
-    Dev(rfq_ctx* ctx, const void* data, size_t n, size_t shift = 0) : c(ctx) {
-        if (rfq_dev_malloc(c, &raw, n + shift)) { fprintf(stderr, "rfq_dev_malloc failed\n"); exit(1); }
-        p = (uint8_t*)raw + shift; if (n && data) rfq_copy_h2d(c, p, data, n); }
-    ~Dev() { rfq_dev_free(c, raw); } };
-
-static int fail(const char* what, const char* why) { fprintf(stderr, "%s: %s\n", what, why); return 1; }
 
 struct Ref { std::vector<uint8_t> B, Q, names; std::vector<int32_t> lens; std::vector<uint64_t> off; rfq_merge_rows_result s; };
 // the rules of include/rfq_hip.h as plain loops; the rows at stride L_out, padded
@@ -92,8 +78,7 @@ static Ref reference(const Rows& r, uint32_t L_out, uint8_t pad_b, uint8_t pad_q
 }
 
 static rfq_rows_in rows_in(const Rows& r, const Dev& b, const Dev& q, const Dev& l, const Dev& nm, const Dev& off) {
-    rfq_rows_in in; memset(&in, 0, sizeof in);
-    in.n_rows = r.n; in.row_len = r.L; in.base_mode = r.codes ? RFQ_ROWS_CODE : RFQ_ROWS_ASCII; in.d_bases = b.p; in.d_quals = q.p; in.d_lens = (const int32_t*)l.p;
+    rfq_rows_in in = rows_in(r.n, r.L, r.codes, b, &q, l);
     in.d_names = nm.p; in.names_len = r.names.size(); in.d_name_off = (const uint64_t*)off.p;
     return in;
 }

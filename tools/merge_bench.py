@@ -31,7 +31,7 @@ def main():
     import numpy as np
     import torch
     import _merge as M
-    import _select as S
+    import _rows as W
     from adapter_bench import make_rows
     from repaq_amd import RfqCodec
     from repaq_amd.tensors import merge_pairs, select_rows
@@ -51,7 +51,7 @@ def main():
     e = M.expected(*(head[k].cpu().numpy() for k in ("bases", "quals", "lens")), None, insert[:nc].cpu().numpy(), True)
     assert got["summary"] == dict(zip(M.FIELDS, e["result"])), (got["summary"], e["result"])
     for k, pad in (("bases", 255), ("quals", 255)):
-        assert np.array_equal(got["merged"][k].cpu().numpy(), S.padded(e[k], args.out_row_len, pad)), k
+        assert np.array_equal(got["merged"][k].cpu().numpy(), W.padded(e[k], args.out_row_len, pad)), k
     merged = insert >= 0
     moved_merge = int((2 * (lens.view(-1, 2).sum(1)[merged].sum()) + 2 * insert[merged].sum()).item())
     moved_select = 2 * int(lens.sum().item()) + 2 * n * L                    # (bases and scores: the reads read, whole rows written)

@@ -4,14 +4,9 @@
 //   patterns over 0 .. 2049 rows, a scan of 16385 rows, pairs and min_len, names at every residue, a name longer than a tile, rows without names - into caller buffers
 //   of exactly the reported sizes (every allocation ends where its data ends), compared with a host reference; then the refusals, each followed by a good call.
 //   Anything unexpected is an error (exit 1).
-#include "../include/rfq_hip.h"
-#include <cstdio>
-#include <cstring>
+#include "asan_common.h"
 #include <string>
 #include <vector>
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 16); }
 
 struct Rows {
     uint32_t n = 0, L = 1; std::vector<uint8_t> B, Q; std::vector<int32_t> lens; std::vector<std::string> names; bool named = true;
@@ -24,14 +19,6 @@ static Rows make_rows(uint32_t n, uint32_t L, bool full, uint32_t name_mod) {
     for (uint32_t i = 0; i < n; i++) { r.lens[i] = full ? (int32_t)L : 1 + (int32_t)(rnd() % L); r.names[i] = std::string(1 + (i * 7 + i / 40) % name_mod, (char)('a' + i % 26)); }
     return r;
 }
-// a device buffer holding `data` `shift` bytes into its allocation, which ends with the data
-struct Dev { rfq_ctx* c; void* raw = nullptr; uint8_t* p = nullptr;
-    Dev(rfq_ctx* ctx, const void* data, size_t n, size_t shift = 0) : c(ctx) {
-        if (rfq_dev_malloc(c, &raw, n + shift)) { fprintf(stderr, "rfq_dev_malloc failed\n"); exit(1); }
-        p = (uint8_t*)raw + shift; if (n && data) rfq_copy_h2d(c, p, data, n); }
-    ~Dev() { rfq_dev_free(c, raw); } };
-
-static int fail(const char* what, const char* why) { fprintf(stderr, "%s: %s\n", what, why); return 1; }
 
 // one size query and one call into exact buffers, against the host's own selection; rule: 0 the longest window, 1 one more, 2 the next multiple of 16
 static int run(rfq_ctx* ctx, const char* what, const Rows& r, int pairs, uint32_t min_len, int rule, size_t in_shift, size_t out_shift) {
@@ -50,8 +37,7 @@ static int run(rfq_ctx* ctx, const char* what, const Rows& r, int pairs, uint32_
     Dev db(ctx, r.B.data(), r.B.size(), in_shift), dq(ctx, r.Q.data(), r.Q.size(), in_shift), dl(ctx, r.lens.data(), n * 4ull);
     Dev dn(ctx, blob.data(), blob.size(), in_shift), dof(ctx, off.data(), off.size() * 8);
     Dev dk(ctx, r.keep.data(), r.has_keep ? n : 0), ds(ctx, r.start.data(), r.has_start ? n * 4ull : 0), dw(ctx, r.len.data(), r.has_len ? n * 4ull : 0);
-    rfq_rows_in in; memset(&in, 0, sizeof in);
-    in.n_rows = n; in.row_len = r.L; in.d_bases = db.p; in.d_quals = dq.p; in.d_lens = (const int32_t*)dl.p;
+    rfq_rows_in in = rows_in(n, r.L, 0, db, &dq, dl);
     if (r.named) { in.d_names = dn.p; in.names_len = blob.size(); in.d_name_off = (const uint64_t*)dof.p; }
     rfq_select_rows_args a; memset(&a, 0, sizeof a); rfq_select_rows_result q, g;
     a.d_keep = r.has_keep ? dk.p : nullptr; a.d_start = r.has_start ? (const int32_t*)ds.p : nullptr; a.d_len = r.has_len ? (const int32_t*)dw.p : nullptr;
@@ -165,8 +151,8 @@ static int refusals(rfq_ctx* ctx) {
         Dev ds(ctx, s.data(), n * 4ull), dw(ctx, w.data(), n * 4ull);
         const size_t rb = (size_t)n * L;
         Dev ob(ctx, nullptr, rb), oq(ctx, nullptr, rb), ol(ctx, nullptr, n * 4ull), on(ctx, nullptr, blob.size()), oo(ctx, nullptr, (n + 1) * 8ull);
-        rfq_rows_in in; memset(&in, 0, sizeof in);
-        in.n_rows = c.which == 5 ? n - 1 : n; in.row_len = L; in.d_bases = db.p; in.d_quals = dq.p; in.d_lens = (const int32_t*)(dl.p + (c.which == 6 ? 2 : 0));
+        rfq_rows_in in = rows_in(c.which == 5 ? n - 1 : n, L, 0, db, &dq, dl);
+        if (c.which == 6) in.d_lens = (const int32_t*)(dl.p + 2);
         in.d_names = dn.p; in.names_len = blob.size(); in.d_name_off = (const uint64_t*)(dof.p + (c.which == 7 ? 4 : 0));
         rfq_select_rows_args a; memset(&a, 0, sizeof a); rfq_select_rows_result g;
         a.d_start = (const int32_t*)ds.p; a.d_len = len_null ? nullptr : (const int32_t*)dw.p; a.pairs = c.which == 5; a.min_len = 1;
