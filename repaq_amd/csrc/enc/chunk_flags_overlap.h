@@ -171,7 +171,9 @@ __device__ __forceinline__ void ov2_pack_rc(uint32_t w, uint32_t& code, uint32_t
 // LOOSE: the rows are not packed from the text but copied from the loose slots k_gather2 has left (the same codes, R2 already reverse-complemented,
 // valid for the pairs of interleaved chunks - the only ones whose result is used): lengths and slots come from the quality prefix pq, the
 // "R1 holds a byte outside A/C/G/T/N" verdict from rflag.  The search then runs behind the gather, beside the position coder.
-struct OvLoose { const uint32_t* pq; const uint32_t* lpk; const uint16_t* lnb; const uint8_t* rflag; };
+// rn: k_gather2's "this read holds an N" flags.  The N words of a read without one are not stored by the gather (lnb is all-zero between batches, k_nbits_cleanup) and are
+// not fetched here: they are zero (one read in ~300 holds an N: 0.46 GB of 2-byte loads on configs[2])
+struct OvLoose { const uint32_t* pq; const uint32_t* lpk; const uint16_t* lnb; const uint8_t* rflag; const uint8_t* rn; };
 template <bool LOOSE, uint32_t CAPB = 256u> __global__ void __launch_bounds__(256) k_overlap(Text T, OvLoose Z, int16_t* __restrict__ ovraw, uint32_t n_pairs) {
     constexpr uint32_t OV2_CAP = CAPB, OV2_CROW = OV2_CROW_OF(CAPB), OV2_NROW = OV2_NROW_OF(CAPB), OV2_WAVE_BYTES = 128u * (OV2_CROW + OV2_NROW); constexpr int OV2_ND = (int)(CAPB / 16u);
     static_assert((OV2_CROW / 4u) % 2u == 1u && (OV2_NROW / 4u) % 2u == 1u && OV2_WAVE_BYTES % 16u == 0u, "row geometry");
@@ -189,6 +191,9 @@ template <bool LOOSE, uint32_t CAPB = 256u> __global__ void __launch_bounds__(25
             else { uint32_t r; read_loc(T, g, s1, r); const uint32_t* pa = t_lo(T, s1) + 4 * (size_t)r; q1 = pa[1]; len1 = (int)(pa[2] - 1u - q1);
                               read_loc(T, g + 1, s2, r); const uint32_t* pb = t_lo(T, s2) + 4 * (size_t)r; q2 = pb[1]; len2 = (int)(pb[2] - 1u - q2); }
         }
+        // my two reads' "holds an N" flags
+        bool h1 = false, h2 = false;
+        if (LOOSE && p < n_pairs) { const uint32_t hh = *(const uint16_t*)(Z.rn + 2u * (size_t)p); h1 = (hh & 0xFFu) != 0u; h2 = (hh >> 8) != 0u; }
         const bool slow = len1 >= 0 && ((uint32_t)len1 > OV2_CAP || (uint32_t)len2 > OV2_CAP), fast = len1 >= 0 && !slow;
         const int mx = wave_max(fast ? (len1 > len2 ? len1 : len2) : 0);
         if (l < 2) s_bad[w][l] = 0;
@@ -212,8 +217,8 @@ template <bool LOOSE, uint32_t CAPB = 256u> __global__ void __launch_bounds__(25
 #pragma unroll
                 for (uint32_t u = 0; u < 4u; u++) {
                     const uint32_t j = j0 + u; const bool o1 = fast && j < nd_ && 16u * j < (uint32_t)len1, o2 = fast && j < nd_ && 16u * j < (uint32_t)len2;
-                    va[u] = o1 ? Z.lpk[ld1 + j] : 0u; ma[u] = o1 ? Z.lnb[ld1 + j] : (uint16_t)0; vb[u] = o2 ? Z.lpk[ld2 + j] : 0u;
-                            mb[u] = o2 ? Z.lnb[ld2 + j] : (uint16_t)0;
+                    va[u] = o1 ? Z.lpk[ld1 + j] : 0u; ma[u] = o1 && h1 ? Z.lnb[ld1 + j] : (uint16_t)0; vb[u] = o2 ? Z.lpk[ld2 + j] : 0u;
+                            mb[u] = o2 && h2 ? Z.lnb[ld2 + j] : (uint16_t)0;
                 }
 #pragma unroll
                 for (uint32_t u = 0; u < 4u; u++) { const uint32_t j = j0 + u; if (fast && j < nd_) { r1w[j] = va[u]; m1w[j] = ma[u]; r2w[j] = vb[u]; m2w[j] = mb[u]; } }

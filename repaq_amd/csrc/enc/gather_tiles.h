@@ -175,8 +175,10 @@ template <bool CHK = false> __device__ __forceinline__ void g2_bases(const uint8
         }
         code >>= 2u * tsh; nbits >>= tsh;
         if (nv0 < 16u) { code &= (1u << (2u * nv0)) - 1u; nbits &= (1u << nv0) - 1u; }   // (what lies outside the line is not the read's)
-        lpk[m.ld + gi] = code; lnb[m.ld + gi] = (uint16_t)nbits;
-        if (nbits) rn[m.gi] = 1;                                           // (the read holds an N: whoever reads the loose slots' N bits asks this first - one read in a few hundred does)
+        lpk[m.ld + gi] = code;
+        // (the read holds an N: whoever reads the loose slots' N bits asks rn[] first - one read in a few hundred does.  lnb is all-zero between batches - the host's
+        // lnb_dirty, k_nbits_cleanup - and only a group that holds an N stores its word: 0.46 GB of zeros on configs[2] otherwise)
+        if (nbits) { lnb[m.ld + gi] = (uint16_t)nbits; rn[m.gi] = 1; }
     }
 }
 // my share (groups part, part + P, ...) of my read's two lines: qualities -> qcat, bases -> the loose slot
@@ -676,10 +678,18 @@ __device__ __forceinline__ void k_rare_zero_chunk(uint32_t* __restrict__ planes,
     const uint32_t nw = (pq[first[c + 1]] - pq[first[c]] + 31u) >> 5; const size_t w0 = (size_t)(qbase[c] >> 5);
     for (uint32_t v = 0; v < G2_PLANES; v++) if (!((dense_mask >> v) & 1u)) for (uint32_t i = threadIdx.x; i < nw; i += blockDim.x) planes[(size_t)v * pstride + w0 + i] = 0u;
 }
+// the loose N-bit slots of the reads [g0, g1) whose rn[] is set, back to zero: read g owns the (len + 15) / 16 words from (pq[g] >> 4) + g on (thread t of n takes reads t, t + n, ...)
+__device__ __forceinline__ void nbits_zero_slots(uint16_t* __restrict__ lnb, const uint8_t* __restrict__ rn, const uint32_t* __restrict__ pq, uint32_t g0, uint32_t g1, uint32_t t, uint32_t n) {
+    for (uint32_t g = g0 + t; g < g1; g += n) if (rn[g]) { const uint32_t a = pq[g], nw = (pq[g + 1] - a + 15u) >> 4; uint16_t* const o = lnb + (size_t)(a >> 4) + g;
+            for (uint32_t i = 0; i < nw; i++) o[i] = 0; }
+}
 // (xplane: the planes of MASKS mode, or null - the chunk's words of the rare planes are zeroed: the repeat sets them afresh)
 __global__ void k_gather_redo_reset(const uint32_t* __restrict__ only, uint32_t* __restrict__ segm, int* __restrict__ segc, uint32_t n_seg,
-                                    uint32_t* __restrict__ xplane, uint64_t pstride, const DevHeader* __restrict__ D, uint32_t nd, const uint32_t* __restrict__ pq, const uint32_t* __restrict__ first, const uint64_t* __restrict__ qbase) {
+                                    uint32_t* __restrict__ xplane, uint64_t pstride, const DevHeader* __restrict__ D, uint32_t nd, const uint32_t* __restrict__ pq, const uint32_t* __restrict__ first, const uint64_t* __restrict__ qbase,
+                                    uint16_t* __restrict__ lnb, const uint8_t* __restrict__ rn) {
     const uint32_t c = blockIdx.x; if (!only[c]) return;
+    // (lnb: phase 1 packed the chunk's mates back to front and left their N bits at mirrored places; the repeat stores only where ITS bits are.  rn[] stays set - a superset)
+    nbits_zero_slots(lnb, rn, pq, first[c], first[c + 1], threadIdx.x, blockDim.x);
     const size_t k = (size_t)c * MAX_STREAMS * n_seg;
     for (uint32_t i = threadIdx.x; i < MAX_STREAMS * n_seg; i += blockDim.x) { segm[k + i] = 0u; segc[k + i] = -1; }
     // (rare[] lies behind the planes)
@@ -695,6 +705,14 @@ __global__ void k_rare_cleanup(uint32_t* __restrict__ rare, uint32_t* __restrict
     else k_rare_zero_chunk(planes, pstride, dense_mask_of(D, nd), pq, first, qbase, c);
     __syncthreads();
     if (threadIdx.x == 0) rc[0] = 0u;
+}
+// behind its last reader (k_seqpack): lnb all-zero again.  The workgroups walk rn[], sixteen flags per thread (one read in ~300 has its flag set), and zero the slots of the
+// reads that hold an N.  No exit on DE_SCRATCH(N)_SMALL: the gather has run whether or not the coders left early.
+__global__ void __launch_bounds__(256) k_nbits_cleanup(uint16_t* __restrict__ lnb, const uint8_t* __restrict__ rn, const uint32_t* __restrict__ pq, uint32_t n_reads) {
+    const uint32_t g0 = 16u * (blockIdx.x * blockDim.x + threadIdx.x); if (g0 >= n_reads) return;
+    const uint4 v = *(const uint4*)(rn + g0);                               // (rn[] is sized to a multiple of 16; what lies behind n_reads is not looked at)
+    if (!(v.x | v.y | v.z | v.w)) return;
+    nbits_zero_slots(lnb, rn, pq, g0, g0 + 16u < n_reads ? g0 + 16u : n_reads, 0u, 1u);
 }
 // 16 consecutive codes / N bits of a loose slot from base index b on (b + 16 may pass the slot's end: the caller masks)
 __device__ __forceinline__ uint32_t loose_codes(const uint32_t* __restrict__ lpk, uint32_t ld, uint32_t b) {

@@ -171,6 +171,9 @@ struct rfq_ctx {
     bool mirror_block = false, mirror_fell = false;
     // encode, match-mask mode: the rare planes of b[B_QPLANE] may hold bits (fresh buffer, or a call that left early): zero them whole
     bool qplane_dirty = true;
+    // encode, tile path: b[B_LNB] (the loose slots' N bits, stored only where a bit is set) may hold bits - fresh or grown buffer, a call that left between the gather and
+    // its cleanup: zero it whole before the next gather
+    bool lnb_dirty = true;
     uint32_t qplane_nd = 0, qplane_mask = 0; // ... dense planes the last batch used: how many, which (the others must be all-zero)
     size_t qplane_stride = 0;              // ... words per plane the buffer is laid out with (fixed while the buffer is)
     // rfq_rows_to_text / rfq_encode_rows: the record offsets of each text, the verdict block, the context-owned texts (they outlive the encoder's own buffers)

@@ -479,7 +479,14 @@ static int enc_gather_tiles(rfq_ctx* ctx, const EncBatch& b, const EncCut& cut, 
     if (f.masks) { ctx->timer.begin("quality_masks", S); ctx->timer.end(S); }
     ctx->timer.begin("gather", S);                                          // (which formulation ran: tests and the bench look at it)
     const size_t nld = (size_t)(cut.total_bases >> 4) + cut.reads_used + 16;
+    const size_t lnb_cap = B[B_LNB].cap;
     uint32_t* lpk; uint16_t* lnb; HIPCHK(ctx, table(B[B_LPK], nld * 4, lpk)); HIPCHK(ctx, table(B[B_LNB], nld * 2, lnb));
+    // lnb, the loose slots' N bits, is all-zero between batches: the gather stores only the words that hold a bit, k_nbits_cleanup (enc_coders) zeroes those again.  A buffer
+    // that has grown or that a call left between here and its cleanup (an error, RFQ_AGAIN_*, a repeat of the batch) is cleared whole; dirty from here until this call's
+    // cleanup is queued.
+    if (B[B_LNB].cap != lnb_cap) ctx->lnb_dirty = true;
+    if (ctx->lnb_dirty) HIPCHK(ctx, hipMemsetAsync(lnb, 0, B[B_LNB].cap, S));
+    ctx->lnb_dirty = true;
     const uint32_t K = 1u << f.kshift;
     const uint32_t bx = grid_x_for(cut.n_chunks, (cut.max_reads + K - 1) / K, 6u * ctx->n_cu);      // (26 KB of LDS: six workgroups per CU)
     // dynamic LDS of k_gather2: the staged text of K of the batch's longest records (+ slack), read 0's name / strand line, and - match-mask mode - three
@@ -513,7 +520,8 @@ static int enc_gather_tiles(rfq_ctx* ctx, const EncBatch& b, const EncCut& cut, 
     for (int phase = 1; phase <= (b.is_pe ? 2 : 1); phase++) {
         const uint32_t* only = phase == 2 ? (const uint32_t*)t.redo : (const uint32_t*)nullptr;
         if (phase == 2) hipLaunchKernelGGL(k_gather_redo_reset, dim3(cut.n_chunks), dim3(64), 0, S, only, t.segm, t.segc, t.n_seg,
-                                           f.masks ? M.planes : (uint32_t*)nullptr, M.pstride, (const DevHeader*)t.D, M.nd, (const uint32_t*)t.R.pq, (const uint32_t*)t.C.first, (const uint64_t*)t.C.qbase);
+                                           f.masks ? M.planes : (uint32_t*)nullptr, M.pstride, (const DevHeader*)t.D, M.nd, (const uint32_t*)t.R.pq, (const uint32_t*)t.C.first, (const uint64_t*)t.C.qbase,
+                                           lnb, (const uint8_t*)rn);
         if (f.masks) hipLaunchKernelGGL(k_mask_bounds, dim3(cut.n_chunks), dim3(64), 0, S, (const uint32_t*)t.R.pq, (const uint32_t*)t.C.first, (const uint64_t*)t.C.qbase,
                 M.planes, M.pstride, (const DevHeader*)t.D, M.nd, bx, only);
 #define RFQ_G2_ARGS b.T, t.R, (const uint32_t*)t.C.first, (const uint64_t*)t.C.qbase, (const DevHeader*)t.D, t.qcat, lpk, lnb, rflag, \
@@ -547,7 +555,7 @@ static int enc_gather_tiles(rfq_ctx* ctx, const EncBatch& b, const EncCut& cut, 
     const bool aux_chain = f.aux_chain = ctx->aux_ready() && !ctx->opt.one_stream; hipStream_t A = aux_chain ? ctx->aux : S;
     if (aux_chain) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, S)); HIPCHK(ctx, hipStreamWaitEvent(A, ctx->ev_fork, 0)); guard.armed = true; }
     if (b.is_pe) {
-        const OvLoose Z = { (const uint32_t*)t.R.pq, (const uint32_t*)lpk, (const uint16_t*)lnb, (const uint8_t*)rflag };
+        const OvLoose Z = { (const uint32_t*)t.R.pq, (const uint32_t*)lpk, (const uint16_t*)lnb, (const uint8_t*)rflag, (const uint8_t*)rn };
         const uint32_t ob = std::min<uint32_t>((np + 255) / 256, 65535u * 16u);
         // (rows of 160 bases where no read is longer: sixteen resident waves per CU instead of twelve)
         if (cut.max_len <= 160u) hipLaunchKernelGGL((k_overlap<true, 160u>), dim3(ob), dim3(256), 0, A, b.T, Z, t.ovraw, np);
@@ -593,7 +601,7 @@ static int enc_gather_bytes(rfq_ctx* ctx, EncBatch& b, const EncCut& cut, EncTab
     hipLaunchKernelGGL(k_chunk_flags_b, dim3(cut.n_chunks), dim3(64), 0, S, t.R, t.C, (const DevHeader*)t.D, b.is_pe ? 1 : 0, (const uint32_t*)t.cbits, (const uint32_t*)t.cfail,
             (uint32_t*)nullptr);
     if (b.is_pe) {
-        const OvLoose noz = { nullptr, nullptr, nullptr, nullptr };
+        const OvLoose noz = { nullptr, nullptr, nullptr, nullptr, nullptr };
         const uint32_t ob = std::min<uint32_t>((cut.n_units + 255) / 256, 65535u * 16u);
         hipLaunchKernelGGL(k_overlap<false>, dim3(ob), dim3(256), 0, S, b.T, noz, t.ovraw, cut.n_units);
     }
@@ -689,6 +697,12 @@ static int enc_coders(rfq_ctx* ctx, const EncBatch& b, const EncCut& cut, EncTab
         hipLaunchKernelGGL(k_rare_cleanup, dim3(cut.n_chunks), dim3(256), 0, S, t.qplane + G2_PLANES * ctx->qplane_stride, t.qplane, (uint64_t)ctx->qplane_stride,
                            (const DevHeader*)t.D, ctx->qplane_nd, (const uint32_t*)t.R.pq, (const uint32_t*)t.C.first, (const uint64_t*)t.C.qbase);
         ctx->qplane_dirty = false;
+    }
+    if (f.fast) {                                                           // the loose N bits back to all-zero, behind k_seqpack (the join above) - also where the coders left early
+        hipLaunchKernelGGL(k_nbits_cleanup, dim3((cut.reads_used + 4095u) / 4096u), dim3(256), 0, S, B[B_LNB].as<uint16_t>(), (const uint8_t*)B[B_RN].as<uint8_t>(),
+                           (const uint32_t*)t.R.pq, cut.reads_used);
+        KCHK(ctx, "k_nbits_cleanup");
+        ctx->lnb_dirty = false;
     }
     ctx->timer.end(S);
     return RFQ_OK;
