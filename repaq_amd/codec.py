@@ -15,6 +15,16 @@ from . import _capi as A
 from ._capi import RfqError, SE, PE_TWO_FILES, PE_INTERLEAVED, U64_MAX  # noqa: F401
 
 
+def _chunk_index(chunk_off, n_chunks):
+    """a caller's chunk index - a POINTER(c_uint64) with n_chunks, or a sequence of n_chunks + 1 offsets - as the (h_chunk_off, n_chunk_off) of an args struct"""
+    if chunk_off is None:
+        return None, 0
+    if not isinstance(chunk_off, C.POINTER(C.c_uint64)):
+        n_chunks = len(chunk_off) - 1
+        chunk_off = C.cast((C.c_uint64 * len(chunk_off))(*chunk_off), C.POINTER(C.c_uint64))
+    return (chunk_off if n_chunks else None), n_chunks
+
+
 class RfqCodec:
     def __init__(self, device=0, library=None):
         self._L = A.load(library)
@@ -117,11 +127,9 @@ class RfqCodec:
     def decode(self, d_rfq, n, has_header=True, split_pe=False, final=True, d_out1=None, cap1=0, d_out2=None, cap2=0, chunk_off=None, n_chunks=0, bug_compat=False):
         """chunk_off / n_chunks: optional chunk index (EncodeResult.h_chunk_off + n_chunks, or a sequence of n_chunks + 1 offsets).
         bug_compat: with split_pe, lose what Repaq::decompressPE loses behind a non-last NO_LINE_BREAK chunk (src/repaq.cpp:376-403); Repaq::decompress (one output) loses nothing."""
-        if chunk_off is not None and not isinstance(chunk_off, C.POINTER(C.c_uint64)):
-            n_chunks = len(chunk_off) - 1
-            chunk_off = C.cast((C.c_uint64 * len(chunk_off))(*chunk_off), C.POINTER(C.c_uint64))
+        chunk_off, n_chunks = _chunk_index(chunk_off, n_chunks)
         a = A.DecodeArgs(d_rfq, n, 1 if has_header else 0, 1 if split_pe else 0, 1 if final else 0, 1 if bug_compat else 0, d_out1, cap1, d_out2, cap2,
-                         chunk_off if (chunk_off is not None and n_chunks) else None, n_chunks if chunk_off is not None else 0, 0)
+                         chunk_off, n_chunks, 0)
         r = A.DecodeResult()
         self._check(self._L.rfq_decode_batch(self._h, C.byref(a), C.byref(r)))
         return r
@@ -132,11 +140,9 @@ class RfqCodec:
         """rfq_decode_rows: row i of d_bases / d_quals (device buffers of n_rows * row_len bytes) = read i of decode(split_pe=False), padded to row_len;
         d_lens: n_rows int32 read lengths.  No output buffer given (row_len=0 and no pointers) = a size query: n_rows, n_chunks, max_len, consumed.
         codes: bases as A0 C1 G2 T3 N4; quality bytes are the characters minus qual_offset.  Returns DecodeRowsResult."""
-        if chunk_off is not None and not isinstance(chunk_off, C.POINTER(C.c_uint64)):
-            n_chunks = len(chunk_off) - 1
-            chunk_off = C.cast((C.c_uint64 * len(chunk_off))(*chunk_off), C.POINTER(C.c_uint64))
-        a = A.DecodeRowsArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off if (chunk_off is not None and n_chunks) else None,
-                             n_chunks if chunk_off is not None else 0, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII, qual_offset, pad_base, pad_qual, 0,
+        chunk_off, n_chunks = _chunk_index(chunk_off, n_chunks)
+        a = A.DecodeRowsArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off,
+                             n_chunks, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII, qual_offset, pad_base, pad_qual, 0,
                              d_bases, bases_cap, d_quals, quals_cap, d_lens, lens_cap)
         r = A.DecodeRowsResult()
         self._check(self._L.rfq_decode_rows(self._h, C.byref(a), C.byref(r)))
@@ -174,11 +180,9 @@ class RfqCodec:
         d_names and n_rows + 1 uint64 offsets at d_name_off, the layout rows_to_text / encode_rows take.  Row i is row i of decode_rows.  No buffers given =
         context-owned results, valid until the next call; size_only: the counts alone.  The text of the strand lines is not carried (rows always write
         "+").  Returns DecodeNamesResult (d_names, names_len, d_name_off, n_rows, n_chunks, max_name, consumed)."""
-        if chunk_off is not None and not isinstance(chunk_off, C.POINTER(C.c_uint64)):
-            n_chunks = len(chunk_off) - 1
-            chunk_off = C.cast((C.c_uint64 * len(chunk_off))(*chunk_off), C.POINTER(C.c_uint64))
-        a = A.DecodeNamesArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off if (chunk_off is not None and n_chunks) else None,
-                              n_chunks if chunk_off is not None else 0, 1 if size_only else 0, d_names, names_cap, d_name_off, off_cap)
+        chunk_off, n_chunks = _chunk_index(chunk_off, n_chunks)
+        a = A.DecodeNamesArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off,
+                              n_chunks, 1 if size_only else 0, d_names, names_cap, d_name_off, off_cap)
         r = A.DecodeNamesResult()
         self._check(self._L.rfq_decode_names(self._h, C.byref(a), C.byref(r)))
         return r

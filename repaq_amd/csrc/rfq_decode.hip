@@ -4,6 +4,7 @@
 // (src/repaq.cpp:262-417; final-newline rule :301-328,375-413).
 #include "rfq_ctx.h"
 #include "rfq_decode_kernels.h"
+#include "dec/ranges.h"
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -17,8 +18,13 @@ static_assert(DB_END <= 120, "rfq_ctx::b too small");
 
 #define RFQ_RANGE_TOO_BIG 2          // internal: the range's text would not fit the 32-bit text offsets of one pass
 // bases: sum of the range's read lengths (the walk's 64-bit total)
-struct DecRange { const DChunk* CH; uint32_t n_chunks, n_reads, max_reads, max_stream, max_npos, max_len, max_bases, max_nrec, max_one, pieces, piece_avg, piece_n1;
+struct DecRange { const DChunk* CH; uint32_t n_chunks, n_reads, max_reads, max_stream, max_npos, max_len, max_bases, max_nrec, max_one, per_read_pieces, piece_avg, piece_n1;
         uint64_t bases; };
+// the nine maxima of a walk: from the status behind the second parse to the first one's (dec_walk), from the walk's status to a range (range_of)
+template <class D, class S> static void take_maxima(D& d, const S& s) {
+    d.max_stream = s.max_stream; d.max_npos = s.max_npos; d.max_len = s.max_len; d.max_bases = s.max_bases; d.max_nrec = s.max_nrec;
+    d.max_one = s.max_one; d.per_read_pieces = s.per_read_pieces; d.piece_avg = s.piece_avg; d.piece_n1 = s.piece_n1;
+}
 // ---- the expanded stage of a range (the text path's fallback emitter and rfq_decode_rows read what it leaves in HBM)
 // read table: per-read values (k_dec_readtab), the quality / stored-base prefixes (two scans), their totals read back.  text: the text bookkeeping
 // (tin / tp, filled by k_dec_textlen) is allocated too.  R.len / R.ov / R.mid are the caller's.
@@ -122,16 +128,16 @@ static FusedPlan plan_fused(const rfq_ctx* ctx, const DecRange& g, bool force_ex
     const bool rle_h = !(HH.flags & (H_DONT_QUAL | H_QUAL_BY_COL));          // legacy run-length quality coding: k_dec_rle on the materialising path
     uint32_t e3k = 6; bool n1big = false;
     while (e3k >= 1 && ((uint64_t)g.max_len << e3k) > E3_QCAP) e3k--;
-    if (g.pieces) {
+    if (g.per_read_pieces) {
         while (e3k >= 1 && ((uint64_t)g.piece_avg << e3k) > 204u) e3k--;
         const uint64_t need1 = ((uint64_t)g.piece_n1 << e3k) * 5u / 4u + 32u;
         if (need1 > ET_N1CAP) { if (e3k == 6 && need1 <= E3_N1BIG) n1big = true; else e3k = 0; }
     }
-    const bool e3_ok = e3k >= (g.pieces ? 6u : 1u) && !(g.pieces && ctx->e3_pieces_failed);
+    const bool e3_ok = e3k >= (g.per_read_pieces ? 6u : 1u) && !(g.per_read_pieces && ctx->e3_pieces_failed);
     // (chunks of 2^30 bases and more: the list chain's saturating position sums - POS_ADV_MAX, dec/pos_lists.h - would no longer be exact)
     const bool on = !force_expanded && !ctx->opt.materialise && !rle_h && g.max_len <= 2000u && g.max_nrec <= 4096u && e3_ok && g.max_bases < (1u << 30) - 65536u;
     // (the per-read piece prefixes only where some chunk stores pieces per read: sequencer names leave none, and the stored-base prefix alone is 4 bytes per read instead of 16)
-    return { on, e3k, n1big, E3_SHARED_OK && !g.pieces && !(HH.flags & H_DONT_QUAL) };
+    return { on, e3k, n1big, E3_SHARED_OK && !g.per_read_pieces && !(HH.flags & H_DONT_QUAL) };
 }
 // what the position-list chain of a range left behind: the shape of its tables (B[DB_SEG*], B[DB_CELL], B[DB_NENT], B[DB_LOFF]), whether lists were built at
 // all (a file without quality streams and N positions has none), and the stream the emitter has to wait for (join: the chain ran beside the main stream)
@@ -241,11 +247,13 @@ static void launch_emit3(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange&
 #undef RFQ_EMIT3_ARGS
 }
 // RfqCodec::decodeChunk + Read::toString for the chunks of one range (reads, bases and text of a range are placed by 32-bit prefix sums).
-// out1 / out2: caller buffers (16-byte aligned) or null = the context's own result buffers; *p1 / *p2 = where the text went.
+// out: caller buffers (16-byte aligned) or null = the context's own result buffers; *T (set on RFQ_OK only) = where the text of R1 / R2 went.
 // force_expanded: the retry of a range whose fused path gave up - straight to the expanded path, whatever made it give up (the retry must terminate by
 // construction, not because a flag happens to be honoured)
-static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, uint8_t* out1, uint64_t ocap1, uint8_t* out2, uint64_t ocap2,
-                        uint8_t** p1, uint8_t** p2, size_t* n1, size_t* n2, uint64_t* nbases, bool force_expanded = false) {
+struct DecDst { uint8_t* p[2]; uint64_t cap[2]; };
+struct DecText { uint8_t* p[2]; size_t n[2]; uint64_t bases; };
+static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g, const DecDst& out, DecText* T, bool force_expanded = false) {
+    uint8_t* const out1 = out.p[0]; uint8_t* const out2 = out.p[1]; uint64_t nbases = 0;
     hipStream_t S = ctx->stream; DBuf* B = ctx->b; const DevHeader* D = ctx->d_hdr.as<DevHeader>();
     DecStatus* dst = B[DB_STATUS].as<DecStatus>(); DecStatus hs;
     const uint32_t n_chunks = g.n_chunks, n_reads = g.n_reads, max_reads = std::max(g.max_reads, 1u);
@@ -265,13 +273,13 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
         int rc = dec_table_fused(ctx, a, g, P, R, &F);
         if (!rc) rc = dec_textlen_fused(ctx, a, g, R);
         if (rc) return rc;
-        *nbases = g.bases;
+        nbases = g.bases;
     } else {
         uint32_t total_bases = 0; U4 pv_tot; memset(&pv_tot, 0, sizeof pv_tot);
         int rc = dec_table_expanded(ctx, a, g, R, true, &total_bases, &pv_tot);
         if (!rc) rc = dec_streams_expanded(ctx, a, g, R, total_bases, pv_tot, true, &E);
         if (rc) return rc;
-        *nbases = total_bases;
+        nbases = total_bases;
         ctx->timer.begin("textlen", S);
         hipLaunchKernelGGL(k_dec_textlen, dim3((max_reads + 255) / 256, n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, D, R, (const uint32_t*)B[DB_XV].as<uint32_t>(),
                            (const uint32_t*)B[DB_YV].as<uint32_t>(), split, dst);
@@ -285,7 +293,7 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
     if (emitted) {
         ctx->timer.end(S);
         ctx->timer.begin("emit", S);
-        launch_emit3(ctx, a, g, P, L, F, out1, ocap1, out2, ocap2, B[DB_PLIST].cap / sizeof(plist_t));
+        launch_emit3(ctx, a, g, P, L, F, out1, out.cap[0], out2, out.cap[1], B[DB_PLIST].cap / sizeof(plist_t));
         KCHK(ctx, "k_dec_emit");
         ctx->timer.end(S);
     }
@@ -300,8 +308,8 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
         // once more, expanded.  DE_LIST_ALIAS: a stream codes positions far beyond its chunk's length table (k_dec_pos_link2): 16-bit list entries would alias.
         // DE_E3_RETRY: per-read name pieces that did not fit a tile of k_dec_emit3 - files like this one: the ranges that follow go straight to the expanded path
         if (P.on && (hs.err & (DE_LIST_ALIAS | DE_E3_RETRY))) {
-            if ((hs.err & DE_E3_RETRY) && g.pieces) ctx->e3_pieces_failed = true;
-            return decode_range(ctx, a, g, out1, ocap1, out2, ocap2, p1, p2, n1, n2, nbases, true);
+            if ((hs.err & DE_E3_RETRY) && g.per_read_pieces) ctx->e3_pieces_failed = true;
+            return decode_range(ctx, a, g, out, T, true);
         }
         if (hs.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "corrupt quality buffer");
         if (L.built && hs.list_need > B[DB_PLIST].cap / sizeof(plist_t)) {       // the lists did not fit the arena: now that their size is known, build them
@@ -315,8 +323,8 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
         if (hs.text1 >= 0xFFFFFFF0ull || hs.text2 >= 0xFFFFFFF0ull) return RFQ_RANGE_TOO_BIG;       // (the caller decodes the range in two halves)
         if ((out1 && ((uintptr_t)out1 & 15u)) || (out2 && ((uintptr_t)out2 & 15u))) return rfq_fail(ctx, RFQ_E_ARG, "output device pointers must be 16-byte aligned");
         uint64_t cap1, cap2;
-        if (out1) { o1 = out1; cap1 = ocap1; } else { HIPCHK(ctx, ctx->out_fq1.ensure((size_t)tt.a + 64)); o1 = ctx->out_fq1.as<uint8_t>(); cap1 = ctx->out_fq1.cap; }
-        if (out2) { o2 = out2; cap2 = ocap2; } else { HIPCHK(ctx, ctx->out_fq2.ensure((size_t)tt.b + 64)); o2 = ctx->out_fq2.as<uint8_t>(); cap2 = ctx->out_fq2.cap; }
+        if (out1) { o1 = out1; cap1 = out.cap[0]; } else { HIPCHK(ctx, ctx->out_fq1.ensure((size_t)tt.a + 64)); o1 = ctx->out_fq1.as<uint8_t>(); cap1 = ctx->out_fq1.cap; }
+        if (out2) { o2 = out2; cap2 = out.cap[1]; } else { HIPCHK(ctx, ctx->out_fq2.ensure((size_t)tt.b + 64)); o2 = ctx->out_fq2.as<uint8_t>(); cap2 = ctx->out_fq2.cap; }
         if (emitted) break;
         ctx->timer.end(S);
         ctx->timer.begin(P.on ? "emit" : "emit_expanded", S);              // the emitter alone: the path's largest kernel (bench.py roofline)
@@ -332,41 +340,14 @@ static int decode_range(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& 
     }
     ctx->timer.collect();
     if (hs.err & (1u << 31)) return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffer too small: need %u / %u bytes", tt.a, tt.b);
-    *n1 = tt.a; *n2 = split ? tt.b : 0; *p1 = o1; *p2 = o2;
+    *T = DecText{ { o1, o2 }, { tt.a, split ? tt.b : 0u }, nbases };
     return RFQ_OK;
 }
 
 // the range of chunks [CH, CH + n_chunks) with the walk's image-wide maxima
 static DecRange range_of(const DecStatus& hs, const DChunk* CH, uint32_t n_chunks, uint64_t reads, uint64_t bases) {
-    DecRange g; g.CH = CH; g.n_chunks = n_chunks; g.n_reads = (uint32_t)reads; g.max_reads = hs.max_reads; g.max_stream = hs.max_stream;
-            g.max_npos = hs.max_npos; g.max_len = hs.max_len; g.max_bases = hs.max_bases; g.max_nrec = hs.max_nrec; g.max_one = hs.max_one;
-            g.pieces = hs.per_read_pieces; g.piece_avg = hs.piece_avg; g.piece_n1 = hs.piece_n1; g.bases = bases;
-    return g;
-}
-// Reads, bases and text of one pass are placed by 32-bit prefix sums: a larger image is decoded range by range - contiguous chunks of about
-// slice_bases bases and fewer than 2^31 reads, cut out of every piece [c0, c1) of the image.  Returned as a stack: the first range on top.
-// ChunkSpan: the chunks [c0, c1) of the image (r1_only: a piece of which the reference writes the first mate only)
-struct ChunkSpan { uint32_t c0, c1; bool r1_only; };
-static std::vector<ChunkSpan> plan_ranges(const std::vector<ChunkSpan>& pieces, const std::vector<DChunk>& hc, uint64_t slice_bases) {
-    std::vector<ChunkSpan> fw, todo;
-    for (auto& pc : pieces) {
-        uint32_t c0 = pc.c0; uint64_t acc = 0, rd = 0;
-        for (uint32_t c = pc.c0; c < pc.c1; c++) {
-            if (c > c0 && (acc + hc[c].bases > slice_bases || rd + hc[c].reads > 0x7FFFFFF0ull)) { fw.push_back({ c0, c, pc.r1_only }); c0 = c; acc = 0; rd = 0; }
-            acc += hc[c].bases; rd += hc[c].reads;
-        }
-        fw.push_back({ c0, pc.c1, pc.r1_only });
-    }
-    for (size_t i = fw.size(); i-- > 0;) todo.push_back(fw[i]);
-    return todo;
-}
-// the range of one span: its reads and bases summed from the host copy of the chunk table, its chunks' read bases made relative to it (k_dec_rebase)
-static int span_range(rfq_ctx* ctx, const DecStatus& hs, DChunk* CHm, const std::vector<DChunk>& hc, const ChunkSpan& r, DecRange* g, uint64_t* reads) {
-    uint64_t rd = 0, rbases = 0; for (uint32_t c = r.c0; c < r.c1; c++) { rd += hc[c].reads; rbases += hc[c].bases; }
-    hipLaunchKernelGGL(k_dec_rebase, dim3((r.c1 - r.c0 + 255) / 256), dim3(256), 0, ctx->stream, CHm + r.c0, r.c1 - r.c0, hc[r.c0].rbase_abs);
-    KCHK(ctx, "k_dec_rebase");
-    *g = range_of(hs, CHm + r.c0, r.c1 - r.c0, rd, rbases); *reads = rd;
-    return RFQ_OK;
+    DecRange g; g.CH = CH; g.n_chunks = n_chunks; g.n_reads = (uint32_t)reads; g.max_reads = hs.max_reads; g.bases = bases;
+    take_maxima(g, hs); return g;
 }
 
 // what every decode call does first: the device, the stage timers, the header (parsed from the image and set, or the one set before);
@@ -461,9 +442,7 @@ static int dec_walk(rfq_ctx* ctx, const rfq_decode_args* a, uint64_t start, DecS
             DecStatus h2; HIPCHK(ctx, ctx->fetch(&h2, dst, sizeof h2, S));
             HIPCHK(ctx, ctx->fetch_sync(S));
             if (h2.pad) { guess = false; continue; }
-            hs.max_stream = h2.max_stream; hs.max_npos = h2.max_npos; hs.max_len = h2.max_len; hs.max_bases = h2.max_bases; hs.max_nrec = h2.max_nrec;
-                    hs.max_one = h2.max_one; hs.per_read_pieces = h2.per_read_pieces; hs.piece_avg = h2.piece_avg; hs.piece_n1 = h2.piece_n1;
-                    memcpy(hs.base_slots, h2.base_slots, sizeof hs.base_slots);
+            take_maxima(hs, h2); memcpy(hs.base_slots, h2.base_slots, sizeof hs.base_slots);
         }
         // let the exact walk decide about a trailing partial chunk (a range that does not end the image may end inside one)
         if (hs.consumed != a->n && a->n - hs.consumed >= 18 && (a->final || hs.n_chunks == 0)) { guess = false; continue; }
@@ -474,6 +453,74 @@ static int dec_walk(rfq_ctx* ctx, const rfq_decode_args* a, uint64_t start, DecS
     if (hs.err & DE_CORRUPT) return rfq_fail(ctx, RFQ_E_FORMAT, "truncated or corrupt rfq chunk at byte %llu", (unsigned long long)hs.consumed);
     return RFQ_OK;
 }
+
+// ---- what text, rows and names share: the walked image and the loop over its ranges
+// rfq_decode_rows_args / rfq_decode_names_args as the text decode's arguments, which the walk and the stages of a range take (split_pe = 0, bug_compat = 0:
+// Repaq::decompress order, nothing lost)
+template <class A> static rfq_decode_args dec_view(const A* x) {
+    rfq_decode_args a; memset(&a, 0, sizeof a);
+    a.d_rfq = x->d_rfq; a.n = x->n; a.has_header = x->has_header; a.final = x->final; a.h_chunk_off = x->h_chunk_off; a.n_chunk_off = x->n_chunk_off;
+    return a;
+}
+// hs: the walk's status; CHm: the chunk table on the device; bases: the 64-bit total of the read lengths - bases, qualities and text are placed by 32-bit
+// prefix sums (a corrupt length table must be refused before any buffer is sized from a wrapped sum); empty: an empty .rfq, nothing walked;
+// hc: the host copy of the chunk table, made once for whoever asks first (dec_host_table: bug_compat, ranges)
+struct DecImage { uint64_t start; DecStatus hs; DChunk* CHm; uint32_t n_chunks; uint64_t reads, bases; bool empty; std::vector<DChunk> hc; };
+static int dec_image(rfq_ctx* ctx, const rfq_decode_args* a, DecImage* img) {
+    img->start = 0; memset(&img->hs, 0, sizeof img->hs); img->empty = a->n == 0 && a->has_header;
+    if (img->empty) { HIPCHK(ctx, hipSetDevice(ctx->device)); ctx->timer.reset(); }      // (no header to parse, no chunk to walk)
+    else {
+        int rc = dec_open(ctx, a, &img->start); if (rc) return rc;
+        if (a->split_pe && !(ctx->h_hdr.flags & H_PAIRED)) return rfq_fail(ctx, RFQ_E_DATA, "The input RFQ file was encoded by single-end FASTQ, you should not specify <out2>");
+        rc = dec_walk(ctx, a, img->start, img->hs); if (rc) return rc;
+    }
+    img->CHm = ctx->b[DB_CHUNKS].as<DChunk>(); img->n_chunks = img->hs.n_chunks; img->reads = img->hs.total_reads;
+    img->bases = 0; for (int i = 0; i < 16; i++) img->bases += img->hs.base_slots[i];
+    return RFQ_OK;
+}
+static int dec_host_table(rfq_ctx* ctx, DecImage& img) {
+    if (img.hc.size() == img.n_chunks) return RFQ_OK;
+    img.hc.resize(img.n_chunks); HIPCHK(ctx, hipMemcpy(img.hc.data(), img.CHm, (size_t)img.n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
+    return RFQ_OK;
+}
+// the range of one span: its reads and bases summed from the host copy of the chunk table, its chunks' read bases made relative to it (k_dec_rebase)
+static int span_range(rfq_ctx* ctx, const DecImage& img, const ChunkSpan& r, DecRange* g, uint64_t* reads) {
+    uint64_t rd = 0, rbases = 0; for (uint32_t c = r.c0; c < r.c1; c++) { rd += img.hc[c].reads; rbases += img.hc[c].bases; }
+    hipLaunchKernelGGL(k_dec_rebase, dim3((r.c1 - r.c0 + 255) / 256), dim3(256), 0, ctx->stream, img.CHm + r.c0, r.c1 - r.c0, img.hc[r.c0].rbase_abs);
+    KCHK(ctx, "k_dec_rebase");
+    *g = range_of(img.hs, img.CHm + r.c0, r.c1 - r.c0, rd, rbases); *reads = rd;
+    return RFQ_OK;
+}
+// body(range, span, whole) over the image.  One pass where the image fits one (whole = true: the chunk table as the walk left it, the stage timers the
+// caller's to collect); else - and when that pass says RFQ_RANGE_TOO_BIG, or the caller names the pieces to decode (bug_compat) - range by range (dec/ranges.h;
+// RFQ_SLICE_BASES: test aid - ranges of that many bases, so that this runs on small images), the stage times of every range summed into `sums` behind the
+// walk's and whatever a failed one-pass attempt got through.  A non-empty `sums` says that ranges ran (and run from then on): the caller publishes it.
+// A range the body calls too big is halved, a single chunk that is too big fails with `too_big`.  plan_ranges cuts at a pass's limits of reads and
+// bases, so only a single chunk can exceed those: what does get halved is a range whose text reaches 4 GiB.
+template <class Body>
+static int dec_each_range(rfq_ctx* ctx, DecImage& img, const std::vector<ChunkSpan>* pieces, StageSums& sums, const char* too_big, Body body) {
+    if (!img.n_chunks) return RFQ_OK;
+    const uint64_t slice_env = ctx->opt.slice_bases, slice_bases = slice_env ? slice_env : 1500000000ull, one_pass = slice_env ? slice_env : RANGE_MAX_BASES;
+    if (!pieces && sums.v.empty() && img.bases < one_pass && img.reads < RANGE_MAX_READS) {
+        const int rc = body(range_of(img.hs, img.CHm, img.n_chunks, img.reads, img.bases), ChunkSpan{ 0, img.n_chunks, false }, true);
+        if (rc != RFQ_RANGE_TOO_BIG) return rc;
+    }
+    { const int rc = dec_host_table(ctx, img); if (rc) return rc; }
+    RangeQueue todo = plan_ranges(pieces ? *pieces : std::vector<ChunkSpan>{ { 0, img.n_chunks, false } }, img.hc.data(), slice_bases);
+    if (sums.v.empty()) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); ctx->timer.collect(); sums.add(ctx->timer); }
+    for (ChunkSpan r; todo.next(&r);) {
+        DecRange g; uint64_t reads = 0;
+        int rc = span_range(ctx, img, r, &g, &reads); if (rc) return rc;
+        ctx->timer.reset();
+        rc = reads >= RANGE_MAX_READS ? RFQ_RANGE_TOO_BIG : body(g, r, false);
+        if (rc == RFQ_RANGE_TOO_BIG) { if (!todo.halve(r)) return rfq_fail(ctx, RFQ_E_ARG, "%s", too_big); continue; }
+        if (rc) return rc;
+        ctx->timer.collect(); sums.add(ctx->timer);
+    }
+    return RFQ_OK;
+}
+// the stage times of a call: the one pass's, or the sums over its ranges
+static void dec_timings(rfq_ctx* ctx, const StageSums& sums) { if (sums.v.empty()) ctx->timer.collect(); else sums.publish(ctx->timer); }
 
 extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_decode_result* res) {
     if (!ctx || !a || !res) return RFQ_E_ARG;
@@ -486,105 +533,46 @@ extern "C" int rfq_decode_batch(rfq_ctx* ctx, const rfq_decode_args* a, rfq_deco
         if (a->split_pe) return rfq_fail(ctx, RFQ_E_DATA, "The input RFQ file was encoded by single-end FASTQ, you should not specify <out2>");
         return RFQ_OK;
     }
-    uint64_t start = 0;
-    { const int rc = dec_open(ctx, a, &start); if (rc) return rc; }
-    const DevHeader& HH = ctx->h_hdr;
-    if (a->split_pe && !(HH.flags & H_PAIRED)) return rfq_fail(ctx, RFQ_E_DATA, "The input RFQ file was encoded by single-end FASTQ, you should not specify <out2>");
-    DecStatus hs;
-    { const int rc = dec_walk(ctx, a, start, hs); if (rc) return rc; }
-    DBuf* B = ctx->b; hipStream_t S = ctx->stream;
-    // 64-bit total of the read lengths: bases, qualities and text are placed by 32-bit prefix sums below (a corrupt length table
-    // must be refused before any buffer is sized from a wrapped sum)
-    uint64_t tb = 0; for (int i = 0; i < 16; i++) tb += hs.base_slots[i];
-    const uint32_t n_chunks = hs.n_chunks; const uint64_t n_reads64 = hs.total_reads;
-    res->consumed = (size_t)hs.consumed; res->n_chunks = n_chunks; res->n_reads = n_reads64;
-    if (n_chunks == 0) return RFQ_OK;
-    const uint32_t last_flags = hs.last_flags; const int split = a->split_pe ? 1 : 0;
-    DChunk* CHm = B[DB_CHUNKS].as<DChunk>();
-    // (RFQ_SLICE_BASES: test aid - ranges of that many bases, so that the slicing logic runs on small images)
-    const uint64_t slice_env = ctx->opt.slice_bases;
-    // (a pass whose text turns out to be >= 4 GiB is redone in ranges)
-    const uint64_t slice_bases = slice_env ? slice_env : 1500000000ull, one_pass = slice_env ? slice_env : 0xFFFFFFF0ull;
-    size_t n1 = 0, n2 = 0; uint64_t nb = 0; uint8_t *o1 = nullptr, *o2 = nullptr;
-    int rc = RFQ_RANGE_TOO_BIG;
-    // bug_compat: Repaq::decompressPE as it stands (src/repaq.cpp:330-417).  A chunk with a NO_LINE_BREAK bit makes the loop read the chunk behind it
-    // to see whether it was the last (:376-387); when it was not, `continue` (:389-392, :400-403) goes on with a fresh read - decompressPE declares
-    // its chunk inside the loop - and the chunk it peeked at is never decoded; it also leaves the body before the flagged chunk's R2 text is written
-    // when it is the R1 bit that is set.  The text is decoded piece by piece: runs of chunks that survive, R1 only where the reference drops R2.
-    // Repaq::decompress (one output, :262-328) peeks the same way but keeps the peeked chunk in a variable that outlives the iteration and decodes it
-    // next: nothing is lost there, and the only effect of the bit - the last chunk's final '\n' dropped - is the default behaviour.
-    std::vector<ChunkSpan> pieces; std::vector<DChunk> hc; bool strip1 = (last_flags & C_NO_LB) != 0, strip2 = (last_flags & C_NO_LB_R2) != 0;
-    const bool compat = a->bug_compat != 0 && split;
+    DecImage img; { const int rc = dec_image(ctx, a, &img); if (rc) return rc; }
+    res->consumed = (size_t)img.hs.consumed; res->n_chunks = img.n_chunks; res->n_reads = img.reads;
+    if (img.n_chunks == 0) return RFQ_OK;
+    hipStream_t S = ctx->stream; const int split = a->split_pe ? 1 : 0;
+    // bug_compat (split output only): the pieces Repaq::decompressPE decodes, and what it strips and consumes (compat_pieces, dec/ranges.h)
+    bool strip1 = (img.hs.last_flags & C_NO_LB) != 0, strip2 = (img.hs.last_flags & C_NO_LB_R2) != 0;
+    CompatPlan cp; const bool compat = a->bug_compat != 0 && split;
     if (compat) {
-        hc.resize(n_chunks);
-        HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
-        uint32_t run = 0, end = n_chunks; strip1 = strip2 = false;
-        for (uint32_t i = 0; i < n_chunks;) {
-            const bool f1 = (hc[i].flags & C_NO_LB) != 0, f2 = split && (hc[i].flags & C_NO_LB_R2) != 0;
-            if (!f1 && !f2) { i++; continue; }
-            if (i + 1 == n_chunks) {                                            // nothing behind it in this image
-                if (!a->final) { end = i; res->consumed = (size_t)hc[i].off; }  // the caller has to show what follows: the chunk stays unconsumed
-                else { strip1 = f1; strip2 = f2; }
-                break;
-            }
-            if (split && f1) { if (i > run) pieces.push_back({ run, i, false }); pieces.push_back({ i, i + 1, true }); }
-            else pieces.push_back({ run, i + 1, false });
-            run = i + 2; i += 2;                                                // (the chunk behind a flagged one that is not the last: lost)
+        const int rc = dec_host_table(ctx, img); if (rc) return rc;
+        cp = compat_pieces(img.hc.data(), img.n_chunks, true, a->final != 0, img.hs.consumed, C_NO_LB, C_NO_LB_R2);
+        strip1 = cp.strip1; strip2 = cp.strip2; res->consumed = (size_t)cp.consumed; res->n_chunks = cp.n_chunks;
+    }
+    // One pass straight into the caller's buffers (or the context's result buffers); a pass whose text turns out to be >= 4 GiB is redone in ranges,
+    // every range into the context's result buffers and from there to its place in the caller's buffers or the context's accumulators.
+    const DecDst dst = { { a->d_out1, a->d_out2 }, { a->cap1, a->cap2 } }; DBuf* const acc[2] = { &ctx->out_acc1, &ctx->out_acc2 };
+    DecText T; memset(&T, 0, sizeof T); StageSums sums;
+    const int rc = dec_each_range(ctx, img, compat ? &cp.pieces : nullptr, sums, "a single chunk decodes to 4 GiB of text or more",
+                                  [&](const DecRange& g, const ChunkSpan& r, bool whole) -> int {
+        if (whole) return decode_range(ctx, a, g, dst, &T);
+        DecText q; const int e = decode_range(ctx, a, g, DecDst{}, &q); if (e) return e;
+        for (int k = 0; k < (split ? 2 : 1); k++) {
+            const size_t m = q.n[k], w = T.n[k];
+            if (!m || (k && r.r1_only)) continue;
+            uint8_t* to;
+            if (dst.p[k]) { if (w + m > dst.cap[k]) return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffer too small"); to = dst.p[k] + w; }
+            else { HIPCHK(ctx, acc[k]->ensure_keep(w + m + 64, w, S)); to = acc[k]->as<uint8_t>() + w; }
+            HIPCHK(ctx, hipMemcpyAsync(to, q.p[k], m, hipMemcpyDeviceToDevice, S));
+            T.n[k] += m;
         }
-        if (run < end) pieces.push_back({ run, end, false });
-        res->n_chunks = 0; for (auto& q : pieces) res->n_chunks += q.c1 - q.c0;
-    }
-    if (!compat && tb < one_pass && n_reads64 < 0x7FFFFFF0ull) {
-        const DecRange g = range_of(hs, CHm, n_chunks, n_reads64, tb);
-        rc = decode_range(ctx, a, g, a->d_out1, a->cap1, a->d_out2, a->cap2, &o1, &o2, &n1, &n2, &nb);
-        if (rc != RFQ_OK && rc != RFQ_RANGE_TOO_BIG) return rc;
-    }
-    if (rc == RFQ_RANGE_TOO_BIG) {
-        // Reads, bases and text of one pass are placed by 32-bit prefix sums: a larger image is decoded range by range (contiguous chunks of
-        // about slice_bases bases; a range whose text still does not fit is halved), every range into the context's own buffers and from
-        // there to its place in the result.
-        if (!compat) { hc.resize(n_chunks); HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
-                pieces.push_back({ 0, n_chunks, false }); }
-        std::vector<ChunkSpan> todo = plan_ranges(pieces, hc, slice_bases);  // stack of [c0, c1), first range on top
-        size_t w1 = 0, w2 = 0; n1 = n2 = 0; nb = 0;
-        StageSums sums; ctx->timer.collect(); sums.add(ctx->timer);             // (the walk, and whatever a failed one-pass attempt got through)
-        while (!todo.empty()) {
-            const ChunkSpan r = todo.back(); todo.pop_back();
-            DecRange g; uint64_t reads = 0;
-            rc = span_range(ctx, hs, CHm, hc, r, &g, &reads);
-            if (rc) return rc;
-            uint8_t *q1 = nullptr, *q2 = nullptr; size_t m1 = 0, m2 = 0; uint64_t mb = 0;
-            ctx->timer.reset();
-            rc = reads > 0x7FFFFFF0ull ? RFQ_RANGE_TOO_BIG : decode_range(ctx, a, g, nullptr, 0, nullptr, 0, &q1, &q2, &m1, &m2, &mb);
-            if (rc == RFQ_RANGE_TOO_BIG) {
-                if (r.c1 - r.c0 < 2) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk decodes to 4 GiB of text or more");
-                const uint32_t mid = r.c0 + (r.c1 - r.c0) / 2; todo.push_back({ mid, r.c1, r.r1_only }); todo.push_back({ r.c0, mid, r.r1_only }); continue;
-            }
-            if (rc != RFQ_OK) return rc;
-            sums.add(ctx->timer);
-            for (int k = 0; k < (split ? 2 : 1); k++) {
-                uint8_t* src = k ? q2 : q1; const size_t m = k ? m2 : m1; size_t& w = k ? w2 : w1; uint8_t* dcall = k ? a->d_out2 : a->d_out1;
-                        const size_t dcap = k ? a->cap2 : a->cap1;
-                if (!m || (k && r.r1_only)) continue;
-                uint8_t* to;
-                if (dcall) { if (w + m > dcap) return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffer too small"); to = dcall + w; }
-                else { DBuf& ab = k ? ctx->out_acc2 : ctx->out_acc1; HIPCHK(ctx, ab.ensure_keep(w + m + 64, w, S)); to = ab.as<uint8_t>() + w; }
-                HIPCHK(ctx, hipMemcpyAsync(to, src, m, hipMemcpyDeviceToDevice, S));
-                w += m;
-            }
-            HIPCHK(ctx, hipStreamSynchronize(S));
-            nb += mb;
-        }
-        n1 = w1; n2 = w2;
-        o1 = a->d_out1 ? a->d_out1 : ctx->out_acc1.as<uint8_t>(); o2 = a->d_out2 ? a->d_out2 : ctx->out_acc2.as<uint8_t>();
-        sums.publish(ctx->timer);
-    }
-    res->n_bases = nb;
+        HIPCHK(ctx, hipStreamSynchronize(S));
+        T.bases += q.bases; return RFQ_OK;
+    });
+    if (rc) return rc;
+    if (!sums.v.empty()) { for (int k = 0; k < 2; k++) T.p[k] = dst.p[k] ? dst.p[k] : acc[k]->as<uint8_t>(); sums.publish(ctx->timer); }
+    res->n_bases = T.bases;
     if (a->final) {   // Repaq::decompress*: drop the final '\n' when the last chunk carries the NO_LINE_BREAK bit
-        if (strip1 && n1) n1--;
-        if (split && strip2 && n2) n2--;
+        if (strip1 && T.n[0]) T.n[0]--;
+        if (split && strip2 && T.n[1]) T.n[1]--;
     }
-    res->d_fq1 = o1; res->n1 = n1; res->d_fq2 = split ? o2 : nullptr; res->n2 = split ? n2 : 0;
+    res->d_fq1 = T.p[0]; res->n1 = T.n[0]; res->d_fq2 = split ? T.p[1] : nullptr; res->n2 = split ? T.n[1] : 0;
     return RFQ_OK;
 }
 
@@ -626,19 +614,12 @@ extern "C" int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* ra, rfq
     const bool query = !ra->d_bases && !ra->d_quals && !ra->d_lens;
     if (!query && ra->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "row_len must be at least 1");
     if ((uintptr_t)ra->d_lens & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens must be 4-byte aligned");
-    // the walk and the expanded stage take the text decode's arguments (split_pe = 0, bug_compat = 0: Repaq::decompress order, nothing lost)
-    rfq_decode_args a; memset(&a, 0, sizeof a);
-    a.d_rfq = ra->d_rfq; a.n = ra->n; a.has_header = ra->has_header; a.final = ra->final; a.h_chunk_off = ra->h_chunk_off; a.n_chunk_off = ra->n_chunk_off;
+    const rfq_decode_args a = dec_view(ra);
     if (a.n == 0 && a.has_header) return RFQ_OK;                              // an empty .rfq: no reads
-    uint64_t start = 0;
-    { const int rc = dec_open(ctx, &a, &start); if (rc) return rc; }
-    DecStatus hs;
-    { const int rc = dec_walk(ctx, &a, start, hs); if (rc) return rc; }
-    hipStream_t S = ctx->stream;
-    uint64_t tb = 0; for (int i = 0; i < 16; i++) tb += hs.base_slots[i];
-    const uint32_t n_chunks = hs.n_chunks; const uint64_t n_rows = n_chunks ? hs.total_reads : 0;
-    res->consumed = (size_t)hs.consumed; res->n_chunks = n_chunks; res->n_rows = n_rows; res->n_bases = n_chunks ? tb : 0; res->max_len = n_chunks ? hs.max_len : 0;
-    if (query || n_chunks == 0) { HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect(); return RFQ_OK; }
+    DecImage img; { const int rc = dec_image(ctx, &a, &img); if (rc) return rc; }
+    const uint32_t n_chunks = img.n_chunks; const uint64_t n_rows = n_chunks ? img.reads : 0;
+    res->consumed = (size_t)img.hs.consumed; res->n_chunks = n_chunks; res->n_rows = n_rows; res->n_bases = n_chunks ? img.bases : 0; res->max_len = n_chunks ? img.hs.max_len : 0;
+    if (query || n_chunks == 0) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); ctx->timer.collect(); return RFQ_OK; }
     const uint64_t L = ra->row_len, need = n_rows * L;
     if (L < res->max_len) return rfq_fail(ctx, RFQ_E_NOSPACE, "row_len %u is shorter than the longest read: need row_len >= %u", ra->row_len, res->max_len);
     if (ra->d_bases && ra->bases_cap < need) return rfq_fail(ctx, RFQ_E_NOSPACE, "base rows too small: need %llu bytes (%llu rows of %u)", (unsigned long long)need,
@@ -651,33 +632,12 @@ extern "C" int rfq_decode_rows(rfq_ctx* ctx, const rfq_decode_rows_args* ra, rfq
     o.codes = ra->base_mode == RFQ_ROWS_CODE ? 1u : 0u;
     o.qoff4 = ra->qual_offset * 0x01010101u; o.pad_b4 = ra->pad_base * 0x01010101u; o.pad_q4 = ra->pad_qual * 0x01010101u;
     o.vec = rows_vec(L, ra->d_bases, ra->d_quals);
-    DChunk* CHm = ctx->b[DB_CHUNKS].as<DChunk>();
-    // the text path's ranges: bases and qualities of a pass are placed by 32-bit prefix sums (RFQ_SLICE_BASES forces ranges on small images)
-    const uint64_t slice_env = ctx->opt.slice_bases;
-    const uint64_t slice_bases = slice_env ? slice_env : 1500000000ull, one_pass = slice_env ? slice_env : 0xFFFFFFF0ull;
-    if (tb < one_pass && n_rows < 0x7FFFFFF0ull) {
-        const int rc = rows_range(ctx, &a, range_of(hs, CHm, n_chunks, n_rows, tb), o);
-        if (rc) return rc;
-        ctx->timer.collect();
-        return RFQ_OK;
-    }
-    std::vector<DChunk> hc(n_chunks);
-    HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
-    std::vector<ChunkSpan> todo = plan_ranges(std::vector<ChunkSpan>{ { 0, n_chunks, false } }, hc, slice_bases);
-    HIPCHK(ctx, hipStreamSynchronize(S));
-    StageSums sums; ctx->timer.collect(); sums.add(ctx->timer);                 // (the walk)
-    while (!todo.empty()) {
-        const ChunkSpan r = todo.back(); todo.pop_back();
-        DecRange g; uint64_t reads = 0;
-        int rc = span_range(ctx, hs, CHm, hc, r, &g, &reads);
-        if (rc) return rc;
-        if (g.bases >= 0xFFFFFFF0ull || reads >= 0x7FFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk holds 4 Gi bases or 2 Gi reads or more");
-        ctx->timer.reset();
-        rc = rows_range(ctx, &a, g, o);
-        if (rc) return rc;
-        ctx->timer.collect(); sums.add(ctx->timer);
-    }
-    sums.publish(ctx->timer);
+    // the text path's ranges: bases and qualities of a pass are placed by 32-bit prefix sums
+    StageSums sums;
+    const int rc = dec_each_range(ctx, img, nullptr, sums, "a single chunk holds 4 Gi bases or 2 Gi reads or more",
+                                  [&](const DecRange& g, const ChunkSpan&, bool) -> int { return g.bases >= RANGE_MAX_BASES ? RFQ_RANGE_TOO_BIG : rows_range(ctx, &a, g, o); });
+    if (rc) return rc;
+    dec_timings(ctx, sums);
     return RFQ_OK;
 }
 
@@ -693,12 +653,12 @@ static int names_lengths(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange&
     ctx->timer.begin("name_lens", S);
     const size_t nr = (size_t)g.n_reads + 2, nc = (size_t)g.n_chunks + 2;
     HIPCHK(ctx, B[DB_XV].ensure(nr * 4)); HIPCHK(ctx, B[DB_YV].ensure(nr * 4)); HIPCHK(ctx, B[DB_PQL].ensure((nr + nc) * 4));
-    if (g.pieces) HIPCHK(ctx, B[DB_PVL].ensure((nr + nc) * 8));
+    if (g.per_read_pieces) HIPCHK(ctx, B[DB_PVL].ensure((nr + nc) * 8));
     HIPCHK(ctx, B[DB_CTEXT].ensure(nc * 8)); HIPCHK(ctx, B[DB_TBASE].ensure(nc * 8)); HIPCHK(ctx, B[DB_SCAN].ensure((nc / SCAN_TILE + 2) * 16 + 1024));
     hipLaunchKernelGGL(k_dec_coords, dim3(2, g.n_chunks), dim3(64), 0, S, a->d_rfq, g.CH, D, B[DB_XV].as<uint32_t>(), B[DB_YV].as<uint32_t>());
     KCHK(ctx, "k_dec_coords");
     hipLaunchKernelGGL(k_dec_namelen, dim3(g.n_chunks), dim3(256), 0, S, a->d_rfq, g.CH, D, (const uint32_t*)B[DB_XV].as<uint32_t>(), (const uint32_t*)B[DB_YV].as<uint32_t>(),
-                       B[DB_PQL].as<uint32_t>(), g.pieces ? B[DB_PVL].as<uint2>() : (uint2*)nullptr, B[DB_CTEXT].as<unsigned long long>(), dst);
+                       B[DB_PQL].as<uint32_t>(), g.per_read_pieces ? B[DB_PVL].as<uint2>() : (uint2*)nullptr, B[DB_CTEXT].as<unsigned long long>(), dst);
     KCHK(ctx, "k_dec_namelen");
     scan_exclusive<unsigned long long>(S, B[DB_CTEXT].as<unsigned long long>(), B[DB_TBASE].as<unsigned long long>(), g.n_chunks, B[DB_SCAN].as<unsigned long long>(), 1);
     ctx->timer.end(S);
@@ -718,7 +678,7 @@ static int names_write(rfq_ctx* ctx, const rfq_decode_args* a, const DecRange& g
     const uint32_t bx = grid_x_for(g.n_chunks, (std::max(g.max_reads, 1u) + NM_READS - 1u) / NM_READS, 5u * ctx->n_cu);
     hipLaunchKernelGGL(k_dec_names, dim3(bx, g.n_chunks), dim3(256), 0, S, a->d_rfq, (uint64_t)a->n, g.CH, ctx->d_hdr.as<DevHeader>(),
                        (const uint32_t*)B[DB_XV].as<uint32_t>(), (const uint32_t*)B[DB_YV].as<uint32_t>(), (const uint32_t*)B[DB_PQL].as<uint32_t>(),
-                       g.pieces ? (const uint2*)B[DB_PVL].as<uint2>() : (const uint2*)nullptr, (const unsigned long long*)B[DB_TBASE].as<unsigned long long>(), o, g.n_chunks);
+                       g.per_read_pieces ? (const uint2*)B[DB_PVL].as<uint2>() : (const uint2*)nullptr, (const unsigned long long*)B[DB_TBASE].as<unsigned long long>(), o, g.n_chunks);
     KCHK(ctx, "k_dec_names");
     ctx->timer.end(S);
     HIPCHK(ctx, hipStreamSynchronize(S));
@@ -732,74 +692,41 @@ extern "C" int rfq_decode_names(rfq_ctx* ctx, const rfq_decode_names_args* na, r
     if (na->n && !na->d_rfq) return rfq_fail(ctx, RFQ_E_ARG, "null rfq pointer");
     if ((uintptr_t)na->d_name_off & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_name_off must be 8-byte aligned");
     const bool query = na->size_only != 0;
-    // the walk takes the text decode's arguments (split_pe = 0, bug_compat = 0: Repaq::decompress order, nothing lost)
-    rfq_decode_args a; memset(&a, 0, sizeof a);
-    a.d_rfq = na->d_rfq; a.n = na->n; a.has_header = na->has_header; a.final = na->final; a.h_chunk_off = na->h_chunk_off; a.n_chunk_off = na->n_chunk_off;
-    DecStatus hs; memset(&hs, 0, sizeof hs);
-    if (a.n == 0 && a.has_header) { HIPCHK(ctx, hipSetDevice(ctx->device)); ctx->timer.reset(); }      // an empty .rfq: no reads
-    else {
-        uint64_t start = 0;
-        { const int rc = dec_open(ctx, &a, &start); if (rc) return rc; }
-        { const int rc = dec_walk(ctx, &a, start, hs); if (rc) return rc; }
-    }
+    const rfq_decode_args a = dec_view(na);
+    DecImage img; { const int rc = dec_image(ctx, &a, &img); if (rc) return rc; }      // (an empty .rfq: no reads, offsets { 0 })
     hipStream_t S = ctx->stream;
-    uint64_t tb = 0; for (int i = 0; i < 16; i++) tb += hs.base_slots[i];
-    const uint32_t n_chunks = hs.n_chunks; const uint64_t n_rows = n_chunks ? hs.total_reads : 0;
-    res->consumed = (size_t)hs.consumed; res->n_chunks = n_chunks; res->n_rows = n_rows;
+    const uint32_t n_chunks = img.n_chunks; const uint64_t n_rows = n_chunks ? img.reads : 0;
+    res->consumed = (size_t)img.hs.consumed; res->n_chunks = n_chunks; res->n_rows = n_rows;
     // (the offsets' size is known here: a caller's array that cannot hold them is refused before any length is looked at)
     if (!query && na->d_name_off && na->off_cap < n_rows + 1) return rfq_fail(ctx, RFQ_E_NOSPACE, "offset array too small: need %llu entries", (unsigned long long)(n_rows + 1));
-    DChunk* CHm = ctx->b[DB_CHUNKS].as<DChunk>();
-    // the ranges of rfq_decode_rows (RFQ_SLICE_BASES forces ranges on small images; the reads of a range count from 0 in 32 bits)
-    const uint64_t slice_env = ctx->opt.slice_bases;
-    const uint64_t slice_bases = slice_env ? slice_env : 1500000000ull, one_pass = slice_env ? slice_env : 0xFFFFFFF0ull;
-    const bool one = tb < one_pass && n_rows < 0x7FFFFFF0ull;
-    std::vector<DChunk> hc; std::vector<ChunkSpan> spans;                      // (spans: the first range LAST - plan_ranges' stack)
-    StageSums sums;
-    if (n_chunks && !one) {
-        hc.resize(n_chunks);
-        HIPCHK(ctx, hipMemcpy(hc.data(), CHm, (size_t)n_chunks * sizeof(DChunk), hipMemcpyDeviceToHost));
-        spans = plan_ranges(std::vector<ChunkSpan>{ { 0, n_chunks, false } }, hc, slice_bases);
-        HIPCHK(ctx, hipStreamSynchronize(S));
-        ctx->timer.collect(); sums.add(ctx->timer);                         // (the walk)
-    }
-    // ---- every range's bytes; 64-bit from here on: range bases are sums on the host, chunk bases a 64-bit scan
-    uint64_t names_len = 0; uint32_t max_name = 0; DecRange g1; memset(&g1, 0, sizeof g1);
-    if (n_chunks && one) {
-        g1 = range_of(hs, CHm, n_chunks, n_rows, tb); NamesSize z;
-        const int rc = names_lengths(ctx, &a, g1, &z); if (rc) return rc;
-        names_len = z.bytes; max_name = z.max_name;
-    } else for (size_t i = spans.size(); i-- > 0;) {
-        DecRange g; uint64_t reads = 0; NamesSize z;
-        int rc = span_range(ctx, hs, CHm, hc, spans[i], &g, &reads); if (rc) return rc;
-        if (reads >= 0x7FFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "a single chunk holds 2 Gi reads or more");
-        ctx->timer.reset();
-        rc = names_lengths(ctx, &a, g, &z); if (rc) return rc;
-        ctx->timer.collect(); sums.add(ctx->timer);
+    // the ranges of rfq_decode_rows (the reads of a range count from 0 in 32 bits), twice: every range's bytes - 64-bit from here on: range bases are
+    // sums on the host, chunk bases a 64-bit scan -, then the writer
+    StageSums sums; const char* const too_big = "a single chunk holds 2 Gi reads or more";
+    uint64_t names_len = 0; uint32_t max_name = 0;
+    int rc = dec_each_range(ctx, img, nullptr, sums, too_big, [&](const DecRange& g, const ChunkSpan&, bool) -> int {
+        NamesSize z; const int e = names_lengths(ctx, &a, g, &z); if (e) return e;
         names_len += z.bytes; max_name = std::max(max_name, z.max_name);
-    }
+        return RFQ_OK;
+    });
+    if (rc) return rc;
     res->names_len = names_len; res->max_name = max_name;
-    if (query) { HIPCHK(ctx, hipStreamSynchronize(S)); if (spans.empty()) ctx->timer.collect(); else sums.publish(ctx->timer); return RFQ_OK; }
+    if (query) { HIPCHK(ctx, hipStreamSynchronize(S)); dec_timings(ctx, sums); return RFQ_OK; }
     if (na->d_names && na->names_cap < names_len) return rfq_fail(ctx, RFQ_E_NOSPACE, "name blob too small: need %llu bytes", (unsigned long long)names_len);
     NamesOut o; memset(&o, 0, sizeof o);
     if (na->d_names) o.names = na->d_names; else { HIPCHK(ctx, ctx->names_blob.ensure((size_t)names_len + 64)); o.names = ctx->names_blob.as<uint8_t>(); }
     if (na->d_name_off) o.off = na->d_name_off; else { HIPCHK(ctx, ctx->names_off.ensure((size_t)(n_rows + 1) * 8)); o.off = ctx->names_off.as<uint64_t>(); }
     o.end = names_len;
-    if (!n_chunks) { HIPCHK(ctx, hipMemsetAsync(o.off, 0, 8, S)); HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect(); }
-    else if (one) {
-        const int rc = names_write(ctx, &a, g1, o); if (rc) return rc;
-        ctx->timer.collect();
-    } else {
-        for (size_t i = spans.size(); i-- > 0;) {
-            DecRange g; uint64_t reads = 0; NamesSize z;
-            int rc = span_range(ctx, hs, CHm, hc, spans[i], &g, &reads); if (rc) return rc;
-            ctx->timer.reset();
-            rc = names_lengths(ctx, &a, g, &z); if (rc) return rc;
-            rc = names_write(ctx, &a, g, o); if (rc) return rc;
-            ctx->timer.collect(); sums.add(ctx->timer);
-            o.base += z.bytes;
-        }
-        sums.publish(ctx->timer);
-    }
+    if (!n_chunks) { HIPCHK(ctx, hipMemsetAsync(o.off, 0, 8, S)); HIPCHK(ctx, hipStreamSynchronize(S)); }
+    // (one pass: the lengths of the sizes pass are still in place; a range's are gone, its buffers were the next range's: once more)
+    rc = dec_each_range(ctx, img, nullptr, sums, too_big, [&](const DecRange& g, const ChunkSpan&, bool whole) -> int {
+        NamesSize z = { 0, 0 };
+        if (!whole) { const int e = names_lengths(ctx, &a, g, &z); if (e) return e; }
+        const int e = names_write(ctx, &a, g, o); if (e) return e;
+        o.base += z.bytes;
+        return RFQ_OK;
+    });
+    if (rc) return rc;
+    dec_timings(ctx, sums);
     res->d_names = o.names; res->d_name_off = o.off;
     return RFQ_OK;
 }

@@ -378,3 +378,46 @@ def check_decode_formulation(codec, form, rfq, split, want, chunk_bases=1_000_00
         got = codec.decode_bytes(rfq, split_pe=split)
         _marker_ok(codec, marker)
     assert got == want, (form, [len(x) for x in (got if split else (got,))])
+
+
+_RANGES_IMAGE = []
+
+
+def ranges_image():
+    """pe150, 1500 pairs in chunks of 20 k bases, no line break at the end of R1 (every chunk carries the R1 bit: bug_compat writes R1 alone of every other chunk and
+    loses the ones between): (image, text pair, interleaved text, bug_compat's text pair) - the texts from the oracle, made once"""
+    if not _RANGES_IMAGE:
+        fq1, fq2 = O.gen(O.NOVA_PE150, 1500, seed=4, nonl=1)
+        rfq = O.encode_file(fq1, fq2, O.PE_TWO_FILES, 20000)
+        _RANGES_IMAGE.append((rfq, O.decode_file(rfq, True), O.decode_file(rfq, False), O.decode_file(rfq, True, bug_compat=True)))
+    return _RANGES_IMAGE[0]
+
+
+def check_decode_ranges(codec, exact):
+    """rfq_decode_batch range by range (RFQ_SLICE_BASES: two chunks per range) on ranges_image(): into the context's accumulators and into the caller's buffers,
+    one output and two; bug_compat's pieces, R1-only ones among them; a caller's buffer that is full in the middle of the ranges.  exact: behind the serial walk."""
+    from repaq_amd import RfqError
+    rfq, pair, one, compat = ranges_image()
+    assert pair == O.decode_file(rfq, True) and len(O.chunk_table(rfq)) - 1 >= 20
+    assert compat != pair and 0 < len(compat[1]) < len(compat[0]) < len(pair[0])          # (text is lost, of R2 more than of R1: pieces of which only R1 is written)
+    opts = {"RFQ_SLICE_BASES": "45000"}
+    if exact:
+        opts["RFQ_WALK"] = "exact"
+    roomy = (len(pair[0]) + 64, len(pair[1]) + 64)
+    with _Options(codec, opts):
+        assert codec.decode_bytes(rfq, split_pe=True) == pair
+        assert "walk" in dict(codec.timings())
+        _marker_ok(codec, "emit_expanded" if exact else "emit")
+        assert codec.decode_bytes(rfq, split_pe=True, out_caps=roomy) == pair
+        assert codec.decode_bytes(rfq, split_pe=False) == one
+        assert codec.decode_bytes(rfq, split_pe=False, out_caps=(len(one) + 64, 0)) == one
+        assert codec.decode_bytes(rfq, split_pe=True, bug_compat=True) == compat
+        assert codec.decode_bytes(rfq, split_pe=True, bug_compat=True, out_caps=roomy) == compat
+        # room for the first ranges, not for all: refused where the text no longer fits (the one-pass refusal says what it needs: not that one)
+        for caps in ((len(pair[0]) // 2, roomy[1]), (roomy[0], len(pair[1]) - 1)):
+            try:
+                codec.decode_bytes(rfq, split_pe=True, out_caps=caps)
+                raise AssertionError("decode into buffers of %r bytes passed" % (caps,))
+            except RfqError as e:
+                assert e.code == -8 and "output buffer too small" in e.message and "need" not in e.message, e
+        assert codec.decode_bytes(rfq, split_pe=True, out_caps=roomy) == pair                 # (the context is as good as new behind the refusal)

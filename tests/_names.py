@@ -52,6 +52,20 @@ def check(codec, rfq: bytes, want=None, **kw):
     return got
 
 
+def check_size_only(codec, rfq: bytes, **kw):
+    """the size query alone: the counts of check(), no pointers, and of the stages the lengths but not the writer"""
+    want = expected(rfq)
+    d = codec.dev_put(rfq)
+    try:
+        q = codec.decode_names(d, len(rfq), size_only=True, **kw)
+    finally:
+        codec.dev_free(d)
+    assert (q.n_rows, q.names_len, q.max_name, q.consumed) == (len(want), sum(len(x) for x in want), max([len(x) for x in want] + [0]), len(rfq))
+    assert q.d_names is None and q.d_name_off is None
+    stages = dict(codec.timings())
+    assert {"walk", "name_lens"} <= set(stages) and "names" not in stages, stages
+
+
 # ---------------------------------------------------------------- small shapes where the writer can go wrong
 def _image(text, text2=b"", paired=O.SE, chunk_bases=8000, min_chunks=3):
     rfq = O.encode_file(text, text2, paired, chunk_bases)

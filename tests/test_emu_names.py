@@ -79,6 +79,7 @@ def test_ranges_forced_by_slice_bases(codec, walk):
         codec.set_option("RFQ_WALK", "exact")
     N.check(codec, rfq)
     assert {"walk", "name_lens", "names"} <= set(dict(codec.timings())), codec.timings()
+    N.check_size_only(codec, rfq)                                      # (the first of the two passes over the ranges alone)
 
 
 @pytest.mark.parametrize("walk", ["guess", "exact"])

@@ -157,3 +157,9 @@ def test_decode_with_chunk_index(codec):
 @pytest.mark.parametrize("name", sorted(E.rle_goldens()))
 def test_legacy_run_length_quality_images_decode_like_the_reference(codec, name):
     E.check_rle_decode(codec, name, E.rle_goldens()[name])
+
+
+@pytest.mark.parametrize("walk", ["guess", "exact"])
+def test_ranges_forced_by_slice_bases(codec, walk):
+    """the text decode range by range at small size: the shared range loop's branches (tests/_engine.check_decode_ranges)"""
+    E.check_decode_ranges(codec, walk == "exact")

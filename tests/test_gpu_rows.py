@@ -117,6 +117,20 @@ def test_formulations(codec, opts):
     W.check(codec, W.generated("bgi_q40"), codes=False, chunk_off=O.chunk_table(W.generated("bgi_q40")))
 
 
+@pytest.mark.parametrize("walk", ["guess", "exact"])
+def test_ranges_with_one_output_left_out(codec, walk):
+    rfq = W.generated("pe150")
+    codec.set_option("RFQ_SLICE_BASES", str(45000))                    # two or three chunks of 20 k bases per range
+    if walk == "exact":
+        codec.set_option("RFQ_WALK", "exact")
+    n, ml, B, Q, lens = W.expected(rfq, row_len=160, codes=True)
+    for which in ("bases", "quals", "lens"):
+        gn, gml, gb, gq, gl = codec.decode_rows_bytes(rfq, row_len=160, codes=True, **{which: False})
+        assert (gn, gml) == (n, ml)
+        for name, got, want in (("bases", gb, B), ("quals", gq, Q), ("lens", gl, lens)):
+            assert (got is None) if name == which else np.array_equal(got, want), (which, name)
+
+
 @pytest.mark.parametrize("step", [700, 5000])
 def test_image_slices_concatenate_to_the_whole(codec, step):
     rfq = W.generated("pe150")
