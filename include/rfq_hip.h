@@ -505,6 +505,59 @@ typedef struct {
 } rfq_merge_rows_result;
 RFQ_API int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_merge_rows_args* args, rfq_merge_rows_result* res);
 
+/* Duplicate removal, between rfq_judge_rows and rfq_select_rows: rows -> a keep byte per row that leaves ONE unit of every class of identical units (in the manner of
+ * fastp --dedup and clumpify dedupe; exact byte equality, no parity with either is claimed), the representative and the size of every class, a class-size histogram
+ * and a summary.  Like rfq_judge_rows it DECIDES and moves no bytes: d_keep is exactly rfq_select_rows' d_keep - adapter -> judge -> dedup -> select -> encode, all on
+ * the GPU.  It is the one step of the family that relates rows to each other.  No float anywhere; the same call gives the same bytes.
+ * Units.  pairs = 0: a unit is a row, U = n_rows.  pairs = 1: a unit is the pair of rows 2k / 2k + 1, U = n_rows / 2.
+ * Key.  With l = rows->d_lens[i] the key of a row is the number k = min(l, key_len) (key_len == 0: k = l) and its base bytes [0, k) as they lie: a byte compare, like
+ * the judge's trans.  rows->base_mode is not looked at - lower case differs from upper case, N is a base like any other.  A pair's key is R1's key followed by R2's,
+ * both lengths included: (AB, C) and (A, BC) differ, and a pair with its mates swapped differs from the pair.  Bytes at positions >= k - padding, or the tail beyond
+ * key_len - never matter; two rows of length 0 are equal.  Lengths cut by rfq_adapter_rows or by the judge come in as rows->d_lens (the composition the judge uses
+ * behind the adapter step); a start offset is not offered.  Names are not looked at, quality rows only with RFQ_DEDUP_BEST_QUAL.
+ * Candidates.  d_in: [n_rows] bytes, NULL = all.  A unit is a candidate when the byte of every one of its rows is non-zero.  A unit that is no candidate gets keep 0,
+ * dup_of -1, count 0 and belongs to no class: a read the judge has failed does not stand in for its passing copies.
+ * Classes.  The candidates with identical keys form a class.  Every output is a function of the classes alone - never of a hash, of the table's size or of the order
+ * in which the units arrive.  The representative of a class: RFQ_DEDUP_FIRST - its lowest unit index; RFQ_DEDUP_BEST_QUAL - the member with the highest sum of quality
+ * bytes over its key window [0, k) (of both mates with pairs), ties to the lowest index.
+ * Outputs; each may be NULL and is then not produced, the result is filled either way.  d_keep: [n_rows] bytes, 1 for the rows of a representative, 0 for all others
+ * (both rows of a pair get the unit's byte).  d_dup_of: [U] int32, the unit index of the unit's representative (its own for a representative, -1 for a unit that is
+ * no candidate).  d_count: [U] uint32, the class size at the representative, 0 elsewhere.  d_hist: [hist_len] uint64, zeroed, then bin c - 1 = the number of classes
+ * of size c, the last bin holds every larger class (the convention of rfq_adapter_rows' insert histogram).
+ * Result.  n_units = U; n_candidates; n_classes = the kept units; n_dups = n_candidates - n_classes; max_class = the largest class size; bases_in / bases_kept = the
+ * sum of l over the rows of the candidates / of the kept units.
+ * RFQ_E_ARG, judged on the host: pairs other than 0 / 1, an odd n_rows with pairs; an unknown mode; RFQ_DEDUP_BEST_QUAL without rows->d_quals; row_len == 0, a NULL
+ * d_lens or d_bases with rows; row_len above 2^22 (the score is 32 bits); a d_lens / d_dup_of / d_count that is not 4-byte or a d_hist that is not 8-byte aligned;
+ * hist_len == 0 with d_hist, or hist_len > 1024; an output that overlaps an input (byte ranges are compared; d_in is an input: the mask is not updated in place);
+ * U >= 2^31 - 1.  RFQ_E_ARG, judged on the device, the message names the first such row: lens[i] < 0 or > row_len, of ANY row, candidate or not - what the outputs
+ * hold is then unspecified; nothing outside the row buffers is read for such a row.  RFQ_E_HIP when the memory of the table cannot be had; the message says how many
+ * bytes.  After any refusal the context stays usable.
+ * The table.  Classes are found through a hash table in context-owned device memory: S slots, S the power of two >= max(1024, 2 * U), 20 bytes a slot, and 16 bytes
+ * of scratch per unit; it is sized and zeroed PER CALL.  A table carried across the batches of one file - duplicates of a read that came in an earlier call - is
+ * not offered: a caller that needs it passes the file's rows in one call.  RFQ_DEDUP=collide keeps four bits of the hash (every probe walks a long chain and every
+ * comparison is a byte compare): another formulation of the same result, for the tests.
+ * The row buffers may have any alignment, on rfq_judge_rows' terms - whole 16-byte groups with row_len % 16 == 0 and 16-byte alignment, otherwise at their own
+ * alignment, never a byte outside [d_x, d_x + n_rows * row_len).  n_rows * row_len may exceed 4 GiB.  Synchronous on the context's stream, one read-back; stage times
+ * through rfq_last_timings (dedup:key, dedup:claim, dedup:resolve). */
+#define RFQ_DEDUP_FIRST     0
+#define RFQ_DEDUP_BEST_QUAL 1
+typedef struct {
+    int32_t  pairs;                       /* 1: a unit is the pair of rows 2k / 2k + 1 (n_rows must be even)            */
+    int32_t  mode;                        /* RFQ_DEDUP_FIRST / RFQ_DEDUP_BEST_QUAL                                      */
+    uint32_t key_len;                     /* > 0: only the first key_len bases of a row are its key; 0: the whole read  */
+    uint32_t hist_len;                    /* entries of d_hist, <= 1024                                                 */
+    const uint8_t* d_in;                  /* [n_rows] bytes, non-zero = the row is a candidate (rfq_judge_rows' d_keep); NULL = every row */
+    uint8_t*  d_keep;                     /* [n_rows] 1 / 0, or NULL                                                    */
+    int32_t*  d_dup_of;                   /* [U] or NULL                                                                */
+    uint32_t* d_count;                    /* [U] or NULL                                                                */
+    uint64_t* d_hist;                     /* [hist_len], 8-byte aligned, or NULL                                        */
+} rfq_dedup_rows_args;
+typedef struct {
+    uint64_t n_units, n_candidates, n_classes, n_dups, max_class;
+    uint64_t bases_in, bases_kept;
+} rfq_dedup_rows_result;
+RFQ_API int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_dedup_rows_args* args, rfq_dedup_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -538,7 +591,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

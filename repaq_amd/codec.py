@@ -376,6 +376,23 @@ class RfqCodec:
         self._check(self._L.rfq_merge_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
+    # --- between the judge and select_rows: one unit of every class of identical units is kept (rfq_dedup_rows)
+    def dedup_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, pairs=False, key_len=0, best_qual=False, mode=None, hist_len=0, d_in=None, d_keep=None,
+                   d_dup_of=None, d_count=None, d_hist=None):
+        """rfq_dedup_rows: the rows as judge_rows takes them (names are not looked at; d_quals only with best_qual, else it may be None) and the rules of
+        include/rfq_hip.h: a unit is a row, or with pairs the rows 2k / 2k + 1; its key the first key_len bases (0: all) of each of its rows, lengths included;
+        units with identical keys form a class, of which the lowest unit index - with best_qual the member with the highest score sum over its key, ties to the
+        lowest index - is kept.  d_in: n_rows bytes, non-zero = the row is a candidate (judge_rows' d_keep; None: all).  d_keep: n_rows bytes - what select_rows
+        takes -, d_dup_of: U int32 (the representative's unit index, -1: no candidate), d_count: U uint32 (the class size at the representative), d_hist: hist_len
+        uint64 (bin c - 1: classes of size c, the last bin every larger one); an output that is None is not produced.  mode: the C constant as it stands, for the
+        tests of the refusal.  Returns DedupRowsResult (n_units, n_candidates, n_classes, n_dups, max_class, bases_in, bases_kept)."""
+        rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, False, 0)
+        a = A.DedupRowsArgs(1 if pairs else 0, mode if mode is not None else (A.DEDUP_BEST_QUAL if best_qual else A.DEDUP_FIRST), key_len, hist_len, d_in, d_keep,
+                            d_dup_of, d_count, d_hist)
+        r = A.DedupRowsResult()
+        self._check(self._L.rfq_dedup_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

@@ -101,6 +101,7 @@ struct RfqOpts {
     bool judge_general = false;       // RFQ_JUDGE=general  rfq_judge_rows: the any-length kernel for every row length, in tiles of 64 window starts (default: rows of up to 1024 bytes are held whole)
     bool adapter_general = false;     // RFQ_ADAPTER=general  rfq_adapter_rows: the any-length kernel (a lane per shift, byte by byte) for every row length (default: rows of up to 1024 bytes as bit planes in LDS)
     bool merge_general = false;       // RFQ_MERGE=general  rfq_merge_rows: the lane-per-byte kernel with the rule as plain branches (default: a lane per 16-byte group, the rule as byte masks in registers)
+    bool dedup_collide = false;       // RFQ_DEDUP=collide  rfq_dedup_rows: four bits of the fingerprint for the start slot and the tag - long probe chains, every tag hit a byte compare (default: all 64)
     bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)
 };
 struct rfq_ctx {
@@ -179,6 +180,8 @@ struct rfq_ctx {
     // rfq_rows_to_text / rfq_encode_rows: the record offsets of each text, the verdict block, the context-owned texts (they outlive the encoder's own buffers)
     DBuf rows_off[2], rows_stat, rows_txt[2];
     DBuf names_blob, names_off;            // rfq_decode_names: the context-owned name lines and their offsets
+    // rfq_dedup_rows: per unit the fingerprint, the score and the class's slot; per slot the table word, the best member and the class size (sized and zeroed per call)
+    DBuf dedup_fp, dedup_score, dedup_slot, dedup_tab, dedup_best, dedup_cnt;
     std::vector<uint64_t> chunk_off;
     std::vector<uint64_t> scan_end[2];     // rfq_scan_batch: end offset of every chunk in each input stream
     StageTimer timer;

@@ -1603,3 +1603,83 @@ extern "C" int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_a
     res->pairs_found = hs.c[0]; res->rows_cut = hs.c[1]; res->rows_cut_overlap = hs.c[2]; res->rows_cut_adapter = hs.c[3]; res->bases_in = hs.c[4]; res->bases_out = hs.c[5];
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- rows -> a keep byte that leaves one unit of every class of identical units: rfq_dedup_rows of include/rfq_hip.h
+// Three kernels and one read-back (enc/rows_dedup.h): the key kernel (which one is the row length's to say, as in rfq_judge_rows) leaves a fingerprint and a score per
+// unit, the claim kernel finds every candidate's class in a hash table of S slots, the resolve kernel writes the outputs.  The table lives in context-owned buffers
+// and is sized and zeroed PER CALL: a table carried across the batches of one file is not offered (include/rfq_hip.h).
+extern "C" int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_dedup_rows_args* a, rfq_dedup_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows;
+    if (a->pairs != 0 && a->pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
+    if (a->pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    if (a->mode != RFQ_DEDUP_FIRST && a->mode != RFQ_DEDUP_BEST_QUAL) return rfq_fail(ctx, RFQ_E_ARG, "unknown mode %d", a->mode);
+    const bool best = a->mode == RFQ_DEDUP_BEST_QUAL;
+    if (n && best && !in->d_quals) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_DEDUP_BEST_QUAL needs rows->d_quals");
+    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if (in->row_len > (1u << 22)) return rfq_fail(ctx, RFQ_E_ARG, "row_len is at most 2^22 = %u: the score is a 32-bit sum (got %u)", 1u << 22, in->row_len);
+    const uint64_t units = a->pairs ? n / 2 : n;
+    if (units >= 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many units for one call (%llu)", (unsigned long long)units);
+    if (n && (!in->d_lens || !in->d_bases)) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens / d_bases");
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_dup_of | (uintptr_t)a->d_count) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_dup_of and d_count must be 4-byte aligned");
+    if ((uintptr_t)a->d_hist & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_hist must be 8-byte aligned");
+    if (a->hist_len > DD_HIST_MAX || (a->d_hist && a->hist_len == 0u)) return rfq_fail(ctx, RFQ_E_ARG, "hist_len must be 1 .. %u with d_hist, at most %u without (got %u)", DD_HIST_MAX, DD_HIST_MAX, a->hist_len);
+    int rc;
+    {
+        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
+        const Span ins[] = { { in->d_bases, rows_in, "rows->d_bases" }, { best ? in->d_quals : nullptr, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" }, { a->d_in, n, "d_in" } };
+        const Span outs[] = { { a->d_keep, n, "d_keep" }, { a->d_dup_of, units * 4ull, "d_dup_of" }, { a->d_count, units * 4ull, "d_count" }, { a->d_hist, a->hist_len * 8ull, "d_hist" } };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+    }
+    res->n_units = units;
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    if (a->d_hist) HIPCHK(ctx, hipMemsetAsync(a->d_hist, 0, (size_t)a->hist_len * 8, S));
+    if (!n) { HIPCHK(ctx, hipStreamSynchronize(S)); return RFQ_OK; }
+    uint64_t slots = 1024;
+    while (slots < 2 * units) slots <<= 1;
+    DedupIn di; memset(&di, 0, sizeof di);
+    {
+        struct Want { DBuf* d; unsigned long long bytes; } const want[] = { { &ctx->dedup_fp, units * 8ull }, { &ctx->dedup_score, units * 4ull }, { &ctx->dedup_slot, units * 4ull },
+                                                                            { &ctx->dedup_tab, slots * 8ull }, { &ctx->dedup_best, slots * 8ull }, { &ctx->dedup_cnt, slots * 4ull } };
+        for (const Want& w : want)
+            if (const hipError_t e = w.d->ensure((size_t)w.bytes); e != hipSuccess) {
+                (void)hipGetLastError();
+                return rfq_fail(ctx, RFQ_E_HIP, "the table of %llu slots for %llu units needs %llu bytes of device memory (a buffer of %llu bytes could not be had): %s",
+                                (unsigned long long)slots, (unsigned long long)units, (unsigned long long)(slots * 20ull + units * 16ull), w.bytes, hipGetErrorString(e));
+            }
+    }
+    di.b = in->d_bases; di.q = best ? in->d_quals : nullptr; di.lens = in->d_lens; di.cand = a->d_in; di.total = n * in->row_len;
+    di.n_rows = (uint32_t)n; di.n_units = (uint32_t)units; di.row_len = in->row_len; di.vec_in = rows_vec(in->row_len, in->d_bases, di.q);
+    di.pairs = a->pairs ? 1u : 0u; di.key_len = a->key_len; di.collide = ctx->opt.dedup_collide ? 1u : 0u; di.hist_len = a->hist_len;
+    di.fp = ctx->dedup_fp.as<unsigned long long>(); di.score = ctx->dedup_score.as<uint32_t>(); di.slot = ctx->dedup_slot.as<uint32_t>();
+    di.tab = ctx->dedup_tab.as<unsigned long long>(); di.best = ctx->dedup_best.as<unsigned long long>(); di.cnt = ctx->dedup_cnt.as<uint32_t>(); di.S = slots;
+    di.keep = a->d_keep; di.dup_of = a->d_dup_of; di.count = a->d_count; di.hist = (unsigned long long*)a->d_hist;
+    const uint32_t ublocks = (uint32_t)((units + 255u) / 256u);
+    ctx->timer.begin("dedup:key", S);
+    { ClearList z; memset(&z, 0, sizeof z); z.add(di.tab, slots * 8, 0u); z.add(di.best, slots * 8, 0u); z.add(di.cnt, slots * 4, 0u); clear_list(S, z); KCHK(ctx, "k_clear_list"); }
+    DedupStat* dst = nullptr;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if (in->row_len > 1024u) hipLaunchKernelGGL(k_dedup_key_long, dim3((uint32_t)units), dim3(64), 0, S, di, dst);
+    else if (in->row_len <= 256u) hipLaunchKernelGGL(k_dedup_key<16>, dim3((uint32_t)((units + 16u * DD_ITER - 1u) / (16u * DD_ITER))), dim3(256), 0, S, di, dst);
+    else hipLaunchKernelGGL(k_dedup_key<64>, dim3((uint32_t)((units + 4u * DD_ITER - 1u) / (4u * DD_ITER))), dim3(256), 0, S, di, dst);
+    KCHK(ctx, "k_dedup_key");
+    ctx->timer.end(S);
+    ctx->timer.begin("dedup:claim", S);
+    hipLaunchKernelGGL(k_dedup_claim, dim3(ublocks), dim3(256), 0, S, di);
+    KCHK(ctx, "k_dedup_claim");
+    ctx->timer.end(S);
+    ctx->timer.begin("dedup:resolve", S);
+    hipLaunchKernelGGL(k_dedup_resolve, dim3(ublocks), dim3(256), 0, S, di, dst);
+    KCHK(ctx, "k_dedup_resolve");
+    ctx->timer.end(S);
+    DedupStat hs; memset(&hs, 0, sizeof hs);
+    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    ctx->timer.collect();
+    if (hs.err & DD_ERR_LEN)
+        return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, (unsigned long long)hs.bad_row);
+    res->n_candidates = hs.c[0]; res->bases_in = hs.c[1]; res->n_classes = hs.c[2]; res->bases_kept = hs.c[3]; res->max_class = hs.c[4]; res->n_dups = hs.c[0] - hs.c[2];
+    return RFQ_OK;
+}

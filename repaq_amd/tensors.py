@@ -50,6 +50,14 @@ the pairs without an overlap come back as they are:
     a = trim_adapters(codec, t, pairs=True); m = merge_pairs(codec, t, a["insert"])
     image = encode_tensors(codec, *(m["merged"][k] for k in ("bases", "quals", "lens", "names", "name_off")))          # SE; m["unmerged"]: the other pairs, PE
 
+judge -> dedup -> select: rfq_dedup_rows relates the rows to each other - of every class of reads (or pairs) with identical bases it keeps one, the first or the
+one with the best scores - and leaves the keep mask select_rows takes.  The judge's mask goes in as `keep`, so that a read that fails does not stand in for its
+passing copies; the windows are still the judge's:
+
+    j = judge_rows(codec, t, cut_tail=True, cut_window=4, cut_mean_q=20, min_mean_q=20)
+    d = dedup_rows(codec, dict(t, lens=j["length"]), pairs=True, keep=j["keep"], best_qual=True)      # d["summary"]["n_dups"]: the duplication count of a QC report
+    s = select_rows(codec, t, keep=d["keep"], start=j["start"], length=j["length"], pairs=True, min_len=36)
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -263,6 +271,45 @@ def merge_pairs(codec, t, insert, row_len=None, pad=255, unmerged=True, codes=Tr
     out = {"merged": merged, "summary": {f: int(getattr(q, f)) for f in MERGE_FIELDS}}
     if unmerged:
         out["unmerged"] = select_rows(codec, t, keep=(insert < 0).repeat_interleave(2), pairs=True)
+    return out
+
+
+DEDUP_FIELDS = ("n_units", "n_candidates", "n_classes", "n_dups", "max_class", "bases_in", "bases_kept")
+
+
+def dedup_rows(codec, t, pairs=False, key_len=0, best_qual=False, keep=None, hist_len=0):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "lens" and, with best_qual, "quals") -> {"keep": [n] uint8 - 1 for the rows of the ONE unit
+    that is kept of every class of units with identical keys (rfq_dedup_rows), what select_rows takes -, "dup_of": [U] int32 (the unit index of the unit's
+    representative, -1: no candidate), "count": [U] int32 (the class size at the representative, 0 elsewhere), "summary": dict of the batch's counts}.  A unit is
+    a row (U = n), with pairs the rows 2k / 2k + 1 (U = n / 2); its key the first key_len bases (0: all) of each of its rows as they lie, the lengths included.
+    The kept member is the lowest index, with best_qual the one with the highest score sum over its key (ties: the lowest index).  keep: [n] bool / uint8 - only
+    units all of whose rows are non-zero there are looked at (judge_rows' "keep"); the others get keep 0, dup_of -1.  hist_len > 0: "hist", [hist_len] int64, bin
+    c - 1 = classes of size c, the last bin every larger class.  One call, ordered with torch's current stream; the context goes back to its own stream afterwards."""
+    bases, lens = t["bases"], t["lens"]
+    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    dev = bases.device
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
+    assert not pairs or n % 2 == 0, "rows in pairs"
+    quals = t["quals"] if best_qual else None
+    if best_qual:
+        assert quals.dtype == torch.uint8 and quals.is_contiguous() and quals.shape == bases.shape and quals.device == dev, "quals: [n, L] uint8 on the rows' device"
+    if keep is not None:
+        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
+    U = n // 2 if pairs else n
+    out_keep = torch.empty((n,), dtype=torch.uint8, device=dev); dup_of = torch.empty((U,), dtype=torch.int32, device=dev)
+    count = torch.empty((U,), dtype=torch.int32, device=dev)
+    hist = torch.empty((hist_len,), dtype=torch.int64, device=dev) if hist_len else None
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        r = codec.dedup_rows(n, L, bases.data_ptr(), quals.data_ptr() if best_qual else None, lens.data_ptr(), pairs=pairs, key_len=key_len, best_qual=best_qual,
+                             hist_len=hist_len, d_in=keep.data_ptr() if keep is not None else None, d_keep=out_keep.data_ptr(), d_dup_of=dup_of.data_ptr(),
+                             d_count=count.data_ptr(), d_hist=hist.data_ptr() if hist_len else None)
+    finally:
+        codec.set_stream(None)
+    out = {"keep": out_keep, "dup_of": dup_of, "count": count, "summary": {f: int(getattr(r, f)) for f in DEDUP_FIELDS}}
+    if hist_len:
+        out["hist"] = hist
     return out
 
 
