@@ -3,8 +3,14 @@ from one call to the next (rfq_ctx: rec_per_byte / lazy_block, mixed_lengths, de
 only grow, the context-owned results of the rows family) is pinned by running every input behind every other one on ONE context.
 
 The order is an Eulerian circuit of the complete digraph with loops (euler): k * k + 1 calls see each of the k * k ordered pairs (predecessor, input) once.  The
-expected results never come from the library: _oracle.encode_file gives the image, _oracle.decode_file of that image the text, both computed once (inputs())."""
+expected results never come from the library: _oracle.encode_file gives the image, _oracle.decode_file of that image the text, both computed once (inputs()).
+
+Refusals are part of a context's history too: the encoder and the decoder leave by many exits, each with state behind it (buffers marked dirty, a header made from
+the refused text, read-backs pending into a frame that has returned, a forked stream to join).  refusals() makes one refusing input per exit, each proven against the
+oracle, and refusal_circuit() walks every ordered pair over the good and the refusing inputs that the circuits above do not have (circuit, refusal_edges).  The same
+over the kinds of call (calls_refusal_circuit), and a small batch behind a large one for every rows call whose scratch only grows (check_nothing_left)."""
 import collections
+import functools
 import threading
 
 import numpy as np
@@ -14,10 +20,14 @@ import _oracle as O
 import _sections
 
 
-def euler(k):
-    """k * k + 1 indices in which every ordered pair (a, b) of range(k), a == b included, is adjacent exactly once (Hierholzer on the complete digraph with loops)"""
-    left = {a: list(range(k)) for a in range(k)}                             # the edges a -> b not walked yet
-    stack, out = [0], []
+def circuit(nodes, edges):
+    """a closed walk over `nodes` that uses every (a, b) of `edges` exactly once (Hierholzer; the digraph must be connected, every node with as many edges in as out -
+    a walk that does not close or leaves an edge out fails here)"""
+    nodes, edges = list(nodes), list(edges)
+    left = {a: [] for a in nodes}                                            # the edges a -> b not walked yet
+    for a, b in edges:
+        left[a].append(b)
+    stack, out = [nodes[0]], []
     while stack:
         v = stack[-1]
         if left[v]:
@@ -25,9 +35,22 @@ def euler(k):
         else:
             out.append(stack.pop())
     out.reverse()
-    assert len(out) == k * k + 1 and out[0] == out[-1], (k, len(out))
-    assert len(set(zip(out, out[1:]))) == k * k, k
+    assert len(out) == len(edges) + 1 and out[0] == out[-1], (len(nodes), len(edges), len(out))
+    assert collections.Counter(zip(out, out[1:])) == collections.Counter(edges) and len(set(edges)) == len(edges), (len(nodes), len(edges))
     return out
+
+
+def euler(k):
+    """k * k + 1 indices in which every ordered pair (a, b) of range(k), a == b included, is adjacent exactly once: the complete digraph with loops"""
+    out = circuit(range(k), [(a, b) for a in range(k) for b in range(k)])
+    assert len(out) == k * k + 1, (k, len(out))
+    return out
+
+
+def refusal_edges(g, r):
+    """nodes 0 .. g - 1 are good, g .. g + r - 1 refuse: every ordered pair but good -> good (those are euler(g)'s) - 2 * g * r + r * r edges, refusal behind refusal
+    and a refusal behind itself among them; every node has g + r edges in and out but the good ones, which have r and r"""
+    return [(a, b) for a in range(g + r) for b in range(g + r) if a >= g or b >= g]
 
 
 # ---------------------------------------------------------------- the inputs
@@ -103,7 +126,7 @@ def _chunk_flags(test):
 
 
 def inputs():
-    """the dozen texts, made once and never changed"""
+    """the thirteen texts, made once and never changed"""
     global _INPUTS
     if _INPUTS is not None:
         return _INPUTS
@@ -154,13 +177,220 @@ def inputs():
         check=_chunk_flags(lambda fl, n: fl & _sections.C_READ_LEN_SAME))
     a, _ = O.gen(O.NOVA_SE150, 3, seed=16)
     add("three_records", a, b"", O.SE, 30000, "buffers far larger than the batch", enc2_mark=("lazy_index",), check=_chunk_flags(lambda fl, n: n == 3))
+    # (a lower-case base is refused where the header is made - chunk 0, RfqHeader::makeQualityTable - and nowhere else: behind it the reference encodes the byte as it
+    # does any base that is not A/C/G/T.  The thirteenth input pins that image; the same byte in chunk 0 is refusals()' lowercase_chunk0)
+    recs = _records(by_name_in(made, "four_quals").fq1); seq = bytearray(recs[-5][1]); seq[70] = ord("a"); recs[-5][1] = bytes(seq)
+    add("lowercase_late", _text(recs), b"", O.SE, 30000, "a byte outside A/C/G/T/N behind chunk 0, under match masks", enc_mark=("quality_masks",), lossless=False)
     assert max(len(i.fq1) + len(i.fq2) for i in made) == len(made[10].fq1) and made[10].name == "se150_big"
     _INPUTS = made
     return made
 
 
+def by_name_in(made, name):
+    return next(i for i in made if i.name == name)
+
+
 def by_name(name):
-    return next(i for i in inputs() if i.name == name)
+    return by_name_in(inputs(), name)
+
+
+# ---------------------------------------------------------------- the refusing inputs
+# Every one is a good text (image) with ONE mutation; refusals() proves on the CPU that the oracle takes the one and refuses the other.  What a step must raise:
+# codes - the RFQ_E_* values allowed (include/rfq_hip.h: RFQ_E_DATA "the reference would error_exit on this input (message = its text)", RFQ_E_UNPINNED for the two
+# inputs both sides refuse rather than reproduce, RFQ_E_NOSPACE for a caller's buffer); message - the oracle's text, compared by the rule of _engine.check_case /
+# _fuzz.check (equal but for surrounding white space), or phrase - the key phrase of a refusal both sides word in their own way (_fuzz.check_block); neither for a
+# refusal that is pinned by its code alone.  kind "enc": fq1 / fq2 / paired / cb, short - the caller's d_out holds that many bytes; kind "dec": image / split / caps /
+# chunk_off.  text - what the library must RETURN, for the one hostile input that is no refusal (an image with a chunk index that lies: the index is not verified and
+# the chain is walked, include/rfq_hip.h, rfq_decode_args.h_chunk_off - the oracle knows no index and decodes the image).
+RFQ_E_DATA, RFQ_E_UNPINNED, RFQ_E_NOSPACE = -5, -7, -8
+Refusal = collections.namedtuple("Refusal", "name kind src exit codes message phrase fq1 fq2 paired cb short image split caps chunk_off text")
+_REFUSALS = None
+MUTANT_LABELS = {}                                                           # {name: (history image, the label _hostile.mutants gave the mutant)}
+QUAL_OVERFLOW_SEED = 12
+COORD_MAX = 2097152                                                          # (RfqCodec::encodeCoords refuses what is LARGER than 2M - 1: this value is the first)
+
+
+def _refusal(name, kind, src, exit, codes, message=None, phrase=None, fq1=b"", fq2=b"", paired=0, cb=0, short=None, image=b"", split=False, caps=None, chunk_off=None,
+             text=None):
+    return Refusal(name, kind, src, exit, tuple(codes), message, phrase, fq1, fq2, paired, cb, short, image, split, caps, chunk_off, text)
+
+
+def _oracle_refuses(fq1, fq2, paired, cb):
+    try:
+        O.encode_file(fq1, fq2, paired, cb)
+    except O.OracleError as e:
+        return str(e)
+    return None
+
+
+def _with_coord(name_line, axis, value):
+    """an Illumina name line (@instrument:run:flowcell:lane:tile:x:y[ comment]) with its x (axis 5) or y (axis 6) replaced"""
+    head, sep, comment = name_line.partition(b" ")
+    f = head.split(b":")
+    assert len(f) == 7, name_line
+    f[axis] = b"%d" % value
+    return b":".join(f) + sep + comment
+
+
+def _late(fq1, fq2, paired, cb, rec):
+    """the oracle's image of the text cut in front of record `rec` (of each file) has at least two chunks: the mutation is behind chunk 0 and behind another chunk"""
+    a = _text(_records(fq1)[:rec]); b = _text(_records(fq2)[:rec]) if fq2 else b""
+    return len(O.chunk_table(O.encode_file(a, b, paired, cb))) - 1 >= 2
+
+
+def refusals():
+    """the refusing inputs of the circuits, made once: [Refusal], encode refusals first"""
+    global _REFUSALS
+    if _REFUSALS is not None:
+        return _REFUSALS
+    import _fuzz
+    import _hostile
+    made = []
+
+    def sized(name, fq1, fq2, paired, cb):
+        """add()'s size rule, on the unmutated text, which the oracle accepts: its image"""
+        want = O.encode_file(fq1, fq2, paired, cb)
+        size, chunks = len(fq1) + len(fq2), len(O.chunk_table(want)) - 1
+        assert 100_000 <= size <= 350_000 and 2 <= chunks <= 6 and 10_000 <= cb <= 30_000, (name, size, chunks, cb)
+        return want
+
+    def enc(name, src, exit, good, bad, paired, cb, late=None, code=RFQ_E_DATA, phrase=None, quotes_150=False):
+        sized(name, good[0], good[1], paired, cb)
+        said = _oracle_refuses(bad[0], bad[1], paired, cb)
+        assert said is not None, "%s: the oracle encodes the mutated text" % name
+        if quotes_150:                                                       # (oracle/rfq_oracle.c quotes 150 bases of the offending line, the reference all of it: the
+            assert len(said.split("\n")[-1]) == 150                          # oracle's whole text is then the phrase the message must hold)
+            phrase = said
+        if late is not None:
+            assert _late(good[0], good[1], paired, cb, late), "%s: record %d is not behind two chunks" % (name, late)
+        assert phrase is None or phrase in said, (name, phrase, said)
+        made.append(_refusal(name, "enc", src, exit, (code,), message=None if phrase else said, phrase=phrase, fq1=bad[0], fq2=bad[1], paired=paired, cb=cb))
+
+    def one_byte(fq, rec, line, at, byte):
+        recs = _records(fq); b = bytearray(recs[rec][line]); b[at] = byte; recs[rec][line] = bytes(b)
+        return _text(recs)
+
+    def coord(fq, rec, axis):
+        recs = _records(fq); recs[rec][0] = _with_coord(recs[rec][0], axis, COORD_MAX)
+        return _text(recs)
+
+    # --- enc_verdict: the coordinate range, found by the coders behind every kernel of the batch, in the LAST chunk
+    i = by_name("four_quals"); n = len(_records(i.fq1))
+    enc("coord_late_masks", "four_quals", "enc_verdict: planes, room repeat, header made", (i.fq1, b""), (coord(i.fq1, n - 5, 5), b""), O.SE, i.cb, late=n - 5)
+    a, b = O.gen(O.NOVA_PE150, 400, seed=11, nppm=20000)                     # (pe150's pairs with N bases in most reads: the loose slots' N bits are stored)
+    assert a.count(b"N") > 1000 and len(a) == len(b)
+    i = by_name("pe150")
+    enc("coord_late_pe", "pe150 with N bases", "enc_verdict: mirrored index, the loose slots' N bits", (a, b), (coord(a, 395, 6), coord(b, 395, 6)), O.PE_TWO_FILES, i.cb,
+        late=395)
+    # (bgi_q40's names hold no coordinates - there is no X or Y to be out of range -: its reads and forty quality values under NovaSeq names)
+    i = by_name("bgi_q40")
+
+    def renamed(fq, mate):
+        recs = _records(fq)
+        for k, r in enumerate(recs):
+            r[0] = b"@A00250:26:H3YTWDSXX:1:%d:%d:%d %d:N:0:ACGT" % (1101 + k // 150, 1000 + 61 * k % 29000, 1000 + 13 * (k % 150), mate)
+        return _text(recs)
+    a, b = renamed(i.fq1, 1), renamed(i.fq2, 2)
+    h = _sections.Header(O.encode_file(a, b, O.PE_TWO_FILES, 20000))
+    assert len(h.normal) >= 5 and h.flags & _sections.H_QUAL_BY_COL and not h.flags & _sections.H_DONT_QUAL, (len(h.normal), hex(h.flags))   # (rfq_encode.hip, enc_form: coder_list)
+    enc("coord_late_list", "bgi_q40 under NovaSeq names", "enc_verdict: the list coder", (a, b), (coord(a, 445, 6), coord(b, 445, 6)), O.PE_TWO_FILES, 20000, late=445)
+    # --- header_errors: chunk 0's bases and qualities
+    i = by_name("rare_quals")
+    enc("lowercase_chunk0", "rare_quals", "header_errors, tile path", (i.fq1, b""), (one_byte(i.fq1, 40, 1, 70, ord("a")), b""), O.SE, i.cb)
+    # (rfq_encode.hip, enc_form: the tile gather takes a batch when two of its longest records and 64 bytes fit G2_CAP = 23552 bytes of staged text - records of more
+    # than 11744 bytes go to the byte-wise gather, whose header verdict is read behind it)
+    a = E.handmade(20, lambda k: "LR.%d" % k, lambda k: 6000 + 7 * k, lambda k: "+", seed=9)
+    assert max(len(b"\n".join(r)) + 1 for r in _records(a)) * 2 + 64 > 23552
+    enc("iupac_chunk0_long", "twenty reads of 6000 bases and more", "header_errors behind the byte-wise gather", (a, b""), (one_byte(a, 1, 1, 3000, ord("R")), b""),
+        O.SE, 30000, quotes_150=True)
+    i = by_name("se_var"); q = _records(i.fq1)[30][3]
+    enc("bad_qual_chunk0", "se_var", "header_errors: mixed lengths", (i.fq1, b""), (one_byte(i.fq1, 30, 3, len(q) // 2, 0x85), b""), O.SE, i.cb)
+    # --- enc_cut
+    i = by_name("se150_big"); recs = _records(i.fq1); n = len(recs); recs[n - 7][3] = recs[n - 7][3][:-1]
+    enc("qual_short_late", "se150_big", "enc_cut, RFQ_E_UNPINNED", (i.fq1, b""), (_text(recs), b""), O.SE, i.cb, late=n - 7, code=RFQ_E_UNPINNED, phrase="shorter than")
+    # --- enc_verdict: no room in the caller's buffer (nothing is wrong with the text: the code alone)
+    i = by_name("long_names")
+    made.append(_refusal("nospace", "enc", "long_names", "enc_verdict, RFQ_E_NOSPACE", (RFQ_E_NOSPACE,), fq1=i.fq1, paired=i.paired, cb=i.cb, short=len(i.want) - 1))
+    # --- enc_verdict: a quality payload beyond the reference's 1.5x buffer.  _fuzz.qual_case(12) is the first seed of a _fuzz generator (of range(200), at 30,000 bases
+    # a chunk) whose text has the size and that the oracle refuses so; there is no unmutated text, so the size rule's chunk count has nothing to count
+    fq1, fq2, paired, _ = _fuzz.qual_case(QUAL_OVERFLOW_SEED)
+    said = _oracle_refuses(fq1, fq2, paired, 30000)
+    assert 100_000 <= len(fq1) + len(fq2) <= 350_000 and said and "1.5x scratch buffer" in said, (len(fq1) + len(fq2), said)
+    made.append(_refusal("qual_overflow", "enc", "_fuzz.qual_case(%d)" % QUAL_OVERFLOW_SEED, "enc_verdict: the 1.5x quality payload", (RFQ_E_UNPINNED,),
+                         phrase="1.5x scratch buffer", fq1=fq1, fq2=fq2, paired=paired, cb=30000))
+
+    # --- decode: mutants of history images, chosen by the label _hostile.mutants(want, seed=7) gives them; the oracle refuses each
+    def mutant(name, src, exit, pick):
+        i = by_name(src); muts = _hostile.mutants(i.want, seed=7)
+        label, img, index = pick(i, muts)
+        MUTANT_LABELS[name] = (src, label)
+        if index is None:
+            try:
+                O.decode_file(img, i.split)
+            except O.OracleError:
+                made.append(_refusal(name, "dec", src, exit, sorted(_hostile.ALLOWED), image=img, split=i.split))
+                return
+            raise AssertionError("%s: the oracle decodes mutant %s of %s" % (name, label, src))
+        assert img == i.want and list(index) != O.chunk_table(i.want)
+        made.append(_refusal(name, "dec", src, exit, (), image=img, split=i.split, chunk_off=list(index), text=i.text))
+
+    def labelled(label):
+        return lambda i, muts: next(m for m in muts if m[0] == label)
+
+    def last_chunk_cut(i, muts):
+        _, chunks = _sections.parse(i.want); c = chunks[-1]
+        return labelled("truncate@%d" % (c.off + c.qual_off))(i, muts)       # (the last chunk's sequence section ends here, its quality payload is missing)
+    mutant("cut_last_chunk", "four_quals", "a truncation at a section boundary of the last chunk", last_chunk_cut)
+    mutant("scribbled_lengths", "se_var", "a scribbled length table", labelled("lengths15@10642"))
+    mutant("scribbled_quality", "rare_quals", "a scribbled quality table", labelled("quality0@11597"))
+    mutant("lying_index", "pe150", "a lying chunk index", labelled("index0"))
+    i = by_name("se150_big")
+    try:
+        O.decode_file(i.want, True)
+        raise AssertionError("the oracle splits an SE image")
+    except O.OracleError as e:
+        made.append(_refusal("se_split", "dec", "se150_big", "an SE image with split_pe", (RFQ_E_DATA,), message=str(e), image=i.want, split=True))
+    i = by_name("long_names")
+    made.append(_refusal("text_nospace", "dec", "long_names", "the speculative emitter, RFQ_E_NOSPACE", (RFQ_E_NOSPACE,), image=i.want, caps=(len(i.text) - 1, 0)))
+    assert len({m.name for m in made}) == len(made)
+    _REFUSALS = made
+    return made
+
+
+def refusal(name):
+    return next(r for r in refusals() if r.name == name)
+
+
+def refuse_step(codec, r):
+    """'' or what is wrong with what the context says to a refusing input"""
+    from repaq_amd import RfqError
+    try:
+        if r.kind == "enc" and r.short is None:
+            got = E.encode(codec, r.fq1, r.fq2, r.paired, r.cb)
+        elif r.kind == "enc":
+            codec.clearHeader()
+            d = codec.dev_put(r.fq1); out = codec.dev_put(b"\0" * r.short)
+            try:
+                assert r.paired == O.SE and out.value % 16 == 0
+                res = codec.encode(d, len(r.fq1), None, 0, r.paired, r.cb, d_out=out, out_cap=r.short, **E.nolb_args(r.fq1, r.fq2, r.paired))
+                got = codec.dev_get(res.d_rfq, res.rfq_len)
+            finally:
+                codec.dev_free(d); codec.dev_free(out)
+        else:
+            got = codec.decode_bytes(r.image, split_pe=r.split, out_caps=r.caps, **({"chunk_off": r.chunk_off} if r.chunk_off else {}))
+    except RfqError as e:
+        if r.text is not None:
+            return "refused (%d: %s) what it must decode" % (e.code, e.message.strip()[:120])
+        if e.code not in r.codes:
+            return "code %d (%s) for one of %s" % (e.code, e.message.strip()[:120], list(r.codes))
+        if r.message is not None and e.message.strip() != r.message.strip():
+            return "the message is %r, the oracle's %r" % (e.message.strip()[:200], r.message.strip()[:200])
+        if r.phrase is not None and r.phrase not in e.message:
+            return "the message %r lacks %r" % (e.message.strip()[:200], r.phrase)
+        return ""
+    if r.text is None:
+        return "a result (%d bytes) instead of the refusal" % (sum(len(x) for x in got) if isinstance(got, tuple) else len(got))
+    return (text_diff(got[0], r.text[0]) or text_diff(got[1], r.text[1])) if r.split else text_diff(got, r.text)
 
 
 def marks_ok(marks, rules):
@@ -252,16 +482,26 @@ def check_markers(make_codec, inp):
         c.close()
 
 
-def walk(codec, seq, kind_of, start=0, stop=None, state=None):
+def walk(codec, seq, kind_of, start=0, stop=None, state=None, nodes=None):
     """steps start .. stop of the sequence on `codec`; kind_of(i) -> "enc" / "dec".  Every failing step is collected (the context goes on: what a wrong state does to
     the calls behind it is part of the picture) and the assert names the input, the call in front of it and - encode state is left by the last ENCODE, decode state
-    by the last decode - the last call of its own kind, with the place.  state: what walk returned for the steps in front of `start` on this context."""
-    ins = inputs(); bad = []
+    by the last decode - the last call of its own kind, with the place.  state: what walk returned for the steps in front of `start` on this context.
+    nodes: what seq indexes, inputs() by default; a Refusal among them is an encode or a decode by its own kind and passes when the context raises what it expects
+    (refuse_step) - a result, another code or another message is collected like a differing image."""
+    from repaq_amd import RfqError
+    ins = inputs() if nodes is None else nodes; bad = []
     state = dict(state or {})
     stop = len(seq) if stop is None else stop
     for i in range(start, stop):
-        inp = ins[seq[i]]; kind = kind_of(i)
-        msg = (encode_step if kind == "enc" else decode_step)(codec, inp)
+        inp = ins[seq[i]]
+        if isinstance(inp, Refusal):
+            kind = inp.kind; msg = refuse_step(codec, inp)
+        else:
+            kind = kind_of(i)
+            try:
+                msg = (encode_step if kind == "enc" else decode_step)(codec, inp)
+            except RfqError as e:                                            # (what an earlier refusal left behind may well be a refusal of a good input)
+                msg = "refused (%d: %s)" % (e.code, e.message.strip()[:120])
         if msg:
             marks = sorted(n for n, _ in codec.timings())
             prev, same = state.get("prev"), state.get(kind)
@@ -273,6 +513,44 @@ def walk(codec, seq, kind_of, start=0, stop=None, state=None):
 
 
 KINDS = {"encode": lambda i: "enc", "decode": lambda i: "dec", "mixed": lambda i: "enc" if i % 2 else "dec"}
+
+
+def refusal_circuit(kind):
+    """(nodes, seq, G, R) of the refusal circuit `kind`: the good inputs and the refusing ones of that kind (both kinds' for "mixed"), every ordered pair of them adjacent
+    once but good -> good, which the circuits over inputs() alone have"""
+    good = list(inputs()); ref = [r for r in refusals() if kind == "mixed" or r.kind == {"encode": "enc", "decode": "dec"}[kind]]
+    g, r = len(good), len(ref)
+    seq = circuit(range(g + r), refusal_edges(g, r))
+    assert len(seq) == 2 * g * r + r * r + 1, (kind, g, r, len(seq))
+    return good + ref, seq, g, r
+
+
+def check_fast_path_kept(codec):
+    """behind a circuit with refusals on `codec`: a uniform file twice, and the second encode is indexed without the read-back (check_mixed_lengths_end_with_the_file's
+    assertion) - no refusal costs the context its fast path for good"""
+    inp = by_name("se150_big")
+    for _ in range(2):
+        msg = encode_step(codec, inp)
+        assert not msg, msg
+        marks = {n for n, _ in codec.timings()}
+    assert "lazy_index" in marks, sorted(marks)
+
+
+def check_header_survives_refusal(codec):
+    """The file in progress behind a refusal at the encoder's LAST exit, without rfq_clear_header.  include/rfq_hip.h gives a refusal no say over the header ("the header
+    currently set / made", rfq_get_header; only rfq_clear_header, rfq_set_header and a decode with has_header change it), and enc_verdict refuses behind the header stage:
+    the header made from the refused text's chunk 0 stays.  It equals the oracle's header of the unmutated text - the mutation lies behind chunk 0, or nowhere (nospace) -
+    and the unmutated text encoded next, as the file in progress, is that header and the oracle's chunks behind it."""
+    for name in ("coord_late_masks", "nospace"):
+        r = refusal(name); good = by_name(r.src)
+        hdr = good.want[:_sections.Header(good.want).len]
+        msg = refuse_step(codec, r)
+        assert not msg, (name, msg)
+        got = codec.header()
+        assert got == hdr, (name, got.hex(), hdr.hex())
+        image = codec.encode_bytes(good.fq1, good.fq2, good.paired, good.cb, **E.nolb_args(good.fq1, good.fq2, good.paired))     # (no clearHeader in front)
+        assert image == good.want, (name, image_diff(image, good.want))
+        assert codec.header() == hdr, name
 
 
 # ---------------------------------------------------------------- one file in two batches
@@ -340,13 +618,14 @@ def run_threads(jobs, timeout_s=120.0):
 # the encoder's and decoder's own result buffers): include/rfq_hip.h says "result pointers stay valid until the next call on the same context" - the next call
 # invalidates them, so each is read BEFORE the next kind's call is issued, inside its own step.
 CALL_KINDS = ("encode", "decode", "scan", "first_diff", "decode_rows", "decode_names", "text_rows", "select_rows", "judge_rows", "adapter_rows", "merge_rows",
-              "rows_to_text", "encode_rows")
+              "rows_to_text", "encode_rows", "dedup_rows")
 
 
 class Calls:
     """the fixtures of the calls circuit and their host references, made once"""
     def __init__(self):
         import _adapter as A
+        import _dedup as D
         import _judge as J
         import _merge as M
         import _names as N
@@ -354,7 +633,7 @@ class Calls:
         import _rows_enc as R
         import _select as S
         import _text_rows as T
-        self.mod = dict(A=A, J=J, M=M, N=N, W=W, R=R, S=S, T=T)
+        self.mod = dict(A=A, D=D, J=J, M=M, N=N, W=W, R=R, S=S, T=T)
         self.fq1, self.fq2 = O.gen(O.NOVA_PE150, 70, seed=21)
         self.paired, self.cb = O.PE_TWO_FILES, 10000
         self.want = O.encode_file(self.fq1, self.fq2, self.paired, self.cb)
@@ -380,6 +659,31 @@ class Calls:
         self.a_want = A.expected(*self.a_rows, self.a_crit, True)
         self.m_rows = M.random_pairs(40, 64, 47, codes=False)
         self.m_want = M.expected(*self.m_rows, False)
+        self.d_rows = D.planted(100, True, 53, sizes=(20, 5, 2) + (1,) * 40)
+        self.d_want = D.expected(*self.d_rows, pairs=True, best=True, hist_len=8)
+        # --- what the refusing kinds send (REFUSING_CALL_KINDS): each a fixture above with the ONE mutation its own module's refusal tests make
+        import _hostile
+        self.code_rows = R.rows_of(self.fq1, self.fq2, self.paired, extra="x16", codes=True)
+        self.code_rows[0][3, 70] = 5                                          # (_rows_enc._refusals: code_5_mid_line)
+        self.junk = dict(T.junk_texts())["nul_and_ff"]                        # (a NUL and a 0xFF in a sequence line: no base code for them, include/rfq_hip.h, rfq_text_rows)
+        label, img, split, _ = _hostile.images()[0]                           # (se150: the image whose mutants _rows.run_hostile / _names.run_hostile send)
+        _, chunks = _sections.parse(img); cut = "truncate@%d" % (chunks[-1].off + chunks[-1].qual_off)
+        self.mutant = next(m for m in _hostile.mutants(img, seed=7) if m[0] == cut)[1]
+        try:
+            O.decode_file(self.mutant, split)
+            raise AssertionError("the oracle decodes %s of %s" % (cut, label))
+        except O.OracleError:
+            pass
+        fq = _qual_recs(260, b"F:,5", 5); recs = _records(fq); recs[-5][0] = _with_coord(recs[-5][0], 5, COORD_MAX)
+        self.se_want = O.encode_file(fq, b"", O.SE, self.cb)
+        assert len(O.chunk_table(self.se_want)) - 1 >= 3 and _late(fq, b"", O.SE, self.cb, len(recs) - 5)
+        self.coord_fq = _text(recs); self.coord_said = _oracle_refuses(self.coord_fq, b"", O.SE, self.cb)
+        assert self.coord_said == "The X/Y coordinate cannot be larger than 2M, but we get: %d" % COORD_MAX, self.coord_said
+        try:
+            O.decode_file(self.se_want, True)
+            raise AssertionError("the oracle splits an SE image")
+        except O.OracleError as e:
+            self.split_said = str(e)
 
     # each returns every output's bytes, as something that compares with ==
     def encode(self, c):
@@ -462,6 +766,102 @@ class Calls:
         return got
 
 
+    def dedup_rows(self, c):
+        D = self.mod["D"]; dev = D.dev_rows(c, *self.d_rows)
+        try:
+            out, summ, raw = D.run(c, dev, pairs=True, best=True, hist_len=8)
+        finally:
+            dev.free()
+        D.compare(out, summ, self.d_want, "calls circuit:")
+        return tuple(sorted(raw.items())), tuple(sorted(summ.items()))
+
+    # --- the refusing kinds: each raises AssertionError unless the call is refused with the code, and the fragment of the message, its module's own tests expect
+    @staticmethod
+    def _refused(codes, fragment, f, exact=False):
+        from repaq_amd import RfqError
+        try:
+            f()
+        except RfqError as e:
+            assert e.code in codes, "code %d (%s) for one of %s" % (e.code, e.message.strip()[:120], sorted(codes))
+            said = e.message.strip()
+            assert fragment is None or (said == fragment.strip() if exact else fragment in said), "the message %r for %r" % (said[:200], fragment)
+            return "refused"
+        raise AssertionError("a result instead of the refusal")
+
+    @staticmethod
+    def _too_long(lens, row_len):
+        """the lengths with row_len + 1 in the last row, and what the message names"""
+        lens = np.array(lens, np.int32); lens[-1] = row_len + 1
+        return lens, "first such row: %d)" % (len(lens) - 1)
+
+    def _on_rows(self, c, dev, call):
+        try:
+            return call(dev)
+        finally:
+            dev.free()
+
+    def bad_select_rows(self, c):
+        S = self.mod["S"]; B, Q, lens, names = self.rows; lens, needle = self._too_long(lens, B.shape[1])
+        dev = S.dev_sel(c, B, Q, lens, names, self.sel["keep"], self.sel["start"], self.sel["length"])
+        return self._on_rows(c, dev, lambda d: self._refused((-3,), needle, lambda: c.select_rows(*d.args(), pairs=True, min_len=30, **S.sel_of(d))))
+
+    def bad_judge_rows(self, c):
+        J, W = self.mod["J"], self.mod["W"]; B, Q, lens = self.j_rows; lens, needle = self._too_long(lens, B.shape[1])
+        return self._on_rows(c, W.DevRows(c, B, Q, lens), lambda d: self._refused((-3,), needle, lambda: J.run(c, d, self.j_crit, False)))
+
+    def bad_adapter_rows(self, c):
+        A, W = self.mod["A"], self.mod["W"]; B, lens = self.a_rows; lens, needle = self._too_long(lens, B.shape[1])
+        return self._on_rows(c, W.DevRows(c, B, None, lens), lambda d: self._refused((-3,), needle, lambda: A.run(c, d, self.a_crit, True)))
+
+    def bad_merge_rows(self, c):
+        M = self.mod["M"]; B, Q, lens, names, insert = self.m_rows; lens, needle = self._too_long(lens, B.shape[1])
+        dev = M.dev_merge(c, B, Q, lens, names, insert)
+        return self._on_rows(c, dev, lambda d: self._refused((-3,), needle, lambda: c.merge_rows(*d.args(), d_insert=d.insert, codes=False)))
+
+    def bad_dedup_rows(self, c):
+        D = self.mod["D"]; B, Q, lens = self.d_rows; lens, needle = self._too_long(lens, B.shape[1])
+        return self._on_rows(c, D.dev_rows(c, B, Q, lens), lambda d: self._refused((-3,), needle, lambda: D.run(c, d, pairs=True, best=True, hist_len=8)))
+
+    def bad_rows_to_text(self, c):
+        dev = self.mod["W"].DevRows(c, *self.code_rows)
+        return self._on_rows(c, dev, lambda d: self._refused((-5,), None, lambda: c.rows_to_text(*d.args(), paired=self.paired, codes=True)))
+
+    def bad_encode_rows(self, c):
+        def call(d):
+            c.clearHeader()
+            c.encode_rows(*d.args(), paired=self.paired, codes=True, chunk_bases=self.cb)
+        return self._on_rows(c, self.mod["W"].DevRows(c, *self.code_rows), lambda d: self._refused((-5,), None, lambda: call(d)))
+
+    def bad_text_rows(self, c):
+        return self._refused((-5,), None, lambda: self.mod["T"].call(c, self.junk, b"", O.SE, None, codes=True, extra="x16"))
+
+    def bad_decode_rows(self, c):
+        import _hostile
+        return self._refused(set(_hostile.ALLOWED), None, lambda: c.decode_rows_bytes(self.mutant))
+
+    def bad_decode_names(self, c):
+        import _hostile
+        return self._refused(set(_hostile.ALLOWED), None, lambda: c.decode_names_bytes(self.mutant))
+
+    def bad_encode(self, c):
+        return self._refused((RFQ_E_DATA,), self.coord_said, lambda: E.encode(c, self.coord_fq, b"", O.SE, self.cb), exact=True)
+
+    def bad_decode(self, c):
+        return self._refused((RFQ_E_DATA,), self.split_said, lambda: c.decode_bytes(self.se_want, split_pe=True), exact=True)
+
+
+REFUSING_CALL_KINDS = ("bad_select_rows", "bad_judge_rows", "bad_adapter_rows", "bad_merge_rows", "bad_dedup_rows", "bad_rows_to_text", "bad_encode_rows",
+                       "bad_text_rows", "bad_decode_rows", "bad_decode_names", "bad_encode", "bad_decode")
+
+
+def calls_refusal_circuit():
+    """(kinds, seq): the good kinds and the refusing ones, every ordered pair adjacent once but good -> good (euler(len(CALL_KINDS)) has those)"""
+    g, r = len(CALL_KINDS), len(REFUSING_CALL_KINDS)
+    seq = circuit(range(g + r), refusal_edges(g, r))
+    assert len(seq) == 2 * g * r + r * r + 1, (g, r, len(seq))
+    return CALL_KINDS + REFUSING_CALL_KINDS, seq
+
+
 _CALLS = None
 
 
@@ -484,20 +884,185 @@ def first_results(make_codec):
     return out
 
 
-def walk_calls(codec, first, seq, start=0, stop=None, prev=None):
+def walk_calls(codec, first, seq, start=0, stop=None, prev=None, kinds=CALL_KINDS):
+    """kinds: what seq indexes; a refusing kind (not in `first`) is checked by its code and message alone"""
+    from repaq_amd import RfqError
     stop = len(seq) if stop is None else stop
     bad = []
     for i in range(start, stop):
-        kind = CALL_KINDS[seq[i]]
+        kind = kinds[seq[i]]
         try:
             got = getattr(calls(), kind)(codec)
-            if got != first[kind]:
+            if kind in first and got != first[kind]:
                 bad.append("step %d: %s behind %s equals its reference but not its own first result" % (i, kind, prev or "a fresh context"))
-        except AssertionError as e:
+        except (AssertionError, RfqError) as e:                              # (behind a refusing kind a good call may be refused: collected like a difference)
             bad.append("step %d: %s behind %s: %s" % (i, kind, prev or "a fresh context", str(e)[:300]))
         prev = kind
     assert not bad, "%d of %d calls differ:\n%s" % (len(bad), stop - start, "\n".join(bad[:12]))
     return prev
+
+
+# ---------------------------------------------------------------- nothing is left of a larger call
+# _dedup.check_state's pattern for the other rows calls, which share rfq_ctx::b[] scratch that only grows: a LARGE batch (5000 rows at a stride of 1100 bytes: the
+# any-length kernels, the largest scratch), then a SMALL one (40 rows at a stride of 150, every one a row of the large batch) on the same context - the small one's
+# bytes and summary are a fresh context's, and the large batch again gives its own first result.  Both sizes are compared with the module's host reference inside
+# every call.  One row in 25 of the large batch is 1100 bases long, the others 100 .. 150: the host references are Python loops over the bases.
+NOTHING_LEFT_CALLS = ("decode_rows", "decode_names", "text_rows", "select_rows", "judge_rows", "adapter_rows", "merge_rows", "rows_to_text", "encode_rows")
+BIG_ROWS, BIG_LEN, SMALL_ROWS, SMALL_LEN = 5000, 1100, 40, 150
+
+
+def _embed(short, long_, L):
+    """row arrays of two strides, one above the other at stride L (what lies behind a short row's own stride is padding: 255)"""
+    out = np.full((len(short) + len(long_), L), 255, np.uint8)
+    out[:len(short), :short.shape[1]] = short; out[len(short):, :long_.shape[1]] = long_
+    return out
+
+
+class Batch:
+    """the inputs of the nine calls at one size, and their host references; small=True: rows that all occur in Batch(False)"""
+    def __init__(self, small, mod):
+        import _rows_enc as R
+        A, J = mod["A"], mod["J"]
+        self.mod, self.small = mod, small
+        rng = np.random.default_rng(61); recs = []
+        for i in range(BIG_ROWS):
+            ln = BIG_LEN if i % 25 == 0 else (SMALL_LEN if i % 25 == 1 else int(rng.integers(100, SMALL_LEN + 1)))
+            seq = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, ln)]; seq[rng.random(ln) < 0.002] = ord("N")
+            q = np.frombuffer(b"FFFFFF:,", np.uint8)[rng.integers(0, 8, ln)]; q[seq == ord("N")] = ord("#")
+            recs.append(b"@A00250:26:H3YTWDSXX:1:%d:%d:%d 1:N:0:ACGT\n" % (1101 + i // 500, 1000 + 37 * i % 29000, 1000 + 11 * (i % 500)) + seq.tobytes() + b"\n+\n" + q.tobytes() + b"\n")
+        if small:
+            short = [i for i in range(BIG_ROWS) if i % 25]                    # (the first of them, record 1, is 150 bases long: the small batch's stride)
+            recs = [recs[i] for i in short[::len(short) // SMALL_ROWS][:SMALL_ROWS]]
+        self.L = SMALL_LEN if small else BIG_LEN
+        self.fq = b"".join(recs); self.cb = 30000 if small else 1_000_000
+        self.want = O.encode_file(self.fq, b"", O.SE, self.cb)
+        assert O.decode_file(self.want) == self.fq
+        self.rows = R.rows_of(self.fq, b"", O.SE)
+        n = len(self.rows[2])
+        assert self.rows[0].shape == (SMALL_ROWS if small else BIG_ROWS, self.L)
+        self.sel = dict(keep=(rng.random(n) < 0.8).astype(np.uint8), start=rng.integers(0, 20, n).astype(np.int32), length=rng.integers(0, 80, n).astype(np.int32),
+                        min_len=30)                                          # (windows within a read of 100 bases)
+        self.j_crit = dict(J.STEPS)["all"]; self.a_crit = A.shape_criteria(SMALL_LEN)[2][1]
+
+    # (every reference is made when its call is first checked, and once)
+    @functools.cached_property
+    def rows_want(self):
+        e = self.mod["W"].expected(self.want)
+        assert e[1] == self.L
+        return e
+
+    @functools.cached_property
+    def names_want(self):
+        return self.mod["N"].expected(self.want)
+
+    @functools.cached_property
+    def recs(self):
+        return self.mod["T"].expect(self.fq, b"", O.SE, self.cb)[1]
+
+    @functools.cached_property
+    def j_want(self):
+        B, Q, lens, _ = self.rows
+        return self.mod["J"].expected(B, Q, lens, self.j_crit, False)
+
+    # pairs: 2400 of rows of 150 bytes and 100 of rows of 1100; the small batch is the first 20 of the short ones
+    @functools.cached_property
+    def a_rows(self):
+        A = self.mod["A"]
+        sB, sl = A.random_pairs(2400, SMALL_LEN, 62, codes=True); lB, ll = A.random_pairs(100, BIG_LEN, 63, codes=True)
+        rows = (sB[:SMALL_ROWS], sl[:SMALL_ROWS]) if self.small else (_embed(sB, lB, BIG_LEN), np.concatenate([sl, ll]))
+        assert rows[0].shape == (SMALL_ROWS if self.small else BIG_ROWS, self.L)
+        return rows
+
+    @functools.cached_property
+    def a_want(self):
+        return self.mod["A"].expected(*self.a_rows, self.a_crit, True)
+
+    @functools.cached_property
+    def m_rows(self):
+        M = self.mod["M"]
+        sB, sQ, sl, sn, si = M.random_pairs(2400, SMALL_LEN, 64, codes=False); lB, lQ, ll, ln_, li = M.random_pairs(100, BIG_LEN, 65, codes=False)
+        rows = ((sB[:SMALL_ROWS], sQ[:SMALL_ROWS], sl[:SMALL_ROWS], sn[:SMALL_ROWS], si[:SMALL_ROWS // 2]) if self.small else
+                (_embed(sB, lB, BIG_LEN), _embed(sQ, lQ, BIG_LEN), np.concatenate([sl, ll]), list(sn) + list(ln_), np.concatenate([si, li])))
+        assert rows[0].shape == (SMALL_ROWS if self.small else BIG_ROWS, self.L)
+        return rows
+
+    @functools.cached_property
+    def m_want(self):
+        return self.mod["M"].expected(*self.m_rows, False)
+
+    def decode_rows(self, c):
+        n, ml, B, Q, lens = self.rows_want
+        gn, gml, gb, gq, gl = c.decode_rows_bytes(self.want)
+        assert (gn, gml) == (n, ml) and np.array_equal(gl, lens) and np.array_equal(gb, B) and np.array_equal(gq, Q), "decode_rows differs from the host's rows"
+        return gn, gml, gb.tobytes(), gq.tobytes(), gl.tobytes()
+
+    def decode_names(self, c):
+        return tuple(self.mod["N"].check(c, self.want, want=self.names_want))
+
+    def text_rows(self, c):
+        r, B, Q, lens, names = self.mod["T"].call(c, self.fq, b"", O.SE, recs=self.recs)
+        return (int(r.n_rows), int(r.consumed1), int(r.max_len)), B.tobytes(), Q.tobytes(), lens.tobytes(), tuple(names)
+
+    def select_rows(self, c):
+        r = self.mod["S"].call(c, *self.rows, **self.sel)
+        return (int(r[0].n_rows), int(r[0].n_bases), int(r[0].dropped_mask), int(r[0].dropped_short)), tuple(r[5])
+
+    def judge_rows(self, c):
+        J, W = self.mod["J"], self.mod["W"]; B, Q, lens, _ = self.rows; dev = W.DevRows(c, B, Q, lens)
+        try:
+            out, summ, raw = J.run(c, dev, self.j_crit, False)
+        finally:
+            dev.free()
+        J.compare(out, summ, self.j_want, "nothing left:")
+        return tuple(sorted(raw.items())), tuple(sorted(summ.items()))
+
+    def adapter_rows(self, c):
+        A, W = self.mod["A"], self.mod["W"]; B, lens = self.a_rows; dev = W.DevRows(c, B, None, lens)
+        try:
+            out, summ, raw = A.run(c, dev, self.a_crit, True)
+        finally:
+            dev.free()
+        A.compare(out, summ, self.a_want, "nothing left:")
+        return tuple(sorted(raw.items())), tuple(sorted(summ.items()))
+
+    def merge_rows(self, c):
+        e, _, _, raw = self.mod["M"].call(c, *self.m_rows, False, paths=(None,), e=self.m_want)
+        return len(e["idx"]), tuple(raw)
+
+    def rows_to_text(self, c):
+        got = c.rows_to_text_bytes(*self.rows)
+        assert got == self.fq, text_diff(got, self.fq)
+        return got
+
+    def encode_rows(self, c):
+        c.clearHeader()
+        got = c.encode_rows_bytes(*self.rows, chunk_bases=self.cb, **E.nolb_args(self.fq, b"", O.SE))
+        assert got == self.want, image_diff(got, self.want)
+        return got
+
+
+_BATCHES = {}
+
+
+def batch(small):
+    if small not in _BATCHES:
+        _BATCHES[small] = Batch(small, calls().mod)
+    return _BATCHES[small]
+
+
+def check_nothing_left(codec, make_codec, kind):
+    """one context: the large batch, the small one, the large one again - see above"""
+    big, small = batch(False), batch(True)
+    fresh = make_codec()
+    try:
+        want = getattr(small, kind)(fresh)
+    finally:
+        fresh.close()
+    first = getattr(big, kind)(codec)
+    got = getattr(small, kind)(codec)
+    assert got == want, "%s: a small batch behind a large one equals its reference but not a fresh context's result" % kind
+    again = getattr(big, kind)(codec)
+    assert again == first, "%s: the large batch again equals its reference but not its own first result" % kind
 
 
 # ---------------------------------------------------------------- state whose loss costs time, not bytes

@@ -2,6 +2,8 @@
 
 A. History.  One context lives through a sequence in which every input follows every other one exactly once (tests/_history.py), encoding, decoding, both in turn,
    one file in two batches with another file's decode between them, and every KIND of call behind every other kind; every result is the oracle's / its host loop's.
+   A': the same with refusals in the sequence - every refusing input and refusing kind of call behind and in front of every good one and every other refusing one -
+   and a small batch behind a large one for every rows call.
 B. Repeats.  Inputs with many more workgroups than the device has compute units, each encoded and decoded R = 16 times on one context under the formulations that
    move the communication between workgroups (the look-back of k_line_index, the plane words at tile edges of k_gather2, the segment counters, the chunk walk's
    atomicMin, the list chain).  Every result is compared ON the device (rfq_compare_bytes) with the oracle's, uploaded once.
@@ -11,6 +13,10 @@ C. Contexts side by side.  include/rfq_hip.h: "distinct contexts may be used con
 B and C can SHOW a race - a mismatch names repeat, offset, chunk, section and stages - and can never rule one out: sixteen equal results are sixteen equal results.
 R is a condition of the test, not a measurement of anything.  No loop here runs until something differs or goes on after a difference."""
 import functools
+import json
+import os
+import subprocess
+import sys
 
 import pytest
 
@@ -66,7 +72,7 @@ def test_input_reaches_its_state_on_a_fresh_context(fresh, name):
 @pytest.mark.parametrize("kind", ["encode", "decode", "mixed"])
 def test_every_input_behind_every_other(fresh, kind):
     seq = H.euler(len(NAMES))
-    assert len(seq) == 145
+    assert len(seq) == 170
     H.walk(fresh(), seq, H.KINDS[kind])
 
 
@@ -83,8 +89,96 @@ def test_mixed_lengths_end_with_the_file(fresh):
 
 def test_every_kind_of_call_behind_every_other(fresh):
     seq = H.euler(len(H.CALL_KINDS))
-    assert len(H.CALL_KINDS) == 13 and len(seq) == 170
+    assert len(H.CALL_KINDS) == 14 and len(seq) == 197
     H.walk_calls(fresh(), H.first_results(fresh), seq)
+
+
+# ---------------------------------------------------------------- A': refusals in sequence on a context that lives on
+# Every refusing input of tests/_history.py behind and in front of every good one and every other refusing one (refusal_circuit).  The circuits that hold decode
+# mutants run in a CHILD process, like tests/test_gpu_rows_hostile.py: a device fault ends the process, and the test says so.
+HERE = os.path.dirname(os.path.abspath(__file__))
+REFUSAL_CHILD = r"""
+import json, sys
+sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)
+import _engine as E, _history as H
+from repaq_amd import RfqCodec
+kind = sys.argv[1]
+c = RfqCodec(device=0, library=E.PRODUCT_LIB)
+assert "gfx950" in c.version()
+E.reset_options(c)
+nodes, seq, g, r = H.refusal_circuit(kind)
+out = {"g": g, "r": r, "steps": len(seq), "failed": ""}
+try:
+    H.walk(c, seq, H.KINDS[kind], nodes=nodes)
+except AssertionError as e:
+    out["failed"] = str(e)
+c.close()
+print("SUMMARY " + json.dumps(out))
+""" % (HERE, os.path.join(HERE, "golden"), os.path.dirname(HERE))
+
+
+def test_every_refusal_behind_and_in_front_of_every_input_encode(fresh):
+    nodes, seq, g, r = H.refusal_circuit("encode")
+    assert (g, r) == (13, 9) and len(seq) == 2 * g * r + r * r + 1
+    codec = fresh()
+    H.walk(codec, seq, H.KINDS["encode"], nodes=nodes)
+    H.check_fast_path_kept(codec)                                            # (no refusal costs the context its fast path for good)
+
+
+@pytest.mark.parametrize("kind,r_want", [("decode", 6), ("mixed", 15)])
+def test_every_refusal_behind_and_in_front_of_every_input(kind, r_want):
+    r = subprocess.run([sys.executable, "-c", REFUSAL_CHILD, kind], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    tail = (r.stdout[-1500:] + "\n" + r.stderr[-3000:])
+    assert r.returncode == 0, "the child process ended with status %d (negative: a signal - a device fault aborts the process):\n%s" % (r.returncode, tail)
+    line = [l for l in r.stdout.splitlines() if l.startswith("SUMMARY ")]
+    assert line, tail
+    s = json.loads(line[-1][8:])
+    assert not s["failed"], s["failed"]
+    assert (s["g"], s["r"]) == (13, r_want) and s["steps"] == 2 * 13 * r_want + r_want * r_want + 1, s
+
+
+def test_the_header_made_survives_a_refusal_at_the_last_exit(fresh):
+    H.check_header_survives_refusal(fresh())
+
+
+@pytest.mark.parametrize("kind", H.NOTHING_LEFT_CALLS)
+def test_nothing_is_left_of_a_larger_call(fresh, kind):
+    H.check_nothing_left(fresh(), fresh, kind)
+
+
+CALLS_CHILD = r"""
+import json, sys
+sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)
+import _engine as E, _history as H
+from repaq_amd import RfqCodec
+made = []
+def make():
+    c = RfqCodec(device=0, library=E.PRODUCT_LIB)
+    assert "gfx950" in c.version()
+    E.reset_options(c)
+    made.append(c)
+    return c
+kinds, seq = H.calls_refusal_circuit()
+out = {"g": len(H.CALL_KINDS), "r": len(H.REFUSING_CALL_KINDS), "steps": len(seq), "failed": ""}
+try:
+    H.walk_calls(make(), H.first_results(make), seq, kinds=kinds)
+except AssertionError as e:
+    out["failed"] = str(e)
+for c in made:
+    c.close()
+print("SUMMARY " + json.dumps(out))
+""" % (HERE, os.path.join(HERE, "golden"), os.path.dirname(HERE))
+
+
+def test_every_refusing_kind_of_call_behind_and_in_front_of_every_kind():
+    r = subprocess.run([sys.executable, "-c", CALLS_CHILD], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    tail = (r.stdout[-1500:] + "\n" + r.stderr[-3000:])
+    assert r.returncode == 0, "the child process ended with status %d (negative: a signal - a device fault aborts the process):\n%s" % (r.returncode, tail)
+    line = [l for l in r.stdout.splitlines() if l.startswith("SUMMARY ")]
+    assert line, tail
+    s = json.loads(line[-1][8:])
+    assert not s["failed"], s["failed"]
+    assert (s["g"], s["r"], s["steps"]) == (14, 12, 2 * 14 * 12 + 12 * 12 + 1), s
 
 
 # ---------------------------------------------------------------- B: the same result every time
@@ -216,6 +310,15 @@ def test_contexts_side_by_side_walk_the_circuit(fresh, n_threads):
         assert len(mine) == len(seq) and set(zip(mine, mine[1:])) == set(zip(seq, seq[1:]))
         return lambda: H.walk(codecs[i], mine, kinds[i])
     H.run_threads([job(i) for i in range(n_threads)])
+
+
+def test_a_context_of_refusals_beside_a_context_of_good_calls(fresh):
+    """one context walks the encode circuit of refusals, one the circuit of good inputs from its middle, at the same time: a refusal's error path (the second stream
+    joined, read-backs dropped) is the context's own"""
+    nodes, rseq, g, r = H.refusal_circuit("encode")
+    seq = H.euler(len(NAMES))
+    refusing, good = fresh(), fresh()
+    H.run_threads([lambda: H.walk(refusing, rseq, H.KINDS["encode"], nodes=nodes), lambda: H.walk(good, _rotated(seq, len(seq) // 2), H.KINDS["mixed"])])
 
 
 def test_switches_stay_with_their_context(fresh):
