@@ -1,10 +1,10 @@
 // enc/rows_adapter.h - rows -> the length adapter removal leaves of every row, the detector that cut it, the insert size and mismatch count of every pair's
 // overlap, one summary and an insert-size histogram (rfq_adapter_rows): the step in front of rfq_judge_rows.  It decides and moves no bytes.
-// Part of rfq_encode_kernels.h (included from there, behind rows_judge.h whose 16-byte pieces it uses; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, behind rows_lanes.h whose 16-byte pieces and unit walk it uses; not a stand-alone header).
 #pragma once
 // Everything is integer arithmetic on the base bytes (include/rfq_hip.h has the rules).  A read becomes three bit planes of 64 positions per word: H and L, the two
 // bits of its class (A 0, C 1, G 2, T 3), and V, "is one of A C G T and lies inside the read".  A lane turns its 16 bytes into three 16-bit masks by SWAR compares
-// and v_dot4 (the judge's pieces) and stores them as 16-bit pieces of the words in LDS.  The reverse complement of R2 is the same masks bit-reversed, stored in
+// and v_dot4 (rows_lanes.h's pieces) and stores them as 16-bit pieces of the words in LDS.  The reverse complement of R2 is the same masks bit-reversed, stored in
 // reverse lane order, H and L inverted: position j of y lies at bit T - l2 + j of its planes (T: the bits a group holds), between NW words of zeros on either side -
 // so "y shifted by d against x" is one funnel of two neighbouring words per plane at bit 2T - insert, the same for every word of x.  Agreement is
 // ~((Hx ^ Hy) | (Lx ^ Ly)) & Vx & Vy: V is 0 outside either read, so no span mask is needed and ov(d) is plain arithmetic; diff = ov - popcount.  A lane takes a
@@ -15,7 +15,6 @@
 //   k_adapter_rows_any         any row length (and every one with RFQ_ADAPTER=general): a wave per unit, a lane per shift / position, the bytes compared one by one
 //                              from the rows themselves.  QUADRATIC in the read length like the rule itself, and with no bit planes to shorten it: slow on very long rows.
 // All sums are integers and leave a workgroup as AR_NSUM atomic adds, the histogram is integer atomic adds: the result is the same bit for bit from run to run.
-#define AR_ERR_LEN 1u                 // a length that is negative or greater than row_len (RFQ_E_ARG)
 #define AR_NSUM 6                     // pairs_found, rows_cut, rows_cut_overlap, rows_cut_adapter, bases_in, bases_out
 #define AR_ITER 4u
 #define AR_NONE 0xFFFFFFFFu
@@ -30,8 +29,7 @@ struct AdapterIn {
     uint32_t adapter_min, adapter_mm_per, hist_len;
     int32_t* len; uint8_t* how; int32_t* insert; int32_t* diff; unsigned long long* hist;     // [n_rows], [n_rows], [n_units], [n_units], [hist_len], or null
 };
-// what the host reads back: zeroed per call, bad_row = ~0
-struct AdapterStat { uint32_t err, pad; unsigned long long bad_row; unsigned long long c[AR_NSUM]; };
+typedef RowsSums<AR_NSUM> AdapterStat;
 typedef uint16_t __attribute__((may_alias)) ar_u16;                           // a lane's 16 positions of a plane word
 
 // ---- the rules
@@ -49,19 +47,13 @@ __device__ __forceinline__ uint32_t ar_ov(int32_t d, uint32_t l1, uint32_t l2) {
     const int64_t lo = d > 0 ? d : 0, e2 = (int64_t)l2 + d, hi = e2 < (int64_t)l1 ? e2 : (int64_t)l1;
     return hi > lo ? (uint32_t)(hi - lo) : 0u;
 }
-__device__ __forceinline__ uint32_t ar_len(const AdapterIn& in, uint64_t g, AdapterStat* st, bool first) {
-    const int32_t l = in.lens[g];
-    if (l >= 0 && (uint32_t)l <= in.row_len) return (uint32_t)l;
-    if (first) { atomicOr(&st->err, AR_ERR_LEN); atomicMin(&st->bad_row, (unsigned long long)g); }
-    return 0u;                                                               // (nothing of such a row is read; the call is refused)
-}
 // a unit's verdict: its rows' lengths and adapter cuts, the overlap's insert (-1: none) and mismatches
 struct ArUnit { uint32_t l[2], cut_a[2]; int32_t insert; uint32_t diff; };
 // One lane per unit writes the unit's outputs and adds it to the sums it keeps for the workgroup.
 __device__ __forceinline__ void ar_result(const AdapterIn& in, uint64_t u, const ArUnit& r, unsigned long long (&acc)[AR_NSUM]) {
     const uint32_t nr = in.pairs ? 2u : 1u;
     for (uint32_t i = 0; i < nr; i++) {
-        const uint64_t g = in.pairs ? 2ull * u + i : u;
+        const uint64_t g = rows_unit_row(in.pairs, u, i);
         const uint32_t l = r.l[i], cut_o = (r.insert >= 0 && (uint32_t)r.insert < l) ? (uint32_t)r.insert : l, cut_a = r.cut_a[i];
         const uint32_t n = cut_o < cut_a ? cut_o : cut_a, how = (cut_o < l ? 1u : 0u) | (cut_a < l ? 2u : 0u);
         if (in.len) in.len[g] = (int32_t)n;
@@ -75,18 +67,6 @@ __device__ __forceinline__ void ar_result(const AdapterIn& in, uint64_t u, const
             acc[0] += 1ull;
             if (in.hist) atomicAdd(&in.hist[(uint32_t)r.insert < in.hist_len - 1u ? (uint32_t)r.insert : in.hist_len - 1u], 1ull);
         }
-    }
-}
-// The workgroup's sums: a reduction per wave, one atomic add per sum that is not 0.  Every thread of the workgroup calls it.
-template <int NW> __device__ __forceinline__ void ar_sums_out(unsigned long long (&acc)[AR_NSUM], AdapterStat* st) {
-    __shared__ unsigned long long s_red[NW][AR_NSUM];
-#pragma unroll
-    for (int k = 0; k < AR_NSUM; k++) { const unsigned long long t = wave_sum<unsigned long long>(acc[k]); if (lane_id() == 0) s_red[wave_id()][k] = t; }
-    if constexpr (NW > 1) __syncthreads(); else wave_lds_sync();
-    if (threadIdx.x < (uint32_t)AR_NSUM) {
-        unsigned long long t = 0;
-        for (int w = 0; w < NW; w++) t += s_red[w][threadIdx.x];
-        if (t) atomicAdd(&st->c[threadIdx.x], t);
     }
 }
 
@@ -109,7 +89,7 @@ __device__ __forceinline__ ArBits ar_bits(uint32_t ascii, const uint32_t (&b)[4]
             const uint32_t f = b[i] & 0xDFDFDFDFu;
             th[i] = f >> 2; tl[i] = (f >> 1) ^ (f >> 2);
             tv[i] = eq_bytes_full(f, 0x41414141u) | eq_bytes_full(f, 0x43434343u) | eq_bytes_full(f, 0x47474747u) | eq_bytes_full(f, 0x54545454u);
-        } else { th[i] = b[i] >> 1; tl[i] = b[i]; tv[i] = ~jr_ge(b[i], 4u) >> 7; }
+        } else { th[i] = b[i] >> 1; tl[i] = b[i]; tv[i] = ~rows_ge(b[i], 4u) >> 7; }
     }
     ArBits r; r.h = ar_bit0s(th); r.l = ar_bit0s(tl); r.v = ar_bit0s(tv) & span;
     return r;
@@ -149,37 +129,35 @@ template <int LPR> __device__ __forceinline__ uint32_t ar_adapter_cut(const Adap
     return best == AR_NONE ? l : best;
 }
 
-// grid ceil(n_units / (256 / LPR * AR_ITER)) x 256 threads.  Group `grp` of the workgroup (LPR lanes; a wave holds 64 / LPR of them) takes unit
-// (blockIdx * AR_ITER + it) * (256 / LPR) + grp in step `it`.  A group's planes live in the group's own part of the LDS, which only its wave touches: no barrier in
-// the loop.  Per group: the forward planes of both rows, F[row][H L V][NW + 1] (the word behind them stays 0: the adapter's funnel reads it), and the planes of y,
-// Y[H L V][3 NW + 1], y's T bits in words NW .. 2 NW - 1 and zeros around them.  The zeros are written once; every step rewrites all T bits of every plane it uses.
+// grid ceil(n_units / (256 / LPR * AR_ITER)) x 256 threads.  A group of the workgroup (UnitGroup: LPR lanes) takes a unit per step, AR_ITER steps.  A group's planes
+// live in the group's own part of the LDS, which only its wave touches: no barrier in the loop.  Per group: the forward planes of both rows, F[row][H L V][NW + 1]
+// (the word behind them stays 0: the adapter's funnel reads it), and the planes of y, Y[H L V][3 NW + 1], y's T bits in words NW .. 2 NW - 1 and zeros around
+// them.  The zeros are written once; every step rewrites all T bits of every plane it uses.
 template <int LPR> __global__ void __launch_bounds__(256) k_adapter_rows(AdapterIn in, AdapterStat* __restrict__ st) {
-    constexpr uint32_t T = LPR * 16u, NW = T / 64u, FW = NW + 1u, YW = 3u * NW + 1u, GS = 6u * FW + 3u * YW, R = 256u / LPR, GW = 64u / LPR;
-    __shared__ unsigned long long s_P[R * GS];
-    const uint32_t grp = threadIdx.x / LPR, gl = threadIdx.x % LPR, x0 = 16u * gl;
-    unsigned long long* const F = s_P + grp * GS; unsigned long long* const Y = F + 6u * FW;
-    for (uint32_t i = gl; i < GS; i += (uint32_t)LPR) F[i] = 0ull;
+    constexpr uint32_t T = LPR * 16u, NW = T / 64u, FW = NW + 1u, YW = 3u * NW + 1u, GS = 6u * FW + 3u * YW;
+    const UnitGroup<LPR> ug{};
+    __shared__ unsigned long long s_P[UnitGroup<LPR>::R * GS];
+    unsigned long long* const F = s_P + ug.grp * GS; unsigned long long* const Y = F + 6u * FW;
+    for (uint32_t i = ug.gl; i < GS; i += (uint32_t)LPR) F[i] = 0ull;
     wave_lds_sync();
-    unsigned long long acc[AR_NSUM];
-#pragma unroll
-    for (int k = 0; k < AR_NSUM; k++) acc[k] = 0ull;
+    unsigned long long acc[AR_NSUM] = {};
     const uint32_t nr = in.pairs ? 2u : 1u;
     for (uint32_t it = 0; it < AR_ITER; it++) {
-        const uint64_t u = ((uint64_t)blockIdx.x * AR_ITER + it) * R + grp;
-        if (u - grp % GW >= in.n_units) break;                              // (the wave's first unit: the same in every lane of the wave)
+        const uint64_t u = ug.unit(it, AR_ITER);
+        if (ug.past(u, in.n_units)) break;
         const bool live = u < in.n_units;
-        const uint64_t g0 = in.pairs ? 2ull * u : u;
+        const uint64_t g0 = rows_unit_row(in.pairs, u, 0u);
         ArUnit r; r.l[0] = r.l[1] = 0u; r.cut_a[0] = r.cut_a[1] = 0u; r.insert = -1; r.diff = 0u;
         for (uint32_t i = 0; i < nr; i++) {
-            const uint32_t l = live ? ar_len(in, g0 + i, st, gl == 0u) : 0u;
+            const uint32_t l = live ? rows_len_checked(in, g0 + i, st, ug.gl == 0u) : 0u;
             r.l[i] = l;
             uint32_t b[4] = { 0u, 0u, 0u, 0u };
-            if (x0 < l) rows_ld16(in.b, in.vec_in, in.total, (g0 + i) * in.row_len, x0, l, b);
-            const ArBits m = ar_bits(in.ascii, b, jr_span(x0, 0u, l));
+            if (ug.x0 < l) rows_ld16(in.b, in.vec_in, in.total, (g0 + i) * in.row_len, ug.x0, l, b);
+            const ArBits m = ar_bits(in.ascii, b, rows_span(ug.x0, 0u, l));
             unsigned long long* const P = F + 3u * i * FW;
-            ((ar_u16*)P)[gl] = (uint16_t)m.h; ((ar_u16*)(P + FW))[gl] = (uint16_t)m.l; ((ar_u16*)(P + 2u * FW))[gl] = (uint16_t)m.v;
+            ((ar_u16*)P)[ug.gl] = (uint16_t)m.h; ((ar_u16*)(P + FW))[ug.gl] = (uint16_t)m.l; ((ar_u16*)(P + 2u * FW))[ug.gl] = (uint16_t)m.v;
             if (i == 1u) {                                                   // y = the reverse complement of R2: position j at bit T - l2 + j
-                const uint32_t s = (uint32_t)LPR - 1u - gl;
+                const uint32_t s = (uint32_t)LPR - 1u - ug.gl;
                 ((ar_u16*)(Y + NW))[s] = (uint16_t)ar_rev16(m.h ^ 0xFFFFu); ((ar_u16*)(Y + YW + NW))[s] = (uint16_t)ar_rev16(m.l ^ 0xFFFFu);
                 ((ar_u16*)(Y + 2u * YW + NW))[s] = (uint16_t)ar_rev16(m.v);
             }
@@ -191,7 +169,7 @@ template <int LPR> __global__ void __launch_bounds__(256) k_adapter_rows(Adapter
             for (uint32_t k0 = 0; ; k0 += (uint32_t)LPR) {
                 const bool act = best == AR_NONE && k0 < nsh;
                 if (!__any(act)) break;
-                uint32_t cand = AR_NONE; const uint32_t k = k0 + gl;
+                uint32_t cand = AR_NONE; const uint32_t k = k0 + ug.gl;
                 if (act && k < nsh) {
                     const int32_t d = ar_shift(k, n0);
                     const uint32_t ov = ar_ov(d, l1, l2);
@@ -215,11 +193,11 @@ template <int LPR> __global__ void __launch_bounds__(256) k_adapter_rows(Adapter
             }
             if (best != AR_NONE) { r.insert = ar_shift(best >> 11, n0) + (int32_t)l2; r.diff = best & 0x7FFu; }
         }
-        for (uint32_t i = 0; i < nr; i++) r.cut_a[i] = ar_adapter_cut<LPR>(in, F + 3u * i * FW, FW, r.l[i], i, gl);
-        if (gl == 0u && live) ar_result(in, u, r, acc);
+        for (uint32_t i = 0; i < nr; i++) r.cut_a[i] = ar_adapter_cut<LPR>(in, F + 3u * i * FW, FW, r.l[i], i, ug.gl);
+        if (ug.gl == 0u && live) ar_result(in, u, r, acc);
         wave_lds_sync();                                                     // (the next unit's planes go where these were read)
     }
-    ar_sums_out<4>(acc, st);
+    rows_sums_out<4>(acc, st->c);
 }
 
 // ---- any row length
@@ -232,12 +210,10 @@ __device__ __forceinline__ uint32_t ar_cls(uint32_t ascii, uint8_t c) {
 // in front of a read's length, so never outside the rows.  The first block that holds an acceptable shift ends the search.
 __global__ void __launch_bounds__(64) k_adapter_rows_any(AdapterIn in, AdapterStat* __restrict__ st) {
     const uint64_t u = blockIdx.x; const uint32_t lane = threadIdx.x, nr = in.pairs ? 2u : 1u;
-    const uint64_t g0 = in.pairs ? 2ull * u : u;
-    unsigned long long acc[AR_NSUM];
-#pragma unroll
-    for (int k = 0; k < AR_NSUM; k++) acc[k] = 0ull;
+    const uint64_t g0 = rows_unit_row(in.pairs, u, 0u);
+    unsigned long long acc[AR_NSUM] = {};
     ArUnit r; r.l[0] = r.l[1] = 0u; r.cut_a[0] = r.cut_a[1] = 0u; r.insert = -1; r.diff = 0u;
-    for (uint32_t i = 0; i < nr; i++) r.l[i] = ar_len(in, g0 + i, st, lane == 0u);
+    for (uint32_t i = 0; i < nr; i++) r.l[i] = rows_len_checked(in, g0 + i, st, lane == 0u);
     if (in.pairs) {
         const uint8_t* const x = in.b + g0 * in.row_len; const uint8_t* const r2 = x + in.row_len;
         const uint32_t l1 = r.l[0], l2 = r.l[1], n0 = ar_n_up(in, l1), nsh = n0 + ar_n_down(in, l2);
@@ -281,5 +257,5 @@ __global__ void __launch_bounds__(64) k_adapter_rows_any(AdapterIn in, AdapterSt
         }
     }
     if (lane == 0u) ar_result(in, u, r, acc);
-    ar_sums_out<1>(acc, st);
+    rows_sums_out<1>(acc, st->c);
 }

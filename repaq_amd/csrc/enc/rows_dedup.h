@@ -1,7 +1,7 @@
 // enc/rows_dedup.h - rows -> a keep byte per row that leaves ONE unit (a row, or a pair of rows) of every class of units with identical keys, the representative
 // and the size of every class, a class-size histogram and one summary (rfq_dedup_rows): the step between rfq_judge_rows and rfq_select_rows that relates rows to
 // each other.  It decides and moves no bytes.
-// Part of rfq_encode_kernels.h (included from there, last, behind rows_judge.h whose 16-byte pieces and group reductions it uses; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, last, behind rows_lanes.h whose 16-byte pieces, group reductions and unit walk it uses; not a stand-alone header).
 #pragma once
 // A key is (k, bytes [0, k)) of a row, k = min(length, key_len); a pair's key is R1's followed by R2's (include/rfq_hip.h has the rules).  Three kernels:
 //   k_dedup_key<16> / <64>   a unit of rows of up to 256 / 1024 bytes is held by a group of 16 lanes (a DPP row) / by a wave, a lane loads ONE 16-byte group of the
@@ -16,7 +16,6 @@
 // The fingerprint is private: it picks the slot a probe starts at and the tag that saves byte compares, and NOTHING ELSE - equality is always decided on the bytes,
 // and what a class reports (its lowest member or its best one, its size) is the same whichever member claimed the slot and in whatever order the others came.  All
 // sums are integers.  RFQ_DEDUP=collide keeps 4 bits of the fingerprint: every probe chain is long and every tag hit a real compare (the tests' "general" form).
-#define DD_ERR_LEN 1u                 // a length that is negative or greater than row_len (RFQ_E_ARG)
 #define DD_NSUM 5                     // n_candidates, bases_in (k_dedup_key); n_classes, bases_kept (k_dedup_resolve); [4] max_class (an atomicMax)
 #define DD_ITER 8u
 #define DD_NONE 0xFFFFFFFFu           // in the score scratch: not a candidate; in the slot scratch: no slot
@@ -33,21 +32,10 @@ struct DedupIn {
     uint64_t S;                                                               // a power of two, >= 2 * n_units
     uint8_t* keep; int32_t* dup_of; uint32_t* count; unsigned long long* hist;        // [n_rows], [n_units], [n_units], [hist_len], or null
 };
-// what the host reads back: zeroed per call, bad_row = ~0
-struct DedupStat { uint32_t err, pad; unsigned long long bad_row; unsigned long long c[DD_NSUM]; };
+typedef RowsSums<DD_NSUM> DedupStat;
 
-__device__ __forceinline__ uint32_t dd_len(const DedupIn& in, uint64_t g, DedupStat* st, bool first) {
-    const int32_t l = in.lens[g];
-    if (l >= 0 && (uint32_t)l <= in.row_len) return (uint32_t)l;
-    if (first) { atomicOr(&st->err, DD_ERR_LEN); atomicMin(&st->bad_row, (unsigned long long)g); }
-    return 0u;                                                               // (nothing of such a row is read; the call is refused)
-}
-// the key window of row g: the claim kernel's form of dd_len (the key kernel has reported a bad length already)
-__device__ __forceinline__ uint32_t dd_klen(const DedupIn& in, uint64_t g) {
-    const int32_t l = in.lens[g];
-    const uint32_t u = (l >= 0 && (uint32_t)l <= in.row_len) ? (uint32_t)l : 0u;
-    return in.key_len && in.key_len < u ? in.key_len : u;
-}
+// the key window of a row of l bytes
+__device__ __forceinline__ uint32_t dd_kwin(const DedupIn& in, uint32_t l) { return in.key_len && in.key_len < l ? in.key_len : l; }
 __device__ __forceinline__ bool dd_cand(const DedupIn& in, uint64_t u) {
     if (!in.cand) return true;
     return in.pairs ? (in.cand[2ull * u] != 0u && in.cand[2ull * u + 1ull] != 0u) : in.cand[u] != 0u;
@@ -69,52 +57,40 @@ __device__ __forceinline__ unsigned long long dd_fold_len(unsigned long long sum
 // R2's fingerprint into R1's: not symmetric, so that a pair with its mates swapped gets another value
 __device__ __forceinline__ unsigned long long dd_fold_mate(unsigned long long f1, unsigned long long f2) { return dd_avalanche(f1 * 0x9FB21C651E98DF25ull + ((f2 << 23) | (f2 >> 41))); }
 
-// The workgroup's sums: a reduction per wave, one atomic add per sum that is not 0 (sums [first, first + N) of the block).  Every thread of the workgroup calls it.
-template <int NW, int N> __device__ __forceinline__ void dd_sums_out(unsigned long long (&acc)[N], unsigned long long* dst) {
-    __shared__ unsigned long long s_red[NW][N];
-#pragma unroll
-    for (int k = 0; k < N; k++) { const unsigned long long t = wave_sum<unsigned long long>(acc[k]); if (lane_id() == 0) s_red[wave_id()][k] = t; }
-    if constexpr (NW > 1) __syncthreads(); else wave_lds_sync();
-    if (threadIdx.x < (uint32_t)N) {
-        unsigned long long t = 0;
-        for (int w = 0; w < NW; w++) t += s_red[w][threadIdx.x];
-        if (t) atomicAdd(&dst[threadIdx.x], t);
-    }
-}
 // one lane per unit: the unit's scratch entries and its part of the sums
 __device__ __forceinline__ void dd_key_out(const DedupIn& in, uint64_t u, bool cand, unsigned long long fp, uint32_t score, unsigned long long lsum, unsigned long long (&acc)[2]) {
     in.fp[u] = fp; in.score[u] = cand ? score : DD_NONE;
     if (cand) { acc[0] += 1ull; acc[1] += lsum; }
 }
 
-// grid ceil(n_units / (256 / LPR * DD_ITER)) x 256 threads.  Group `grp` of the workgroup (LPR lanes) takes unit (blockIdx * DD_ITER + it) * (256 / LPR) + grp in
-// step `it`, one row after the other.  ALL rows' lengths are checked, candidates or not; only a candidate's bytes are loaded.  What depends on the unit only masks:
+// grid ceil(n_units / (256 / LPR * DD_ITER)) x 256 threads.  A group of the workgroup (UnitGroup: LPR lanes) takes a unit per step, DD_ITER steps, one row after
+// the other.  ALL rows' lengths are checked, candidates or not; only a candidate's bytes are loaded.  What depends on the unit only masks:
 // the reductions are called by every lane of the wave.
 template <int LPR> __global__ void __launch_bounds__(256) k_dedup_key(DedupIn in, DedupStat* __restrict__ st) {
-    constexpr uint32_t R = 256u / LPR, GW = 64u / LPR;
-    const uint32_t grp = threadIdx.x / LPR, gl = threadIdx.x % LPR, x0 = 16u * gl, nr = in.pairs ? 2u : 1u;
+    const UnitGroup<LPR> ug{};
+    const uint32_t nr = in.pairs ? 2u : 1u;
     unsigned long long acc[2] = { 0ull, 0ull };
     for (uint32_t it = 0; it < DD_ITER; it++) {
-        const uint64_t u = ((uint64_t)blockIdx.x * DD_ITER + it) * R + grp;
-        if (u - grp % GW >= in.n_units) break;                              // (the wave's first unit: the same in every lane of the wave)
+        const uint64_t u = ug.unit(it, DD_ITER);
+        if (ug.past(u, in.n_units)) break;
         const bool live = u < in.n_units, cand = live && dd_cand(in, u);
         unsigned long long fp = 0ull, lsum = 0ull; uint32_t score = 0u;
         for (uint32_t i = 0; i < nr; i++) {
-            const uint64_t g = in.pairs ? 2ull * u + i : u;
-            const uint32_t l = live ? dd_len(in, g, st, gl == 0u) : 0u, k = in.key_len && in.key_len < l ? in.key_len : l;
+            const uint64_t g = rows_unit_row(in.pairs, u, i);
+            const uint32_t l = live ? rows_len_checked(in, g, st, ug.gl == 0u) : 0u, k = dd_kwin(in, l);
             const uint64_t rowbase = g * in.row_len;
             uint32_t b[4] = { 0u, 0u, 0u, 0u }, q[4] = { 0u, 0u, 0u, 0u };
-            const bool mine = cand && x0 < k;
-            if (mine) { rows_ld16(in.b, in.vec_in, in.total, rowbase, x0, k, b); if (in.q) rows_ld16(in.q, in.vec_in, in.total, rowbase, x0, k, q); }
-            const unsigned long long hs = grp_sum<LPR>(mine ? dd_mix16(b, gl) : 0ull);
-            const uint32_t sc = grp_sum<LPR>(jr_sum16(q));
+            const bool mine = cand && ug.x0 < k;
+            if (mine) { rows_ld16(in.b, in.vec_in, in.total, rowbase, ug.x0, k, b); if (in.q) rows_ld16(in.q, in.vec_in, in.total, rowbase, ug.x0, k, q); }
+            const unsigned long long hs = grp_sum<LPR>(mine ? dd_mix16(b, ug.gl) : 0ull);
+            const uint32_t sc = grp_sum<LPR>(rows_sum16(q));
             const unsigned long long f = dd_fold_len(hs, k);
             fp = i == 0u ? f : dd_fold_mate(fp, f);
             score += sc; lsum += l;
         }
-        if (gl == 0u && live) dd_key_out(in, u, cand, fp, score, lsum, acc);
+        if (ug.gl == 0u && live) dd_key_out(in, u, cand, fp, score, lsum, acc);
     }
-    dd_sums_out<4, 2>(acc, st->c);
+    rows_sums_out<4>(acc, st->c);
 }
 // grid n_units x 64 threads: a wave per unit, everything about the unit is the same in every lane.  A lane adds up its groups' parts over the tiles, one reduction
 // per row.
@@ -124,8 +100,8 @@ __global__ void __launch_bounds__(64) k_dedup_key_long(DedupIn in, DedupStat* __
     unsigned long long acc[2] = { 0ull, 0ull };
     unsigned long long fp = 0ull, lsum = 0ull; uint32_t score = 0u;
     for (uint32_t i = 0; i < nr; i++) {
-        const uint64_t g = in.pairs ? 2ull * u + i : u;
-        const uint32_t l = dd_len(in, g, st, threadIdx.x == 0u), k = in.key_len && in.key_len < l ? in.key_len : l;
+        const uint64_t g = rows_unit_row(in.pairs, u, i);
+        const uint32_t l = rows_len_checked(in, g, st, threadIdx.x == 0u), k = dd_kwin(in, l);
         const uint64_t rowbase = g * in.row_len;
         unsigned long long h = 0ull; uint32_t s = 0u;
         if (cand) for (uint32_t t0 = 0; t0 < k; t0 += 1024u) {
@@ -134,14 +110,14 @@ __global__ void __launch_bounds__(64) k_dedup_key_long(DedupIn in, DedupStat* __
             uint32_t b[4], q[4] = { 0u, 0u, 0u, 0u };
             rows_ld16(in.b, in.vec_in, in.total, rowbase, p0, k, b);
             if (in.q) rows_ld16(in.q, in.vec_in, in.total, rowbase, p0, k, q);
-            h += dd_mix16(b, p0 >> 4); s += jr_sum16(q);
+            h += dd_mix16(b, p0 >> 4); s += rows_sum16(q);
         }
         const unsigned long long f = dd_fold_len(wave_sum<unsigned long long>(h), k);
         fp = i == 0u ? f : dd_fold_mate(fp, f);
         score += wave_sum<uint32_t>(s); lsum += l;
     }
     if (threadIdx.x == 0u) dd_key_out(in, u, cand, fp, score, lsum, acc);
-    dd_sums_out<1, 2>(acc, st->c);
+    rows_sums_out<1>(acc, st->c);
 }
 
 // ---- the table.  A slot is tag32 << 32 | (unit + 1), 0 = empty.  It is read through the compare-and-swap's return value or through a relaxed agent-scope atomic
@@ -157,9 +133,9 @@ __device__ __forceinline__ unsigned long long dd_peek(const unsigned long long* 
 __device__ __forceinline__ bool dd_same(const DedupIn& in, uint64_t u, uint64_t v) {
     const uint32_t nr = in.pairs ? 2u : 1u;
     for (uint32_t i = 0; i < nr; i++) {
-        const uint64_t g = in.pairs ? 2ull * u + i : u, h = in.pairs ? 2ull * v + i : v;
-        const uint32_t k = dd_klen(in, g);
-        if (k != dd_klen(in, h)) return false;
+        const uint64_t g = rows_unit_row(in.pairs, u, i), h = rows_unit_row(in.pairs, v, i);
+        const uint32_t k = dd_kwin(in, rows_len_or0(in, g));       // (the key kernel has reported a bad length already)
+        if (k != dd_kwin(in, rows_len_or0(in, h))) return false;
         const uint64_t gb = g * in.row_len, hb = h * in.row_len;
         for (uint32_t off = 0; off < k; off += 16u) {
             uint32_t a[4], c[4];
@@ -211,9 +187,9 @@ __global__ void __launch_bounds__(256) k_dedup_resolve(DedupIn in, DedupStat* __
         const bool is_rep = s != DD_NONE && rep == (uint32_t)u;
         const uint32_t nr = in.pairs ? 2u : 1u; unsigned long long lsum = 0ull;
         for (uint32_t i = 0; i < nr; i++) {
-            const uint64_t g = in.pairs ? 2ull * u + i : u;
+            const uint64_t g = rows_unit_row(in.pairs, u, i);
             if (in.keep) in.keep[g] = is_rep ? 1u : 0u;
-            if (is_rep) { const int32_t l = in.lens[g]; lsum += (l >= 0 && (uint32_t)l <= in.row_len) ? (uint32_t)l : 0u; }
+            if (is_rep) lsum += rows_len_or0(in, g);
         }
         if (in.dup_of) in.dup_of[u] = s != DD_NONE ? (int32_t)rep : -1;
         if (in.count) in.count[u] = is_rep ? c : 0u;
@@ -222,7 +198,7 @@ __global__ void __launch_bounds__(256) k_dedup_resolve(DedupIn in, DedupStat* __
             if (hist) atomicAdd(&s_hist[(c < in.hist_len ? c : in.hist_len) - 1u], 1u);
         }
     }
-    dd_sums_out<4, 2>(acc, st->c + 2);
+    rows_sums_out<4>(acc, st->c + 2);
     mx = wave_max<uint32_t>(mx);
     if (lane_id() == 0) s_max[wave_id()] = mx;
     __syncthreads();

@@ -1,6 +1,6 @@
 // enc/rows_judge.h - rows -> a verdict per row: a keep byte, a window (start, len), a reason byte and four metrics, in the arrays rfq_select_rows takes, and
 // one QC summary of the batch (rfq_judge_rows): the step that DECIDES, between rfq_decode_rows / rfq_text_rows and rfq_select_rows
-// Part of rfq_encode_kernels.h (included from there, last; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, behind rows_lanes.h whose group reductions, 16-byte pieces and unit walk it uses; not a stand-alone header).
 #pragma once
 // Everything is integer arithmetic on the row bytes (include/rfq_hip.h has the rules).  A lane owns 16 consecutive positions of a row: one 16-byte load of the
 // bases and one of the qualities, turned at once into 16-bit masks (is G, is N, below qual_q, >= 20, >= 30, differs from the byte before) by SWAR compares and
@@ -11,7 +11,6 @@
 //   k_judge_rows_long         any row length: a wave per row walks the row in tiles of `tile` window starts (1024; RFQ_JUDGE=general: 64, so that small rows
 //                             have seams) with the cut window's halo behind them (tile + window - 1 <= 2047 bytes, two loads per lane), once per step.
 // All sums are integers and leave a workgroup as JR_NSUM atomic adds: the result is the same bit for bit from run to run.
-#define JR_ERR_LEN 1u                 // a length that is negative or greater than row_len (RFQ_E_ARG)
 #define JR_NSUM 14                    // n_kept, why x 5, (bases, qsum, q20, q30) of the reads, the same of the kept windows
 #define JR_ITER 8u
 #define JR_CUT_FRONT 1u
@@ -29,97 +28,20 @@ struct JudgeIn {
     uint32_t tile;                                                            // k_judge_rows_long: window starts per tile (a multiple of 16, <= 1024)
     uint8_t* keep; int32_t* start; int32_t* len; uint8_t* why; uint32_t* metrics;   // [n_rows] each ([n_rows][4]), or null
 };
-// what the host reads back: zeroed per call, bad_row = ~0
-struct JudgeStat { uint32_t err, pad; unsigned long long bad_row; unsigned long long c[JR_NSUM]; };
-
-// ---- reductions over a group of LPR lanes (16: a DPP row; 64: the wave), the result in every lane of the group.  Called by ALL lanes of the wave.
-#ifdef RFQ_SIMT_EMULATION
-template <class T> __device__ __forceinline__ T row_incl_sum(T v) {
-    const int l = lane_id() & 15;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) { T t = __shfl_up(v, (unsigned)d); if (l >= d) v = t + v; }
-    return v;
-}
-template <class T> __device__ __forceinline__ T row_sum(T v) {
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ uint32_t row_min(uint32_t v) {
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) { const uint32_t t = __shfl_xor(v, d); if (t < v) v = t; }
-    return v;
-}
-__device__ __forceinline__ uint32_t row_max(uint32_t v) {
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) { const uint32_t t = __shfl_xor(v, d); if (t > v) v = t; }
-    return v;
-}
-#else
-// row_shr:1/2/4/8 - the scan of RFQ_DPP_SCAN without its two steps across the rows; row_ror:1/2/4/8 - after them every lane holds its row's 16 values combined
-#define RFQ_DPP_ROW_ALL(v, OP) { RFQ_DPP_STEP(v, OP, v, 0x121, 0xF) RFQ_DPP_STEP(v, OP, v, 0x122, 0xF) RFQ_DPP_STEP(v, OP, v, 0x124, 0xF) RFQ_DPP_STEP(v, OP, v, 0x128, 0xF) }
-template <class T> __device__ __forceinline__ T row_incl_sum(T v) {
-    RFQ_DPP_STEP(v, RFQ_OP_ADD, T(), 0x111, 0xF) RFQ_DPP_STEP(v, RFQ_OP_ADD, T(), 0x112, 0xF) RFQ_DPP_STEP(v, RFQ_OP_ADD, T(), 0x114, 0xF) RFQ_DPP_STEP(v, RFQ_OP_ADD, T(), 0x118, 0xF)
-    return v;
-}
-template <class T> __device__ __forceinline__ T row_sum(T v) { RFQ_DPP_ROW_ALL(v, RFQ_OP_ADD) return v; }
-__device__ __forceinline__ uint32_t row_min(uint32_t v) { RFQ_DPP_ROW_ALL(v, RFQ_OP_MIN) return v; }
-__device__ __forceinline__ uint32_t row_max(uint32_t v) { RFQ_DPP_ROW_ALL(v, RFQ_OP_MAX) return v; }
-#endif
-template <int LPR, class T> __device__ __forceinline__ T grp_incl_sum(T v) { if constexpr (LPR == 16) return row_incl_sum(v); else return wave_incl_sum(v); }
-template <int LPR, class T> __device__ __forceinline__ T grp_sum(T v) { if constexpr (LPR == 16) return row_sum(v); else return wave_sum(v); }
-template <int LPR> __device__ __forceinline__ uint32_t grp_min(uint32_t v) { if constexpr (LPR == 16) return row_min(v); else return wave_min(v); }
-template <int LPR> __device__ __forceinline__ uint32_t grp_max(uint32_t v) { if constexpr (LPR == 16) return row_max(v); else return wave_max(v); }
+typedef RowsSums<JR_NSUM> JudgeStat;
 
 // ---- a lane's 16 bytes
-// 0x80 in every byte of w that is >= k (k in 0 .. 256; bytes are unsigned)
-__device__ __forceinline__ uint32_t jr_ge(uint32_t w, uint32_t k) {
-    const uint32_t lo = w & 0x7F7F7F7Fu;
-    return k <= 128u ? ((lo + (128u - k) * 0x01010101u) | w) & 0x80808080u : ((lo + (256u - k) * 0x01010101u) & w) & 0x80808080u;
+__device__ __forceinline__ uint32_t jr_g_bits(const JudgeIn& in, const uint32_t (&b)[4]) {
+    return in.ascii ? rows_eq_bits(b, 0xDFDFDFDFu, 0x47474747u) : rows_eq_bits(b, 0xFFFFFFFFu, 0x02020202u);
 }
-// bit j = the 0x80 flag of byte j of the 16 bytes
-__device__ __forceinline__ uint32_t jr_bits(const uint32_t (&t)[4]) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) m |= udot4((t[i] >> 7) & 0x01010101u, 0x08040201u, 0u) << (4 * i);
-    return m;
+__device__ __forceinline__ uint32_t jr_n_bits(const JudgeIn& in, const uint32_t (&b)[4]) {
+    return in.ascii ? rows_eq_bits(b, 0xDFDFDFDFu, 0x4E4E4E4Eu) : rows_eq_bits(b, 0xFFFFFFFFu, 0x04040404u);
 }
-__device__ __forceinline__ uint32_t jr_ge_bits(const uint32_t (&q)[4], uint32_t k) { const uint32_t t[4] = { jr_ge(q[0], k), jr_ge(q[1], k), jr_ge(q[2], k), jr_ge(q[3], k) }; return jr_bits(t); }
-__device__ __forceinline__ uint32_t jr_eq_bits(const uint32_t (&b)[4], uint32_t fold, uint32_t pat) {
-    const uint32_t t[4] = { eq_bytes_full(b[0] & fold, pat), eq_bytes_full(b[1] & fold, pat), eq_bytes_full(b[2] & fold, pat), eq_bytes_full(b[3] & fold, pat) };
-    return jr_bits(t);
-}
-__device__ __forceinline__ uint32_t jr_g_bits(const JudgeIn& in, const uint32_t (&b)[4]) { return in.ascii ? jr_eq_bits(b, 0xDFDFDFDFu, 0x47474747u) : jr_eq_bits(b, 0xFFFFFFFFu, 0x02020202u); }
-__device__ __forceinline__ uint32_t jr_n_bits(const JudgeIn& in, const uint32_t (&b)[4]) { return in.ascii ? jr_eq_bits(b, 0xDFDFDFDFu, 0x4E4E4E4Eu) : jr_eq_bits(b, 0xFFFFFFFFu, 0x04040404u); }
 // bit j: byte j differs from the byte in front of it (prev: the byte in front of byte 0)
 __device__ __forceinline__ uint32_t jr_trans_bits(const uint32_t (&b)[4], uint32_t prev) {
     const uint32_t t[4] = { ~eq_bytes_full(b[0], (b[0] << 8) | (prev & 0xFFu)), ~eq_bytes_full(b[1], (b[1] << 8) | (b[0] >> 24)), ~eq_bytes_full(b[2], (b[2] << 8) | (b[1] >> 24)),
                             ~eq_bytes_full(b[3], (b[3] << 8) | (b[2] >> 24)) };
-    return jr_bits(t);
-}
-// bit j: position x0 + j lies in [lo, hi)
-__device__ __forceinline__ uint32_t jr_span(uint32_t x0, uint32_t lo, uint32_t hi) {
-    if (hi <= lo || hi <= x0 || lo >= x0 + 16u) return 0u;
-    const uint32_t f = lo > x0 ? lo - x0 : 0u, t = hi - x0 < 16u ? hi - x0 : 16u;
-    return ((1u << t) - 1u) & ~((1u << f) - 1u);
-}
-__device__ __forceinline__ uint32_t jr_sum16(const uint32_t (&q)[4]) { return udot4(q[3], 0x01010101u, udot4(q[2], 0x01010101u, udot4(q[1], 0x01010101u, udot4(q[0], 0x01010101u, 0u)))); }
-// Bytes [off, off + 16) of the row that starts at byte `rowbase` of buf (off a multiple of 16, off < lim <= row_len): bytes at positions >= lim come back 0.
-// Never a byte outside the buffer: whole aligned groups lie inside their row; else 16 bytes at the row's own alignment wherever they still lie inside the
-// buffer; only at the buffer's very end byte by byte.
-__device__ __forceinline__ void rows_ld16(const uint8_t* buf, uint32_t vec_in, uint64_t total, uint64_t rowbase, uint32_t off, uint32_t lim, uint32_t (&w)[4]) {
-    const uint64_t p = rowbase + off; const uint32_t have = lim - off < 16u ? lim - off : 16u;
-    if (vec_in) rt_ld16(buf + p, true, w);
-    else if (p + 16u <= total) rt_ld16(buf + p, false, w);
-    else {
-        w[0] = w[1] = w[2] = w[3] = 0u;
-        for (uint32_t i = 0; i < have; i++) w[i >> 2] |= (uint32_t)buf[p + i] << (8u * (i & 3u));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) w[i] &= low_bytes((int)have - 4 * i);
-}
-__device__ __forceinline__ void jr_ld(const JudgeIn& in, const uint8_t* buf, uint64_t rowbase, uint32_t off, uint32_t lim, uint32_t (&w)[4]) {
-    rows_ld16(buf, in.vec_in, in.total, rowbase, off, lim, w);
+    return rows_bits(t);
 }
 // E[i] lives at word i + i / 16: the lanes of a group read and write 16 positions apart - 17 words, another bank each
 __device__ __forceinline__ uint32_t jr_ix(uint32_t i) { return i + (i >> 4); }
@@ -163,85 +85,64 @@ __device__ __forceinline__ void jr_verdict(const JudgeIn& in, uint64_t g, const 
     acc[6] += r.l; acc[7] += r.qsum_in; acc[8] += r.q20i; acc[9] += r.q30i;
     if (why == 0u) { acc[10] += n; acc[11] += r.qsum; acc[12] += r.q20o; acc[13] += r.q30o; }
 }
-// The workgroup's sums: a DPP reduction per wave, one atomic add per sum that is not 0.  Every thread of the workgroup calls it.
-template <int NW> __device__ __forceinline__ void jr_sums_out(unsigned long long (&acc)[JR_NSUM], JudgeStat* st) {
-    __shared__ unsigned long long s_red[NW][JR_NSUM];
-#pragma unroll
-    for (int k = 0; k < JR_NSUM; k++) { const unsigned long long t = wave_sum<unsigned long long>(acc[k]); if (lane_id() == 0) s_red[wave_id()][k] = t; }
-    if constexpr (NW > 1) __syncthreads(); else wave_lds_sync();
-    if (threadIdx.x < (uint32_t)JR_NSUM) {
-        unsigned long long t = 0;
-        for (int w = 0; w < NW; w++) t += s_red[w][threadIdx.x];
-        if (t) atomicAdd(&st->c[threadIdx.x], t);
-    }
-}
-__device__ __forceinline__ uint32_t jr_len(const JudgeIn& in, uint64_t g, JudgeStat* st, bool first) {
-    const int32_t l = in.lens[g];
-    if (l >= 0 && (uint32_t)l <= in.row_len) return (uint32_t)l;
-    if (first) { atomicOr(&st->err, JR_ERR_LEN); atomicMin(&st->bad_row, (unsigned long long)g); }
-    return 0u;                                                               // (nothing of such a row is read; the call is refused)
-}
 
-// grid ceil(n_rows / (256 / LPR * JR_ITER)) x 256 threads.  Group `grp` of the workgroup (LPR lanes; a wave holds 64 / LPR of them) judges row
-// (blockIdx * JR_ITER + it) * (256 / LPR) + grp in step `it`.  A group's E lives in the group's own part of the LDS, which only its wave touches: no barrier in
-// the loop.  Steps are switched by kernel arguments (the same in every lane); what depends on the ROW - an empty window - only masks: the reductions are called
-// by every lane of the wave in every step that is on.
+// grid ceil(n_rows / (256 / LPR * JR_ITER)) x 256 threads.  A group of the workgroup (UnitGroup: LPR lanes) judges a row per step, JR_ITER steps.  A group's E
+// lives in the group's own part of the LDS, which only its wave touches: no barrier in the loop.  Steps are switched by kernel arguments (the same in
+// every lane); what depends on the ROW - an empty window - only masks: the reductions are called by every lane of the wave in every step that is on.
 template <int LPR> __global__ void __launch_bounds__(256) k_judge_rows(JudgeIn in, JudgeStat* __restrict__ st) {
-    constexpr uint32_t T = LPR * 16u, ES = T + T / 16u + 1u, R = 256u / LPR, GW = 64u / LPR;
-    __shared__ uint32_t s_E[R * ES];
-    const uint32_t grp = threadIdx.x / LPR, gl = threadIdx.x % LPR, x0 = 16u * gl;
-    uint32_t* const E = s_E + grp * ES;
-    unsigned long long acc[JR_NSUM];
-#pragma unroll
-    for (int k = 0; k < JR_NSUM; k++) acc[k] = 0ull;
+    constexpr uint32_t T = LPR * 16u, ES = T + T / 16u + 1u;
+    const UnitGroup<LPR> ug{};
+    __shared__ uint32_t s_E[UnitGroup<LPR>::R * ES];
+    uint32_t* const E = s_E + ug.grp * ES;
+    unsigned long long acc[JR_NSUM] = {};
     const uint32_t cw = in.cut_window, kq = in.qual_q < 256u ? in.qual_q : 256u;
     for (uint32_t it = 0; it < JR_ITER; it++) {
-        const uint64_t g = ((uint64_t)blockIdx.x * JR_ITER + it) * R + grp;
-        if (g - grp % GW >= in.n_rows) break;                               // (the wave's first row: the same in every lane of the wave)
+        const uint64_t g = ug.unit(it, JR_ITER);
+        if (ug.past(g, in.n_rows)) break;
         const bool live = g < in.n_rows;
-        const uint32_t l = live ? jr_len(in, g, st, gl == 0u) : 0u;
+        const uint32_t l = live ? rows_len_checked(in, g, st, ug.gl == 0u) : 0u;
         const uint64_t rowbase = g * in.row_len;
         uint32_t b[4] = { 0u, 0u, 0u, 0u }, q[4] = { 0u, 0u, 0u, 0u };
-        if (x0 < l) { if (in.b) jr_ld(in, in.b, rowbase, x0, l, b); if (in.q) jr_ld(in, in.q, rowbase, x0, l, q); }
+        if (ug.x0 < l) { if (in.b) rows_ld16(in.b, in.vec_in, in.total, rowbase, ug.x0, l, b); if (in.q) rows_ld16(in.q, in.vec_in, in.total, rowbase, ug.x0, l, q); }
         const uint32_t prev = wave_shr1(b[3] >> 24, 0u);                    // (a group's lane 0 never looks at it: position 0 has no byte in front)
         const uint32_t mG = jr_g_bits(in, b), mN = jr_n_bits(in, b), mT = jr_trans_bits(b, prev);
-        const uint32_t m20 = jr_ge_bits(q, 20u), m30 = jr_ge_bits(q, 30u), mLow = in.qual_q ? ~jr_ge_bits(q, kq) & 0xFFFFu : 0u;
-        const uint32_t s16 = jr_sum16(q), inc = grp_incl_sum<LPR>(s16);
-        jr_put(E, x0, inc - s16, q);
-        if (gl == 0u) E[0] = 0u;
+        const uint32_t m20 = rows_ge_bits(q, 20u), m30 = rows_ge_bits(q, 30u), mLow = in.qual_q ? ~rows_ge_bits(q, kq) & 0xFFFFu : 0u;
+        const uint32_t s16 = rows_sum16(q), inc = grp_incl_sum<LPR>(s16);
+        jr_put(E, ug.x0, inc - s16, q);
+        if (ug.gl == 0u) E[0] = 0u;
         wave_lds_sync();
         uint32_t a = in.trim_front < l ? in.trim_front : l, e = l - (in.trim_tail < l ? in.trim_tail : l);
         if (e < a) e = a;
         if (in.poly_g) {
-            const uint32_t last1 = grp_max<LPR>(jr_last1(~mG & jr_span(x0, a, e), x0));      // behind the last base of [a, e) that is no G
+            const uint32_t last1 = grp_max<LPR>(jr_last1(~mG & rows_span(ug.x0, a, e), ug.x0));      // behind the last base of [a, e) that is no G
             const uint32_t r = e - (last1 > a ? last1 : a);
             if (r >= in.poly_g) e -= r;
         }
         if (in.cut_flags & JR_CUT_FRONT) {
             const uint32_t w = cw < e - a ? cw : e - a; const unsigned long long thr = (unsigned long long)in.cut_mean_q * w;
-            const uint32_t valid = e > a ? jr_span(x0, a, e - w + 1u) : 0u;
-            const uint32_t p = grp_min<LPR>(jr_first(jr_good(E, x0, w, thr, valid), x0));
+            const uint32_t valid = e > a ? rows_span(ug.x0, a, e - w + 1u) : 0u;
+            const uint32_t p = grp_min<LPR>(jr_first(jr_good(E, ug.x0, w, thr, valid), ug.x0));
             if (e > a) { if (p == 0xFFFFFFFFu) e = a; else a = p; }
         }
         if (in.cut_flags & JR_CUT_RIGHT) {
             const uint32_t w = cw < e - a ? cw : e - a; const unsigned long long thr = (unsigned long long)in.cut_mean_q * w;
-            const uint32_t valid = e > a ? jr_span(x0, a, e - w + 1u) : 0u;
-            const uint32_t p = grp_min<LPR>(jr_first(valid & ~jr_good(E, x0, w, thr, valid), x0));
+            const uint32_t valid = e > a ? rows_span(ug.x0, a, e - w + 1u) : 0u;
+            const uint32_t p = grp_min<LPR>(jr_first(valid & ~jr_good(E, ug.x0, w, thr, valid), ug.x0));
             if (e > a && p != 0xFFFFFFFFu) e = p;
         }
         if (in.cut_flags & JR_CUT_TAIL) {
             const uint32_t w = cw < e - a ? cw : e - a; const unsigned long long thr = (unsigned long long)in.cut_mean_q * w;
-            const uint32_t valid = e > a ? jr_span(x0, a, e - w + 1u) : 0u;
-            const uint32_t p1 = grp_max<LPR>(jr_last1(jr_good(E, x0, w, thr, valid), x0));
+            const uint32_t valid = e > a ? rows_span(ug.x0, a, e - w + 1u) : 0u;
+            const uint32_t p1 = grp_max<LPR>(jr_last1(jr_good(E, ug.x0, w, thr, valid), ug.x0));
             if (e > a) { if (p1 == 0u) e = a; else e = p1 - 1u + w; }
         }
         if (in.max_len && e - a > in.max_len) e = a + in.max_len;
-        const uint32_t win = jr_span(x0, a, e), all = jr_span(x0, 0u, l);
+        const uint32_t win = rows_span(ug.x0, a, e), all = rows_span(ug.x0, 0u, l);
         const unsigned long long c0 = (unsigned long long)__popc(mN & win) | ((unsigned long long)__popc(mLow & win) << 16) |
-                                      ((unsigned long long)__popc(mT & jr_span(x0, a + 1u, e)) << 32) | ((unsigned long long)__popc(m20 & win) << 48);
+                                      ((unsigned long long)__popc(mT & rows_span(ug.x0, a + 1u, e)) << 32) | ((unsigned long long)__popc(m20 & win) << 48);
         const unsigned long long c1 = (unsigned long long)__popc(m30 & win) | ((unsigned long long)__popc(m20 & all) << 16) | ((unsigned long long)__popc(m30 & all) << 32);
         const unsigned long long t0 = grp_sum<LPR>(c0), t1 = grp_sum<LPR>(c1);
-        if (gl == 0u && live) {
+        if (ug.gl == 0u && live) {
             JrRow r; r.a = a; r.e = e; r.l = l; r.qsum = E[jr_ix(e)] - E[jr_ix(a)]; r.qsum_in = E[jr_ix(l)];
             r.n_cnt = (uint32_t)t0 & 0xFFFFu; r.lowq = (uint32_t)(t0 >> 16) & 0xFFFFu; r.trans = (uint32_t)(t0 >> 32) & 0xFFFFu; r.q20o = (uint32_t)(t0 >> 48);
             r.q30o = (uint32_t)t1 & 0xFFFFu; r.q20i = (uint32_t)(t1 >> 16) & 0xFFFFu; r.q30i = (uint32_t)(t1 >> 32) & 0xFFFFu;
@@ -249,7 +150,7 @@ template <int LPR> __global__ void __launch_bounds__(256) k_judge_rows(JudgeIn i
         }
         wave_lds_sync();                                                     // (the next row's sums go where these were read)
     }
-    jr_sums_out<4>(acc, st);
+    rows_sums_out<4>(acc, st->c);
 }
 
 // ---- any row length
@@ -257,9 +158,9 @@ template <int LPR> __global__ void __launch_bounds__(256) k_judge_rows(JudgeIn i
 // t0 + 1024 + x0 where they lie in front of t0 + ext (ext: what the tile's windows reach, <= 2047).  Called by the whole wave.
 __device__ __forceinline__ void jr_tile_sums(const JudgeIn& in, uint64_t rowbase, uint32_t t0, uint32_t ext, uint32_t hi, uint32_t x0, uint32_t* E) {
     uint32_t q0[4] = { 0u, 0u, 0u, 0u }, q1[4] = { 0u, 0u, 0u, 0u };
-    if (x0 < ext && t0 + x0 < hi) jr_ld(in, in.q, rowbase, t0 + x0, hi, q0);
-    if (1024u + x0 < ext && t0 + 1024u + x0 < hi) jr_ld(in, in.q, rowbase, t0 + 1024u + x0, hi, q1);
-    const uint32_t s0 = jr_sum16(q0), s1 = jr_sum16(q1), i0 = wave_incl_sum(s0), i1 = wave_incl_sum(s1), tot0 = wave_last(i0);
+    if (x0 < ext && t0 + x0 < hi) rows_ld16(in.q, in.vec_in, in.total, rowbase, t0 + x0, hi, q0);
+    if (1024u + x0 < ext && t0 + 1024u + x0 < hi) rows_ld16(in.q, in.vec_in, in.total, rowbase, t0 + 1024u + x0, hi, q1);
+    const uint32_t s0 = rows_sum16(q0), s1 = rows_sum16(q1), i0 = wave_incl_sum(s0), i1 = wave_incl_sum(s1), tot0 = wave_last(i0);
     jr_put(E, x0, i0 - s0, q0); jr_put(E, 1024u + x0, tot0 + i1 - s1, q1);
     if (x0 == 0u) E[0] = 0u;
     wave_lds_sync();
@@ -271,18 +172,17 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
     __shared__ uint32_t s_E[2048u + 128u + 1u];
     uint32_t* const E = s_E;
     const uint64_t g = blockIdx.x; const uint32_t x0 = 16u * threadIdx.x, T = in.tile, cw = in.cut_window, kq = in.qual_q < 256u ? in.qual_q : 256u;
-    const uint32_t l = jr_len(in, g, st, threadIdx.x == 0u);
+    const uint32_t l = rows_len_checked(in, g, st, threadIdx.x == 0u);
     const uint64_t rowbase = g * in.row_len;
     const bool mine = x0 < T;                                                // (this lane holds window starts of a tile)
-    unsigned long long acc[JR_NSUM];
-#pragma unroll
-    for (int k = 0; k < JR_NSUM; k++) acc[k] = 0ull;
+    unsigned long long acc[JR_NSUM] = {};
     JrRow r; r.l = l; r.qsum = r.qsum_in = 0ull; r.n_cnt = r.lowq = r.trans = r.q20o = r.q30o = r.q20i = r.q30i = 0u;
     if (in.q) for (uint32_t t0 = 0; t0 < l; t0 += T) {
         uint32_t q[4] = { 0u, 0u, 0u, 0u };
-        if (mine && t0 + x0 < l) jr_ld(in, in.q, rowbase, t0 + x0, l, q);
-        const uint32_t all = mine ? jr_span(t0 + x0, 0u, l) : 0u;
-        const unsigned long long c = (unsigned long long)jr_sum16(q) | ((unsigned long long)__popc(jr_ge_bits(q, 20u) & all) << 32) | ((unsigned long long)__popc(jr_ge_bits(q, 30u) & all) << 48);
+        if (mine && t0 + x0 < l) rows_ld16(in.q, in.vec_in, in.total, rowbase, t0 + x0, l, q);
+        const uint32_t all = mine ? rows_span(t0 + x0, 0u, l) : 0u;
+        const unsigned long long c = (unsigned long long)rows_sum16(q) | ((unsigned long long)__popc(rows_ge_bits(q, 20u) & all) << 32) |
+                                     ((unsigned long long)__popc(rows_ge_bits(q, 30u) & all) << 48);
         const unsigned long long t = wave_sum<unsigned long long>(c);
         r.qsum_in += (uint32_t)t; r.q20i += (uint32_t)(t >> 32) & 0xFFFFu; r.q30i += (uint32_t)(t >> 48);
     }
@@ -292,8 +192,8 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
         uint32_t last1 = 0u;
         for (uint32_t t0 = (e - 1u) / T * T, lo_t = a / T * T; ; t0 -= T) {
             uint32_t b[4] = { 0u, 0u, 0u, 0u };
-            if (mine && t0 + x0 < e) jr_ld(in, in.b, rowbase, t0 + x0, e, b);
-            last1 = wave_max(mine ? jr_last1(~jr_g_bits(in, b) & jr_span(t0 + x0, a, e), t0 + x0) : 0u);
+            if (mine && t0 + x0 < e) rows_ld16(in.b, in.vec_in, in.total, rowbase, t0 + x0, e, b);
+            last1 = wave_max(mine ? jr_last1(~jr_g_bits(in, b) & rows_span(t0 + x0, a, e), t0 + x0) : 0u);
             if (last1 || t0 == lo_t) break;
         }
         const uint32_t run = e - (last1 > a ? last1 : a);
@@ -304,7 +204,7 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
         uint32_t p = 0xFFFFFFFFu;
         for (uint32_t t0 = a / T * T; t0 <= last && p == 0xFFFFFFFFu; t0 += T) {
             jr_tile_sums(in, rowbase, t0, T + w - 1u, e, x0, E);
-            const uint32_t valid = mine ? jr_span(t0 + x0, a, last + 1u) : 0u;
+            const uint32_t valid = mine ? rows_span(t0 + x0, a, last + 1u) : 0u;
             p = wave_min(jr_first(jr_good(E, x0, w, thr, valid), t0 + x0));
             wave_lds_sync();
         }
@@ -315,7 +215,7 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
         uint32_t p = 0xFFFFFFFFu;
         for (uint32_t t0 = a / T * T; t0 <= last && p == 0xFFFFFFFFu; t0 += T) {
             jr_tile_sums(in, rowbase, t0, T + w - 1u, e, x0, E);
-            const uint32_t valid = mine ? jr_span(t0 + x0, a, last + 1u) : 0u;
+            const uint32_t valid = mine ? rows_span(t0 + x0, a, last + 1u) : 0u;
             p = wave_min(jr_first(valid & ~jr_good(E, x0, w, thr, valid), t0 + x0));
             wave_lds_sync();
         }
@@ -326,7 +226,7 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
         uint32_t p1 = 0u;
         for (uint32_t t0 = last / T * T, lo_t = a / T * T; ; t0 -= T) {
             jr_tile_sums(in, rowbase, t0, T + w - 1u, e, x0, E);
-            const uint32_t valid = mine ? jr_span(t0 + x0, a, last + 1u) : 0u;
+            const uint32_t valid = mine ? rows_span(t0 + x0, a, last + 1u) : 0u;
             p1 = wave_max(jr_last1(jr_good(E, x0, w, thr, valid), t0 + x0));
             wave_lds_sync();
             if (p1 || t0 == lo_t) break;
@@ -337,7 +237,7 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
     if (e > a) for (uint32_t t0 = a / T * T; t0 < e; t0 += T) {
         uint32_t b[4] = { 0u, 0u, 0u, 0u }, q[4] = { 0u, 0u, 0u, 0u };
         const uint32_t p0 = t0 + x0; const bool on = mine && p0 < e;
-        if (on) { if (in.b) jr_ld(in, in.b, rowbase, p0, e, b); if (in.q) jr_ld(in, in.q, rowbase, p0, e, q); }
+        if (on) { if (in.b) rows_ld16(in.b, in.vec_in, in.total, rowbase, p0, e, b); if (in.q) rows_ld16(in.q, in.vec_in, in.total, rowbase, p0, e, q); }
         if (on && a > p0) {                                                  // (the qualities in front of the window do not count)
             const uint32_t f = a - p0 < 16u ? a - p0 : 16u;
 #pragma unroll
@@ -345,15 +245,16 @@ __global__ void __launch_bounds__(64) k_judge_rows_long(JudgeIn in, JudgeStat* _
         }
         uint32_t prev = wave_shr1(b[3] >> 24, 0u);
         if (threadIdx.x == 0u && in.b && p0 > a) prev = in.b[rowbase + p0 - 1u];      // (the tile in front holds it: a byte of the row, inside the window)
-        const uint32_t win = on ? jr_span(p0, a, e) : 0u, mLow = in.qual_q ? ~jr_ge_bits(q, kq) & 0xFFFFu : 0u;
+        const uint32_t win = on ? rows_span(p0, a, e) : 0u, mLow = in.qual_q ? ~rows_ge_bits(q, kq) & 0xFFFFu : 0u;
         const unsigned long long c0 = (unsigned long long)__popc(jr_n_bits(in, b) & win) | ((unsigned long long)__popc(mLow & win) << 16) |
-                                      ((unsigned long long)__popc(on ? jr_trans_bits(b, prev) & jr_span(p0, a + 1u, e) : 0u) << 32) | ((unsigned long long)__popc(jr_ge_bits(q, 20u) & win) << 48);
-        const unsigned long long c1 = (unsigned long long)__popc(jr_ge_bits(q, 30u) & win) | ((unsigned long long)jr_sum16(q) << 16);
+                                      ((unsigned long long)__popc(on ? jr_trans_bits(b, prev) & rows_span(p0, a + 1u, e) : 0u) << 32) |
+                                      ((unsigned long long)__popc(rows_ge_bits(q, 20u) & win) << 48);
+        const unsigned long long c1 = (unsigned long long)__popc(rows_ge_bits(q, 30u) & win) | ((unsigned long long)rows_sum16(q) << 16);
         const unsigned long long u0 = wave_sum<unsigned long long>(c0), u1 = wave_sum<unsigned long long>(c1);
         r.n_cnt += (uint32_t)u0 & 0xFFFFu; r.lowq += (uint32_t)(u0 >> 16) & 0xFFFFu; r.trans += (uint32_t)(u0 >> 32) & 0xFFFFu; r.q20o += (uint32_t)(u0 >> 48);
         r.q30o += (uint32_t)u1 & 0xFFFFu; r.qsum += u1 >> 16;
     }
     r.a = a; r.e = e;
     if (threadIdx.x == 0u) jr_verdict(in, g, r, acc);
-    jr_sums_out<1>(acc, st);
+    rows_sums_out<1>(acc, st->c);
 }

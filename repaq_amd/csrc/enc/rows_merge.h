@@ -1,7 +1,7 @@
 // enc/rows_merge.h - pairs of rows -> one row per overlapping pair: the fragment both mates were read from, `insert` bases long, the consensus of the two where they
 // overlap, under R1's name (rfq_merge_rows): what consumes the insert sizes rfq_adapter_rows leaves.  It moves bytes and decides nothing about the alignment.
 // Part of rfq_encode_kernels.h (included from there, last: it uses rows_select.h's table entry, tables body (rows_tables), writers' arguments (RowsOut) and names
-// kernel, rows_judge.h's 16-byte pieces and rows_adapter.h's base classes; not a stand-alone header).
+// kernel, rows_lanes.h's 16-byte pieces and rows_adapter.h's base classes; not a stand-alone header).
 #pragma once
 // The shape is rfq_select_rows': k_merge_judge validates EVERY pair and leaves a merged flag and the merged name size per pair (scanned by the host's scan_exclusive
 // to the output row index and the output name offset) with the maxima and sums; after ONE read-back the host decides; k_merge_tables turns the two scans into a table
@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(256) k_merge_tables(MergeIn in, const uint32_t
 // ---- four bytes at a time
 // 0xFF in every byte of w that is one of A C G T (code mode: below 4; ASCII mode: the letter in either case)
 __device__ __forceinline__ uint32_t mg_acgt(uint32_t ascii, uint32_t w) {
-    if (!ascii) return ((~jr_ge(w, 4u) & 0x80808080u) >> 7) * 0xFFu;
+    if (!ascii) return ((~rows_ge(w, 4u) & 0x80808080u) >> 7) * 0xFFu;
     const uint32_t f = w & 0xDFDFDFDFu;
     return eq_bytes_full(f, 0x41414141u) | eq_bytes_full(f, 0x43434343u) | eq_bytes_full(f, 0x47474747u) | eq_bytes_full(f, 0x54545454u);
 }

@@ -1105,6 +1105,50 @@ template <class A, class Tables, class Rows> static int rows_write(rfq_ctx* ctx,
     ctx->timer.collect();
     return RFQ_OK;
 }
+// ---- the argument rules the rows calls word alike.  Each is called where its call tests it: the first refusal met is the one reported.
+static int rows_pairs_arg(rfq_ctx* ctx, int32_t pairs, uint64_t n) {
+    if (pairs != 0 && pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
+    if (pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    return RFQ_OK;
+}
+static int rows_base_mode_arg(rfq_ctx* ctx, const rfq_rows_in* in) {
+    return in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE ? rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode) : (int)RFQ_OK;
+}
+// (asked: rfq_select_rows asks of no rows too, the others of n_rows != 0)
+static int rows_src_len_arg(rfq_ctx* ctx, const rfq_rows_in* in, bool asked) { return asked && in->row_len == 0 ? rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1") : (int)RFQ_OK; }
+static int rows_len_refusal(rfq_ctx* ctx, uint32_t row_len, unsigned long long row) {
+    return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", row_len, row);
+}
+// the bytes a call reads of its rows, in ins[0 .. 5) (rows_dst_spans' mirror); a call appends its own inputs and takes out (p = null) an array it does not read
+template <size_t N> static void rows_src_spans(const rfq_rows_in* in, bool named, Span (&ins)[N]) {
+    static_assert(N >= 5, "five spans of the rows, then the call's own");
+    const unsigned long long n = in->n_rows, rows_in = n * in->row_len;
+    ins[0] = { in->d_bases, rows_in, "rows->d_bases" }; ins[1] = { in->d_quals, rows_in, "rows->d_quals" }; ins[2] = { in->d_lens, n * 4ull, "rows->d_lens" };
+    ins[3] = { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }; ins[4] = { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" };
+}
+// ---- the path of a deciding call (rfq_judge_rows, rfq_adapter_rows, rfq_dedup_rows: a verdict per unit, no row moved - enc/rows_lanes.h).  A call keeps its own
+// argument rules, its *In block and its result fields.  Its histogram starts at zero, rows or not; with no rows that is all the call does (the caller returns)
+static int rows_hist_fresh(rfq_ctx* ctx, hipStream_t S, uint64_t* d_hist, uint32_t hist_len, uint64_t n) {
+    if (d_hist) HIPCHK(ctx, hipMemsetAsync(d_hist, 0, (size_t)hist_len * 8, S));
+    if (!n) HIPCHK(ctx, hipStreamSynchronize(S));
+    return RFQ_OK;
+}
+// Which kernel is the row length's to say: up to 256 bytes a DPP row of 16 lanes holds a unit's row (k16), up to 1024 a wave (k64) - 256 threads, 16 / 4 units at
+// a time, `iter` times -, beyond that (or where the call's `general` option is set) a wave per unit walks it (k_long).  The caller's KCHK names the kernel.
+template <class In, class Stat> static void rows_launch_by_len(hipStream_t S, bool general, uint32_t row_len, uint64_t units, uint32_t iter,
+        void (*k16)(In, Stat*), void (*k64)(In, Stat*), void (*k_long)(In, Stat*), const In& in, Stat* dst) {
+    if (general || row_len > 1024u) { hipLaunchKernelGGL(k_long, dim3((uint32_t)units), dim3(64), 0, S, in, dst); return; }
+    const auto k = row_len <= 256u ? k16 : k64; const uint32_t per = (row_len <= 256u ? 16u : 4u) * iter;
+    hipLaunchKernelGGL(k, dim3((uint32_t)((units + per - 1u) / per)), dim3(256), 0, S, in, dst);
+}
+// the verdict block back on the host, the stage times collected; a bad length refuses the call
+template <class Stat> static int rows_sums_back(rfq_ctx* ctx, hipStream_t S, const Stat* dst, Stat* hs, uint32_t row_len) {
+    memset(hs, 0, sizeof *hs);
+    HIPCHK(ctx, ctx->fetch(hs, dst, sizeof *hs, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    ctx->timer.collect();
+    return hs->err & ROWS_ERR_LEN ? rows_len_refusal(ctx, row_len, hs->bad_row) : (int)RFQ_OK;
+}
 // ---------------------------------------------------------------- rows -> FASTQ text (-> image): rfq_rows_to_text, rfq_encode_rows of include/rfq_hip.h
 // The judged part (k_rows_sizes + one scan per text) ends in ONE read-back - the texts' sizes, the bases, the error bits - and the writer (k_rows_text)
 // runs only on rows that passed; what the writer itself finds in the bytes comes back with a second look at the same block.
@@ -1148,7 +1192,7 @@ static int rows_text_impl(rfq_ctx* ctx, const rfq_rows_in* in, int32_t paired, u
     for (int t = 0; t < nt; t++) HIPCHK(ctx, ctx->fetch(&total[t], off[t] + nrec[t], 8, S));
     HIPCHK(ctx, ctx->fetch_sync(S));
     const unsigned long long br = hs.bad_row;
-    if (hs.err & RT_ERR_LEN) return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, br);
+    if (hs.err & RT_ERR_LEN) return rows_len_refusal(ctx, in->row_len, br);
     if (hs.err & RT_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
     if (hs.err & RT_ERR_LEN0) return rfq_fail(ctx, RFQ_E_DATA, "a read of no bases (first such row: %llu): an empty sequence line ends the reference's reader", br);
     if (hs.err & RT_ERR_NAME0) return rfq_fail(ctx, RFQ_E_DATA, "a name of no bytes (first such row: %llu)", br);
@@ -1347,21 +1391,17 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     ctx->err.clear();
     const uint64_t n = in->n_rows; const bool named = in->d_name_off != nullptr;
     int rc;
-    if (a->pairs != 0 && a->pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
-    if (a->pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    if ((rc = rows_pairs_arg(ctx, a->pairs, n)) != RFQ_OK) return rc;
     if ((rc = rows_dst_len(ctx, a)) != RFQ_OK) return rc;
-    if (in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if ((rc = rows_src_len_arg(ctx, in, true)) != RFQ_OK) return rc;
     if (n >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
     if ((rc = rows_dst_named(ctx, a, named)) != RFQ_OK) return rc;
     if (n && (!in->d_lens || (a->d_bases && !in->d_bases) || (a->d_quals && !in->d_quals) || (a->d_names && in->names_len && !in->d_names)))
         return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
     if ((rc = rows_dst_aligned(ctx, in, a, (uintptr_t)a->d_start | (uintptr_t)a->d_len, "d_lens, d_start and d_len")) != RFQ_OK) return rc;
     {   // the bytes a call can write (its cap, and never more than n_rows rows of row_len) against the bytes it reads
-        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
-        const Span ins[] = {
-            { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" },
-            { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }, { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" },
-            { a->d_keep, n, "d_keep" }, { a->d_start, n * 4ull, "d_start" }, { a->d_len, n * 4ull, "d_len" } };
+        Span ins[8]; rows_src_spans(in, named, ins);
+        ins[5] = { a->d_keep, n, "d_keep" }; ins[6] = { a->d_start, n * 4ull, "d_start" }; ins[7] = { a->d_len, n * 4ull, "d_len" };
         Span outs[5]; rows_dst_spans(a, n, in->names_len, outs);
         if ((rc = rows_apart(ctx, outs, ins, ": selection in place is not offered")) != RFQ_OK) return rc;
     }
@@ -1377,7 +1417,7 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     }, &hs, &j);
     if (rc != RFQ_OK) return rc;
     const unsigned long long br = hs.bad_row;
-    if (hs.err & SL_ERR_LEN) return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, br);
+    if (hs.err & SL_ERR_LEN) return rows_len_refusal(ctx, in->row_len, br);
     if (hs.err & SL_ERR_WIN) return rfq_fail(ctx, RFQ_E_ARG, "a window starts below 0, has a negative length or ends behind its read (first such row: %llu)", br);
     if (hs.err & SL_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
     res->n_rows = j.n_out; res->n_bases = hs.n_bases; res->names_len = j.names_len; res->max_len = hs.max_len; res->max_name = hs.max_name;
@@ -1408,8 +1448,8 @@ extern "C" int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_mer
     int rc;
     if (n & 1u) return rfq_fail(ctx, RFQ_E_ARG, "merging takes rows in pairs (got %llu rows)", (unsigned long long)n);
     if ((rc = rows_dst_len(ctx, a)) != RFQ_OK) return rc;
-    if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode);
-    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
     if (n >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
     if ((rc = rows_dst_named(ctx, a, named)) != RFQ_OK) return rc;
     if (n && !a->d_insert) return rfq_fail(ctx, RFQ_E_ARG, "null d_insert");
@@ -1418,11 +1458,8 @@ extern "C" int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_mer
         return rfq_fail(ctx, RFQ_E_ARG, "a row output needs rows->d_bases and rows->d_quals, both: the rule looks at the bases and the scores");
     if ((rc = rows_dst_aligned(ctx, in, a, (uintptr_t)a->d_insert, "d_lens and d_insert")) != RFQ_OK) return rc;
     {   // the bytes a call can write (its cap, and never more than n_rows / 2 rows of row_len) against the bytes it reads
-        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
-        const Span ins[] = {
-            { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" },
-            { in->d_names, named ? (unsigned long long)in->names_len : 0ull, "rows->d_names" }, { in->d_name_off, named ? (n + 1) * 8ull : 0ull, "rows->d_name_off" },
-            { a->d_insert, np * 4ull, "d_insert" } };
+        Span ins[6]; rows_src_spans(in, named, ins);
+        ins[5] = { a->d_insert, np * 4ull, "d_insert" };
         Span outs[5]; rows_dst_spans(a, np, in->names_len, outs);
         if ((rc = rows_apart(ctx, outs, ins, ": merging in place is not offered")) != RFQ_OK) return rc;
     }
@@ -1440,7 +1477,7 @@ extern "C" int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_mer
     if (hs.err) {                                                            // the first offender's key says which rule it broke (enc/rows_merge.h)
         const unsigned long long row = hs.bad_row >> 2;
         switch ((uint32_t)(hs.bad_row & 3u)) {
-        case MG_ERR_LEN: return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, row);
+        case MG_ERR_LEN: return rows_len_refusal(ctx, in->row_len, row);
         case MG_ERR_INS: return rfq_fail(ctx, RFQ_E_ARG, "a pair with insert >= 0 has no position that both mates cover: an empty mate, insert == 0 or insert > l1 + l2 - 1 (first such pair: %llu)", row / 2);
         default: return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, row);
         }
@@ -1466,18 +1503,18 @@ extern "C" int rfq_merge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_mer
         });
 }
 // ---------------------------------------------------------------- rows -> keep, window, reason and metrics per row, one QC summary: rfq_judge_rows of include/rfq_hip.h
-// One kernel and one read-back (the verdict block with the sums).  Which kernel is the row length's to say: up to 256 bytes a DPP row of 16 lanes holds a row,
-// up to 1024 a wave, beyond that (or with RFQ_JUDGE=general, in tiles of 64) a wave walks it in tiles (enc/rows_judge.h).
+// One kernel (rows_launch_by_len; with RFQ_JUDGE=general the wave-per-row kernel in tiles of 64, enc/rows_judge.h) and one read-back (the verdict block with the sums).
 extern "C" int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_judge_rows_args* a, rfq_judge_rows_result* res) {
     if (!ctx || !in || !a || !res) return RFQ_E_ARG;
     memset(res, 0, sizeof *res);
     ctx->err.clear();
     const uint64_t n = in->n_rows;
+    int rc;
     if (a->cut_flags & ~(RFQ_CUT_FRONT | RFQ_CUT_RIGHT | RFQ_CUT_TAIL)) return rfq_fail(ctx, RFQ_E_ARG, "unknown cut_flags bits (0x%x)", a->cut_flags);
     if (a->cut_flags && (a->cut_window < 1u || a->cut_window > 1000u)) return rfq_fail(ctx, RFQ_E_ARG, "cut_window must be 1 .. 1000 with a cut flag (got %u)", a->cut_window);
     if (a->max_lowq_pct > 100u || a->min_complexity_pct > 100u) return rfq_fail(ctx, RFQ_E_ARG, "a percentage is 0 .. 100 (max_lowq_pct %u, min_complexity_pct %u)", a->max_lowq_pct, a->min_complexity_pct);
-    if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode);
-    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
     if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
     if (n && !in->d_lens) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens");
     const bool need_q = a->cut_flags || a->min_mean_q || a->qual_q, need_b = a->poly_g || a->max_n >= 0 || a->min_complexity_pct;
@@ -1485,10 +1522,8 @@ extern "C" int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_jud
     if (n && need_b && !in->d_bases) return rfq_fail(ctx, RFQ_E_ARG, "a base criterion (poly_g, max_n, min_complexity_pct) needs rows->d_bases");
     if (((uintptr_t)in->d_lens | (uintptr_t)a->d_start | (uintptr_t)a->d_len | (uintptr_t)a->d_metrics) & 3u)
         return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_start, d_len and d_metrics must be 4-byte aligned");
-    int rc;
     {
-        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
-        const Span ins[] = { { in->d_bases, rows_in, "rows->d_bases" }, { in->d_quals, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" } };
+        Span ins[5]; rows_src_spans(in, false, ins);
         const Span outs[] = {
             { a->d_keep, n, "d_keep" }, { a->d_start, n * 4ull, "d_start" }, { a->d_len, n * 4ull, "d_len" }, { a->d_why, n, "d_why" }, { a->d_metrics, n * 16ull, "d_metrics" } };
         if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
@@ -1505,31 +1540,22 @@ extern "C" int rfq_judge_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_jud
     ji.max_len = a->max_len; ji.min_len = a->min_len; ji.max_n = a->max_n; ji.min_mean_q = a->min_mean_q; ji.qual_q = a->qual_q; ji.max_lowq_pct = a->max_lowq_pct;
     ji.min_complexity_pct = a->min_complexity_pct;
     ji.keep = a->d_keep; ji.start = a->d_start; ji.len = a->d_len; ji.why = a->d_why; ji.metrics = a->d_metrics;
-    const bool general = ctx->opt.judge_general || in->row_len > 1024u;
     ji.tile = ctx->opt.judge_general ? 64u : 1024u;
     ctx->timer.begin("judge:rows", S);
-    JudgeStat* dst = nullptr;
+    JudgeStat* dst = nullptr; JudgeStat hs;
     if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
-    if (general) hipLaunchKernelGGL(k_judge_rows_long, dim3((uint32_t)n), dim3(64), 0, S, ji, dst);
-    else if (in->row_len <= 256u) hipLaunchKernelGGL(k_judge_rows<16>, dim3((uint32_t)((n + 16u * JR_ITER - 1u) / (16u * JR_ITER))), dim3(256), 0, S, ji, dst);
-    else hipLaunchKernelGGL(k_judge_rows<64>, dim3((uint32_t)((n + 4u * JR_ITER - 1u) / (4u * JR_ITER))), dim3(256), 0, S, ji, dst);
+    rows_launch_by_len(S, ctx->opt.judge_general, in->row_len, n, JR_ITER, k_judge_rows<16>, k_judge_rows<64>, k_judge_rows_long, ji, dst);
     KCHK(ctx, "k_judge_rows");
     ctx->timer.end(S);
-    JudgeStat hs; memset(&hs, 0, sizeof hs);
-    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
-    HIPCHK(ctx, ctx->fetch_sync(S));
-    ctx->timer.collect();
-    if (hs.err & JR_ERR_LEN)
-        return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, (unsigned long long)hs.bad_row);
+    if ((rc = rows_sums_back(ctx, S, dst, &hs, in->row_len)) != RFQ_OK) return rc;
     res->n_kept = hs.c[0]; res->why_short = hs.c[1]; res->why_n = hs.c[2]; res->why_meanq = hs.c[3]; res->why_lowq = hs.c[4]; res->why_complex = hs.c[5];
     res->bases_in = hs.c[6]; res->qsum_in = hs.c[7]; res->q20_in = hs.c[8]; res->q30_in = hs.c[9];
     res->bases_out = hs.c[10]; res->qsum_out = hs.c[11]; res->q20_out = hs.c[12]; res->q30_out = hs.c[13];
     return RFQ_OK;
 }
 // ---------------------------------------------------------------- rows -> the length adapter removal leaves, insert sizes, a summary: rfq_adapter_rows of include/rfq_hip.h
-// One kernel and one read-back, like rfq_judge_rows.  The adapters come as host bytes and travel as two class planes of 64 bits in the kernel arguments.  Which
-// kernel is the row length's to say: up to 256 bytes a DPP row of 16 lanes holds a pair, up to 1024 a wave, beyond that (or with RFQ_ADAPTER=general) a wave
-// compares a pair byte by byte (enc/rows_adapter.h).
+// One kernel (rows_launch_by_len; RFQ_ADAPTER=general: the wave-per-pair kernel that compares byte by byte, enc/rows_adapter.h) and one read-back, like rfq_judge_rows.
+// The adapters come as host bytes and travel as two class planes of 64 bits in the kernel arguments.
 static int adapter_planes(rfq_ctx* ctx, const uint8_t* h, uint32_t m, const char* what, unsigned long long* H, unsigned long long* L, uint32_t* len) {
     *H = *L = 0ull; *len = 0u;
     if (!h || !m) return RFQ_OK;
@@ -1548,19 +1574,18 @@ extern "C" int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_a
     memset(res, 0, sizeof *res);
     ctx->err.clear();
     const uint64_t n = in->n_rows;
-    if (a->pairs != 0 && a->pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
-    if (a->pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    int rc;
+    if ((rc = rows_pairs_arg(ctx, a->pairs, n)) != RFQ_OK) return rc;
     if (a->pairs && (a->min_overlap == 0u || a->max_diff_pct > 100u)) return rfq_fail(ctx, RFQ_E_ARG, "with pairs min_overlap is >= 1 and max_diff_pct 0 .. 100 (got %u, %u)", a->min_overlap, a->max_diff_pct);
     if (!a->pairs && ((a->h_adapter2 && a->adapter2_len) || a->d_insert || a->d_diff || a->d_insert_hist))
         return rfq_fail(ctx, RFQ_E_ARG, "h_adapter2, d_insert, d_diff and d_insert_hist are for pairs");
     AdapterIn ai; memset(&ai, 0, sizeof ai);
-    int rc;
     if ((rc = adapter_planes(ctx, a->h_adapter1, a->adapter1_len, "adapter 1", &ai.a_h[0], &ai.a_l[0], &ai.a_m[0])) != RFQ_OK) return rc;
     if ((rc = adapter_planes(ctx, a->h_adapter2, a->adapter2_len, "adapter 2", &ai.a_h[1], &ai.a_l[1], &ai.a_m[1])) != RFQ_OK) return rc;
     if ((ai.a_m[0] || ai.a_m[1]) && (a->adapter_min < 1u || a->adapter_min > 64u)) return rfq_fail(ctx, RFQ_E_ARG, "adapter_min must be 1 .. 64 with an adapter (got %u)", a->adapter_min);
     if (a->hist_len > 65536u || (a->d_insert_hist && a->hist_len == 0u)) return rfq_fail(ctx, RFQ_E_ARG, "hist_len must be 1 .. 65536 with d_insert_hist, at most 65536 without (got %u)", a->hist_len);
-    if (in->base_mode != RFQ_ROWS_ASCII && in->base_mode != RFQ_ROWS_CODE) return rfq_fail(ctx, RFQ_E_ARG, "bad base_mode %d", in->base_mode);
-    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
     if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
     if (n && (!in->d_lens || !in->d_bases)) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens / d_bases");
     if (((uintptr_t)in->d_lens | (uintptr_t)a->d_len | (uintptr_t)a->d_insert | (uintptr_t)a->d_diff) & 3u)
@@ -1568,7 +1593,8 @@ extern "C" int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_a
     if ((uintptr_t)a->d_insert_hist & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_insert_hist must be 8-byte aligned");
     const uint64_t units = a->pairs ? n / 2 : n;
     {
-        const Span ins[] = { { in->d_bases, (unsigned long long)n * in->row_len, "rows->d_bases" }, { in->d_lens, n * 4ull, "rows->d_lens" } };
+        Span ins[5]; rows_src_spans(in, false, ins);
+        ins[1].p = nullptr;                                                  // (the scores are not read)
         const Span outs[] = { { a->d_len, n * 4ull, "d_len" }, { a->d_how, n, "d_how" }, { a->d_insert, units * 4ull, "d_insert" }, { a->d_diff, units * 4ull, "d_diff" },
                               { a->d_insert_hist, a->hist_len * 8ull, "d_insert_hist" } };
         if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
@@ -1576,8 +1602,7 @@ extern "C" int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_a
     res->n_rows = n; res->n_pairs = a->pairs ? units : 0;
     hipStream_t S = ctx->stream;
     if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
-    if (a->d_insert_hist) HIPCHK(ctx, hipMemsetAsync(a->d_insert_hist, 0, (size_t)a->hist_len * 8, S));
-    if (!n) { HIPCHK(ctx, hipStreamSynchronize(S)); return RFQ_OK; }
+    if ((rc = rows_hist_fresh(ctx, S, a->d_insert_hist, a->hist_len, n)) != RFQ_OK || !n) return rc;
     ai.b = in->d_bases; ai.lens = in->d_lens; ai.total = n * in->row_len; ai.n_rows = (uint32_t)n; ai.n_units = (uint32_t)units; ai.row_len = in->row_len;
     ai.vec_in = rows_vec(in->row_len, in->d_bases, nullptr);
     ai.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u; ai.pairs = a->pairs ? 1u : 0u;
@@ -1585,26 +1610,18 @@ extern "C" int rfq_adapter_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_a
     if (!a->pairs) { ai.a_h[1] = ai.a_l[1] = 0ull; ai.a_m[1] = 0u; }
     ai.adapter_min = a->adapter_min; ai.adapter_mm_per = a->adapter_mm_per; ai.hist_len = a->hist_len;
     ai.len = a->d_len; ai.how = a->d_how; ai.insert = a->d_insert; ai.diff = a->d_diff; ai.hist = (unsigned long long*)a->d_insert_hist;
-    const bool general = ctx->opt.adapter_general || in->row_len > 1024u;
     ctx->timer.begin("adapter:rows", S);
-    AdapterStat* dst = nullptr;
+    AdapterStat* dst = nullptr; AdapterStat hs;
     if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
-    if (general) hipLaunchKernelGGL(k_adapter_rows_any, dim3((uint32_t)units), dim3(64), 0, S, ai, dst);
-    else if (in->row_len <= 256u) hipLaunchKernelGGL(k_adapter_rows<16>, dim3((uint32_t)((units + 16u * AR_ITER - 1u) / (16u * AR_ITER))), dim3(256), 0, S, ai, dst);
-    else hipLaunchKernelGGL(k_adapter_rows<64>, dim3((uint32_t)((units + 4u * AR_ITER - 1u) / (4u * AR_ITER))), dim3(256), 0, S, ai, dst);
+    rows_launch_by_len(S, ctx->opt.adapter_general, in->row_len, units, AR_ITER, k_adapter_rows<16>, k_adapter_rows<64>, k_adapter_rows_any, ai, dst);
     KCHK(ctx, "k_adapter_rows");
     ctx->timer.end(S);
-    AdapterStat hs; memset(&hs, 0, sizeof hs);
-    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
-    HIPCHK(ctx, ctx->fetch_sync(S));
-    ctx->timer.collect();
-    if (hs.err & AR_ERR_LEN)
-        return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, (unsigned long long)hs.bad_row);
+    if ((rc = rows_sums_back(ctx, S, dst, &hs, in->row_len)) != RFQ_OK) return rc;
     res->pairs_found = hs.c[0]; res->rows_cut = hs.c[1]; res->rows_cut_overlap = hs.c[2]; res->rows_cut_adapter = hs.c[3]; res->bases_in = hs.c[4]; res->bases_out = hs.c[5];
     return RFQ_OK;
 }
 // ---------------------------------------------------------------- rows -> a keep byte that leaves one unit of every class of identical units: rfq_dedup_rows of include/rfq_hip.h
-// Three kernels and one read-back (enc/rows_dedup.h): the key kernel (which one is the row length's to say, as in rfq_judge_rows) leaves a fingerprint and a score per
+// Three kernels and one read-back (enc/rows_dedup.h): the key kernel (which one: rows_launch_by_len) leaves a fingerprint and a score per
 // unit, the claim kernel finds every candidate's class in a hash table of S slots, the resolve kernel writes the outputs.  The table lives in context-owned buffers
 // and is sized and zeroed PER CALL: a table carried across the batches of one file is not offered (include/rfq_hip.h).
 extern "C" int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_dedup_rows_args* a, rfq_dedup_rows_result* res) {
@@ -1612,12 +1629,12 @@ extern "C" int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_ded
     memset(res, 0, sizeof *res);
     ctx->err.clear();
     const uint64_t n = in->n_rows;
-    if (a->pairs != 0 && a->pairs != 1) return rfq_fail(ctx, RFQ_E_ARG, "pairs must be 0 or 1");
-    if (a->pairs && (n & 1u)) return rfq_fail(ctx, RFQ_E_ARG, "pairs takes rows in pairs (got %llu rows)", (unsigned long long)n);
+    int rc;
+    if ((rc = rows_pairs_arg(ctx, a->pairs, n)) != RFQ_OK) return rc;
     if (a->mode != RFQ_DEDUP_FIRST && a->mode != RFQ_DEDUP_BEST_QUAL) return rfq_fail(ctx, RFQ_E_ARG, "unknown mode %d", a->mode);
     const bool best = a->mode == RFQ_DEDUP_BEST_QUAL;
     if (n && best && !in->d_quals) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_DEDUP_BEST_QUAL needs rows->d_quals");
-    if (n && in->row_len == 0) return rfq_fail(ctx, RFQ_E_ARG, "the rows' row_len must be >= 1");
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
     if (in->row_len > (1u << 22)) return rfq_fail(ctx, RFQ_E_ARG, "row_len is at most 2^22 = %u: the score is a 32-bit sum (got %u)", 1u << 22, in->row_len);
     const uint64_t units = a->pairs ? n / 2 : n;
     if (units >= 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many units for one call (%llu)", (unsigned long long)units);
@@ -1625,18 +1642,17 @@ extern "C" int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_ded
     if (((uintptr_t)in->d_lens | (uintptr_t)a->d_dup_of | (uintptr_t)a->d_count) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_dup_of and d_count must be 4-byte aligned");
     if ((uintptr_t)a->d_hist & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_hist must be 8-byte aligned");
     if (a->hist_len > DD_HIST_MAX || (a->d_hist && a->hist_len == 0u)) return rfq_fail(ctx, RFQ_E_ARG, "hist_len must be 1 .. %u with d_hist, at most %u without (got %u)", DD_HIST_MAX, DD_HIST_MAX, a->hist_len);
-    int rc;
     {
-        const unsigned long long rows_in = (unsigned long long)n * in->row_len;
-        const Span ins[] = { { in->d_bases, rows_in, "rows->d_bases" }, { best ? in->d_quals : nullptr, rows_in, "rows->d_quals" }, { in->d_lens, n * 4ull, "rows->d_lens" }, { a->d_in, n, "d_in" } };
+        Span ins[6]; rows_src_spans(in, false, ins);
+        if (!best) ins[1].p = nullptr;                                       // (the scores are read in BEST_QUAL only)
+        ins[5] = { a->d_in, n, "d_in" };
         const Span outs[] = { { a->d_keep, n, "d_keep" }, { a->d_dup_of, units * 4ull, "d_dup_of" }, { a->d_count, units * 4ull, "d_count" }, { a->d_hist, a->hist_len * 8ull, "d_hist" } };
         if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
     }
     res->n_units = units;
     hipStream_t S = ctx->stream;
     if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
-    if (a->d_hist) HIPCHK(ctx, hipMemsetAsync(a->d_hist, 0, (size_t)a->hist_len * 8, S));
-    if (!n) { HIPCHK(ctx, hipStreamSynchronize(S)); return RFQ_OK; }
+    if ((rc = rows_hist_fresh(ctx, S, a->d_hist, a->hist_len, n)) != RFQ_OK || !n) return rc;
     uint64_t slots = 1024;
     while (slots < 2 * units) slots <<= 1;
     DedupIn di; memset(&di, 0, sizeof di);
@@ -1659,11 +1675,9 @@ extern "C" int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_ded
     const uint32_t ublocks = (uint32_t)((units + 255u) / 256u);
     ctx->timer.begin("dedup:key", S);
     { ClearList z; memset(&z, 0, sizeof z); z.add(di.tab, slots * 8, 0u); z.add(di.best, slots * 8, 0u); z.add(di.cnt, slots * 4, 0u); clear_list(S, z); KCHK(ctx, "k_clear_list"); }
-    DedupStat* dst = nullptr;
+    DedupStat* dst = nullptr; DedupStat hs;
     if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
-    if (in->row_len > 1024u) hipLaunchKernelGGL(k_dedup_key_long, dim3((uint32_t)units), dim3(64), 0, S, di, dst);
-    else if (in->row_len <= 256u) hipLaunchKernelGGL(k_dedup_key<16>, dim3((uint32_t)((units + 16u * DD_ITER - 1u) / (16u * DD_ITER))), dim3(256), 0, S, di, dst);
-    else hipLaunchKernelGGL(k_dedup_key<64>, dim3((uint32_t)((units + 4u * DD_ITER - 1u) / (4u * DD_ITER))), dim3(256), 0, S, di, dst);
+    rows_launch_by_len(S, false, in->row_len, units, DD_ITER, k_dedup_key<16>, k_dedup_key<64>, k_dedup_key_long, di, dst);
     KCHK(ctx, "k_dedup_key");
     ctx->timer.end(S);
     ctx->timer.begin("dedup:claim", S);
@@ -1674,12 +1688,7 @@ extern "C" int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_ded
     hipLaunchKernelGGL(k_dedup_resolve, dim3(ublocks), dim3(256), 0, S, di, dst);
     KCHK(ctx, "k_dedup_resolve");
     ctx->timer.end(S);
-    DedupStat hs; memset(&hs, 0, sizeof hs);
-    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
-    HIPCHK(ctx, ctx->fetch_sync(S));
-    ctx->timer.collect();
-    if (hs.err & DD_ERR_LEN)
-        return rfq_fail(ctx, RFQ_E_ARG, "a read length is negative or greater than row_len = %u (first such row: %llu)", in->row_len, (unsigned long long)hs.bad_row);
+    if ((rc = rows_sums_back(ctx, S, dst, &hs, in->row_len)) != RFQ_OK) return rc;
     res->n_candidates = hs.c[0]; res->bases_in = hs.c[1]; res->n_classes = hs.c[2]; res->bases_kept = hs.c[3]; res->max_class = hs.c[4]; res->n_dups = hs.c[0] - hs.c[2];
     return RFQ_OK;
 }

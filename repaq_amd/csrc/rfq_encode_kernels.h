@@ -23,6 +23,7 @@
 #include "enc/assemble.h"                     // chunk layout (incl. the mSize bug) and image assembly
 #include "enc/rows_text.h"                    // rows -> FASTQ text in front of the encoder (rfq_rows_to_text, rfq_encode_rows)
 #include "enc/text_rows.h"                    // FASTQ text -> rows, lengths and names from the line index (rfq_text_rows)
+#include "enc/rows_lanes.h"                   // what the rows kernels below share: group reductions, 16-byte pieces, the deciding calls' walk, length check and sums
 #include "enc/rows_select.h"                  // rows -> the kept rows, trimmed, with their names (rfq_select_rows)
 #include "enc/rows_judge.h"                   // rows -> keep, window, reason and metrics per row + a QC summary (rfq_judge_rows)
 #include "enc/rows_adapter.h"                 // rows -> the length adapter removal leaves, insert sizes of the pairs + a summary (rfq_adapter_rows)

@@ -718,3 +718,40 @@ def check_composition(codec):
             g.free()
         for p in bufs:
             codec.dev_free(p)
+
+
+# ---------------------------------------------------------------- test 12: the seams of the shared walk
+AR_ITER = 4                                                                   # (enc/rows_adapter.h)
+_walk_sets = {}
+
+
+def walk_sets(L, counts):
+    """per count of PAIRS: rows, mode and the reference under overlap and adapters at once - made once per row length, shared by the default and the general path"""
+    if L not in _walk_sets:
+        c = shape_criteria(L)[2][1]
+        _walk_sets[L] = [(random_pairs(p, L, 31 * L + p, p % 2 == 1), p % 2 == 1) for p in counts]
+        _walk_sets[L] = [(B, lens, codes, expected(B, lens, c, codes)) for (B, lens), codes in _walk_sets[L]]
+    return _walk_sets[L]
+
+
+def check_walk(codec, label):
+    L, path, counts = W.walk_case(label, AR_ITER)
+    for B, lens, codes, e in walk_sets(L, counts):
+        check(codec, B, lens, shape_criteria(L)[2][1], codes, shifts=(len(lens) % 16,), paths=(path,), e=e, what="walk L %d pairs %d" % (L, len(lens) // 2))
+
+
+def check_walk_bad_length(codec):
+    """a bad length in R2 of the last pair, a workgroup's first pair behind its last step: the refusal names the row"""
+    import _rows_enc as R
+    from repaq_amd import RfqError
+    for L in (256, 272):
+        n = 2 * (256 // (16 if L <= 256 else 64) * AR_ITER + 1)
+        B, lens = random_pairs(n // 2, L, 5, codes=True)
+        lens[n - 1] = L + 1
+        dev = W.DevRows(codec, B, None, lens)
+        try:
+            with R.pytest_raises(RfqError) as ei:
+                run(codec, dev, shape_criteria(L)[2][1], True)
+            assert ei.value.code == -3 and "first such row: %d)" % (n - 1) in ei.value.message, (L, ei.value)
+        finally:
+            dev.free()

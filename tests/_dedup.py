@@ -576,3 +576,40 @@ def check_composition(codec):
             g.free()
         for p in bufs:
             codec.dev_free(p)
+
+
+# ---------------------------------------------------------------- test 12: the seams of the shared walk
+DD_ITER = 8                                                                   # (enc/rows_dedup.h)
+
+
+def check_walk(codec, label):
+    """FIRST over rows and BEST_QUAL over pairs, the last unit a copy of the first with the higher scores: a class of two whose representative FIRST and BEST_QUAL
+    choose differently (from two units on)"""
+    L, _, counts = W.walk_case(label, DD_ITER)
+    for U in counts:
+        for pairs, best in ((False, False), (True, True)):
+            nr = 2 if pairs else 1; n = nr * U
+            rng = np.random.default_rng(31 * L + n)
+            B = _rand(rng, n, L); Q = rng.integers(0, 40, (n, L)).astype(np.uint8); lens = rng.integers(min(L, 12), L + 1, n).astype(np.int32)
+            if U > 1:
+                B[n - nr:] = B[:nr]; lens[n - nr:] = lens[:nr]; Q[n - nr:] = 41
+            e = check(codec, B, Q, lens, pairs=pairs, best=best, hist_len=4, shifts=(n % 16,), paths=(None,), what="walk L %d units %d pairs %d" % (L, U, pairs))
+            if U > 1:
+                assert e["dup_of"][U - 1] == e["dup_of"][0] == (U - 1 if best else 0) and e["summary"]["n_dups"] >= 1
+
+
+def check_walk_bad_length(codec):
+    """a bad length in the last row, a workgroup's first unit behind its last step: the refusal names it"""
+    from repaq_amd import RfqError
+    for L in (256, 272):
+        n = 256 // (16 if L <= 256 else 64) * DD_ITER + 1
+        rng = np.random.default_rng(5)
+        B = _rand(rng, n, L); lens = rng.integers(0, L + 1, n).astype(np.int32)
+        lens[n - 1] = L + 1
+        dev = dev_rows(codec, B, np.zeros_like(B), lens)
+        try:
+            with R.pytest_raises(RfqError) as ei:
+                run(codec, dev, best=True, hist_len=4)
+            assert ei.value.code == -3 and "first such row: %d)" % (n - 1) in ei.value.message, (L, ei.value)
+        finally:
+            dev.free()

@@ -535,3 +535,38 @@ def check_composition(codec):
         for p in bufs:
             codec.dev_free(p)
     return fq1, fq2, w1, w2
+
+
+# ---------------------------------------------------------------- test 11: the seams of the shared walk
+JR_ITER = 8                                                                   # (enc/rows_judge.h)
+_walk_sets = {}
+
+
+def walk_sets(L, counts):
+    """per count: rows, mode and the reference under every criterion at once - made once per row length, shared by the default and the general path"""
+    if L not in _walk_sets:
+        _walk_sets[L] = [(random_rows(n, L, 31 * L + n, codes=n % 2 == 1), n % 2 == 1) for n in counts]
+        _walk_sets[L] = [(rows, codes, expected(*rows, STEPS[-1][1], codes)) for rows, codes in _walk_sets[L]]
+    return _walk_sets[L]
+
+
+def check_walk(codec, label):
+    L, path, counts = W.walk_case(label, JR_ITER)
+    for (B, Q, lens), codes, e in walk_sets(L, counts):
+        check(codec, B, Q, lens, STEPS[-1][1], codes, shifts=(len(lens) % 16,), paths=(path,), e=e, what="walk L %d n %d" % (L, len(lens)))
+
+
+def check_walk_bad_length(codec):
+    """a bad length in the last row of a workgroup's first row behind its last step: the refusal names it"""
+    from repaq_amd import RfqError
+    for L in (256, 272):
+        n = 256 // (16 if L <= 256 else 64) * JR_ITER + 1
+        B, Q, lens = random_rows(n, L, 5, codes=True)
+        lens[n - 1] = L + 1
+        dev = W.DevRows(codec, B, Q, lens)
+        try:
+            with R.pytest_raises(RfqError) as ei:
+                run(codec, dev, STEPS[-1][1], True)
+            assert ei.value.code == -3 and "first such row: %d)" % (n - 1) in ei.value.message, (L, ei.value)
+        finally:
+            dev.free()

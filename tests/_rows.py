@@ -83,6 +83,29 @@ class Guarded:
         self.codec.dev_free(self.raw)
 
 
+def walk_counts(row_len, iters):
+    """the unit counts at which the walk of a deciding call's common-path kernel has a seam (enc/rows_lanes.h, UnitGroup): a group of LPR lanes takes a unit, G =
+    64 / LPR units a wave, R = 256 / LPR a workgroup's step, R * iters a workgroup - one less, exactly and one more of each, and a third workgroup begun.  LPR is
+    16 up to row_len 256 and 64 up to 1024; beyond that a wave takes a unit and a few counts do.  (G - 1 is 0 at LPR 64: the call of no rows.)"""
+    if row_len > 1024:
+        return [1, 2, 5]
+    lpr = 16 if row_len <= 256 else 64
+    R, G = 256 // lpr, 64 // lpr
+    return sorted({1, G - 1, G, G + 1, R - 1, R, R + 1, R * iters - 1, R * iters, R * iters + 1, 2 * R * iters + G + 1})
+
+
+# (row_len, the call's `general` option, all the walk's counts): 256 the last row length of the <16> kernel, 272 the first of <64>, 1024 its last, 1040 the first of
+# the wave-per-unit kernel
+WALK_CASES = [(256, None, True), (272, None, True), (272, "general", True), (1024, None, False), (1040, None, False)]
+WALK_IDS = ["%d%s" % (L, "_" + p if p else "") for L, p, _ in WALK_CASES]
+
+
+def walk_case(label, iters):
+    """(row_len, option, unit counts) of a WALK_IDS label"""
+    L, path, every = WALK_CASES[WALK_IDS.index(label)]
+    return L, path, (walk_counts(L, iters) if every else [1, 2, 5])
+
+
 class DevRows:
     """Rows in device memory as the rows calls take them: base rows, optionally quality rows (Q None: NULL), lengths, optionally names (None: rows without names;
     name_off: other offsets than the names' own).  shift: bytes by which the row buffers and the name blob are moved off their 256-byte aligned start.  Every

@@ -102,3 +102,13 @@ def test_stage_time_is_reported(codec):
 # ---- 11: text -> adapter -> judge -> select -> text
 def test_text_adapter_judge_select_text(codec):
     A.check_composition(codec)
+
+
+# ---- 12: the seams of the shared walk (unit counts around a wave, a step, a workgroup; row lengths around each kernel)
+@pytest.mark.parametrize("case", A.W.WALK_IDS)
+def test_walk_seams(codec, case):
+    A.check_walk(codec, case)
+
+
+def test_walk_bad_length_in_the_last_unit(codec):
+    A.check_walk_bad_length(codec)

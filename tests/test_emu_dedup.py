@@ -87,3 +87,13 @@ def test_the_switch_is_listed_and_resets(codec):
 # ---- 8: text -> judge -> dedup -> select -> text
 def test_text_judge_dedup_select_text(codec):
     D.check_composition(codec)
+
+
+# ---- 12: the seams of the shared walk (unit counts around a wave, a step, a workgroup; row lengths around each kernel)
+@pytest.mark.parametrize("case", [x for x in D.W.WALK_IDS if "general" not in x])
+def test_walk_seams(codec, case):
+    D.check_walk(codec, case)
+
+
+def test_walk_bad_length_in_the_last_unit(codec):
+    D.check_walk_bad_length(codec)

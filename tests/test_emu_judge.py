@@ -87,3 +87,13 @@ def test_the_switch_is_listed_and_resets(codec):
 # ---- 10: text -> judge -> select -> text
 def test_text_judge_select_text(codec):
     J.check_composition(codec)
+
+
+# ---- 11: the seams of the shared walk (unit counts around a wave, a step, a workgroup; row lengths around each kernel)
+@pytest.mark.parametrize("case", J.W.WALK_IDS)
+def test_walk_seams(codec, case):
+    J.check_walk(codec, case)
+
+
+def test_walk_bad_length_in_the_last_unit(codec):
+    J.check_walk_bad_length(codec)

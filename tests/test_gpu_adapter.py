@@ -138,3 +138,13 @@ def test_trim_adapters_with_tensors(codec, side_stream):
     B, lens = (t[k].cpu().numpy() for k in ("bases", "lens"))
     e1 = A.expected(B, lens, A.crit(adapter1=A.AD1, adapter_min=4, adapter_mm_per=8), False)
     assert set(single) == {"length", "how", "summary"} and np.array_equal(single["length"].cpu().numpy(), e1["length"]) and single["summary"] == e1["summary"]
+
+
+# ---- 12: the seams of the shared walk (unit counts around a wave, a step, a workgroup; row lengths around each kernel)
+@pytest.mark.parametrize("case", A.W.WALK_IDS)
+def test_walk_seams(codec, case):
+    A.check_walk(codec, case)
+
+
+def test_walk_bad_length_in_the_last_unit(codec):
+    A.check_walk_bad_length(codec)

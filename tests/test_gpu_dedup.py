@@ -151,3 +151,13 @@ def test_hot_slots(codec):
                 first = raw
     finally:
         dev.free()
+
+
+# ---- 12: the seams of the shared walk (unit counts around a wave, a step, a workgroup; row lengths around each kernel)
+@pytest.mark.parametrize("case", [x for x in D.W.WALK_IDS if "general" not in x])
+def test_walk_seams(codec, case):
+    D.check_walk(codec, case)
+
+
+def test_walk_bad_length_in_the_last_unit(codec):
+    D.check_walk_bad_length(codec)

@@ -126,3 +126,13 @@ def test_filter_rows_with_tensors(codec, side_stream):
     assert torch.equal(d["lens"], s["lens"]) and torch.equal(d["names"], s["names"])
     inside = torch.arange(L, device=dev)[None, :] < s["lens"][:, None]
     assert torch.equal(d["bases"][:, :L][inside], s["bases"][:, :L][inside]) and torch.equal(d["quals"][:, :L][inside], s["quals"][:, :L][inside])
+
+
+# ---- 11: the seams of the shared walk (unit counts around a wave, a step, a workgroup; row lengths around each kernel)
+@pytest.mark.parametrize("case", J.W.WALK_IDS)
+def test_walk_seams(codec, case):
+    J.check_walk(codec, case)
+
+
+def test_walk_bad_length_in_the_last_unit(codec):
+    J.check_walk_bad_length(codec)
