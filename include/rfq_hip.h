@@ -558,6 +558,59 @@ typedef struct {
 } rfq_dedup_rows_result;
 RFQ_API int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_dedup_rows_args* args, rfq_dedup_rows_result* res);
 
+/* The QC profile, beside the steps that decide: rows under rfq_select_rows' triple (keep, start, len) -> the tables a QC report is built from (in the manner of fastp's
+ * and FastQC's reports; integer rules of this project's own, no parity with either is claimed).  Like rfq_judge_rows it moves no rows: one call on the raw rows is the
+ * profile "before filtering", one call with the triple the judge, the adapter step and dedup produce is the profile "after filtering".  No float anywhere, products in
+ * 64 bits; the same call gives the same bytes, whatever kernel, grid or order of arrival.  Names and rows->qual_offset are not looked at: a quality byte IS the score.
+ * Mates.  M = 1 + pairs.  With pairs row i belongs to mate i & 1 and read 1 and read 2 are profiled apart; without, every row is mate 0.  A row is COUNTED when d_keep
+ * is NULL or d_keep[i] != 0 - the pair rule stays the caller's (rfq_dedup_rows and rfq_select_rows write or apply it to both rows of a pair).
+ * Window.  [a, a + n) of row i with a = d_start[i] (NULL: 0) and n = d_len[i] (NULL: lens[i] - a).  Position j of the row is cycle c = j - a and is tabulated in table
+ * row min(c, cycles - 1): the last row collects what lies beyond (the convention of the family's histograms); the result's max_len, the longest counted window, says
+ * whether that happened.
+ * Base classes are rfq_adapter_rows': class 0 .. 3 = code 0 .. 3 or A C G T in either case, class 4 (other) = every other byte; GC is class 1 or 2.
+ * Outputs, all uint64 and 8-byte aligned; each may be NULL and is then not produced; they are zeroed, then filled, with rows or without.
+ *   d_base_cnt   [M][cycles][5]      the counted positions of a cycle and class
+ *   d_base_qsum  [M][cycles][5]      the sum of their scores
+ *   d_qual_hist  [M][cycles][qbins]  the counted positions of a cycle and score; scores >= qbins - 1 go in the last bin
+ *   d_len_hist   [M][len_bins]       the counted rows by min(n, len_bins - 1); a window of 0 is counted in bin 0
+ *   d_meanq_hist [M][qbins]          the counted rows with n > 0 by min(qsum / n, qbins - 1), integer division
+ *   d_gc_hist    [M][101]            the counted rows with acgt > 0 by 100 * gc / acgt, acgt: the window's positions of class 0 .. 3
+ * Quantiles are the caller's, from d_qual_hist; tables of several calls add up (a table carried across calls is not offered).
+ * Result, per mate over the windows of the counted rows: counted, bases, qsum, q20, q30 (scores >= 20 / 30), gc, other; max_len; n_rows.  It is filled also when every
+ * output is NULL.  The score fields are 0 without rows->d_quals, gc and other without rows->d_bases.
+ * RFQ_E_ARG, judged on the host: pairs other than 0 / 1, an odd n_rows with pairs; a bad base_mode; row_len == 0 or a NULL d_lens with rows; cycles outside 1 .. 65536
+ * with a per-cycle table; qbins outside 1 .. 256 with a table that has score bins; len_bins == 0 or > 2^20 with d_len_hist; rows->d_quals == NULL with d_base_qsum,
+ * d_qual_hist or d_meanq_hist and rows->d_bases == NULL with d_base_cnt, d_base_qsum or d_gc_hist (with rows); a d_lens / d_start / d_len that is not 4-byte or a table
+ * that is not 8-byte aligned; an output that overlaps an input or another output (byte ranges are compared); n_rows >= 2^31.  RFQ_E_ARG, judged on the device, the
+ * message names the first such row - ALL rows are judged, counted or not: lens[i] < 0 or > row_len; start < 0, len < 0 or start + len > lens[i] (in 64 bits).  What the
+ * tables hold is then unspecified; nothing outside the row buffers is read for such a row.  After any refusal the context stays usable.
+ * The row buffers may have any alignment, on rfq_judge_rows' terms - never a byte outside [d_x, d_x + n_rows * row_len).  n_rows * row_len may exceed 4 GiB.  Rows of up to
+ * 1024 bytes whose tables fit a compute unit's LDS are tabulated there and flushed once per workgroup; longer rows, larger tables (and every call with
+ * RFQ_PROFILE=general) add to the tables in device memory position by position - the same bytes, slower.  Synchronous on the context's stream, one read-back; stage time
+ * through rfq_last_timings (profile:rows). */
+#define RFQ_PROFILE_GC_BINS 101
+typedef struct {
+    int32_t  pairs;                       /* 1: row i is of mate i & 1 (n_rows must be even)                            */
+    uint32_t cycles;                      /* rows of the per-cycle tables, 1 .. 65536                                   */
+    uint32_t qbins;                       /* score bins, 1 .. 256                                                       */
+    uint32_t len_bins;                    /* entries of d_len_hist per mate, 1 .. 2^20                                  */
+    const uint8_t* d_keep;                /* [n_rows] bytes, non-zero = the row is counted; NULL = every row            */
+    const int32_t* d_start;               /* [n_rows] or NULL (0)                                                       */
+    const int32_t* d_len;                 /* [n_rows] or NULL (to the end of the read)                                  */
+    uint64_t* d_base_cnt;                 /* [M][cycles][5] or NULL                                                     */
+    uint64_t* d_base_qsum;                /* [M][cycles][5] or NULL                                                     */
+    uint64_t* d_qual_hist;                /* [M][cycles][qbins] or NULL                                                 */
+    uint64_t* d_len_hist;                 /* [M][len_bins] or NULL                                                      */
+    uint64_t* d_meanq_hist;               /* [M][qbins] or NULL                                                         */
+    uint64_t* d_gc_hist;                  /* [M][101] or NULL                                                           */
+} rfq_profile_rows_args;
+typedef struct {
+    uint64_t n_rows;
+    uint64_t counted[2], bases[2], qsum[2], q20[2], q30[2], gc[2], other[2];   /* [mate]; [1] is 0 without pairs        */
+    uint64_t max_len;                     /* the longest counted window                                                 */
+} rfq_profile_rows_result;
+RFQ_API int rfq_profile_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_profile_rows_args* args, rfq_profile_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -591,7 +644,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

@@ -170,6 +170,19 @@ class DedupRowsResult(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("n_units", "n_candidates", "n_classes", "n_dups", "max_class", "bases_in", "bases_kept")]
 
 
+PROFILE_GC_BINS = 101
+PROFILE_TABLES = ("base_cnt", "base_qsum", "qual_hist", "len_hist", "meanq_hist", "gc_hist")
+
+
+class ProfileRowsArgs(C.Structure):
+    _fields_ = [("pairs", C.c_int32), ("cycles", C.c_uint32), ("qbins", C.c_uint32), ("len_bins", C.c_uint32), ("d_keep", C.c_void_p), ("d_start", C.c_void_p),
+                ("d_len", C.c_void_p)] + [("d_" + t, C.c_void_p) for t in PROFILE_TABLES]
+
+
+class ProfileRowsResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64)] + [(f, C.c_uint64 * 2) for f in ("counted", "bases", "qsum", "q20", "q30", "gc", "other")] + [("max_len", C.c_uint64)]
+
+
 _libs = {}
 
 
@@ -208,6 +221,7 @@ def load(path=None):
     L.rfq_adapter_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(AdapterRowsArgs), C.POINTER(AdapterRowsResult)]
     L.rfq_merge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(MergeRowsArgs), C.POINTER(MergeRowsResult)]
     L.rfq_dedup_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(DedupRowsArgs), C.POINTER(DedupRowsResult)]
+    L.rfq_profile_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(ProfileRowsArgs), C.POINTER(ProfileRowsResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -231,6 +245,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

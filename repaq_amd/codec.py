@@ -393,6 +393,22 @@ class RfqCodec:
         self._check(self._L.rfq_dedup_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
+    # --- the report beside the steps that decide: rows under select_rows' triple -> the tables of a QC report (rfq_profile_rows)
+    def profile_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, codes=False, pairs=False, d_keep=None, d_start=None, d_len=None, cycles=0, qbins=0, len_bins=0,
+                     d_base_cnt=None, d_base_qsum=None, d_qual_hist=None, d_len_hist=None, d_meanq_hist=None, d_gc_hist=None, base_mode=None):
+        """rfq_profile_rows: the rows as judge_rows takes them (names are not looked at; a quality byte is the score) and select_rows' triple - d_keep n_rows mask
+        bytes (non-zero = counted; None: every row), d_start / d_len n_rows int32 windows (None: 0 / to the end of the read).  With M = 1 + pairs (row i is of mate
+        i & 1) the tables, uint64 each: d_base_cnt / d_base_qsum [M][cycles][5] (positions / score sum per cycle and class A C G T other), d_qual_hist
+        [M][cycles][qbins], d_len_hist [M][len_bins], d_meanq_hist [M][qbins], d_gc_hist [M][101]; the last row / bin of each collects what lies beyond; a table
+        that is None is not produced.  Returns ProfileRowsResult (n_rows, max_len and, per mate, counted, bases, qsum, q20, q30, gc, other)."""
+        rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, codes, 0)
+        if base_mode is not None:
+            rows.base_mode = base_mode
+        a = A.ProfileRowsArgs(1 if pairs else 0, cycles, qbins, len_bins, d_keep, d_start, d_len, d_base_cnt, d_base_qsum, d_qual_hist, d_len_hist, d_meanq_hist, d_gc_hist)
+        r = A.ProfileRowsResult()
+        self._check(self._L.rfq_profile_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

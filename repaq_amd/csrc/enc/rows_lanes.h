@@ -119,7 +119,9 @@ __device__ __forceinline__ uint64_t rows_unit_row(uint32_t pairs, uint64_t u, ui
 template <int LPR> struct UnitGroup {
     static constexpr uint32_t R = 256u / LPR, GW = 64u / LPR;
     const uint32_t grp = threadIdx.x / LPR, gl = threadIdx.x % LPR, x0 = 16u * gl;
-    __device__ __forceinline__ uint64_t unit(uint32_t it, uint32_t iter) const { return ((uint64_t)blockIdx.x * iter + it) * R + grp; }
+    __device__ __forceinline__ uint64_t unit(uint32_t it, uint32_t iter) const { return unit_of(blockIdx.x, it, iter); }
+    // the same for a workgroup that is the blk-th of its kind (rfq_profile_rows: the workgroups of a mate count among themselves)
+    __device__ __forceinline__ uint64_t unit_of(uint32_t blk, uint32_t it, uint32_t iter) const { return ((uint64_t)blk * iter + it) * R + grp; }
     // the wave's FIRST unit lies behind the last one - the same in every lane of the wave, so a loop may end on it with wave-wide reductions in its body
     __device__ __forceinline__ bool past(uint64_t u, uint64_t n_units) const { return u - grp % GW >= n_units; }
 };

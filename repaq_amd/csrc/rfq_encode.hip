@@ -1692,3 +1692,89 @@ extern "C" int rfq_dedup_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_ded
     res->n_candidates = hs.c[0]; res->bases_in = hs.c[1]; res->n_classes = hs.c[2]; res->bases_kept = hs.c[3]; res->max_class = hs.c[4]; res->n_dups = hs.c[0] - hs.c[2];
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- rows under a keep / start / length triple -> the tables of a QC report: rfq_profile_rows of include/rfq_hip.h
+// One kernel and one read-back (enc/rows_profile.h).  Rows of up to 1024 bytes whose tables fit a compute unit's LDS go to k_profile_rows<16> / <64>: the grid is
+// PF_WG_PER_CU workgroups per compute unit - a workgroup pays for its table once, at its end - and the steps each takes follow from that; beyond PF_ROWS_MAX rows
+// per workgroup (the bound of a 32-bit cell) the grid grows instead.  Everything else (and RFQ_PROFILE=general) goes to the wave-per-row kernel.
+static int profile_win_refusal(rfq_ctx* ctx, unsigned long long row) {
+    return rfq_fail(ctx, RFQ_E_ARG, "a window is negative or ends behind its read: start < 0, len < 0 or start + len > lens[i] (first such row: %llu)", row);
+}
+extern "C" int rfq_profile_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_profile_rows_args* a, rfq_profile_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows;
+    int rc;
+    if ((rc = rows_pairs_arg(ctx, a->pairs, n)) != RFQ_OK) return rc;
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
+    const bool per_cycle = a->d_base_cnt || a->d_base_qsum || a->d_qual_hist, per_score = a->d_qual_hist || a->d_meanq_hist;
+    if (per_cycle && (a->cycles < 1u || a->cycles > 65536u)) return rfq_fail(ctx, RFQ_E_ARG, "cycles must be 1 .. 65536 with a per-cycle table (got %u)", a->cycles);
+    if (per_score && (a->qbins < 1u || a->qbins > 256u)) return rfq_fail(ctx, RFQ_E_ARG, "qbins must be 1 .. 256 with d_qual_hist or d_meanq_hist (got %u)", a->qbins);
+    if (a->d_len_hist && (a->len_bins < 1u || a->len_bins > (1u << 20))) return rfq_fail(ctx, RFQ_E_ARG, "len_bins must be 1 .. 2^20 with d_len_hist (got %u)", a->len_bins);
+    if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    if (n && !in->d_lens) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens");
+    if (n && !in->d_quals && (a->d_base_qsum || a->d_qual_hist || a->d_meanq_hist)) return rfq_fail(ctx, RFQ_E_ARG, "d_base_qsum, d_qual_hist and d_meanq_hist need rows->d_quals");
+    if (n && !in->d_bases && (a->d_base_cnt || a->d_base_qsum || a->d_gc_hist)) return rfq_fail(ctx, RFQ_E_ARG, "d_base_cnt, d_base_qsum and d_gc_hist need rows->d_bases");
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_start | (uintptr_t)a->d_len) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_start and d_len must be 4-byte aligned");
+    if (((uintptr_t)a->d_base_cnt | (uintptr_t)a->d_base_qsum | (uintptr_t)a->d_qual_hist | (uintptr_t)a->d_len_hist | (uintptr_t)a->d_meanq_hist | (uintptr_t)a->d_gc_hist) & 7u)
+        return rfq_fail(ctx, RFQ_E_ARG, "the tables must be 8-byte aligned");
+    const unsigned long long M = a->pairs ? 2ull : 1ull;
+    const Span outs[] = { { a->d_base_cnt, M * a->cycles * 40ull, "d_base_cnt" }, { a->d_base_qsum, M * a->cycles * 40ull, "d_base_qsum" },
+                          { a->d_qual_hist, M * a->cycles * a->qbins * 8ull, "d_qual_hist" }, { a->d_len_hist, M * a->len_bins * 8ull, "d_len_hist" },
+                          { a->d_meanq_hist, M * a->qbins * 8ull, "d_meanq_hist" }, { a->d_gc_hist, M * PF_GC_BINS * 8ull, "d_gc_hist" } };
+    {
+        Span ins[8]; rows_src_spans(in, false, ins);
+        ins[5] = { a->d_keep, n, "d_keep" }; ins[6] = { a->d_start, n * 4ull, "d_start" }; ins[7] = { a->d_len, n * 4ull, "d_len" };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+        for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) for (size_t k = i + 1; k < sizeof outs / sizeof outs[0]; k++)
+            if (sel_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the output %s", outs[i].what, outs[k].what);
+    }
+    res->n_rows = n;
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    for (const Span& o : outs) if (o.p) HIPCHK(ctx, hipMemsetAsync(const_cast<void*>(o.p), 0, (size_t)o.n, S));
+    if (!n) { HIPCHK(ctx, hipStreamSynchronize(S)); return RFQ_OK; }
+    ProfileIn pi; memset(&pi, 0, sizeof pi);
+    pi.b = in->d_bases; pi.q = in->d_quals; pi.lens = in->d_lens; pi.keep = a->d_keep; pi.start = a->d_start; pi.len = a->d_len;
+    pi.total = n * in->row_len; pi.n_rows = (uint32_t)n; pi.row_len = in->row_len; pi.vec_in = rows_vec(in->row_len, in->d_bases, in->d_quals);
+    pi.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u; pi.pairs = a->pairs ? 1u : 0u;
+    pi.cycles = per_cycle ? a->cycles : 1u; pi.qbins = per_score ? a->qbins : 1u; pi.len_bins = a->d_len_hist ? a->len_bins : 1u;
+    pi.base_cnt = (unsigned long long*)a->d_base_cnt; pi.base_qsum = (unsigned long long*)a->d_base_qsum; pi.qual_hist = (unsigned long long*)a->d_qual_hist;
+    pi.len_hist = (unsigned long long*)a->d_len_hist; pi.meanq_hist = (unsigned long long*)a->d_meanq_hist; pi.gc_hist = (unsigned long long*)a->d_gc_hist;
+    pi.tile = ctx->opt.profile_general ? 64u : 1024u;
+    // the common path's LDS: a table that is not asked for takes no room (enc/rows_profile.h has the layout)
+    pi.ch = (pi.cycles + 15u) / 16u; pi.qs = pi.qbins | 1u;
+    unsigned long long words = 0;
+    const unsigned long long cs = 16ull * pi.ch;
+    pi.o_base = 0u; if (a->d_base_cnt || a->d_base_qsum) words += cs * 10ull;
+    pi.o_qh = (uint32_t)words; if (a->d_qual_hist) words += cs * pi.qs;
+    pi.o_len = (uint32_t)words; if (a->d_len_hist) words += pi.len_bins;
+    pi.o_mq = (uint32_t)words; if (a->d_meanq_hist) words += pi.qbins;
+    pi.o_gc = (uint32_t)words; if (a->d_gc_hist) words += PF_GC_BINS;
+    words += words & 1ull;
+    const bool lds = !ctx->opt.profile_general && in->row_len <= 1024u && words * 4ull <= PF_LDS_MAX;
+    ctx->timer.begin("profile:rows", S);
+    ProfileStat* dst = nullptr; ProfileStat hs;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if (lds) {
+        const uint32_t R = in->row_len <= 256u ? 16u : 4u, gcap = std::max(1u, PF_WG_PER_CU * ctx->n_cu / (uint32_t)M);       // rows a step, workgroups of a mate
+        const uint64_t units = n / M;
+        const uint64_t steps = std::min<uint64_t>(std::max<uint64_t>((units + (uint64_t)R * gcap - 1u) / ((uint64_t)R * gcap), 1u), PF_ROWS_MAX / R);
+        const uint64_t gm = (units + R * steps - 1u) / (R * steps);
+        pi.steps = (uint32_t)steps; pi.lds_words = (uint32_t)words;
+        const auto k = in->row_len <= 256u ? k_profile_rows<16> : k_profile_rows<64>;
+        hipLaunchKernelGGL(k, dim3((uint32_t)(gm * M)), dim3(256), (size_t)words * 4u, S, pi, dst);
+    } else hipLaunchKernelGGL(k_profile_rows_long, dim3((uint32_t)n), dim3(64), 0, S, pi, dst);
+    KCHK(ctx, "k_profile_rows");
+    ctx->timer.end(S);
+    rc = rows_sums_back(ctx, S, dst, &hs, in->row_len);                      // (a bad length refuses; a bad window in a row in front of it, or alone, is the one to name)
+    if ((hs.err & PF_ERR_WIN) && (rc == RFQ_OK || ~hs.c[15] < hs.bad_row)) return profile_win_refusal(ctx, ~hs.c[15]);
+    if (rc != RFQ_OK) return rc;
+    for (int m = 0; m < 2; m++) {
+        const unsigned long long* c = hs.c + 7 * m;
+        res->counted[m] = c[0]; res->bases[m] = c[1]; res->qsum[m] = c[2]; res->q20[m] = c[3]; res->q30[m] = c[4]; res->gc[m] = c[5]; res->other[m] = c[6];
+    }
+    res->max_len = hs.c[14];
+    return RFQ_OK;
+}

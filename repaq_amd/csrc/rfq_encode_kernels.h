@@ -29,3 +29,4 @@
 #include "enc/rows_adapter.h"                 // rows -> the length adapter removal leaves, insert sizes of the pairs + a summary (rfq_adapter_rows)
 #include "enc/rows_merge.h"                   // pairs -> one read per overlapping pair, the consensus of both mates, with R1's names (rfq_merge_rows)
 #include "enc/rows_dedup.h"                   // rows -> a keep byte that leaves one unit of every class of identical units, class sizes + a summary (rfq_dedup_rows)
+#include "enc/rows_profile.h"                 // rows under a keep / start / length triple -> per-cycle base content, position x score, length / mean-quality / GC tables (rfq_profile_rows)

@@ -58,6 +58,13 @@ passing copies; the windows are still the judge's:
     d = dedup_rows(codec, dict(t, lens=j["length"]), pairs=True, keep=j["keep"], best_qual=True)      # d["summary"]["n_dups"]: the duplication count of a QC report
     s = select_rows(codec, t, keep=d["keep"], start=j["start"], length=j["length"], pairs=True, min_len=36)
 
+the report: rfq_profile_rows tabulates the rows under the same triple select_rows takes - base content and mean score per cycle, the position x score
+distribution, the distributions of length, mean score and GC content, read 1 and read 2 apart - without moving a byte.  One call on the raw rows is the profile
+"before filtering", one with the triple the profile "after filtering":
+
+    before = profile_rows(codec, t, pairs=True)
+    after = profile_rows(codec, t, pairs=True, keep=d["keep"], start=j["start"], length=j["length"])          # after["base_cnt"]: [2, cycles, 5] int64 ...
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -310,6 +317,45 @@ def dedup_rows(codec, t, pairs=False, key_len=0, best_qual=False, keep=None, his
     out = {"keep": out_keep, "dup_of": dup_of, "count": count, "summary": {f: int(getattr(r, f)) for f in DEDUP_FIELDS}}
     if hist_len:
         out["hist"] = hist
+    return out
+
+
+PROFILE_TABLES = ("base_cnt", "base_qsum", "qual_hist", "len_hist", "meanq_hist", "gc_hist")
+PROFILE_FIELDS = ("counted", "bases", "qsum", "q20", "q30", "gc", "other")
+
+
+def profile_rows(codec, t, pairs=False, codes=True, keep=None, start=None, length=None, cycles=None, qbins=64, len_bins=None, tables=PROFILE_TABLES):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "quals", "lens"; codes: what they were made with) under select_rows' triple - keep: [n] bool /
+    uint8 (None: every row), start / length: [n] int32 windows (None: 0 / to the end of the read), what judge_rows, trim_adapters and dedup_rows leave - -> the tables
+    of a QC report (rfq_profile_rows), int64 each, M = 2 with pairs (row i is of mate i & 1: read 1 and read 2 apart), else 1: "base_cnt" / "base_qsum" [M, cycles, 5]
+    (positions / score sum per cycle and class A C G T other), "qual_hist" [M, cycles, qbins], "len_hist" [M, len_bins], "meanq_hist" [M, qbins], "gc_hist" [M, 101];
+    the last row / bin of each collects what lies beyond.  cycles / len_bins default to the rows' stride (+ 1 for the lengths); tables: the ones wanted.  "summary":
+    n_rows, max_len (the longest counted window) and, per mate, lists of counted, bases, qsum, q20, q30, gc, other.  No row is moved.  One call, ordered with torch's
+    current stream; the context goes back to its own stream afterwards."""
+    bases, quals, lens = t["bases"], t["quals"], t["lens"]
+    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    dev = bases.device
+    assert quals.dtype == torch.uint8 and quals.is_contiguous() and quals.shape == bases.shape and quals.device == dev, "quals: [n, L] uint8 on the rows' device"
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
+    assert not pairs or n % 2 == 0, "rows in pairs"
+    if keep is not None:
+        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
+    for name, w in (("start", start), ("length", length)):
+        assert w is None or (w.dtype == torch.int32 and w.is_contiguous() and w.numel() == n and w.device == dev), name + ": [n] int32 on the rows' device"
+    assert set(tables) <= set(PROFILE_TABLES), "tables: of " + ", ".join(PROFILE_TABLES)
+    cycles = L if cycles is None else cycles; len_bins = L + 1 if len_bins is None else len_bins
+    M = 2 if pairs else 1
+    shapes = dict(base_cnt=(M, cycles, 5), base_qsum=(M, cycles, 5), qual_hist=(M, cycles, qbins), len_hist=(M, len_bins), meanq_hist=(M, qbins), gc_hist=(M, 101))
+    out = {k: torch.empty(shapes[k], dtype=torch.int64, device=dev) for k in PROFILE_TABLES if k in tables}
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        r = codec.profile_rows(n, L, bases.data_ptr(), quals.data_ptr(), lens.data_ptr(), codes=codes, pairs=pairs, d_keep=keep.data_ptr() if keep is not None else None,
+                               d_start=start.data_ptr() if start is not None else None, d_len=length.data_ptr() if length is not None else None, cycles=cycles,
+                               qbins=qbins, len_bins=len_bins, **{"d_" + k: v.data_ptr() for k, v in out.items()})
+    finally:
+        codec.set_stream(None)
+    out["summary"] = dict({f: [int(getattr(r, f)[m]) for m in range(M)] for f in PROFILE_FIELDS}, n_rows=int(r.n_rows), max_len=int(r.max_len))
     return out
 
 
