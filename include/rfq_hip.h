@@ -611,6 +611,74 @@ typedef struct {
 } rfq_profile_rows_result;
 RFQ_API int rfq_profile_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_profile_rows_args* args, rfq_profile_rows_result* res);
 
+/* Screening against reference k-mers, beside rfq_judge_rows and rfq_dedup_rows: what IS a read - the PhiX spike-in, rRNA, the host, a bait set?  rfq_screen_build
+ * makes an exact set of canonical k-mers from reference sequences, rfq_screen_rows counts for every row the k-mers that are in the set and leaves a keep byte (in the
+ * manner of BBDuk and FastQ Screen; integer rules of this project's own, no parity with either is claimed).  Like the judge and dedup it DECIDES and moves no bytes:
+ * d_keep is what rfq_dedup_rows takes as d_in and rfq_select_rows as d_keep.  No float anywhere; the same call gives the same outputs.
+ * Base classes are rfq_adapter_rows': class 0 .. 3 = code 0 .. 3 (RFQ_ROWS_CODE) or A C G T in either case (RFQ_ROWS_ASCII), every other byte is "other".
+ * k-mer.  k is 4 .. 31.  The k-mer at position p of a sequence of l bases exists when p + k <= l and is VALID when all its k positions are of class 0 .. 3.  Its forward
+ * value is sum class(p + i) * 4^(k - 1 - i), its reverse-complement value sum (3 - class(p + k - 1 - i)) * 4^(k - 1 - i), its canonical value the smaller of the two (a
+ * k-mer that is its own reverse complement - even k - is canonical as it stands).
+ * rfq_screen_build.  References are ASCII text on the device, a blob and n_refs + 1 uint64 offsets (the layout of rfq_rows_in's names).  The set is every canonical
+ * value of every valid k-mer of every reference; k-mers do not span two references.  The index goes into a CALLER-owned device buffer: a 64-byte header (magic,
+ * version, k, S, n_kmers, flags) and S 64-bit slots, S the power of two >= max(1024, 2 * refs_len) - known without a read-back; size_only = 1 returns slots and
+ * index_bytes and writes nothing.  A slot is 0 (empty) or bit 63 | value; open addressing, a slot is claimed with one compare-and-swap.  WHICH slot a value lands in
+ * may depend on the order of arrival: the index BYTES are private and may differ from run to run; the set, n_kmers (the distinct values) and every output of
+ * rfq_screen_rows are the same every time.  Result: n_refs, ref_bases (the references' bytes), n_positions (valid k-mers), n_kmers, slots, index_bytes.
+ * RFQ_E_ARG, judged on the host: k outside 4 .. 31; a NULL d_refs or d_ref_off with n_refs > 0; a d_ref_off that is not 8-byte or a d_index that is not 16-byte aligned;
+ * a NULL d_index on a call that writes; an index that overlaps the references.  RFQ_E_ARG, judged on the device, the message names the first such reference: offsets
+ * that decrease or end past refs_len.  RFQ_E_NOSPACE, nothing written, the message says what is needed: index_cap too small.  An empty set (no reference, or none
+ * with k valid bases in a row) is NOT an error: every later screen reports 0 hits.
+ * rfq_screen_rows.  Units and candidates are rfq_dedup_rows': pairs makes rows 2u / 2u + 1 one unit; d_in NULL = all rows; a unit is a candidate when the byte of every
+ * one of its rows is non-zero.  Lengths come from rows->d_lens - what rfq_adapter_rows or the judge cut comes in there; the window is [0, lens[i]).  Names and quality
+ * rows are not read.  Outputs; each may be NULL and is then not produced: d_kmers [n_rows] uint32, the row's valid k-mers; d_hits [n_rows] uint32, those whose canonical
+ * value is in the set; d_keep [n_rows] bytes.  A row of a unit that is no candidate gets 0 / 0 / 0.  With H and K the unit's sums of hits and k-mers over its rows the
+ * unit MATCHES when H >= max(min_hits, 1) and 100 * H >= min_pct * K (64 bits, min_pct 0 .. 100).  RFQ_SCREEN_DROP_MATCHED (contaminant removal): keep = candidate and
+ * not matched; RFQ_SCREEN_KEEP_MATCHED (bait): keep = candidate and matched; both rows of a pair get the unit's byte.  Result: n_units, n_candidates, n_matched, n_kept,
+ * kmers, hits (sums over the candidates), bases_in / bases_kept (the sum of l over the rows of the candidates / of the kept units).
+ * RFQ_E_ARG, judged on the host: pairs other than 0 / 1, an odd n_rows with pairs; an unknown mode; min_pct > 100; a bad base_mode; row_len == 0, a NULL d_lens or
+ * d_bases with rows; a NULL or misaligned (16 bytes) d_index, index_bytes < 64; a d_lens / d_kmers / d_hits that is not 4-byte aligned; an output that overlaps an
+ * input (byte ranges are compared; the index and d_in are inputs); n_rows >= 2^31.  RFQ_E_DATA for an index whose header is not one rfq_screen_build writes: it is read
+ * back once and checked for the magic, the version, k in range, S a power of two and 64 + 8 * S <= index_bytes.  RFQ_E_ARG, judged on the device, the message names
+ * the first such row - ALL rows are judged, candidates or not: lens[i] < 0 or > row_len; what the outputs hold is then unspecified.  After any refusal the context
+ * stays usable.
+ * A probe walk takes at most S steps whatever the slots hold: an index that was written over cannot hang the call.  Nothing outside [d_index, d_index + index_bytes) and
+ * the row buffers is read.  The row buffers may have any alignment, on rfq_judge_rows' terms - never a byte outside [d_x, d_x + n_rows * row_len).  n_rows * row_len may
+ * exceed 4 GiB.  An index of up to 16384 slots (PhiX, adapter sets, a mitochondrion) is copied into a compute unit's LDS by every workgroup and probed there; a larger
+ * one is probed in device memory.  Rows beyond 1024 bytes (and every call with RFQ_SCREEN=general) go to a wave-per-unit kernel with the table in device memory - the
+ * same outputs.  RFQ_SCREEN=collide makes rfq_screen_build keep four bits of the hash (recorded in the header's flags, so that every lookup agrees): long probe chains,
+ * for the tests.  Synchronous on the context's stream; rfq_screen_rows has one read-back beside the header's; stage times through rfq_last_timings (screen:build,
+ * screen:rows).
+ * NOT offered: per-reference attribution (build one index per reference and screen once per index, as FastQ Screen does with its genomes); k-mers that tolerate
+ * mismatches; k > 31; trimming at a k-mer; a window other than [0, lens[i]). */
+#define RFQ_SCREEN_DROP_MATCHED 0
+#define RFQ_SCREEN_KEEP_MATCHED 1
+typedef struct {
+    uint32_t k;                           /* 4 .. 31                                                                    */
+    int32_t  size_only;                   /* 1: only slots and index_bytes are reported, nothing is written             */
+    const uint8_t*  d_refs; size_t refs_len;            /* the references' ASCII bytes back to back                     */
+    const uint64_t* d_ref_off; uint64_t n_refs;         /* [n_refs + 1], 8-byte aligned: reference i is [off[i], off[i + 1]) */
+    void* d_index; size_t index_cap;      /* the caller's buffer, 16-byte aligned                                       */
+} rfq_screen_build_args;
+typedef struct {
+    uint64_t n_refs, ref_bases, n_positions, n_kmers, slots, index_bytes;
+} rfq_screen_build_result;
+RFQ_API int rfq_screen_build(rfq_ctx* ctx, const rfq_screen_build_args* args, rfq_screen_build_result* res);
+typedef struct {
+    int32_t  pairs;                       /* 1: a unit is the pair of rows 2u / 2u + 1 (n_rows must be even)            */
+    int32_t  mode;                        /* RFQ_SCREEN_DROP_MATCHED / RFQ_SCREEN_KEEP_MATCHED                          */
+    uint32_t min_hits, min_pct;           /* a unit matches with H >= max(min_hits, 1) and 100 * H >= min_pct * K       */
+    const void* d_index; size_t index_bytes;            /* what rfq_screen_build wrote                                  */
+    const uint8_t* d_in;                  /* [n_rows] bytes, non-zero = the row is a candidate; NULL = every row        */
+    uint32_t* d_kmers;                    /* [n_rows] or NULL                                                           */
+    uint32_t* d_hits;                     /* [n_rows] or NULL                                                           */
+    uint8_t*  d_keep;                     /* [n_rows] 1 / 0, or NULL                                                    */
+} rfq_screen_rows_args;
+typedef struct {
+    uint64_t n_units, n_candidates, n_matched, n_kept, kmers, hits, bases_in, bases_kept;
+} rfq_screen_rows_result;
+RFQ_API int rfq_screen_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_screen_rows_args* args, rfq_screen_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -644,7 +712,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general, RFQ_SCREEN=general|collide; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

@@ -183,6 +183,28 @@ class ProfileRowsResult(C.Structure):
     _fields_ = [("n_rows", C.c_uint64)] + [(f, C.c_uint64 * 2) for f in ("counted", "bases", "qsum", "q20", "q30", "gc", "other")] + [("max_len", C.c_uint64)]
 
 
+SCREEN_DROP_MATCHED, SCREEN_KEEP_MATCHED = 0, 1
+SCREEN_HEADER_BYTES = 64
+
+
+class ScreenBuildArgs(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("size_only", C.c_int32), ("d_refs", C.c_void_p), ("refs_len", C.c_size_t), ("d_ref_off", C.c_void_p), ("n_refs", C.c_uint64),
+                ("d_index", C.c_void_p), ("index_cap", C.c_size_t)]
+
+
+class ScreenBuildResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_refs", "ref_bases", "n_positions", "n_kmers", "slots", "index_bytes")]
+
+
+class ScreenRowsArgs(C.Structure):
+    _fields_ = [("pairs", C.c_int32), ("mode", C.c_int32), ("min_hits", C.c_uint32), ("min_pct", C.c_uint32), ("d_index", C.c_void_p), ("index_bytes", C.c_size_t),
+                ("d_in", C.c_void_p), ("d_kmers", C.c_void_p), ("d_hits", C.c_void_p), ("d_keep", C.c_void_p)]
+
+
+class ScreenRowsResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_units", "n_candidates", "n_matched", "n_kept", "kmers", "hits", "bases_in", "bases_kept")]
+
+
 _libs = {}
 
 
@@ -222,6 +244,8 @@ def load(path=None):
     L.rfq_merge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(MergeRowsArgs), C.POINTER(MergeRowsResult)]
     L.rfq_dedup_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(DedupRowsArgs), C.POINTER(DedupRowsResult)]
     L.rfq_profile_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(ProfileRowsArgs), C.POINTER(ProfileRowsResult)]
+    L.rfq_screen_build.argtypes = [C.c_void_p, C.POINTER(ScreenBuildArgs), C.POINTER(ScreenBuildResult)]
+    L.rfq_screen_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(ScreenRowsArgs), C.POINTER(ScreenRowsResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -245,6 +269,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_screen_build", "rfq_screen_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

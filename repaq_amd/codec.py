@@ -33,6 +33,7 @@ class RfqCodec:
         if rc != A.RFQ_OK:
             raise RfqError(rc, "rfq_create(device=%d) failed: no usable MI355X / HIP device (there is no CPU fallback)" % device)
         self._h = h
+        self.device = device
 
     def close(self):
         if getattr(self, "_h", None):
@@ -407,6 +408,34 @@ class RfqCodec:
         a = A.ProfileRowsArgs(1 if pairs else 0, cycles, qbins, len_bins, d_keep, d_start, d_len, d_base_cnt, d_base_qsum, d_qual_hist, d_len_hist, d_meanq_hist, d_gc_hist)
         r = A.ProfileRowsResult()
         self._check(self._L.rfq_profile_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
+    # --- what a read is: reference sequences -> an index of canonical k-mers, rows against it -> k-mers, hits and a keep byte (rfq_screen_build, rfq_screen_rows)
+    def screen_build(self, d_refs, refs_len, d_ref_off, n_refs, k=25, d_index=None, index_cap=0, size_only=False):
+        """rfq_screen_build: the references as ASCII bytes back to back on the device (d_refs, refs_len) with n_refs + 1 uint64 offsets (d_ref_off) -> the set of the
+        canonical values of their valid k-mers (k in 4 .. 31; a k-mer lies inside one reference and is all ACGT, either case) as an index in the caller's buffer
+        d_index (16-byte aligned, index_cap bytes).  size_only: nothing is written, the result says how large the buffer has to be.  Returns ScreenBuildResult
+        (n_refs, ref_bases, n_positions, n_kmers, slots, index_bytes)."""
+        a = A.ScreenBuildArgs(k, 1 if size_only else 0, d_refs, refs_len, d_ref_off, n_refs, d_index, index_cap)
+        r = A.ScreenBuildResult()
+        self._check(self._L.rfq_screen_build(self._h, C.byref(a), C.byref(r)))
+        return r
+
+    def screen_rows(self, n_rows, row_len, d_bases, d_lens, d_index, index_bytes, codes=False, pairs=False, min_hits=1, min_pct=0, keep_matched=False, mode=None,
+                    d_in=None, d_kmers=None, d_hits=None, d_keep=None, base_mode=None):
+        """rfq_screen_rows: base rows and lengths (qualities and names are not looked at) against an index of screen_build.  A unit is a row, or with pairs the rows
+        2u / 2u + 1; d_in: n_rows bytes, non-zero = the row is a candidate (judge_rows' d_keep; None: all).  d_kmers / d_hits: n_rows uint32 - the row's valid
+        k-mers and those in the set -, d_keep: n_rows bytes - what dedup_rows takes as d_in and select_rows as d_keep; an output that is None is not produced.  A unit
+        matches with H >= max(min_hits, 1) and 100 * H >= min_pct * K over its rows; it is kept when it does not match (keep_matched: when it does).  mode: the C
+        constant as it stands, for the tests of the refusal.  Returns ScreenRowsResult (n_units, n_candidates, n_matched, n_kept, kmers, hits, bases_in,
+        bases_kept)."""
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
+        if base_mode is not None:
+            rows.base_mode = base_mode
+        a = A.ScreenRowsArgs(1 if pairs else 0, mode if mode is not None else (A.SCREEN_KEEP_MATCHED if keep_matched else A.SCREEN_DROP_MATCHED), min_hits, min_pct,
+                             d_index, index_bytes, d_in, d_kmers, d_hits, d_keep)
+        r = A.ScreenRowsResult()
+        self._check(self._L.rfq_screen_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
     # --- --compare on the device: first offset at which two device texts differ (n when identical)

@@ -103,6 +103,8 @@ struct RfqOpts {
     bool merge_general = false;       // RFQ_MERGE=general  rfq_merge_rows: the lane-per-byte kernel with the rule as plain branches (default: a lane per 16-byte group, the rule as byte masks in registers)
     bool dedup_collide = false;       // RFQ_DEDUP=collide  rfq_dedup_rows: four bits of the fingerprint for the start slot and the tag - long probe chains, every tag hit a byte compare (default: all 64)
     bool profile_general = false;     // RFQ_PROFILE=general  rfq_profile_rows: the any-length kernel (a wave per row, tables in device memory) for every row length, in tiles of 64 positions (default: rows of up to 1024 bytes into tables in LDS)
+    // RFQ_SCREEN=general|collide  general, rfq_screen_rows: the table in device memory and the any-length kernel (a wave per unit) for every row length (default: rows of up to 1024 bytes held whole, a table of up to 16384 slots in LDS); collide, rfq_screen_build: four bits of the hash for the start slot, recorded in the index - long probe chains (default: a 64-bit multiplicative hash)
+    enum Screen { SCREEN_DEFAULT, SCREEN_GENERAL, SCREEN_COLLIDE } screen = SCREEN_DEFAULT;
     bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)
 };
 struct rfq_ctx {

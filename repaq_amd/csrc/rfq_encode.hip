@@ -1778,3 +1778,114 @@ extern "C" int rfq_profile_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_p
     res->max_len = hs.c[14];
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- references -> an index of canonical k-mers, rows against it -> k-mers, hits, a keep byte: rfq_screen_build, rfq_screen_rows of include/rfq_hip.h
+// The index is the CALLER's (enc/rows_screen.h has its layout): nothing of a screen outlives the call.  The build is two small kernels and one read-back; the rows
+// call reads the index's header back, then one kernel (by row length; with the table in LDS where it fits) and one read-back, like rfq_judge_rows.
+static uint64_t screen_slots(uint64_t refs_len) { uint64_t s = 1024; while (s < 2 * refs_len) s <<= 1; return s; }
+extern "C" int rfq_screen_build(rfq_ctx* ctx, const rfq_screen_build_args* a, rfq_screen_build_result* res) {
+    if (!ctx || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    if (a->k < SC_K_MIN || a->k > SC_K_MAX) return rfq_fail(ctx, RFQ_E_ARG, "k must be %u .. %u (got %u)", SC_K_MIN, SC_K_MAX, a->k);
+    if (a->n_refs && (!a->d_refs || !a->d_ref_off)) return rfq_fail(ctx, RFQ_E_ARG, "null d_refs / d_ref_off with references");
+    if ((uintptr_t)a->d_ref_off & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_ref_off must be 8-byte aligned");
+    if ((uintptr_t)a->d_index & 15u) return rfq_fail(ctx, RFQ_E_ARG, "d_index must be 16-byte aligned");
+    const uint64_t refs_len = a->n_refs ? a->refs_len : 0;
+    if (refs_len >= (1ull << 38) || a->n_refs >= (1ull << 38)) return rfq_fail(ctx, RFQ_E_ARG, "too many reference bytes or references for one index (%llu, %llu)", (unsigned long long)refs_len, (unsigned long long)a->n_refs);
+    const uint64_t slots = screen_slots(refs_len), need = sizeof(ScreenHdr) + 8ull * slots;
+    res->n_refs = a->n_refs; res->slots = slots; res->index_bytes = need;
+    if (a->size_only) return RFQ_OK;
+    if (!a->d_index) return rfq_fail(ctx, RFQ_E_ARG, "null d_index");
+    if (a->index_cap < need) {
+        memset(res, 0, sizeof *res);
+        return rfq_fail(ctx, RFQ_E_NOSPACE, "index buffer too small: need %llu bytes (%llu slots)", (unsigned long long)need, (unsigned long long)slots);
+    }
+    int rc;
+    {
+        const Span outs[] = { { a->d_index, need, "d_index" } }; const Span ins[] = { { a->d_refs, refs_len, "d_refs" }, { a->d_ref_off, (a->n_refs + 1) * 8ull, "d_ref_off" } };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+    }
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    ScreenBuildIn bi; memset(&bi, 0, sizeof bi);
+    bi.blob = a->d_refs; bi.off = (const unsigned long long*)a->d_ref_off; bi.refs_len = refs_len; bi.n_refs = a->n_refs; bi.k = a->k; bi.collide = ctx->opt.screen == RfqOpts::SCREEN_COLLIDE ? 1u : 0u;
+    bi.hdr = (ScreenHdr*)a->d_index; bi.tab = (unsigned long long*)((uint8_t*)a->d_index + sizeof(ScreenHdr)); bi.S = slots;
+    ctx->timer.begin("screen:build", S);
+    HIPCHK(ctx, hipMemsetAsync(a->d_index, 0, (size_t)need, S));
+    ScreenBuildStat* dst = nullptr; ScreenBuildStat hs;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if (a->n_refs) { hipLaunchKernelGGL(k_screen_refs, dim3((uint32_t)((a->n_refs + 255u) / 256u)), dim3(256), 0, S, bi, dst); KCHK(ctx, "k_screen_refs"); }
+    hipLaunchKernelGGL(k_screen_build, dim3((uint32_t)std::max<uint64_t>(1, (refs_len + 255u) / 256u)), dim3(256), 0, S, bi, dst);
+    KCHK(ctx, "k_screen_build");
+    ctx->timer.end(S);
+    if ((rc = rows_sums_back(ctx, S, dst, &hs, 0u)) != RFQ_OK) return rc;
+    if (hs.err & SC_ERR_REFS) {
+        const unsigned long long br = hs.bad_row;
+        memset(res, 0, sizeof *res);
+        return rfq_fail(ctx, RFQ_E_ARG, "the reference offsets decrease or end past refs_len = %llu (first such reference: %llu)", (unsigned long long)refs_len, br);
+    }
+    res->ref_bases = hs.c[0]; res->n_positions = hs.c[1]; res->n_kmers = hs.c[2];
+    return RFQ_OK;
+}
+extern "C" int rfq_screen_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_screen_rows_args* a, rfq_screen_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows;
+    int rc;
+    if ((rc = rows_pairs_arg(ctx, a->pairs, n)) != RFQ_OK) return rc;
+    if (a->mode != RFQ_SCREEN_DROP_MATCHED && a->mode != RFQ_SCREEN_KEEP_MATCHED) return rfq_fail(ctx, RFQ_E_ARG, "unknown mode %d", a->mode);
+    if (a->min_pct > 100u) return rfq_fail(ctx, RFQ_E_ARG, "min_pct must be 0 .. 100 (got %u)", a->min_pct);
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
+    if (n && (!in->d_lens || !in->d_bases)) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens / d_bases");
+    if (!a->d_index || ((uintptr_t)a->d_index & 15u) || a->index_bytes < sizeof(ScreenHdr)) return rfq_fail(ctx, RFQ_E_ARG, "d_index must be an index of rfq_screen_build: not NULL, 16-byte aligned, at least %zu bytes", sizeof(ScreenHdr));
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_kmers | (uintptr_t)a->d_hits) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_kmers and d_hits must be 4-byte aligned");
+    const uint64_t units = a->pairs ? n / 2 : n;
+    const Span outs[] = { { a->d_kmers, n * 4ull, "d_kmers" }, { a->d_hits, n * 4ull, "d_hits" }, { a->d_keep, n, "d_keep" } };
+    {
+        Span ins[7]; rows_src_spans(in, false, ins);
+        ins[1].p = nullptr;                                                  // (the scores are not read)
+        ins[5] = { a->d_in, n, "d_in" }; ins[6] = { a->d_index, a->index_bytes, "d_index" };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+    }
+    if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    ScreenHdr hd; memset(&hd, 0, sizeof hd);
+    HIPCHK(ctx, ctx->fetch(&hd, a->d_index, sizeof hd, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    if (hd.magic != SC_MAGIC || hd.version != SC_VERSION) return rfq_fail(ctx, RFQ_E_DATA, "d_index does not begin with the header rfq_screen_build writes");
+    if (hd.k < SC_K_MIN || hd.k > SC_K_MAX) return rfq_fail(ctx, RFQ_E_DATA, "the index's k is %u: not in %u .. %u", hd.k, SC_K_MIN, SC_K_MAX);
+    if (hd.S == 0 || (hd.S & (hd.S - 1)) || hd.S > (a->index_bytes - sizeof(ScreenHdr)) / 8u)
+        return rfq_fail(ctx, RFQ_E_DATA, "the index's slot count %llu is no power of two or exceeds index_bytes = %zu", (unsigned long long)hd.S, a->index_bytes);
+    res->n_units = units;
+    if (!n) return RFQ_OK;
+    ScreenIn si; memset(&si, 0, sizeof si);
+    si.b = in->d_bases; si.lens = in->d_lens; si.cand = a->d_in; si.total = n * in->row_len; si.n_rows = (uint32_t)n; si.n_units = (uint32_t)units; si.row_len = in->row_len;
+    si.vec_in = rows_vec(in->row_len, in->d_bases, nullptr);
+    si.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u; si.pairs = a->pairs ? 1u : 0u; si.keep_matched = a->mode == RFQ_SCREEN_KEEP_MATCHED ? 1u : 0u;
+    si.min_hits = a->min_hits; si.min_pct = a->min_pct; si.k = hd.k; si.collide = hd.flags & SC_FLAG_COLLIDE ? 1u : 0u;
+    si.tab = (const unsigned long long*)((const uint8_t*)a->d_index + sizeof(ScreenHdr)); si.S = hd.S;
+    si.kmers = a->d_kmers; si.hits = a->d_hits; si.keep = a->d_keep;
+    const bool general = ctx->opt.screen == RfqOpts::SCREEN_GENERAL, lds = !general && in->row_len <= 1024u && hd.S >= 2u && hd.S <= SC_LDS_SLOTS;
+    ctx->timer.begin("screen:rows", S);
+    ScreenStat* dst = nullptr; ScreenStat hs;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if (lds) {
+        // a workgroup pays for its copy of the slots once: at most two workgroups per compute unit (one where the slots take more than 64 KiB), the steps follow
+        const uint32_t R = (uint32_t)SC_LDS_NT / (in->row_len <= 256u ? 16u : 64u), gcap = std::max(1u, ctx->n_cu * (hd.S * 8u <= 65536u ? 2u : 1u));
+        const uint64_t steps = std::max<uint64_t>((units + (uint64_t)R * gcap - 1u) / ((uint64_t)R * gcap), 1u);
+        si.steps = (uint32_t)steps;
+        const auto k = in->row_len <= 256u ? k_screen_rows<16, SC_LDS_NT, true> : k_screen_rows<64, SC_LDS_NT, true>;
+        hipLaunchKernelGGL(k, dim3((uint32_t)((units + R * steps - 1u) / (R * steps))), dim3(SC_LDS_NT), (size_t)hd.S * 8u, S, si, dst);
+    } else {
+        si.steps = SC_ITER;
+        rows_launch_by_len(S, general, in->row_len, units, SC_ITER, k_screen_rows<16, 256, false>, k_screen_rows<64, 256, false>, k_screen_rows_long, si, dst);
+    }
+    KCHK(ctx, "k_screen_rows");
+    ctx->timer.end(S);
+    if ((rc = rows_sums_back(ctx, S, dst, &hs, in->row_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    res->n_candidates = hs.c[0]; res->n_matched = hs.c[1]; res->n_kept = hs.c[2]; res->kmers = hs.c[3]; res->hits = hs.c[4]; res->bases_in = hs.c[5]; res->bases_kept = hs.c[6];
+    return RFQ_OK;
+}

@@ -65,6 +65,13 @@ distribution, the distributions of length, mean score and GC content, read 1 and
     before = profile_rows(codec, t, pairs=True)
     after = profile_rows(codec, t, pairs=True, keep=d["keep"], start=j["start"], length=j["length"])          # after["base_cnt"]: [2, cycles, 5] int64 ...
 
+judge -> screen -> dedup -> select: rfq_screen_rows asks what a read IS - it counts, per read, the k-mers that occur in a set of reference sequences (the PhiX
+spike-in, rRNA, a host, a bait set) and leaves the keep mask the next step takes; the set is built once, on the GPU, and is the caller's tensor:
+
+    phix = screen_index(codec, [open("phix.fa").read().split("\n", 1)[1].replace("\n", "")], k=25)
+    c = screen_rows(codec, dict(t, lens=j["length"]), phix, pairs=True, keep=j["keep"])                  # c["summary"]["n_matched"]: the spike-in's pairs
+    d = dedup_rows(codec, dict(t, lens=j["length"]), pairs=True, keep=c["keep"])
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -357,6 +364,66 @@ def profile_rows(codec, t, pairs=False, codes=True, keep=None, start=None, lengt
         codec.set_stream(None)
     out["summary"] = dict({f: [int(getattr(r, f)[m]) for m in range(M)] for f in PROFILE_FIELDS}, n_rows=int(r.n_rows), max_len=int(r.max_len))
     return out
+
+
+SCREEN_BUILD_FIELDS = ("n_refs", "ref_bases", "n_positions", "n_kmers", "slots", "index_bytes")
+SCREEN_FIELDS = ("n_units", "n_candidates", "n_matched", "n_kept", "kmers", "hits", "bases_in", "bases_kept")
+
+
+def screen_index(codec, refs, k=25):
+    """Reference sequences -> the index screen_rows takes (rfq_screen_build): the exact set of the canonical k-mers (k in 4 .. 31) of every reference; a k-mer lies
+    inside ONE reference and is all ACGT, either case.  refs: a list of bytes / str (put on the codec's device), or a (blob, offsets) pair of device tensors - uint8
+    and [n_refs + 1] int64, the layout of pack_names.  -> {"index": uint8 tensor (private bytes: which slot a k-mer lands in may differ from run to run, the set does
+    not), "k", "n_kmers" (distinct values), "slots", "summary": dict of the call's counts}.  One index per reference set; for per-reference counts build one index
+    per reference.  A size query and one call, both ordered with torch's current stream; the context goes back to its own stream afterwards."""
+    if isinstance(refs, tuple):
+        blob, off = refs
+    else:
+        blob, off = pack_names([r.encode() if isinstance(r, str) else bytes(r) for r in refs], torch.device("cuda", codec.device))
+    assert blob.dtype == torch.uint8 and blob.is_cuda and blob.is_contiguous(), "refs: a contiguous uint8 blob on the GPU"
+    assert off.dtype in (torch.int64, torch.uint64) and off.is_contiguous() and off.numel() >= 1 and off.device == blob.device, "offsets: [n_refs + 1] int64 on the blob's device"
+    n_refs = off.numel() - 1
+    # (references of no bytes at all are still references: the call wants a pointer for them, and an empty tensor has none)
+    at = blob if blob.numel() else torch.zeros((1,), dtype=torch.uint8, device=blob.device)
+    src = (at.data_ptr(), blob.numel(), off.data_ptr(), n_refs)
+    codec.set_stream(torch.cuda.current_stream(blob.device).cuda_stream)
+    try:
+        q = codec.screen_build(*src, k=k, size_only=True)
+        index = torch.empty((int(q.index_bytes),), dtype=torch.uint8, device=blob.device)
+        r = codec.screen_build(*src, k=k, d_index=index.data_ptr(), index_cap=index.numel())
+    finally:
+        codec.set_stream(None)
+    return {"index": index, "k": k, "n_kmers": int(r.n_kmers), "slots": int(r.slots), "summary": {f: int(getattr(r, f)) for f in SCREEN_BUILD_FIELDS}}
+
+
+def screen_rows(codec, t, index, pairs=False, codes=True, keep=None, min_hits=1, min_pct=0, keep_matched=False):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "lens"; codes: what they were made with) against screen_index's index (the dict, or its "index"
+    tensor) -> {"keep": [n] uint8 - what dedup_rows takes as keep and select_rows as keep -, "hits": [n] int32 (the row's k-mers whose canonical value is in the
+    set), "kmers": [n] int32 (its valid k-mers), "summary": dict of the batch's counts} (rfq_screen_rows).  A unit is a row, with pairs the rows 2k / 2k + 1; with H
+    and K its hits and k-mers over its rows it matches when H >= max(min_hits, 1) and 100 * H >= min_pct * K.  A unit that matches is dropped - a contaminant -,
+    with keep_matched it is the one that stays - a bait.  keep: [n] bool / uint8 - only units all of whose rows are non-zero there are looked at (judge_rows'
+    "keep"); the others get 0 / 0 / 0.  "lens" may be what trim_adapters or judge_rows left.  One call, ordered with torch's current stream; the context goes back
+    to its own stream afterwards."""
+    bases, lens = t["bases"], t["lens"]
+    index = index["index"] if isinstance(index, dict) else index
+    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    dev = bases.device
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
+    assert index.dtype == torch.uint8 and index.is_contiguous() and index.device == dev, "index: screen_index's uint8 tensor on the rows' device"
+    assert not pairs or n % 2 == 0, "rows in pairs"
+    if keep is not None:
+        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
+    out_keep = torch.empty((n,), dtype=torch.uint8, device=dev)
+    hits = torch.empty((n,), dtype=torch.int32, device=dev); kmers = torch.empty((n,), dtype=torch.int32, device=dev)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        r = codec.screen_rows(n, L, bases.data_ptr(), lens.data_ptr(), index.data_ptr(), index.numel(), codes=codes, pairs=pairs, min_hits=min_hits, min_pct=min_pct,
+                              keep_matched=keep_matched, d_in=keep.data_ptr() if keep is not None else None, d_kmers=kmers.data_ptr(), d_hits=hits.data_ptr(),
+                              d_keep=out_keep.data_ptr())
+    finally:
+        codec.set_stream(None)
+    return {"keep": out_keep, "hits": hits, "kmers": kmers, "summary": {f: int(getattr(r, f)) for f in SCREEN_FIELDS}}
 
 
 def filter_rows(codec, t, pairs=False, codes=True, min_len=1, row_len=None, pad=255, **criteria):
