@@ -679,6 +679,87 @@ typedef struct {
 } rfq_screen_rows_result;
 RFQ_API int rfq_screen_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_screen_rows_args* args, rfq_screen_rows_result* res);
 
+/* Counting canonical k-mers, beside rfq_screen_rows: WHICH k-mers do the reads hold, and how often - the k-mer section of a QC report, the k-mer spectrum (genome
+ * size, error rate, the valley between error k-mers and real ones), screening by abundance.  rfq_kmers_init formats a table in a CALLER-owned device buffer,
+ * rfq_kmers_rows adds the k-mers of rows to it, rfq_kmers_read takes out its spectrum, its (value, count) list and a screen index of selected values.  The table is the
+ * caller's and survives between calls: several rfq_kmers_rows calls on one table give the table of the concatenated rows, in whatever order the calls came - the
+ * one result of the rows family that adds up across the batches of a file.  No float anywhere; the same calls give the same outputs.
+ * The k-mer rules are rfq_screen_*'s, word for word: k is 4 .. 31; base classes are rfq_adapter_rows'; a k-mer is VALID when all its k positions are of class 0 .. 3;
+ * its canonical value is the smaller of its forward and reverse-complement values; a k-mer that is its own reverse complement counts once per occurrence.
+ * The table, 16-byte aligned: a 64-byte header (a magic of its own, version, k, S, n_kmers, total, flags), S slots of 64 bits - 0 = empty, else bit 63 | canonical
+ * value: the screen index's slot format and linear probing, its hash taken of the value mixed once more (the k-mers of reads share suffixes - poly-A and poly-G
+ * tails, repeats - as reference k-mers do not) - and S counts of 64 bits, count[s] beside slot[s].  WHICH slot a value lands in may differ from run
+ * to run: the table BYTES are private; the set of (value, count) pairs, the header's counts and every output of the calls below are the same every time.
+ * rfq_kmers_init.  slots is what the caller asks for; S is the power of two >= max(1024, slots), table_bytes = 64 + 16 * S.  SIZING RULE: slots >= 2 x the distinct
+ * values expected (at most 4^k / 2 + 2^k / 2 values exist at all: 512 for k = 5).  size_only = 1 reports slots (S) and table_bytes and writes nothing; otherwise the
+ * header is written and the rest zeroed.  RFQ_E_ARG: k outside 4 .. 31, slots > 2^36, a misaligned d_table, a NULL d_table on a call that writes, more than 65536 slots
+ * under RFQ_KMERS=collide.  RFQ_E_NOSPACE, nothing written, the message says what is needed: table_cap too small.  RFQ_KMERS=collide at the time of the call is
+ * recorded in the header's flags: later calls agree with it whatever the switch says then.
+ * rfq_kmers_rows adds 1 to count[value] for every valid k-mer of every COUNTED row.  A row is counted when d_in is NULL or d_in[i] != 0 (rfq_profile_rows' rule: no
+ * pairs here, the pair rule is already in the mask).  The window is [0, rows->d_lens[i]) - what rfq_adapter_rows or the judge cut comes in there.  Names and quality
+ * rows are not read.  d_kmers [n_rows] uint32, optional: the row's valid k-mers, 0 for a row that is not counted - for the same rows and mask rfq_screen_rows' d_kmers
+ * byte for byte.  Result: n_rows, n_counted, bases_in (the sum of l over the counted rows), added (the occurrences this call added), n_new (the values this call
+ * claimed), n_kmers and total (the table's distinct values and sum of counts after the call, also written to the header), lost.
+ * A table that is too full: a probe walk takes at most min(S, W) steps, W = 512 (S under the recorded collide flag).  A k-mer whose walk ends without an empty slot
+ * or its own value is LOST.  With lost > 0 the call returns RFQ_E_NOSPACE (the message gives lost, n_kmers and S; the result fields stay filled in) and the header
+ * gets an INCOMPLETE flag: every later rfq_kmers_rows or rfq_kmers_read on that table is RFQ_E_DATA until rfq_kmers_init formats it again.  A call is therefore
+ * either exact or refused, never silently short; with slots >= 2 x the distinct values no walk comes near W.
+ * RFQ_E_ARG, judged on the host: a bad base_mode; row_len == 0, a NULL d_lens or d_bases with rows; a NULL or misaligned (16 bytes) d_table, table_bytes < 64; a
+ * d_lens / d_kmers that is not 4-byte aligned; d_kmers overlapping an input (the table and d_in are inputs) or the table overlapping an input; n_rows >= 2^31.
+ * RFQ_E_DATA, after one read-back of the header: a magic or version that is not rfq_kmers_init's (a screen index handed in as a table is refused that way; a table
+ * handed to rfq_screen_rows is refused by that call's magic check), k out of range, S no power of two or 64 + 16 * S > table_bytes, the INCOMPLETE flag.  RFQ_E_ARG,
+ * judged on the device, the message names the first such row - ALL rows are judged, counted or not: lens[i] < 0 or > row_len; the table then holds the k-mers of the
+ * other counted rows (such a row adds none) and its header says so.  After any refusal the context stays usable.
+ * Every slot number is masked to S and every walk bounded: a table whose bytes were written over cannot hang a call or make it read or write outside
+ * [d_table, d_table + table_bytes).  ONE table takes ONE call at a time: two contexts (or two streams) counting into one table at once is NOT offered.
+ * rfq_kmers_read.  An entry is SELECTED when max(min_count, 1) <= count and (max_count == 0 or count <= max_count).  Outputs; each may be NULL and is then not
+ * produced: d_hist [hist_len] uint64, hist_len <= 65536 - zeroed first; bin c - 1 = the number of distinct values with count c over ALL entries, the last bin collects
+ * every larger count (the family's convention): the k-mer spectrum; d_values / d_counts [list_cap] uint64 each - the selected entries, the value without bit 63 and
+ * its count, at the same position of both; their order is unspecified, the set is the same every time; d_index / index_cap - a screen index of the selected values,
+ * S_idx the power of two >= max(1024, 2 * n_selected), the header what rfq_screen_build writes (its flags by RFQ_SCREEN at the time of the call), n_kmers =
+ * n_selected: rfq_screen_rows takes it unchanged - the bridge to screening by abundance.  size_only = 1 fills the result and writes nothing.  Result: k, slots,
+ * n_kmers, total, max_count (the largest count in the table), n_selected, selected_total, index_slots, index_bytes.  An empty table reads as empty, its index is the
+ * empty set.  RFQ_E_NOSPACE, nothing written, the message says what is needed: list_cap < n_selected with a list, index_cap < index_bytes with d_index.  RFQ_E_ARG:
+ * the table arguments as above; hist_len > 65536 or 0 with d_hist; d_hist / d_values / d_counts not 8-byte, d_index not 16-byte aligned; an output that overlaps the
+ * table or another output.  RFQ_E_DATA: the header checks of rfq_kmers_rows; slots that do not hold what the header counts.
+ * Rows of up to 1024 bytes are held whole; a workgroup combines its k-mers in a table in LDS and flushes it once (a hot value - poly-A, an adapter, every value at k =
+ * 5 - costs one 64-bit atomic per workgroup, not one per occurrence).  RFQ_KMERS=direct leaves the LDS stage out, RFQ_KMERS=general takes the wave-per-row kernel
+ * for every row length; every value gives the same table contents and outputs.  Synchronous on the context's stream; stage times through rfq_last_timings
+ * (kmers:init, kmers:rows, kmers:read).
+ * NOT offered: per-cycle k-mer tables; k > 31; counts per reference; a top-N on the device (sort d_counts); two writers on one table. */
+typedef struct {
+    uint32_t k;                           /* 4 .. 31                                                                    */
+    int32_t  size_only;                   /* 1: only slots and table_bytes are reported, nothing is written             */
+    uint64_t slots;                       /* asked for: >= 2 x the distinct values expected                             */
+    void* d_table; size_t table_cap;      /* the caller's buffer, 16-byte aligned                                       */
+} rfq_kmers_init_args;
+typedef struct {
+    uint64_t slots, table_bytes;
+} rfq_kmers_init_result;
+RFQ_API int rfq_kmers_init(rfq_ctx* ctx, const rfq_kmers_init_args* args, rfq_kmers_init_result* res);
+typedef struct {
+    void* d_table; size_t table_bytes;    /* what rfq_kmers_init formatted                                              */
+    const uint8_t* d_in;                  /* [n_rows] bytes, non-zero = the row is counted; NULL = every row            */
+    uint32_t* d_kmers;                    /* [n_rows] or NULL                                                           */
+} rfq_kmers_rows_args;
+typedef struct {
+    uint64_t n_rows, n_counted, bases_in, added, n_new, n_kmers, total, lost;
+} rfq_kmers_rows_result;
+RFQ_API int rfq_kmers_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_kmers_rows_args* args, rfq_kmers_rows_result* res);
+typedef struct {
+    const void* d_table; size_t table_bytes;
+    uint64_t min_count, max_count;        /* selected: max(min_count, 1) <= count and (max_count == 0 or count <= max_count) */
+    int32_t  size_only;                   /* 1: the result is filled, nothing is written                                */
+    uint32_t hist_len;                    /* bins of d_hist, <= 65536                                                   */
+    uint64_t* d_hist;                     /* [hist_len] or NULL                                                         */
+    uint64_t* d_values; uint64_t* d_counts; size_t list_cap;      /* [list_cap] each, or NULL                           */
+    void* d_index; size_t index_cap;      /* a screen index of the selected values, 16-byte aligned, or NULL            */
+} rfq_kmers_read_args;
+typedef struct {
+    uint64_t k, slots, n_kmers, total, max_count, n_selected, selected_total, index_slots, index_bytes;
+} rfq_kmers_read_result;
+RFQ_API int rfq_kmers_read(rfq_ctx* ctx, const rfq_kmers_read_args* args, rfq_kmers_read_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -712,7 +793,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general, RFQ_SCREEN=general|collide; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general, RFQ_SCREEN=general|collide, RFQ_KMERS=general|collide|direct; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

@@ -205,6 +205,35 @@ class ScreenRowsResult(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("n_units", "n_candidates", "n_matched", "n_kept", "kmers", "hits", "bases_in", "bases_kept")]
 
 
+KMERS_HEADER_BYTES = 64
+
+
+class KmersInitArgs(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("size_only", C.c_int32), ("slots", C.c_uint64), ("d_table", C.c_void_p), ("table_cap", C.c_size_t)]
+
+
+class KmersInitResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("slots", "table_bytes")]
+
+
+class KmersRowsArgs(C.Structure):
+    _fields_ = [("d_table", C.c_void_p), ("table_bytes", C.c_size_t), ("d_in", C.c_void_p), ("d_kmers", C.c_void_p)]
+
+
+class KmersRowsResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_rows", "n_counted", "bases_in", "added", "n_new", "n_kmers", "total", "lost")]
+
+
+class KmersReadArgs(C.Structure):
+    _fields_ = [("d_table", C.c_void_p), ("table_bytes", C.c_size_t), ("min_count", C.c_uint64), ("max_count", C.c_uint64), ("size_only", C.c_int32),
+                ("hist_len", C.c_uint32), ("d_hist", C.c_void_p), ("d_values", C.c_void_p), ("d_counts", C.c_void_p), ("list_cap", C.c_size_t),
+                ("d_index", C.c_void_p), ("index_cap", C.c_size_t)]
+
+
+class KmersReadResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("k", "slots", "n_kmers", "total", "max_count", "n_selected", "selected_total", "index_slots", "index_bytes")]
+
+
 _libs = {}
 
 
@@ -246,6 +275,9 @@ def load(path=None):
     L.rfq_profile_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(ProfileRowsArgs), C.POINTER(ProfileRowsResult)]
     L.rfq_screen_build.argtypes = [C.c_void_p, C.POINTER(ScreenBuildArgs), C.POINTER(ScreenBuildResult)]
     L.rfq_screen_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(ScreenRowsArgs), C.POINTER(ScreenRowsResult)]
+    L.rfq_kmers_init.argtypes = [C.c_void_p, C.POINTER(KmersInitArgs), C.POINTER(KmersInitResult)]
+    L.rfq_kmers_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(KmersRowsArgs), C.POINTER(KmersRowsResult)]
+    L.rfq_kmers_read.argtypes = [C.c_void_p, C.POINTER(KmersReadArgs), C.POINTER(KmersReadResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -269,6 +301,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_screen_build", "rfq_screen_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_screen_build", "rfq_screen_rows", "rfq_kmers_init", "rfq_kmers_rows", "rfq_kmers_read", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

@@ -438,6 +438,41 @@ class RfqCodec:
         self._check(self._L.rfq_screen_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
+    # --- which k-mers the reads hold, and how often: a caller-owned table that adds up across calls, and its reader (rfq_kmers_init, rfq_kmers_rows, rfq_kmers_read)
+    def kmers_init(self, k=25, slots=0, d_table=None, table_cap=0, size_only=False):
+        """rfq_kmers_init: formats an empty table of canonical k-mers (k in 4 .. 31) with counts in the caller's buffer d_table (16-byte aligned, table_cap bytes):
+        S = the power of two >= max(1024, slots) slots, 64 + 16 * S bytes; ask for slots >= 2 x the distinct values expected.  size_only: nothing is written, the
+        result says how large the buffer has to be.  Returns KmersInitResult (slots, table_bytes)."""
+        a = A.KmersInitArgs(k, 1 if size_only else 0, slots, d_table, table_cap)
+        r = A.KmersInitResult()
+        self._check(self._L.rfq_kmers_init(self._h, C.byref(a), C.byref(r)))
+        return r
+
+    def kmers_rows(self, n_rows, row_len, d_bases, d_lens, d_table, table_bytes, codes=False, d_in=None, d_kmers=None, base_mode=None):
+        """rfq_kmers_rows: adds 1 to the count of the canonical value of every valid k-mer of every counted row (qualities and names are not looked at) in a table of
+        kmers_init; calls on one table add up.  d_in: n_rows bytes, non-zero = the row is counted (judge_rows' d_keep; None: all).  d_kmers: n_rows uint32 - the
+        row's valid k-mers, what screen_rows' d_kmers holds - or None.  A table that is too full refuses the call (RFQ_E_NOSPACE) and stays refused until it is
+        formatted again.  Returns KmersRowsResult (n_rows, n_counted, bases_in, added, n_new, n_kmers, total, lost)."""
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
+        if base_mode is not None:
+            rows.base_mode = base_mode
+        a = A.KmersRowsArgs(d_table, table_bytes, d_in, d_kmers)
+        r = A.KmersRowsResult()
+        self._check(self._L.rfq_kmers_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
+    def kmers_read(self, d_table, table_bytes, min_count=1, max_count=0, size_only=False, hist_len=0, d_hist=None, d_values=None, d_counts=None, list_cap=0,
+                   d_index=None, index_cap=0):
+        """rfq_kmers_read: what a table of kmers_init / kmers_rows holds.  An entry is selected when max(min_count, 1) <= count and (max_count == 0 or count <=
+        max_count).  d_hist: hist_len uint64, bin c - 1 = the distinct values with count c over all entries, the last bin every larger count (the k-mer spectrum);
+        d_values / d_counts: list_cap uint64 each, the selected entries in an unspecified order; d_index (16-byte aligned, index_cap bytes): a screen index of the
+        selected values, which screen_rows takes; an output that is None is not produced.  size_only: nothing is written.  Returns KmersReadResult (k, slots,
+        n_kmers, total, max_count, n_selected, selected_total, index_slots, index_bytes)."""
+        a = A.KmersReadArgs(d_table, table_bytes, min_count, max_count, 1 if size_only else 0, hist_len, d_hist, d_values, d_counts, list_cap, d_index, index_cap)
+        r = A.KmersReadResult()
+        self._check(self._L.rfq_kmers_read(self._h, C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

@@ -105,6 +105,8 @@ struct RfqOpts {
     bool profile_general = false;     // RFQ_PROFILE=general  rfq_profile_rows: the any-length kernel (a wave per row, tables in device memory) for every row length, in tiles of 64 positions (default: rows of up to 1024 bytes into tables in LDS)
     // RFQ_SCREEN=general|collide  general, rfq_screen_rows: the table in device memory and the any-length kernel (a wave per unit) for every row length (default: rows of up to 1024 bytes held whole, a table of up to 16384 slots in LDS); collide, rfq_screen_build: four bits of the hash for the start slot, recorded in the index - long probe chains (default: a 64-bit multiplicative hash)
     enum Screen { SCREEN_DEFAULT, SCREEN_GENERAL, SCREEN_COLLIDE } screen = SCREEN_DEFAULT;
+    // RFQ_KMERS=general|collide|direct  general, rfq_kmers_rows: the any-length kernel (a wave per row) for every row length, adds straight to device memory; direct: the common kernels without the workgroup's LDS table (default: rows of up to 1024 bytes held whole, a workgroup combines in LDS and flushes once); collide, rfq_kmers_init: four bits of the hash for the start slot, recorded in the table - long probe chains, at most 65536 slots (default: a 64-bit multiplicative hash)
+    enum Kmers { KMERS_DEFAULT, KMERS_GENERAL, KMERS_COLLIDE, KMERS_DIRECT } kmers = KMERS_DEFAULT;
     bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)
 };
 struct rfq_ctx {

@@ -1889,3 +1889,169 @@ extern "C" int rfq_screen_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_sc
     res->n_candidates = hs.c[0]; res->n_matched = hs.c[1]; res->n_kept = hs.c[2]; res->kmers = hs.c[3]; res->hits = hs.c[4]; res->bases_in = hs.c[5]; res->bases_kept = hs.c[6];
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- rows -> a table of canonical k-mers with counts that adds up across calls, and its reader: rfq_kmers_init, rfq_kmers_rows, rfq_kmers_read of include/rfq_hip.h
+// The table is the CALLER's (enc/rows_kmers.h has its layout) and is the one thing of the rows family that outlives a call.  rfq_kmers_rows reads the header back, runs
+// one kernel (by row length and RFQ_KMERS) and a one-thread kernel that carries the call's sums into the header, then one read-back; rfq_kmers_read is a count pass,
+// a read-back - room is judged before anything is written - and a writing pass.
+static uint64_t kmers_pow2(uint64_t want) { uint64_t s = 1024; while (s < want) s <<= 1; return s; }
+extern "C" int rfq_kmers_init(rfq_ctx* ctx, const rfq_kmers_init_args* a, rfq_kmers_init_result* res) {
+    if (!ctx || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    if (a->k < SC_K_MIN || a->k > SC_K_MAX) return rfq_fail(ctx, RFQ_E_ARG, "k must be %u .. %u (got %u)", SC_K_MIN, SC_K_MAX, a->k);
+    if (a->slots > (1ull << 36)) return rfq_fail(ctx, RFQ_E_ARG, "slots is at most 2^36 (got %llu)", (unsigned long long)a->slots);
+    const bool collide = ctx->opt.kmers == RfqOpts::KMERS_COLLIDE;
+    const uint64_t S = kmers_pow2(a->slots), need = sizeof(KmersHdr) + 16ull * S;
+    if (collide && S > KM_COLLIDE_SLOTS) return rfq_fail(ctx, RFQ_E_ARG, "RFQ_KMERS=collide takes at most %u slots: its probe chains are as long as the table is full (got %llu)", KM_COLLIDE_SLOTS, (unsigned long long)S);
+    if ((uintptr_t)a->d_table & 15u) return rfq_fail(ctx, RFQ_E_ARG, "d_table must be 16-byte aligned");
+    res->slots = S; res->table_bytes = need;
+    if (a->size_only) return RFQ_OK;
+    if (!a->d_table) { memset(res, 0, sizeof *res); return rfq_fail(ctx, RFQ_E_ARG, "null d_table"); }
+    if (a->table_cap < need) {
+        memset(res, 0, sizeof *res);
+        return rfq_fail(ctx, RFQ_E_NOSPACE, "table buffer too small: need %llu bytes (%llu slots)", (unsigned long long)need, (unsigned long long)S);
+    }
+    hipStream_t St = ctx->stream; int rc;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    ctx->timer.begin("kmers:init", St);
+    HIPCHK(ctx, hipMemsetAsync(a->d_table, 0, (size_t)need, St));
+    hipLaunchKernelGGL(k_kmers_format, dim3(1), dim3(64), 0, St, (KmersHdr*)a->d_table, a->k, (unsigned long long)S, collide ? KM_FLAG_COLLIDE : 0u);
+    KCHK(ctx, "k_kmers_format");
+    ctx->timer.end(St);
+    HIPCHK(ctx, hipStreamSynchronize(St));
+    ctx->timer.collect();
+    return RFQ_OK;
+}
+// the table's header back on the host and judged: what rfq_kmers_rows and rfq_kmers_read do first (one read-back)
+static int kmers_header(rfq_ctx* ctx, hipStream_t S, const void* d_table, size_t table_bytes, KmersHdr* hd) {
+    memset(hd, 0, sizeof *hd);
+    HIPCHK(ctx, ctx->fetch(hd, d_table, sizeof *hd, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    if (hd->magic != KM_MAGIC || hd->version != KM_VERSION) return rfq_fail(ctx, RFQ_E_DATA, "d_table does not begin with the header rfq_kmers_init writes");
+    if (hd->k < SC_K_MIN || hd->k > SC_K_MAX) return rfq_fail(ctx, RFQ_E_DATA, "the table's k is %u: not in %u .. %u", hd->k, SC_K_MIN, SC_K_MAX);
+    if (hd->S == 0 || (hd->S & (hd->S - 1)) || hd->S > (table_bytes - sizeof(KmersHdr)) / 16u)
+        return rfq_fail(ctx, RFQ_E_DATA, "the table's slot count %llu is no power of two or exceeds table_bytes = %zu", (unsigned long long)hd->S, table_bytes);
+    if (hd->flags & KM_FLAG_INCOMPLETE)
+        return rfq_fail(ctx, RFQ_E_DATA, "the table is INCOMPLETE: an earlier rfq_kmers_rows lost k-mers in it (%llu values in %llu slots); format a larger one with rfq_kmers_init", (unsigned long long)hd->n_kmers, (unsigned long long)hd->S);
+    return RFQ_OK;
+}
+static int kmers_table_arg(rfq_ctx* ctx, const void* d_table, size_t table_bytes) {
+    if (!d_table || ((uintptr_t)d_table & 15u) || table_bytes < sizeof(KmersHdr)) return rfq_fail(ctx, RFQ_E_ARG, "d_table must be a table of rfq_kmers_init: not NULL, 16-byte aligned, at least %zu bytes", sizeof(KmersHdr));
+    return RFQ_OK;
+}
+extern "C" int rfq_kmers_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_kmers_rows_args* a, rfq_kmers_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows;
+    int rc;
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
+    if (n && (!in->d_lens || !in->d_bases)) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens / d_bases");
+    if ((rc = kmers_table_arg(ctx, a->d_table, a->table_bytes)) != RFQ_OK) return rc;
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_kmers) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens and d_kmers must be 4-byte aligned");
+    if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    {
+        Span ins[7]; rows_src_spans(in, false, ins);
+        ins[1].p = nullptr;                                                  // (the scores are not read)
+        ins[5] = { a->d_in, n, "d_in" }; ins[6] = { a->d_table, a->table_bytes, "d_table" };
+        const Span outs[] = { { a->d_kmers, n * 4ull, "d_kmers" } };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+        ins[6].p = nullptr;                                                  // (the table is written too: it lies on none of the call's inputs)
+        const Span tab[] = { { a->d_table, a->table_bytes, "d_table" } };
+        if ((rc = rows_apart(ctx, tab, ins, "")) != RFQ_OK) return rc;
+    }
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    KmersHdr hd;
+    if ((rc = kmers_header(ctx, S, a->d_table, a->table_bytes, &hd)) != RFQ_OK) return rc;
+    res->n_rows = n; res->n_kmers = hd.n_kmers; res->total = hd.total;
+    if (!n) return RFQ_OK;
+    KmersIn ki; memset(&ki, 0, sizeof ki);
+    ki.b = in->d_bases; ki.lens = in->d_lens; ki.cand = a->d_in; ki.total = n * in->row_len; ki.n_rows = (uint32_t)n; ki.row_len = in->row_len;
+    ki.vec_in = rows_vec(in->row_len, in->d_bases, nullptr); ki.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u;
+    ki.k = hd.k; ki.collide = hd.flags & KM_FLAG_COLLIDE ? 1u : 0u; ki.walk = (uint32_t)(ki.collide ? std::min<uint64_t>(hd.S, 0xFFFFFFFFull) : std::min<uint64_t>(hd.S, KM_WALK));
+    ki.tab = (unsigned long long*)((uint8_t*)a->d_table + sizeof(KmersHdr)); ki.cnt = ki.tab + hd.S; ki.S = hd.S; ki.kmers = a->d_kmers;
+    const bool general = ctx->opt.kmers == RfqOpts::KMERS_GENERAL, direct = ctx->opt.kmers == RfqOpts::KMERS_DIRECT;
+    // a workgroup pays for the flush of its LDS table once: KM_WG_PER_CU workgroups per compute unit, the steps follow (at least KM_ITER, the family's walk; RFQ_KMERS=direct keeps the same grid)
+    const uint32_t R = in->row_len <= 256u ? 16u : 4u; const uint64_t gcap = std::max<uint64_t>(1, (uint64_t)KM_WG_PER_CU * ctx->n_cu);
+    ki.steps = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + R * gcap - 1u) / (R * gcap), KM_ITER), KM_STEPS_MAX);
+    ctx->timer.begin("kmers:rows", S);
+    KmersStat* dst = nullptr; KmersStat hs;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if (direct) rows_launch_by_len(S, general, in->row_len, n, ki.steps, k_kmers_rows<16, false>, k_kmers_rows<64, false>, k_kmers_rows_long, ki, dst);
+    else rows_launch_by_len(S, general, in->row_len, n, ki.steps, k_kmers_rows<16, true>, k_kmers_rows<64, true>, k_kmers_rows_long, ki, dst);
+    KCHK(ctx, "k_kmers_rows");
+    hipLaunchKernelGGL(k_kmers_hdr, dim3(1), dim3(64), 0, S, (KmersHdr*)a->d_table, (const KmersStat*)dst);
+    KCHK(ctx, "k_kmers_hdr");
+    ctx->timer.end(S);
+    if ((rc = rows_sums_back(ctx, S, dst, &hs, in->row_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    res->n_counted = hs.c[0]; res->bases_in = hs.c[1]; res->added = hs.c[2]; res->n_new = hs.c[3]; res->lost = hs.c[4];
+    res->n_kmers = hd.n_kmers + hs.c[3]; res->total = hd.total + hs.c[2];
+    if (hs.c[4]) return rfq_fail(ctx, RFQ_E_NOSPACE, "the table is too full: %llu k-mers lost with %llu values in %llu slots; the table is now INCOMPLETE - format one of at least twice the distinct values expected",
+                                 (unsigned long long)hs.c[4], (unsigned long long)res->n_kmers, (unsigned long long)hd.S);
+    return RFQ_OK;
+}
+extern "C" int rfq_kmers_read(rfq_ctx* ctx, const rfq_kmers_read_args* a, rfq_kmers_read_result* res) {
+    if (!ctx || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    int rc;
+    if ((rc = kmers_table_arg(ctx, a->d_table, a->table_bytes)) != RFQ_OK) return rc;
+    if (a->hist_len > 65536u || (a->d_hist && a->hist_len == 0u)) return rfq_fail(ctx, RFQ_E_ARG, "hist_len must be 1 .. 65536 with d_hist, at most 65536 without (got %u)", a->hist_len);
+    if (((uintptr_t)a->d_hist | (uintptr_t)a->d_values | (uintptr_t)a->d_counts) & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_hist, d_values and d_counts must be 8-byte aligned");
+    if ((uintptr_t)a->d_index & 15u) return rfq_fail(ctx, RFQ_E_ARG, "d_index must be 16-byte aligned");
+    const bool write = !a->size_only, list = write && (a->d_values || a->d_counts);
+    if (write) {
+        // (what the call can write at most: the caps are judged against the table's contents below)
+        const Span outs[] = { { a->d_hist, a->hist_len * 8ull, "d_hist" }, { a->d_values, (unsigned long long)a->list_cap * 8ull, "d_values" }, { a->d_counts, (unsigned long long)a->list_cap * 8ull, "d_counts" },
+                              { a->d_index, a->index_cap, "d_index" } };
+        const Span ins[] = { { a->d_table, a->table_bytes, "d_table" } };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+        for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) for (size_t k = i + 1; k < sizeof outs / sizeof outs[0]; k++)
+            if (sel_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the output %s", outs[i].what, outs[k].what);
+    }
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    KmersHdr hd;
+    if ((rc = kmers_header(ctx, S, a->d_table, a->table_bytes, &hd)) != RFQ_OK) return rc;
+    KmersReadIn ri; memset(&ri, 0, sizeof ri);
+    ri.tab = (const unsigned long long*)((const uint8_t*)a->d_table + sizeof(KmersHdr)); ri.cnt = ri.tab + hd.S; ri.S = hd.S;
+    ri.min_count = std::max<unsigned long long>(a->min_count, 1ull); ri.max_count = a->max_count; ri.k = hd.k;
+    const uint32_t blocks = (uint32_t)((hd.S + 256ull * KM_READ_ITER - 1u) / (256ull * KM_READ_ITER));
+    ctx->timer.begin("kmers:read", S);
+    KmersReadStat* dst = nullptr; KmersReadStat hs;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    hipLaunchKernelGGL(k_kmers_count, dim3(blocks), dim3(256), 0, S, ri, dst);
+    KCHK(ctx, "k_kmers_count");
+    memset(&hs, 0, sizeof hs);
+    HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+    HIPCHK(ctx, ctx->fetch_sync(S));
+    if (hs.c[0] != hd.n_kmers || hs.c[1] != hd.total) {
+        ctx->timer.end(S); HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect();
+        return rfq_fail(ctx, RFQ_E_DATA, "the table's header counts %llu values and %llu occurrences, its slots hold %llu and %llu: it was written over",
+                        (unsigned long long)hd.n_kmers, (unsigned long long)hd.total, (unsigned long long)hs.c[0], (unsigned long long)hs.c[1]);
+    }
+    const uint64_t iS = kmers_pow2(2 * hs.c[2]), ibytes = sizeof(ScreenHdr) + 8ull * iS;
+    res->k = hd.k; res->slots = hd.S; res->n_kmers = hs.c[0]; res->total = hs.c[1]; res->n_selected = hs.c[2]; res->selected_total = hs.c[3]; res->max_count = hs.c[4];
+    res->index_slots = iS; res->index_bytes = ibytes;
+    const bool short_list = list && a->list_cap < hs.c[2], short_index = write && a->d_index && a->index_cap < ibytes;
+    if (!write || short_list || short_index || !(a->d_hist || list || a->d_index)) {
+        ctx->timer.end(S); HIPCHK(ctx, hipStreamSynchronize(S)); ctx->timer.collect();
+        if (write && (short_list || short_index))
+            return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need %llu list entries, %llu index bytes (%llu slots)", (unsigned long long)hs.c[2], (unsigned long long)ibytes, (unsigned long long)iS);
+        return RFQ_OK;
+    }
+    ri.hist = (unsigned long long*)a->d_hist; ri.hist_len = a->hist_len; ri.values = (unsigned long long*)a->d_values; ri.counts = (unsigned long long*)a->d_counts; ri.list_cap = a->list_cap;
+    if (a->d_index) {
+        ri.ihdr = (ScreenHdr*)a->d_index; ri.itab = (unsigned long long*)((uint8_t*)a->d_index + sizeof(ScreenHdr)); ri.iS = iS; ri.icollide = ctx->opt.screen == RfqOpts::SCREEN_COLLIDE ? 1u : 0u;
+        HIPCHK(ctx, hipMemsetAsync(a->d_index, 0, (size_t)ibytes, S));
+    }
+    if (a->d_hist) HIPCHK(ctx, hipMemsetAsync(a->d_hist, 0, (size_t)a->hist_len * 8u, S));
+    hipLaunchKernelGGL(k_kmers_write, dim3(blocks), dim3(256), 0, S, ri, dst);
+    KCHK(ctx, "k_kmers_write");
+    ctx->timer.end(S);
+    HIPCHK(ctx, hipStreamSynchronize(S));
+    ctx->timer.collect();
+    return RFQ_OK;
+}

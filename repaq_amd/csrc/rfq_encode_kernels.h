@@ -31,3 +31,4 @@
 #include "enc/rows_dedup.h"                   // rows -> a keep byte that leaves one unit of every class of identical units, class sizes + a summary (rfq_dedup_rows)
 #include "enc/rows_profile.h"                 // rows under a keep / start / length triple -> per-cycle base content, position x score, length / mean-quality / GC tables (rfq_profile_rows)
 #include "enc/rows_screen.h"                  // references -> an index of canonical k-mers; rows against it -> k-mers, hits and a keep byte per row + a summary (rfq_screen_build, rfq_screen_rows)
+#include "enc/rows_kmers.h"                   // rows -> a caller-owned table of canonical k-mers with counts that adds up across calls; the table -> spectrum, (value, count) list, a screen index (rfq_kmers_init, rfq_kmers_rows, rfq_kmers_read)

@@ -72,6 +72,14 @@ spike-in, rRNA, a host, a bait set) and leaves the keep mask the next step takes
     c = screen_rows(codec, dict(t, lens=j["length"]), phix, pairs=True, keep=j["keep"])                  # c["summary"]["n_matched"]: the spike-in's pairs
     d = dedup_rows(codec, dict(t, lens=j["length"]), pairs=True, keep=c["keep"])
 
+the k-mers themselves: rfq_kmers_rows counts WHICH k-mers the reads hold, and how often, into a table that is the caller's tensor and adds up across the batches of
+a file; its reader gives the spectrum, the (value, count) pairs and a screen index of the values in a count range - screening by abundance:
+
+    tab = kmer_table(codec, k=25, slots=1 << 28)                                                        # >= 2 x the distinct k-mers expected
+    count_kmers(codec, dict(t, lens=j["length"]), tab, keep=j["keep"])                                  # per batch, in any order
+    kc = kmer_counts(codec, tab, min_count=2, hist_len=256, index=True)                                 # kc["hist"]: the spectrum; kc["values"], kc["counts"]: sorted by value
+    c = screen_rows(codec, t, kc["index"], pairs=True, keep_matched=True, min_pct=50)                   # the pairs at least half made of k-mers seen twice
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -424,6 +432,83 @@ def screen_rows(codec, t, index, pairs=False, codes=True, keep=None, min_hits=1,
     finally:
         codec.set_stream(None)
     return {"keep": out_keep, "hits": hits, "kmers": kmers, "summary": {f: int(getattr(r, f)) for f in SCREEN_FIELDS}}
+
+
+KMERS_ROWS_FIELDS = ("n_rows", "n_counted", "bases_in", "added", "n_new", "n_kmers", "total", "lost")
+KMERS_READ_FIELDS = ("k", "slots", "n_kmers", "total", "max_count", "n_selected", "selected_total", "index_slots", "index_bytes")
+
+
+def kmer_table(codec, k=25, slots=1 << 20):
+    """An empty table of canonical k-mers (k in 4 .. 31) with counts, which count_kmers adds to and kmer_counts reads (rfq_kmers_init) -> {"table": uint8 tensor on
+    the codec's device (private bytes: which slot a k-mer lands in may differ from run to run, the counts do not), "k", "slots"}.  slots: at least twice the
+    distinct values expected - the power of two >= max(1024, slots) is taken, 16 bytes a slot; a table that turns out too small refuses the count and has to be
+    made again.  The table outlives the calls: count the batches of a file into one.  A size query and one call, both ordered with torch's current stream; the
+    context goes back to its own stream afterwards."""
+    dev = torch.device("cuda", codec.device)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        q = codec.kmers_init(k=k, slots=slots, size_only=True)
+        table = torch.empty((int(q.table_bytes),), dtype=torch.uint8, device=dev)
+        r = codec.kmers_init(k=k, slots=slots, d_table=table.data_ptr(), table_cap=table.numel())
+    finally:
+        codec.set_stream(None)
+    return {"table": table, "k": k, "slots": int(r.slots)}
+
+
+def count_kmers(codec, t, table, codes=True, keep=None):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "lens"; codes: what they were made with) into kmer_table's table (the dict, or its "table"
+    tensor): 1 is added to the count of the canonical value of every valid k-mer of every counted row (rfq_kmers_rows) -> {"kmers": [n] int32 (the row's valid
+    k-mers, what screen_rows' "kmers" holds; 0 for a row that is not counted), "summary": dict of the call's counts - added, n_new, and the table's n_kmers and
+    total after the call}.  keep: [n] bool / uint8 - only rows that are non-zero there are counted (judge_rows' "keep"; rows, not pairs).  "lens" may be what
+    trim_adapters or judge_rows left.  Calls on one table add up, in any order; ONE call at a time on a table.  One call, ordered with torch's current stream; the
+    context goes back to its own stream afterwards."""
+    bases, lens = t["bases"], t["lens"]
+    table = table["table"] if isinstance(table, dict) else table
+    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    dev = bases.device
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
+    assert table.dtype == torch.uint8 and table.is_contiguous() and table.device == dev, "table: kmer_table's uint8 tensor on the rows' device"
+    if keep is not None:
+        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
+    kmers = torch.empty((n,), dtype=torch.int32, device=dev)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        r = codec.kmers_rows(n, L, bases.data_ptr(), lens.data_ptr(), table.data_ptr(), table.numel(), codes=codes, d_in=keep.data_ptr() if keep is not None else None,
+                             d_kmers=kmers.data_ptr())
+    finally:
+        codec.set_stream(None)
+    return {"kmers": kmers, "summary": {f: int(getattr(r, f)) for f in KMERS_ROWS_FIELDS}}
+
+
+def kmer_counts(codec, table, min_count=1, max_count=0, hist_len=0, index=False):
+    """What kmer_table's table holds (rfq_kmers_read) -> {"values": [m] int64, "counts": [m] int64 - the entries with max(min_count, 1) <= count and (max_count ==
+    0 or count <= max_count), SORTED by value (torch.sort: the C call leaves their order open), a value the 2k bits of the canonical k-mer, the first base highest -,
+    "hist": [hist_len] int64 or None - bin c - 1 = the distinct values seen c times over ALL entries, the last bin every larger count: the k-mer spectrum -, "index":
+    with index=True the dict screen_rows takes - a screen index of the selected values, the bridge to screening by abundance -, else None, "summary": dict of the
+    read's counts}.  The most frequent k-mers are torch.topk on "counts".  A size query and one call, both ordered with torch's current stream; the context goes
+    back to its own stream afterwards."""
+    table = table["table"] if isinstance(table, dict) else table
+    assert table.dtype == torch.uint8 and table.is_cuda and table.is_contiguous(), "table: kmer_table's uint8 tensor on the GPU"
+    dev = table.device
+    tb = (table.data_ptr(), table.numel())
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        q = codec.kmers_read(*tb, min_count=min_count, max_count=max_count, size_only=True)
+        m = int(q.n_selected)
+        values = torch.empty((m,), dtype=torch.int64, device=dev); counts = torch.empty((m,), dtype=torch.int64, device=dev)
+        hist = torch.empty((hist_len,), dtype=torch.int64, device=dev) if hist_len else None
+        ix = torch.empty((int(q.index_bytes),), dtype=torch.uint8, device=dev) if index else None
+        # (an empty tensor has no pointer to hand over: no list is asked for then)
+        r = codec.kmers_read(*tb, min_count=min_count, max_count=max_count, hist_len=hist_len, d_hist=hist.data_ptr() if hist_len else None,
+                             d_values=values.data_ptr() if m else None, d_counts=counts.data_ptr() if m else None, list_cap=m,
+                             d_index=ix.data_ptr() if index else None, index_cap=ix.numel() if index else 0)
+    finally:
+        codec.set_stream(None)
+    values, order = torch.sort(values)
+    counts = counts[order]
+    out_index = {"index": ix, "k": int(r.k), "n_kmers": m, "slots": int(r.index_slots)} if index else None
+    return {"values": values, "counts": counts, "hist": hist, "index": out_index, "summary": {f: int(getattr(r, f)) for f in KMERS_READ_FIELDS}}
 
 
 def filter_rows(codec, t, pairs=False, codes=True, min_len=1, row_len=None, pad=255, **criteria):
