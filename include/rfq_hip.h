@@ -760,6 +760,77 @@ typedef struct {
 } rfq_kmers_read_result;
 RFQ_API int rfq_kmers_read(rfq_ctx* ctx, const rfq_kmers_read_args* args, rfq_kmers_read_result* res);
 
+/* Demultiplexing, in front of every other step of the rows family: WHOSE read is this?  A pooled run carries the sample in an inline barcode at the front of R1,
+ * sometimes a second one at the front of R2; index reads handed over as rows of their own do the same job.  rfq_demux_rows compares a fixed window of every row with
+ * a set of barcodes and leaves, per unit, the sample - and the keep byte and the start rfq_select_rows takes, so that one rfq_select_rows call per sample splits the
+ * batch and cuts the barcode off (integer rules of this project's own, in the manner of cutadapt's demultiplexing, fastq-multx and bcl2fastq's --barcode-mismatches;
+ * no parity with any of them is claimed).  Like the judge it DECIDES and moves no bytes.  No float anywhere; the same call gives the same bytes.
+ * Units and candidates are rfq_dedup_rows': pairs = 0, a unit is a row; pairs = 1, a unit is rows 2u / 2u + 1; d_in NULL = every row; a unit is a candidate when the
+ * byte of every one of its rows is non-zero.  U is the number of units.
+ * Barcode sets.  Set 1 is n1 barcodes of len1 bases each, HOST bytes h_bc1[n1][len1], A C G T in either case; it is read from the row at [off1, off1 + len1) of row u
+ * (row 2u with pairs).  The optional set 2 (n2, len2, off2, h_bc2) is for pairs only and is read from row 2u + 1.  1 <= len <= 32, 1 <= n <= 4096 per set, with set 2
+ * n1 * n2 <= 2^20.  Two equal barcodes in one set are refused.
+ * Distance.  Base classes are rfq_adapter_rows': class 0 .. 3 = code 0 .. 3 (RFQ_ROWS_CODE) or A C G T in either case (RFQ_ROWS_ASCII), every other byte is "other".  A
+ * position AGREES when the row's byte is of class 0 .. 3 and equals the barcode's class; a byte of class other (N) never agrees.  dist(row, b) is the number of the len
+ * positions that do not agree.  A row with lens[i] < off + len has no window: it sets RFQ_DEMUX_SHORT and nothing of it is compared.
+ * Match of a row within its set.  best is the lowest index among the barcodes at the least distance d1; d2 is the least distance among all OTHER barcodes (len + 1
+ * when the set has one barcode).  The row MATCHES when d1 <= max_mm and d2 - d1 >= min_delta: min_delta = 0 lets the lowest index win a tie, 1 asks for a unique
+ * best.  Otherwise it sets RFQ_DEMUX_NONE (d1 > max_mm) or RFQ_DEMUX_AMBIG.  max_mm <= 32, min_delta <= 33.
+ * Sample of a unit.  One set: the sample is best, n_samples = n1.  Two sets, h_pairs NULL: sample = best1 * n2 + best2, n_samples = n1 * n2.  Two sets with a sample
+ * sheet h_pairs[n_samples][2], HOST int32 pairs (i, j): sample s is the pair listed s-th, 1 <= n_samples <= 65536, every index in range and no pair listed twice; a
+ * unit whose two rows both match but whose pair is not listed sets RFQ_DEMUX_COMBO - the index-hopping count of a dual-indexed run.  why is the OR of the bits of
+ * the unit's rows; the unit is ASSIGNED when it is a candidate and why == 0.
+ * Outputs; each may be NULL and is then not produced, the result is filled either way.  d_sample [U] int32: the sample, or -1.  d_why [U] uint8: the RFQ_DEMUX_*
+ * bits; a unit that is no candidate gets RFQ_DEMUX_MASKED alone.  d_best [n_rows] int32: the row's best - set for every candidate row that has a window, matched or
+ * not; -1 for a row without a set, without a window, or of a unit that is no candidate.  d_dist [n_rows] uint8: d1 wherever d_best is set, 255 wherever it is -1.
+ * d_keep [n_rows] uint8: 1 for the rows of an assigned unit, 0 otherwise.  d_start [n_rows] int32, what rfq_select_rows takes as d_start: for a row of an ASSIGNED
+ * unit that has a set min(lens[i], off + len + skip) - skip1 / skip2 are linker bases cut with the barcode, the prefix [0, off) goes too -, 0 for every other row: the
+ * unassigned bin keeps its reads whole.  d_counts [n_samples + 1] uint64, 8-byte aligned, zeroed then filled: the candidate units per sample, the last entry the
+ * candidate units that were not assigned.  Result: n_units, n_candidates, n_assigned, n_samples; n_exact, the assigned units whose every compared distance is 0;
+ * why_none, why_ambig, why_short, why_combo, the units with that bit; bases_in, the sum of l over the rows of the candidates; bases_out, the sum of l - start over the
+ * rows of the assigned units.
+ * RFQ_E_ARG, judged on the host: pairs other than 0 / 1, an odd n_rows with pairs; set 2, h_pairs, skip2 or off2 without pairs, h_pairs without set 2; no set 1; a
+ * length, count, max_mm or min_delta out of range; a barcode byte other than ACGTacgt, duplicate barcodes, a bad sample sheet; off + len + skip not representable in
+ * int32; a bad base_mode; row_len == 0, a NULL d_lens or d_bases with rows; a d_lens / d_sample / d_best / d_start that is not 4-byte or a d_counts that is not 8-byte
+ * aligned; an output that overlaps an input or another output (byte ranges are compared; d_in is an input); n_rows >= 2^31.  RFQ_E_ARG, judged on the device, the
+ * message names the first such row - ALL rows are judged, candidates or not: lens[i] < 0 or > row_len; what the outputs hold is then unspecified, and nothing outside
+ * the row buffers is read.  After any refusal the context stays usable.
+ * The row buffers may have any alignment, on rfq_judge_rows' terms - never a byte outside [d_bases, d_bases + n_rows * row_len).  n_rows * row_len may exceed 4 GiB.
+ * Quality rows and names are not read.  The host packs every barcode into 2-bit classes and uploads the sets - and the dense [n1][n2] table it makes of the sample
+ * sheet - per call into scratch of the context's that only grows.  One kernel: a lane per unit, the sets in a compute unit's LDS (at most 34 KiB), the counts in an LDS table of up
+ * to 8192 cells flushed once per workgroup (beyond that 64-bit atomic adds in device memory).  RFQ_DEMUX=general takes the other formulation - a lane per unit
+ * compares byte by byte against the barcodes' ASCII bytes in device memory - with the same bytes in every output.  Synchronous on the context's stream, one read-back;
+ * stage time through rfq_last_timings (demux:rows).
+ * NOT offered: barcodes of different lengths within one set, indels, a barcode searched at several offsets or at the 3' end, N as a wildcard in a barcode; barcodes
+ * read out of the name line, UMI extraction; grouping the rows by sample in one pass on the device (one rfq_select_rows call per sample does it). */
+#define RFQ_DEMUX_NONE   1                /* d1 > max_mm                                                                */
+#define RFQ_DEMUX_AMBIG  2                /* d2 - d1 < min_delta                                                        */
+#define RFQ_DEMUX_SHORT  4                /* lens[i] < off + len: no window                                             */
+#define RFQ_DEMUX_COMBO  8                /* both rows matched, the pair is not in the sample sheet                     */
+#define RFQ_DEMUX_MASKED 128              /* the unit is no candidate                                                   */
+typedef struct {
+    int32_t  pairs;                       /* 1: a unit is the pair of rows 2u / 2u + 1 (n_rows must be even)            */
+    uint32_t n1, len1, off1, skip1;       /* set 1: barcodes, bases each, the window's start, linker bases behind it    */
+    const uint8_t* h_bc1;                 /* HOST [n1][len1] ACGTacgt                                                   */
+    uint32_t n2, len2, off2, skip2;       /* set 2 (pairs only, read from row 2u + 1); n2 == 0 and h_bc2 NULL: none     */
+    const uint8_t* h_bc2;                 /* HOST [n2][len2] or NULL                                                    */
+    const int32_t* h_pairs;               /* HOST [n_samples][2] (i, j), or NULL: every combination, i * n2 + j         */
+    uint32_t n_samples;                   /* rows of h_pairs, 1 .. 65536; ignored without h_pairs                       */
+    uint32_t max_mm, min_delta;           /* a row matches with d1 <= max_mm and d2 - d1 >= min_delta                   */
+    const uint8_t* d_in;                  /* [n_rows] bytes, non-zero = the row is a candidate; NULL = every row        */
+    int32_t*  d_sample;                   /* [U] or NULL                                                                */
+    uint8_t*  d_why;                      /* [U] or NULL                                                                */
+    int32_t*  d_best;                     /* [n_rows] or NULL                                                           */
+    uint8_t*  d_dist;                     /* [n_rows] or NULL                                                           */
+    uint8_t*  d_keep;                     /* [n_rows] 1 / 0, or NULL                                                    */
+    int32_t*  d_start;                    /* [n_rows] or NULL                                                           */
+    uint64_t* d_counts;                   /* [n_samples + 1], 8-byte aligned, or NULL                                   */
+} rfq_demux_rows_args;
+typedef struct {
+    uint64_t n_units, n_candidates, n_assigned, n_samples, n_exact, why_none, why_ambig, why_short, why_combo, bases_in, bases_out;
+} rfq_demux_rows_result;
+RFQ_API int rfq_demux_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_demux_rows_args* args, rfq_demux_rows_result* res);
+
 /* stage timings of the last batch / rows call, in milliseconds, measured with HIP events on the context's stream.
  * names[i] is a static string; returns the number of stages written (<= cap). */
 RFQ_API int rfq_last_timings(const rfq_ctx* ctx, const char** names, float* ms, int cap);
@@ -793,7 +864,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general, RFQ_SCREEN=general|collide, RFQ_KMERS=general|collide|direct; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general, RFQ_SCREEN=general|collide, RFQ_KMERS=general|collide|direct, RFQ_DEMUX=general; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

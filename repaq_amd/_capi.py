@@ -234,6 +234,22 @@ class KmersReadResult(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("k", "slots", "n_kmers", "total", "max_count", "n_selected", "selected_total", "index_slots", "index_bytes")]
 
 
+DEMUX_NONE, DEMUX_AMBIG, DEMUX_SHORT, DEMUX_COMBO, DEMUX_MASKED = 1, 2, 4, 8, 128
+
+
+class DemuxRowsArgs(C.Structure):
+    _fields_ = [("pairs", C.c_int32), ("n1", C.c_uint32), ("len1", C.c_uint32), ("off1", C.c_uint32), ("skip1", C.c_uint32), ("h_bc1", C.c_char_p),
+                ("n2", C.c_uint32), ("len2", C.c_uint32), ("off2", C.c_uint32), ("skip2", C.c_uint32), ("h_bc2", C.c_char_p),
+                ("h_pairs", C.POINTER(C.c_int32)), ("n_samples", C.c_uint32), ("max_mm", C.c_uint32), ("min_delta", C.c_uint32), ("d_in", C.c_void_p),
+                ("d_sample", C.c_void_p), ("d_why", C.c_void_p), ("d_best", C.c_void_p), ("d_dist", C.c_void_p), ("d_keep", C.c_void_p), ("d_start", C.c_void_p),
+                ("d_counts", C.c_void_p)]
+
+
+class DemuxRowsResult(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_units", "n_candidates", "n_assigned", "n_samples", "n_exact", "why_none", "why_ambig", "why_short", "why_combo",
+                                          "bases_in", "bases_out")]
+
+
 _libs = {}
 
 
@@ -278,6 +294,7 @@ def load(path=None):
     L.rfq_kmers_init.argtypes = [C.c_void_p, C.POINTER(KmersInitArgs), C.POINTER(KmersInitResult)]
     L.rfq_kmers_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(KmersRowsArgs), C.POINTER(KmersRowsResult)]
     L.rfq_kmers_read.argtypes = [C.c_void_p, C.POINTER(KmersReadArgs), C.POINTER(KmersReadResult)]
+    L.rfq_demux_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(DemuxRowsArgs), C.POINTER(DemuxRowsResult)]
     L.rfq_scan_batch.argtypes = [C.c_void_p, C.POINTER(EncodeArgs), C.POINTER(ScanResult)]
     L.rfq_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
     L.rfq_dev_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -301,6 +318,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_screen_build", "rfq_screen_rows", "rfq_kmers_init", "rfq_kmers_rows", "rfq_kmers_read", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_screen_build", "rfq_screen_rows", "rfq_kmers_init", "rfq_kmers_rows", "rfq_kmers_read", "rfq_demux_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

@@ -473,6 +473,46 @@ class RfqCodec:
         self._check(self._L.rfq_kmers_read(self._h, C.byref(a), C.byref(r)))
         return r
 
+    # --- whose read is this: rows against one or two sets of barcodes (rfq_demux_rows)
+    @staticmethod
+    def _barcode_set(barcodes, length=None):
+        """(n, len, the [n][len] bytes) of a list of str / bytes of one length, or of bytes already laid out with `length` given"""
+        if barcodes is None:
+            return 0, 0, None
+        if isinstance(barcodes, (bytes, bytearray)):
+            assert length, "barcodes as one bytes object need their length"
+            return len(barcodes) // length, length, bytes(barcodes)
+        bcs = [b.encode() if isinstance(b, str) else bytes(b) for b in barcodes]
+        ln = length if length is not None else (len(bcs[0]) if bcs else 0)
+        assert all(len(b) == ln for b in bcs), "the barcodes of a set have one length"
+        return len(bcs), ln, b"".join(bcs)
+
+    def demux_rows(self, n_rows, row_len, d_bases, d_lens, barcodes1, barcodes2=None, sheet=None, codes=False, pairs=False, off1=0, off2=0, skip1=0, skip2=0,
+                   max_mm=1, min_delta=1, d_in=None, d_sample=None, d_why=None, d_best=None, d_dist=None, d_keep=None, d_start=None, d_counts=None, base_mode=None,
+                   raw=None):
+        """rfq_demux_rows: base rows and lengths (qualities and names are not looked at) against one or two sets of barcodes.  barcodes1 / barcodes2: a list of str
+        / bytes of one length (A C G T in either case), read at [off, off + len) of row u / of rows 2u and 2u + 1 with pairs; sheet: a list of (i, j) pairs, sample
+        s the pair listed s-th (None: every combination, i * n2 + j).  A row matches its set with d1 <= max_mm and d2 - d1 >= min_delta (Hamming distances of the
+        best and the second best barcode; an N never agrees).  d_in: n_rows bytes, non-zero = the row is a candidate.  d_sample [U] int32, d_why [U] uint8, d_best
+        [n_rows] int32, d_dist [n_rows] uint8, d_keep [n_rows] uint8 and d_start [n_rows] int32 - what select_rows takes -, d_counts [n_samples + 1] uint64; an
+        output that is None is not produced.  raw: a dict of DemuxRowsArgs fields set as they stand, for the tests of the refusals.  Returns DemuxRowsResult
+        (n_units, n_candidates, n_assigned, n_samples, n_exact, why_none, why_ambig, why_short, why_combo, bases_in, bases_out)."""
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
+        if base_mode is not None:
+            rows.base_mode = base_mode
+        n1, len1, b1 = self._barcode_set(barcodes1)
+        n2, len2, b2 = self._barcode_set(barcodes2)
+        flat = None
+        if sheet is not None:
+            flat = (C.c_int32 * max(2 * len(sheet), 1))(*[int(x) for p in sheet for x in p])
+        a = A.DemuxRowsArgs(1 if pairs else 0, n1, len1, off1, skip1, b1, n2, len2, off2, skip2, b2, flat, len(sheet) if sheet is not None else 0, max_mm, min_delta,
+                            d_in, d_sample, d_why, d_best, d_dist, d_keep, d_start, d_counts)
+        for k, v in (raw or {}).items():
+            setattr(a, k, v)
+        r = A.DemuxRowsResult()
+        self._check(self._L.rfq_demux_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:
         out = C.c_uint64(0)

@@ -107,6 +107,7 @@ struct RfqOpts {
     enum Screen { SCREEN_DEFAULT, SCREEN_GENERAL, SCREEN_COLLIDE } screen = SCREEN_DEFAULT;
     // RFQ_KMERS=general|collide|direct  general, rfq_kmers_rows: the any-length kernel (a wave per row) for every row length, adds straight to device memory; direct: the common kernels without the workgroup's LDS table (default: rows of up to 1024 bytes held whole, a workgroup combines in LDS and flushes once); collide, rfq_kmers_init: four bits of the hash for the start slot, recorded in the table - long probe chains, at most 65536 slots (default: a 64-bit multiplicative hash)
     enum Kmers { KMERS_DEFAULT, KMERS_GENERAL, KMERS_COLLIDE, KMERS_DIRECT } kmers = KMERS_DEFAULT;
+    bool demux_general = false;       // RFQ_DEMUX=general  rfq_demux_rows: a lane per unit compares byte by byte against the barcodes' ASCII bytes in device memory, counts by global atomics (default: the window as 2-bit classes against the packed sets in LDS, counts in an LDS table)
     bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)
 };
 struct rfq_ctx {
@@ -187,6 +188,8 @@ struct rfq_ctx {
     DBuf names_blob, names_off;            // rfq_decode_names: the context-owned name lines and their offsets
     // rfq_dedup_rows: per unit the fingerprint, the score and the class's slot; per slot the table word, the best member and the class size (sized and zeroed per call)
     DBuf dedup_fp, dedup_score, dedup_slot, dedup_tab, dedup_best, dedup_cnt;
+    // rfq_demux_rows: the packed sets, their ASCII bytes and the sample table, built on the host and uploaded per call (the device scratch only grows)
+    DBuf demux_sets; std::vector<uint8_t> demux_host;
     std::vector<uint64_t> chunk_off;
     std::vector<uint64_t> scan_end[2];     // rfq_scan_batch: end offset of every chunk in each input stream
     StageTimer timer;

@@ -2055,3 +2055,126 @@ extern "C" int rfq_kmers_read(rfq_ctx* ctx, const rfq_kmers_read_args* a, rfq_km
     ctx->timer.collect();
     return RFQ_OK;
 }
+// ---------------------------------------------------------------- rows against barcode sets -> a sample per unit, the keep byte and start of rfq_select_rows, counts per sample: rfq_demux_rows of include/rfq_hip.h
+// One kernel and one read-back (enc/rows_demux.h).  The sets come as host bytes: they are judged and packed here - 2 bits a base, base j in bits 2j and 2j + 1, W
+// words a barcode (1 up to 16 bases, 2 beyond; both sets at the W of the longer) -, the sample sheet becomes a dense [n1][n2] table, and everything goes to the
+// device in ONE stream-ordered copy into scratch of the context's that only grows.  RFQ_DEMUX=general launches the byte-by-byte kernel on the same scratch.
+static int demux_set_arg(rfq_ctx* ctx, int which, const uint8_t* h, uint32_t n, uint32_t len, uint32_t off, uint32_t skip) {
+    if (!h) return rfq_fail(ctx, RFQ_E_ARG, "set %d: null h_bc%d with n%d = %u", which, which, which, n);
+    if (n < 1u || n > DM_N_MAX) return rfq_fail(ctx, RFQ_E_ARG, "set %d: the number of barcodes must be 1 .. %u (got %u)", which, DM_N_MAX, n);
+    if (len < 1u || len > DM_LEN_MAX) return rfq_fail(ctx, RFQ_E_ARG, "set %d: the barcode length must be 1 .. %u (got %u)", which, DM_LEN_MAX, len);
+    if ((unsigned long long)off + len + skip > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "set %d: off + len + skip = %llu does not fit an int32", which, (unsigned long long)off + len + skip);
+    return RFQ_OK;
+}
+// barcode k of the set into W words at dst; a byte that is no base refuses the call
+static int demux_pack(rfq_ctx* ctx, int which, const uint8_t* h, uint32_t k, uint32_t len, uint32_t W, uint32_t* dst) {
+    for (uint32_t w = 0; w < W; w++) dst[w] = 0u;
+    for (uint32_t j = 0; j < len; j++) {
+        uint32_t c;
+        switch (h[(size_t)k * len + j] & 0xDFu) { case 'A': c = 0; break; case 'C': c = 1; break; case 'G': c = 2; break; case 'T': c = 3; break;
+        default: return rfq_fail(ctx, RFQ_E_ARG, "set %d: barcode %u holds a byte that is not one of ACGTacgt (0x%02x at %u)", which, k, h[(size_t)k * len + j], j); }
+        dst[j >> 4] |= c << (2u * (j & 15u));
+    }
+    return RFQ_OK;
+}
+extern "C" int rfq_demux_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_demux_rows_args* a, rfq_demux_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows;
+    int rc;
+    if ((rc = rows_pairs_arg(ctx, a->pairs, n)) != RFQ_OK) return rc;
+    const bool set2 = a->h_bc2 || a->n2;
+    if (!a->pairs && (set2 || a->len2 || a->h_pairs || a->skip2 || a->off2)) return rfq_fail(ctx, RFQ_E_ARG, "set 2 (h_bc2, n2, len2, off2, skip2) and h_pairs are for pairs");
+    if (a->h_pairs && !set2) return rfq_fail(ctx, RFQ_E_ARG, "h_pairs needs set 2");
+    if (!a->h_bc1 && !a->n1) return rfq_fail(ctx, RFQ_E_ARG, "no set 1: h_bc1 and n1 must be given");
+    if ((rc = demux_set_arg(ctx, 1, a->h_bc1, a->n1, a->len1, a->off1, a->skip1)) != RFQ_OK) return rc;
+    if (set2 && (rc = demux_set_arg(ctx, 2, a->h_bc2, a->n2, a->len2, a->off2, a->skip2)) != RFQ_OK) return rc;
+    if (set2 && (unsigned long long)a->n1 * a->n2 > (1ull << 20)) return rfq_fail(ctx, RFQ_E_ARG, "n1 * n2 is at most 2^20 (got %u * %u)", a->n1, a->n2);
+    if (a->max_mm > 32u || a->min_delta > 33u) return rfq_fail(ctx, RFQ_E_ARG, "max_mm is at most 32 and min_delta at most 33 (got %u, %u)", a->max_mm, a->min_delta);
+    if (a->h_pairs && (a->n_samples < 1u || a->n_samples > 65536u)) return rfq_fail(ctx, RFQ_E_ARG, "n_samples must be 1 .. 65536 with h_pairs (got %u)", a->n_samples);
+    const uint32_t nb[2] = { a->n1, set2 ? a->n2 : 0u }, len[2] = { a->len1, set2 ? a->len2 : 0u };
+    const uint8_t* const hb[2] = { a->h_bc1, a->h_bc2 };
+    const uint32_t W = std::max(len[0], len[1]) <= 16u ? 1u : 2u;
+    const uint32_t n_samples = !set2 ? a->n1 : (a->h_pairs ? a->n_samples : a->n1 * a->n2);
+    // the blob: packed set 1, packed set 2, the table, the sets' ASCII bytes (8-byte aligned up to the bytes: a two-word barcode is read as one 64-bit word)
+    const size_t o_p[2] = { 0, (size_t)nb[0] * W * 4u }, o_tab = o_p[1] + (size_t)nb[1] * W * 4u, tab_bytes = a->h_pairs ? (size_t)nb[0] * nb[1] * 4u : 0u;
+    const size_t o_t[2] = { o_tab + tab_bytes, o_tab + tab_bytes + (size_t)nb[0] * len[0] }, blob_bytes = o_t[1] + (size_t)nb[1] * len[1];
+    std::vector<uint8_t>& blob = ctx->demux_host;
+    blob.assign(blob_bytes + 8u, 0);
+    for (int s = 0; s < 2; s++) {
+        if (!nb[s]) continue;
+        uint32_t* const pk = (uint32_t*)(blob.data() + o_p[s]);
+        for (uint32_t k = 0; k < nb[s]; k++) if ((rc = demux_pack(ctx, s + 1, hb[s], k, len[s], W, pk + (size_t)k * W)) != RFQ_OK) return rc;
+        // two equal barcodes: equal packed words (the sort is of indices, so that the message names the pair)
+        std::vector<uint32_t> order(nb[s]);
+        for (uint32_t k = 0; k < nb[s]; k++) order[k] = k;
+        const auto key = [&](uint32_t k) { return (unsigned long long)pk[(size_t)k * W] | (W == 2u ? (unsigned long long)pk[(size_t)k * W + 1u] << 32 : 0ull); };
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return key(x) != key(y) ? key(x) < key(y) : x < y; });
+        for (uint32_t k = 1; k < nb[s]; k++)
+            if (key(order[k]) == key(order[k - 1])) return rfq_fail(ctx, RFQ_E_ARG, "set %d: barcodes %u and %u are equal", s + 1, order[k - 1], order[k]);
+        memcpy(blob.data() + o_t[s], hb[s], (size_t)nb[s] * len[s]);
+    }
+    if (a->h_pairs) {
+        int32_t* const tab = (int32_t*)(blob.data() + o_tab);
+        for (size_t i = 0; i < (size_t)nb[0] * nb[1]; i++) tab[i] = -1;
+        for (uint32_t s = 0; s < n_samples; s++) {
+            const int32_t i = a->h_pairs[2u * s], j = a->h_pairs[2u * s + 1u];
+            if (i < 0 || (uint32_t)i >= nb[0] || j < 0 || (uint32_t)j >= nb[1]) return rfq_fail(ctx, RFQ_E_ARG, "the sample sheet's pair %u is (%d, %d): not in [0, %u) x [0, %u)", s, i, j, nb[0], nb[1]);
+            int32_t& cell = tab[(size_t)i * nb[1] + (uint32_t)j];
+            if (cell >= 0) return rfq_fail(ctx, RFQ_E_ARG, "the sample sheet lists the pair (%d, %d) twice (samples %d and %u)", i, j, cell, s);
+            cell = (int32_t)s;
+        }
+    }
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, n != 0)) != RFQ_OK) return rc;
+    if (n && (!in->d_lens || !in->d_bases)) return rfq_fail(ctx, RFQ_E_ARG, "null d_lens / d_bases");
+    if (((uintptr_t)in->d_lens | (uintptr_t)a->d_sample | (uintptr_t)a->d_best | (uintptr_t)a->d_start) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "d_lens, d_sample, d_best and d_start must be 4-byte aligned");
+    if ((uintptr_t)a->d_counts & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_counts must be 8-byte aligned");
+    if (n > 0x7FFFFFFFull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    const uint64_t units = a->pairs ? n / 2 : n;
+    {
+        Span ins[6]; rows_src_spans(in, false, ins);
+        ins[1].p = nullptr;                                                  // (the scores are not read)
+        ins[5] = { a->d_in, n, "d_in" };
+        const Span outs[] = { { a->d_sample, units * 4ull, "d_sample" }, { a->d_why, units, "d_why" }, { a->d_best, n * 4ull, "d_best" }, { a->d_dist, n, "d_dist" }, { a->d_keep, n, "d_keep" },
+                              { a->d_start, n * 4ull, "d_start" }, { a->d_counts, ((unsigned long long)n_samples + 1ull) * 8ull, "d_counts" } };
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
+        for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) for (size_t k = i + 1; k < sizeof outs / sizeof outs[0]; k++)
+            if (sel_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the output %s", outs[i].what, outs[k].what);
+    }
+    res->n_units = units; res->n_samples = n_samples;
+    hipStream_t S = ctx->stream;
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    if ((rc = rows_hist_fresh(ctx, S, a->d_counts, n_samples + 1u, n)) != RFQ_OK || !n) return rc;
+    HIPCHK(ctx, ctx->demux_sets.ensure(blob.size()));
+    uint8_t* const dblob = ctx->demux_sets.as<uint8_t>();
+    DemuxIn di; memset(&di, 0, sizeof di);
+    di.b = in->d_bases; di.lens = in->d_lens; di.cand = a->d_in; di.total = n * in->row_len; di.n_rows = (uint32_t)n; di.n_units = (uint32_t)units; di.row_len = in->row_len;
+    di.vec_in = rows_vec(in->row_len, in->d_bases, nullptr);
+    di.ascii = in->base_mode == RFQ_ROWS_ASCII ? 1u : 0u; di.pairs = a->pairs ? 1u : 0u;
+    di.n[0] = nb[0]; di.n[1] = nb[1]; di.len[0] = len[0]; di.len[1] = len[1]; di.off[0] = a->off1; di.off[1] = set2 ? a->off2 : 0u; di.skip[0] = a->skip1; di.skip[1] = set2 ? a->skip2 : 0u;
+    di.max_mm = a->max_mm; di.min_delta = a->min_delta; di.n_samples = n_samples;
+    for (int s = 0; s < 2; s++) { di.packed[s] = (const uint32_t*)(dblob + o_p[s]); di.text[s] = dblob + o_t[s]; }
+    di.table = a->h_pairs ? (const int32_t*)(dblob + o_tab) : nullptr;
+    di.sample = a->d_sample; di.why = a->d_why; di.best = a->d_best; di.dist = a->d_dist; di.keep = a->d_keep; di.start = a->d_start; di.counts = (unsigned long long*)a->d_counts;
+    ctx->timer.begin("demux:rows", S);
+    HIPCHK(ctx, hipMemcpyAsync(dblob, blob.data(), blob.size(), hipMemcpyHostToDevice, S));
+    DemuxStat* dst = nullptr; DemuxStat hs;
+    if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+    if (ctx->opt.demux_general) hipLaunchKernelGGL(k_demux_rows_general, dim3((uint32_t)((units + 255u) / 256u)), dim3(256), 0, S, di, dst);
+    else {
+        // a workgroup pays for its copy of the sets and the flush of its counts once: DM_WG_PER_CU workgroups per compute unit, the steps follow
+        di.lds_counts = a->d_counts && n_samples + 1u <= DM_LDS_COUNTS ? 1u : 0u;
+        const uint64_t gcap = std::max<uint64_t>(1, (uint64_t)DM_WG_PER_CU * ctx->n_cu), steps = std::max<uint64_t>((units + 256u * gcap - 1u) / (256u * gcap), 1u);
+        di.steps = (uint32_t)steps;
+        const auto k = W == 1u ? k_demux_rows<1> : k_demux_rows<2>;
+        hipLaunchKernelGGL(k, dim3((uint32_t)((units + 256u * steps - 1u) / (256u * steps))), dim3(256), ((size_t)(nb[0] + nb[1]) * W + (di.lds_counts ? n_samples + 1u : 0u)) * 4u + 8u, S, di, dst);
+    }
+    KCHK(ctx, "k_demux_rows");
+    ctx->timer.end(S);
+    if ((rc = rows_sums_back(ctx, S, dst, &hs, in->row_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    res->n_candidates = hs.c[0]; res->n_assigned = hs.c[1]; res->n_exact = hs.c[2]; res->why_none = hs.c[3]; res->why_ambig = hs.c[4]; res->why_short = hs.c[5]; res->why_combo = hs.c[6];
+    res->bases_in = hs.c[7]; res->bases_out = hs.c[8];
+    return RFQ_OK;
+}

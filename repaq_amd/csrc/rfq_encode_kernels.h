@@ -32,3 +32,4 @@
 #include "enc/rows_profile.h"                 // rows under a keep / start / length triple -> per-cycle base content, position x score, length / mean-quality / GC tables (rfq_profile_rows)
 #include "enc/rows_screen.h"                  // references -> an index of canonical k-mers; rows against it -> k-mers, hits and a keep byte per row + a summary (rfq_screen_build, rfq_screen_rows)
 #include "enc/rows_kmers.h"                   // rows -> a caller-owned table of canonical k-mers with counts that adds up across calls; the table -> spectrum, (value, count) list, a screen index (rfq_kmers_init, rfq_kmers_rows, rfq_kmers_read)
+#include "enc/rows_demux.h"                   // rows against one or two sets of barcodes -> a sample per unit, the keep byte and start rfq_select_rows takes, counts per sample + a summary (rfq_demux_rows)

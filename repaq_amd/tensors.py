@@ -80,6 +80,12 @@ a file; its reader gives the spectrum, the (value, count) pairs and a screen ind
     kc = kmer_counts(codec, tab, min_count=2, hist_len=256, index=True)                                 # kc["hist"]: the spectrum; kc["values"], kc["counts"]: sorted by value
     c = screen_rows(codec, t, kc["index"], pairs=True, keep_matched=True, min_pct=50)                   # the pairs at least half made of k-mers seen twice
 
+in front of all of these, a pooled run: rfq_demux_rows says WHOSE a read is - it compares the inline barcode at the front of R1 (and R2) with the sample sheet's
+and leaves the sample per pair, the keep byte and the start select_rows takes, and the count per sample; one select_rows pass per sample splits the batch:
+
+    dm = demux_rows(codec, t, i7, i5, sheet=[(0, 0), (1, 1), ...], pairs=True, skip1=1)                  # dm["counts"], dm["summary"]["why_combo"]: index hopping
+    per_sample = split_rows(codec, t, dm["sample"], len(sheet), start=dm["start"], pairs=True)           # the unassigned rows last, whole
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -509,6 +515,73 @@ def kmer_counts(codec, table, min_count=1, max_count=0, hist_len=0, index=False)
     counts = counts[order]
     out_index = {"index": ix, "k": int(r.k), "n_kmers": m, "slots": int(r.index_slots)} if index else None
     return {"values": values, "counts": counts, "hist": hist, "index": out_index, "summary": {f: int(getattr(r, f)) for f in KMERS_READ_FIELDS}}
+
+
+DEMUX_FIELDS = ("n_units", "n_candidates", "n_assigned", "n_samples", "n_exact", "why_none", "why_ambig", "why_short", "why_combo", "bases_in", "bases_out")
+
+
+def demux_rows(codec, t, barcodes1, barcodes2=None, sheet=None, pairs=False, codes=True, keep=None, off1=0, off2=0, skip1=0, skip2=0, max_mm=1, min_delta=1):
+    """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "lens"; codes: what they were made with) against one or two sets of inline barcodes
+    (rfq_demux_rows) -> {"sample": [U] int32 (the unit's sample, -1: none), "why": [U] uint8 (the DEMUX_* bits of repaq_amd._capi: 1 no barcode within max_mm,
+    2 ambiguous, 4 the read ends in front of the window's end, 8 both matched but the pair is not in the sheet, 128 masked by `keep`), "best": [n] int32 (the row's
+    nearest barcode, -1 where nothing was compared), "dist": [n] uint8 (its distance, 255 where best is -1), "keep": [n] uint8 and "start": [n] int32 - what
+    select_rows and split_rows take: 1 and the first base behind barcode and linker for the rows of an assigned unit, 0 and 0 otherwise -, "counts": [n_samples + 1]
+    int64 (the candidate units per sample, last the unassigned), "summary": dict of the batch's counts}.  A unit is a row, with pairs the rows 2k / 2k + 1 (U units).
+    barcodes1 / barcodes2: a list of str / bytes of ONE length per set (1 .. 32 bases, at most 4096, A C G T), read at [off, off + len) of R1 / R2; barcodes2 and
+    sheet need pairs.  sheet: a list of (i, j), sample s the pair listed s-th; None: every combination, sample i * n2 + j.  A row matches with d1 <= max_mm and
+    d2 - d1 >= min_delta, d1 / d2 the Hamming distances of the best and the second-best barcode (an N never agrees; min_delta=0 lets the lowest index win a tie).
+    skip1 / skip2: linker bases cut with the barcode.  keep: [n] bool / uint8 - only units all of whose rows are non-zero there are looked at.  Barcodes of
+    several lengths in one set, indels, barcodes at other places than a fixed offset from the read's start, N as a wildcard, barcodes in the name line and UMIs are
+    not offered.  One call, ordered with torch's current stream; the context goes back to its own stream afterwards."""
+    bases, lens = t["bases"], t["lens"]
+    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    dev = bases.device
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
+    assert not pairs or n % 2 == 0, "rows in pairs"
+    if keep is not None:
+        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
+    U = n // 2 if pairs else n
+    n_samples = len(barcodes1) if barcodes2 is None else (len(sheet) if sheet is not None else len(barcodes1) * len(barcodes2))
+    sample = torch.empty((U,), dtype=torch.int32, device=dev); why = torch.empty((U,), dtype=torch.uint8, device=dev)
+    best = torch.empty((n,), dtype=torch.int32, device=dev); dist = torch.empty((n,), dtype=torch.uint8, device=dev)
+    out_keep = torch.empty((n,), dtype=torch.uint8, device=dev); start = torch.empty((n,), dtype=torch.int32, device=dev)
+    counts = torch.empty((n_samples + 1,), dtype=torch.int64, device=dev)
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        r = codec.demux_rows(n, L, bases.data_ptr(), lens.data_ptr(), barcodes1, barcodes2, sheet, codes=codes, pairs=pairs, off1=off1, off2=off2, skip1=skip1, skip2=skip2,
+                             max_mm=max_mm, min_delta=min_delta, d_in=keep.data_ptr() if keep is not None else None, d_sample=sample.data_ptr(), d_why=why.data_ptr(),
+                             d_best=best.data_ptr(), d_dist=dist.data_ptr(), d_keep=out_keep.data_ptr(), d_start=start.data_ptr(), d_counts=counts.data_ptr())
+    finally:
+        codec.set_stream(None)
+    return {"sample": sample, "why": why, "best": best, "dist": dist, "keep": out_keep, "start": start, "counts": counts, "summary": {f: int(getattr(r, f)) for f in DEMUX_FIELDS}}
+
+
+def split_rows(codec, t, sample, n_samples, start=None, length=None, pairs=False, unassigned=True, **select_kw):
+    """The rows of `t` by sample: one select_rows call per sample, the keep mask `sample == s` made on the device (with pairs spread to both rows of a pair by a torch
+    index) -> a list of n_samples select_rows results, entry s the rows of sample s, and with unassigned=True one more, last, for the units with sample < 0.  Only
+    the bins that hold a unit get a call (one torch.bincount and one read-back say which); the others are None.  sample: demux_rows' "sample" ([U] int32); start /
+    length: what select_rows takes - demux_rows' "start" cuts barcode and linker off the assigned rows and leaves the unassigned ones whole -; select_kw: min_len,
+    row_len, pad.  select_rows' min_len = 1 holds here too: a unit one of whose rows has nothing left behind its start (barcode, prefix and linker took the whole read,
+    or an unassigned mate is empty) is dropped from its bin with both rows, so a bin may hold fewer units than demux_rows' "counts" says - the result's "dropped" counts them;
+    min_len=0 keeps them, as rows of length 0 that rows_to_fastq and encode_tensors refuse.  A select_rows pass reads a mask byte and a few words per row and moves only the rows it keeps, so a pass per sample is cheap beside moving the rows
+    once (DESIGN.md has the measured time).  Grouping the rows by sample in ONE pass is not offered."""
+    dev = t["bases"].device
+    n = int(t["bases"].shape[0])
+    U = n // 2 if pairs else n
+    assert sample.dtype == torch.int32 and sample.numel() == U and sample.device == dev, "sample: [U] int32 on the rows' device"
+    bins = torch.where(sample >= 0, sample, torch.full_like(sample, n_samples)).to(torch.int64)
+    have = torch.bincount(bins, minlength=n_samples + 1).cpu().tolist()
+    unit_of = torch.arange(n, device=dev) // 2 if pairs else None
+    out = []
+    for s in range(n_samples + (1 if unassigned else 0)):
+        if not have[s]:
+            out.append(None)
+            continue
+        mask = bins == s
+        mask = (mask[unit_of] if pairs else mask).to(torch.uint8).contiguous()
+        out.append(select_rows(codec, t, keep=mask, start=start, length=length, pairs=pairs, **select_kw))
+    return out
 
 
 def filter_rows(codec, t, pairs=False, codes=True, min_len=1, row_len=None, pad=255, **criteria):
