@@ -342,6 +342,58 @@ typedef struct {
 } rfq_select_rows_result;
 RFQ_API int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_select_rows_args* args, rfq_select_rows_result* res);
 
+/* rfq_select_rows with the kept rows GROUPED by an integer bin per unit, in ONE pass over the rows: a stable partition - the reads of one sample next to each other
+ * (d_bin = rfq_demux_rows' d_sample as it lies), rows by length bin, by rfq_dedup_rows' representative, by rfq_screen_rows' verdict.  A unit is a row, with pairs the
+ * rows 2k / 2k + 1; d_bin has one entry per unit.  T = n_bins + rest bins in all, 1 <= n_bins, T <= 65536, rest 0 or 1.  A unit with 0 <= bin < n_bins belongs to
+ * that bin; one with bin < 0 to bin n_bins with rest = 1, with rest = 0 it is dropped with all its rows; bin >= n_bins is RFQ_E_ARG.
+ * Who stays is otherwise rfq_select_rows' rule, unchanged: the mask, the windows and their validation, min_len, the pair rule.  Why a row is dropped, counted once,
+ * in this order: dropped_mask - keep[i] == 0; dropped_bin - its unit's bin < 0 with rest = 0; dropped_short - its window is shorter than min_len; dropped_mate (pairs
+ * only) - the row would stand, its mate does not.  n_in == n_rows + the four.
+ * Order: the output rows are the kept rows sorted by (bin, input row) - a stable sort; the rows of a pair stay adjacent, R1 first.  d_bin_off[b], b in [0, T], is the
+ * first output ROW of bin b (empty bins included), d_bin_off[T] == n_rows of the result.  lens, name_off and the blob are in output order, so the names of bin b
+ * are the blob bytes [name_off[bin_off[b]], name_off[bin_off[b + 1]]).
+ * The contract in one sentence: for every bin b the output rows [bin_off[b], bin_off[b + 1]) are byte for byte what rfq_select_rows writes with the same d_start /
+ * d_len / pairs / min_len / row_len / pads and the mask "keep AND bin == b" spread to the rows of a unit - their lengths, their names and their name offsets less
+ * the first included.  n_bins_used: the bins that hold a row.
+ * rows->d_name_off == NULL means rows without names: d_names / d_name_off of the arguments must then be NULL too (RFQ_E_ARG), names_len and max_name are 0.
+ * All SIX output pointers NULL (d_bin_off with the five of rfq_select_rows) = a size query: the whole result is filled, nothing is written.  An output that is NULL is
+ * not produced; d_bin_off alone gives the rows per bin without moving a row (row_len is looked at only where one of the other five is asked for).  RFQ_E_NOSPACE
+ * (nothing written; the message says "need ...") when row_len < max_len, a cap is too small or bin_cap < T + 1.
+ * RFQ_E_ARG, judged on the host: what rfq_select_rows refuses (an odd n_rows with pairs, row_len == 0 where rows are written, misaligned d_lens / d_start / d_len /
+ * d_name_off, an output that overlaps an input); d_bin == NULL with rows; n_bins == 0; T > 65536; rest not 0 or 1; a d_bin that is not 4-byte or a d_bin_off that is
+ * not 8-byte aligned; an output that overlaps d_bin, d_bin_off overlapping an input (byte ranges; of d_bin_off min(bin_cap, T + 1) entries).  RFQ_E_ARG, judged on the
+ * device before anything is written: rfq_select_rows' (the message names the first such row) and a bin >= n_bins (the message names the first such UNIT).  ALL rows
+ * and units are judged, kept or not.  After any refusal the context stays usable.
+ * The row buffers may have any alignment, in and out; n_rows * row_len and the blob may exceed 4 GiB (n_rows < 2^32 - 16).  The same call writes the same bytes: no
+ * atomic decides where a row goes.  Scratch is O(units) and the context's own.  Synchronous on the context's stream; stage times through rfq_last_timings
+ * (group:judge, group:rank, group:tables, group:rows, group:names). */
+typedef struct {
+    const uint8_t* d_keep;                /* [n_rows] bytes, non-zero = keep; NULL = every row                          */
+    const int32_t* d_start;               /* [n_rows] first base kept of row i; NULL = 0                                */
+    const int32_t* d_len;                 /* [n_rows] bases kept from there; NULL = to the end of the read              */
+    int32_t  pairs;                       /* 1: rows 2k / 2k + 1 are one unit (n_rows must be even)                     */
+    uint32_t min_len;                     /* a row whose window is shorter is dropped                                   */
+    const int32_t* d_bin;                 /* [units] the unit's bin: 0 .. n_bins - 1; < 0: the rest bin, or dropped     */
+    uint32_t n_bins;                      /* >= 1; n_bins + rest <= 65536                                               */
+    int32_t  rest;                        /* 1: units with bin < 0 make bin n_bins; 0: they are dropped                 */
+    uint64_t* d_bin_off; size_t bin_cap;  /* [n_bins + rest + 1] (entries) first output row of each bin, 8-byte aligned, or NULL */
+    uint32_t row_len;                     /* OUTPUT stride (>= 1, >= the longest kept window)                           */
+    uint8_t  pad_base, pad_qual, reserved[2];
+    uint8_t* d_bases; size_t bases_cap;   /* [n_out][row_len] or NULL                                                   */
+    uint8_t* d_quals; size_t quals_cap;   /* [n_out][row_len] or NULL                                                   */
+    int32_t* d_lens;  size_t lens_cap;    /* [n_out] (entries) or NULL                                                  */
+    uint8_t* d_names; size_t names_cap;   /* blob, any alignment, or NULL                                               */
+    uint64_t* d_name_off; size_t off_cap; /* [n_out + 1] (entries), 8-byte aligned, or NULL                             */
+} rfq_group_rows_args;
+typedef struct {
+    uint64_t n_rows, n_bases, names_len;  /* of the OUTPUT                                                              */
+    uint32_t max_len, max_name;
+    uint64_t n_in, dropped_mask, dropped_short, dropped_mate;
+    uint64_t dropped_bin;                 /* n_in == n_rows + the four                                                  */
+    uint32_t n_bins_used, reserved;       /* bins that hold a row                                                       */
+} rfq_group_rows_result;
+RFQ_API int rfq_group_rows(rfq_ctx* ctx, const rfq_rows_in* rows, const rfq_group_rows_args* args, rfq_group_rows_result* res);
+
 /* The step that DECIDES, in front of rfq_select_rows: rows -> per row a keep byte, a window (start, len), a reason byte and four metrics - exactly the d_keep /
  * d_start / d_len arrays rfq_select_rows takes - and one QC summary of the batch.  Quality trimming and filtering by integer rules of this project's own
  * (a sliding window in the manner of Trimmomatic, filters in the manner of fastp; no parity with either is claimed).  No float anywhere, products in 64 bits.
@@ -802,7 +854,7 @@ RFQ_API int rfq_kmers_read(rfq_ctx* ctx, const rfq_kmers_read_args* args, rfq_km
  * compares byte by byte against the barcodes' ASCII bytes in device memory - with the same bytes in every output.  Synchronous on the context's stream, one read-back;
  * stage time through rfq_last_timings (demux:rows).
  * NOT offered: barcodes of different lengths within one set, indels, a barcode searched at several offsets or at the 3' end, N as a wildcard in a barcode; barcodes
- * read out of the name line, UMI extraction; grouping the rows by sample in one pass on the device (one rfq_select_rows call per sample does it). */
+ * read out of the name line, UMI extraction.  Grouping the rows by sample in one pass is rfq_group_rows' (d_bin = d_sample). */
 #define RFQ_DEMUX_NONE   1                /* d1 > max_mm                                                                */
 #define RFQ_DEMUX_AMBIG  2                /* d2 - d1 < min_delta                                                        */
 #define RFQ_DEMUX_SHORT  4                /* lens[i] < off + len: no window                                             */

@@ -116,6 +116,21 @@ class SelectRowsResult(C.Structure):
                 ("n_in", C.c_uint64), ("dropped_mask", C.c_uint64), ("dropped_short", C.c_uint64), ("dropped_mate", C.c_uint64)]
 
 
+class GroupRowsArgs(C.Structure):
+    _fields_ = [("d_keep", C.c_void_p), ("d_start", C.c_void_p), ("d_len", C.c_void_p), ("pairs", C.c_int32), ("min_len", C.c_uint32),
+                ("d_bin", C.c_void_p), ("n_bins", C.c_uint32), ("rest", C.c_int32), ("d_bin_off", C.c_void_p), ("bin_cap", C.c_size_t), ("row_len", C.c_uint32),
+                ("pad_base", C.c_uint8), ("pad_qual", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("d_bases", C.c_void_p), ("bases_cap", C.c_size_t), ("d_quals", C.c_void_p), ("quals_cap", C.c_size_t),
+                ("d_lens", C.c_void_p), ("lens_cap", C.c_size_t), ("d_names", C.c_void_p), ("names_cap", C.c_size_t),
+                ("d_name_off", C.c_void_p), ("off_cap", C.c_size_t)]
+
+
+class GroupRowsResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_bases", C.c_uint64), ("names_len", C.c_uint64), ("max_len", C.c_uint32), ("max_name", C.c_uint32),
+                ("n_in", C.c_uint64), ("dropped_mask", C.c_uint64), ("dropped_short", C.c_uint64), ("dropped_mate", C.c_uint64), ("dropped_bin", C.c_uint64),
+                ("n_bins_used", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 CUT_FRONT, CUT_RIGHT, CUT_TAIL = 1, 2, 4
 WHY_SHORT, WHY_N, WHY_MEANQ, WHY_LOWQ, WHY_COMPLEX = 1, 2, 4, 8, 16
 
@@ -284,6 +299,7 @@ def load(path=None):
     L.rfq_encode_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(EncodeArgs), C.POINTER(EncodeResult)]
     L.rfq_text_rows.argtypes = [C.c_void_p, C.POINTER(TextRowsArgs), C.POINTER(TextRowsResult)]
     L.rfq_select_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(SelectRowsArgs), C.POINTER(SelectRowsResult)]
+    L.rfq_group_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(GroupRowsArgs), C.POINTER(GroupRowsResult)]
     L.rfq_judge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(JudgeRowsArgs), C.POINTER(JudgeRowsResult)]
     L.rfq_adapter_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(AdapterRowsArgs), C.POINTER(AdapterRowsResult)]
     L.rfq_merge_rows.argtypes = [C.c_void_p, C.POINTER(RowsIn), C.POINTER(MergeRowsArgs), C.POINTER(MergeRowsResult)]
@@ -318,6 +334,6 @@ def load(path=None):
 
 
 EXPORTS = ["rfq_version", "rfq_create", "rfq_destroy", "rfq_last_error", "rfq_set_stream", "rfq_set_header", "rfq_get_header", "rfq_clear_header",
-           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_screen_build", "rfq_screen_rows", "rfq_kmers_init", "rfq_kmers_rows", "rfq_kmers_read", "rfq_demux_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
+           "rfq_encode_batch", "rfq_scan_batch", "rfq_decode_batch", "rfq_decode_rows", "rfq_decode_names", "rfq_rows_to_text", "rfq_encode_rows", "rfq_text_rows", "rfq_select_rows", "rfq_group_rows", "rfq_judge_rows", "rfq_adapter_rows", "rfq_merge_rows", "rfq_dedup_rows", "rfq_profile_rows", "rfq_screen_build", "rfq_screen_rows", "rfq_kmers_init", "rfq_kmers_rows", "rfq_kmers_read", "rfq_demux_rows", "rfq_last_timings", "rfq_dev_malloc", "rfq_dev_free", "rfq_copy_h2d", "rfq_copy_d2h",
            "rfq_copy_h2d_async", "rfq_copy_done", "rfq_copy_sync",
            "rfq_copy_d2d", "rfq_copy_peer", "rfq_host_alloc", "rfq_host_free", "rfq_compare_bytes", "rfq_selftest_wave", "rfq_set_option", "rfq_get_option", "rfq_option_name", "rfq_host_register", "rfq_host_unregister"]

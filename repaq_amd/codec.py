@@ -322,6 +322,24 @@ class RfqCodec:
         self._check(self._L.rfq_select_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
         return r
 
+    # --- select_rows with the kept rows grouped by a bin per unit, in one pass (rfq_group_rows)
+    def group_rows(self, n_rows, row_len_in, d_bases, d_quals, d_lens, d_names=None, names_len=0, d_name_off=None, d_bin=None, n_bins=1, rest=True, d_keep=None,
+                   d_start=None, d_len=None, pairs=False, min_len=1, row_len=0, pad_base=255, pad_qual=255, out_bin_off=None, bin_cap=0, out_bases=None, bases_cap=0,
+                   out_quals=None, quals_cap=0, out_lens=None, lens_cap=0, out_names=None, names_cap=0, out_name_off=None, off_cap=0, raw=None):
+        """rfq_group_rows: select_rows' arguments and d_bin - one int32 per unit (a row, with pairs the rows 2k / 2k + 1): 0 .. n_bins - 1, below 0 the rest bin
+        (rest=True: bin n_bins) or dropped (rest=False); a bin >= n_bins is refused.  The kept rows come out sorted by (bin, input row), stable; out_bin_off:
+        n_bins + rest + 1 uint64, the first output row of every bin and the row count last.  No output pointer at all (six of them) = a size query, an output
+        that is None is not produced.  raw: fields of the argument struct set as given (the tests' refusals).  Returns GroupRowsResult (select's fields,
+        dropped_bin, n_bins_used)."""
+        rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, False, 0)
+        a = A.GroupRowsArgs(d_keep, d_start, d_len, 1 if pairs else 0, min_len, d_bin, n_bins, 1 if rest else 0, out_bin_off, bin_cap, row_len, pad_base, pad_qual,
+                            (C.c_uint8 * 2)(), out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap, out_name_off, off_cap)
+        for k, v in (raw or {}).items():
+            setattr(a, k, v)
+        r = A.GroupRowsResult()
+        self._check(self._L.rfq_group_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
+        return r
+
     # --- the step that decides: rows -> keep, window, reason and metrics per row (rfq_judge_rows)
     def judge_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, codes=False, trim_front=0, trim_tail=0, poly_g=0, cut_front=False, cut_right=False,
                    cut_tail=False, cut_flags=None, cut_window=0, cut_mean_q=0, max_len=0, min_len=0, max_n=-1, min_mean_q=0, qual_q=0, max_lowq_pct=0,

@@ -43,9 +43,13 @@ __device__ __forceinline__ uint32_t sel_window(const SelIn& in, uint32_t i, uint
 // its row with one atomicMin.
 #define SJ_ITER 8u
 #define SJ_ROWS (256u * SJ_ITER)
-__global__ void __launch_bounds__(256) k_sel_judge(SelIn in, uint32_t* __restrict__ flag, uint64_t* __restrict__ nsz, SelStat* __restrict__ st) {
+// The body is a template over a Rule, so that a call with a further rule per unit (rfq_group_rows, enc/rows_group.h) judges through the same lines: rule.drops(g, err)
+// - the rule of its own by which row g falls, asked of every row the mask lets through, in front of `short` (and what is wrong with the row's input to it);
+// rule.bad(st, g) - where an offending row is left; rule.row(g, kept, nl) - the verdict of row g and the bytes of its name; rule.finish(st, dr) - what the rule itself
+// sums up (dr: the thread's rows that fell by it), called by every thread behind the common reduction.
+template <class Stat, class Rule> __device__ __forceinline__ void sel_judge(const SelIn& in, Stat* __restrict__ st, Rule& rule) {
     __shared__ uint32_t s_dm[4], s_ds[4], s_dt[4];
-    uint32_t ml = 0, mn = 0, err = 0, dm = 0, ds = 0, dt = 0; unsigned long long nb = 0;
+    uint32_t ml = 0, mn = 0, err = 0, dm = 0, ds = 0, dt = 0, dr = 0; unsigned long long nb = 0;
     for (uint32_t it = 0; it < SJ_ITER; it++) {
         const uint64_t g64 = (uint64_t)blockIdx.x * SJ_ROWS + it * 256u + threadIdx.x;
         if (g64 >= in.n_rows) break;
@@ -56,12 +60,14 @@ __global__ void __launch_bounds__(256) k_sel_judge(SelIn in, uint32_t* __restric
             const uint64_t a = in.name_off[g], b = in.name_off[g + 1];
             if (b < a || (g + 1u == in.n_rows && b > in.names_len)) e |= SL_ERR_NOFF; else nl = b - a;
         }
+        uint32_t re = 0; const bool falls = rule.drops(g, re);
+        if (why != 1u && falls) why = 4u;                                    // (counted behind the mask and in front of `short`)
         if (why == 0 && in.pairs) { uint32_t ms, mw, me; if (sel_window(in, g ^ 1u, ms, mw, me) != 0) why = 3u; }      // (n_rows is even: the host saw to it)
         if (e) { err |= e; atomicMin(&st->bad_row, (unsigned long long)g); }
+        if (re) { err |= re; rule.bad(st, g); }
         const bool kept = why == 0;
-        flag[g] = kept ? 1u : 0u;
-        if (nsz) nsz[g] = kept ? nl : 0ull;
-        dm += why == 1u; ds += why == 2u; dt += why == 3u;
+        rule.row(g, kept, nl);
+        dm += why == 1u; ds += why == 2u; dt += why == 3u; dr += why == 4u;
         if (kept) {
             const uint32_t n32 = nl > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)nl;
             if (w > ml) ml = w; if (n32 > mn) mn = n32; nb += w;
@@ -77,6 +83,19 @@ __global__ void __launch_bounds__(256) k_sel_judge(SelIn in, uint32_t* __restric
         if (y) atomicAdd(&st->d_short, y);
         if (z) atomicAdd(&st->d_mate, z);
     }
+    rule.finish(st, dr);
+}
+// rfq_select_rows: no further rule; the verdict goes to flag[] / nsz[]
+struct SelPlain {
+    uint32_t* __restrict__ flag; uint64_t* __restrict__ nsz;
+    __device__ __forceinline__ bool drops(uint32_t, uint32_t&) const { return false; }
+    __device__ __forceinline__ void bad(SelStat*, uint32_t) const {}
+    __device__ __forceinline__ void row(uint32_t g, bool kept, uint64_t nl) const { flag[g] = kept ? 1u : 0u; if (nsz) nsz[g] = kept ? nl : 0ull; }
+    __device__ __forceinline__ void finish(SelStat*, uint32_t) const {}
+};
+__global__ void __launch_bounds__(256) k_sel_judge(SelIn in, uint32_t* __restrict__ flag, uint64_t* __restrict__ nsz, SelStat* __restrict__ st) {
+    SelPlain rule{ flag, nsz };
+    sel_judge(in, st, rule);
 }
 
 // The tables of a compacting call, a thread per INPUT unit (select: a row, merge: a pair): pos[] / noff[] are the exclusive scans of the kept flags / kept name sizes

@@ -126,6 +126,7 @@ extern "C" void rfq_destroy(rfq_ctx* c) {
     for (auto& b : c->rows_txt) b.release();
     c->rows_stat.release(); c->names_blob.release(); c->names_off.release();
     c->dedup_fp.release(); c->dedup_score.release(); c->dedup_slot.release(); c->dedup_tab.release(); c->dedup_best.release(); c->dedup_cnt.release(); c->demux_sets.release();
+    c->group_kk.release(); c->group_used.release(); c->group_hist.release(); for (auto& b : c->group_key) b.release(); for (auto& b : c->group_idx) b.release();
     c->timer.destroy();
     if (c->copy) { (void)hipStreamDestroy(c->copy); for (auto& e : c->copy_ev) if (e) (void)hipEventDestroy(e); }
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);

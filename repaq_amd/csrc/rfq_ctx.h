@@ -190,6 +190,8 @@ struct rfq_ctx {
     DBuf dedup_fp, dedup_score, dedup_slot, dedup_tab, dedup_best, dedup_cnt;
     // rfq_demux_rows: the packed sets, their ASCII bytes and the sample table, built on the host and uploaded per call (the device scratch only grows)
     DBuf demux_sets; std::vector<uint8_t> demux_host;
+    // rfq_group_rows: the judge's word per unit, the bit per bin that holds a row, the two (key, unit) arrays of the sort and its digit table (sized per call, they only grow)
+    DBuf group_kk, group_used, group_key[2], group_idx[2], group_hist;
     std::vector<uint64_t> chunk_off;
     std::vector<uint64_t> scan_end[2];     // rfq_scan_batch: end offset of every chunk in each input stream
     StageTimer timer;

@@ -975,12 +975,13 @@ static int rows_begin(rfq_ctx* ctx) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return RFQ_OK;
 }
-// the context's verdict block as a fresh Stat: all zero, bad_row (and the text's first_empty) all ones - "no such row" under the kernels' atomicMin
+// the context's verdict block as a fresh Stat: all zero, bad_row (and the text's first_empty, the grouping's bad_unit) all ones - "no such row" under the kernels' atomicMin
 template <class Stat> static int rows_stat_fresh(rfq_ctx* ctx, hipStream_t S, Stat** dst) {
     HIPCHK(ctx, ctx->rows_stat.ensure(sizeof(Stat)));
     Stat* const d = *dst = ctx->rows_stat.as<Stat>();
     HIPCHK(ctx, hipMemsetAsync(d, 0, sizeof(Stat), S));
     if constexpr (std::is_same<Stat, TextRowsStat>::value) HIPCHK(ctx, hipMemsetAsync(&d->first_empty, 0xFF, sizeof d->first_empty, S));
+    if constexpr (std::is_same<Stat, GroupStat>::value) HIPCHK(ctx, hipMemsetAsync(&d->bad_unit, 0xFF, sizeof d->bad_unit, S));
     HIPCHK(ctx, hipMemsetAsync(&d->bad_row, 0xFF, sizeof d->bad_row, S));
     return RFQ_OK;
 }
@@ -1433,6 +1434,140 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
         [&](RowsOut& r, const SelRow* tab) -> int {
             r.vec_in = rows_vec(in->row_len, a->d_bases ? in->d_bases : nullptr, a->d_quals ? in->d_quals : nullptr);      // (of the buffers that are read)
             hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)r.n_out + r.per - 1) / r.per)), dim3(256), 0, ctx->stream, r, tab);
+            return launched(ctx, "k_sel_rows");
+        });
+}
+// ---------------------------------------------------------------- rows -> the kept rows grouped by a bin per unit, in one pass: rfq_group_rows of include/rfq_hip.h
+// rfq_select_rows with another ordering step (enc/rows_group.h).  The judging pass is select's under one more rule (k_group_judge) and leaves a word per unit and
+// every sum a size query answers - nothing is scanned in input order -, k_group_used counts the bins that hold a row: ONE read-back.  The host refuses or goes on:
+// the stable rank (group_rank: one or two passes of histogram, scan, scatter), then rows_write with tables made in OUTPUT order and select's two writers as they are.
+static const RowsStages GROUP_STAGES = { "group:judge", "group:tables", "group:rows", "group:names" };
+// The kept units sorted by (key, unit), stable: *skey / *sidx [units_out].  One pass of 8-bit digits up to 256 bins, two beyond; the first reads the judge's words.
+static int group_rank(rfq_ctx* ctx, const uint32_t* kk, uint32_t units, uint32_t units_out, uint32_t T, const uint16_t** skey, const uint32_t** sidx) {
+    hipStream_t S = ctx->stream;
+    const int passes = T > 256u ? 2 : 1;
+    for (int p = 0; p < passes; p++) { HIPCHK(ctx, ctx->group_key[p].ensure((size_t)units_out * 2 + 16)); HIPCHK(ctx, ctx->group_idx[p].ensure((size_t)units_out * 4 + 16)); }
+    const uint32_t tiles0 = (uint32_t)(((uint64_t)units + GR_TILE - 1) / GR_TILE);
+    const uint64_t cells0 = 256ull * tiles0;
+    HIPCHK(ctx, ctx->group_hist.ensure((size_t)(cells0 + 2) * 4));
+    // (the scans' scratch once, for the digit table here and for the name sizes of the output rows behind this: growing it later would wait for the device)
+    HIPCHK(ctx, ctx->b[B_SCANTMP].ensure(std::max<size_t>(1024, ((size_t)std::max<uint64_t>(cells0, 2ull * units_out) / SCAN_TILE + 2) * 16)));
+    uint32_t* hist = ctx->group_hist.as<uint32_t>();
+    for (int p = 0; p < passes; p++) {
+        GrSrc s; memset(&s, 0, sizeof s);
+        if (p == 0) { s.kk = kk; s.n = units; } else { s.key = ctx->group_key[0].as<uint16_t>(); s.idx = ctx->group_idx[0].as<uint32_t>(); s.n = units_out; }
+        s.shift = 8u * (uint32_t)p;
+        const uint32_t tiles = (uint32_t)(((uint64_t)s.n + GR_TILE - 1) / GR_TILE);
+        hipLaunchKernelGGL(k_gr_hist, dim3(tiles), dim3(256), 0, S, s, tiles, hist);
+        KCHK(ctx, "k_gr_hist");
+        scan_exclusive<uint32_t>(S, hist, hist, 256ull * tiles, ctx->b[B_SCANTMP].as<uint32_t>(), 0);
+        KCHK(ctx, "scan_exclusive");
+        hipLaunchKernelGGL(k_gr_scatter, dim3(tiles), dim3(256), 0, S, s, tiles, (const uint32_t*)hist, ctx->group_key[p].as<uint16_t>(), ctx->group_idx[p].as<uint32_t>());
+        KCHK(ctx, "k_gr_scatter");
+    }
+    *skey = ctx->group_key[passes - 1].as<uint16_t>(); *sidx = ctx->group_idx[passes - 1].as<uint32_t>();
+    return RFQ_OK;
+}
+extern "C" int rfq_group_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_group_rows_args* a, rfq_group_rows_result* res) {
+    if (!ctx || !in || !a || !res) return RFQ_E_ARG;
+    memset(res, 0, sizeof *res);
+    ctx->err.clear();
+    const uint64_t n = in->n_rows; const bool named = in->d_name_off != nullptr;
+    int rc;
+    if ((rc = rows_pairs_arg(ctx, a->pairs, n)) != RFQ_OK) return rc;
+    const bool rows_asked = !rows_size_query(a), size_query = !rows_asked && !a->d_bin_off;      // (the five outputs of select; all six)
+    if ((rc = rows_dst_len(ctx, a)) != RFQ_OK) return rc;
+    if ((rc = rows_src_len_arg(ctx, in, true)) != RFQ_OK) return rc;
+    if (n >= 0xFFFFFFF0ull) return rfq_fail(ctx, RFQ_E_ARG, "too many rows for one call (%llu)", (unsigned long long)n);
+    if ((rc = rows_dst_named(ctx, a, named)) != RFQ_OK) return rc;
+    if (n && (!in->d_lens || (a->d_bases && !in->d_bases) || (a->d_quals && !in->d_quals) || (a->d_names && in->names_len && !in->d_names)))
+        return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
+    if (n && !a->d_bin) return rfq_fail(ctx, RFQ_E_ARG, "null d_bin");
+    if (a->n_bins == 0) return rfq_fail(ctx, RFQ_E_ARG, "n_bins must be >= 1");
+    if (a->rest != 0 && a->rest != 1) return rfq_fail(ctx, RFQ_E_ARG, "rest must be 0 or 1");
+    const uint64_t T64 = (uint64_t)a->n_bins + (uint64_t)a->rest;
+    if (T64 > GR_MAX_BINS) return rfq_fail(ctx, RFQ_E_ARG, "n_bins + rest is at most %u (got %llu)", GR_MAX_BINS, (unsigned long long)T64);
+    const uint32_t T = (uint32_t)T64, nr = a->pairs ? 2u : 1u;
+    const uint64_t units = n / nr;
+    if ((rc = rows_dst_aligned(ctx, in, a, (uintptr_t)a->d_start | (uintptr_t)a->d_len | (uintptr_t)a->d_bin, "d_lens, d_start, d_len and d_bin")) != RFQ_OK) return rc;
+    if ((uintptr_t)a->d_bin_off & 7u) return rfq_fail(ctx, RFQ_E_ARG, "d_bin_off must be 8-byte aligned");
+    {   // the bytes a call can write against the bytes it reads: select's spans, with d_bin among the inputs and d_bin_off among the outputs
+        Span ins[9]; rows_src_spans(in, named, ins);
+        ins[5] = { a->d_keep, n, "d_keep" }; ins[6] = { a->d_start, n * 4ull, "d_start" }; ins[7] = { a->d_len, n * 4ull, "d_len" }; ins[8] = { a->d_bin, units * 4ull, "d_bin" };
+        Span five[5]; rows_dst_spans(a, n, in->names_len, five);
+        Span outs[6]; for (int i = 0; i < 5; i++) outs[i] = five[i];
+        outs[5] = { a->d_bin_off, std::min<unsigned long long>(a->bin_cap, T64 + 1) * 8ull, "d_bin_off" };
+        if ((rc = rows_apart(ctx, outs, ins, ": grouping in place is not offered")) != RFQ_OK) return rc;
+    }
+    if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
+    hipStream_t S = ctx->stream;
+    res->n_in = n;
+    SelIn si; memset(&si, 0, sizeof si);
+    si.lens = in->d_lens; si.name_off = in->d_name_off; si.keep = a->d_keep; si.start = a->d_start; si.len = a->d_len;
+    si.names_len = in->names_len; si.n_rows = (uint32_t)n; si.row_len = in->row_len; si.pairs = a->pairs ? 1u : 0u; si.min_len = a->min_len;
+    GroupStat hs; memset(&hs, 0, sizeof hs);
+    uint32_t* kk = nullptr;
+    if (n) {
+        ctx->timer.begin(GROUP_STAGES.judge, S);
+        GroupIn gi; memset(&gi, 0, sizeof gi);
+        gi.bin = a->d_bin; gi.n_bins = a->n_bins; gi.rest = (uint32_t)a->rest; gi.words = (T + 31u) / 32u;
+        HIPCHK(ctx, table(ctx->group_kk, (size_t)units * 4 + 16, kk));
+        HIPCHK(ctx, table(ctx->group_used, (size_t)GR_MAX_BINS / 8, gi.used));
+        HIPCHK(ctx, hipMemsetAsync(gi.used, 0, (size_t)gi.words * 4, S));
+        gi.kk = kk;
+        GroupStat* dst = nullptr;
+        if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_group_judge, dim3((uint32_t)((n + SJ_ROWS - 1u) / SJ_ROWS)), dim3(256), 0, S, si, gi, dst);
+        KCHK(ctx, "k_group_judge");
+        hipLaunchKernelGGL(k_group_used, dim3(1), dim3(256), 0, S, (const uint32_t*)gi.used, gi.words, dst);
+        KCHK(ctx, "k_group_used");
+        ctx->timer.end(S);
+        HIPCHK(ctx, ctx->fetch(&hs, dst, sizeof hs, S));
+        HIPCHK(ctx, ctx->fetch_sync(S));
+    }
+    const unsigned long long br = hs.bad_row;
+    if (hs.err & SL_ERR_LEN) return rows_len_refusal(ctx, in->row_len, br);
+    if (hs.err & SL_ERR_WIN) return rfq_fail(ctx, RFQ_E_ARG, "a window starts below 0, has a negative length or ends behind its read (first such row: %llu)", br);
+    if (hs.err & SL_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
+    if (hs.err & GR_ERR_BIN) return rfq_fail(ctx, RFQ_E_ARG, "a bin is not below n_bins = %u (first such unit: %llu)", a->n_bins, (unsigned long long)hs.bad_unit);
+    const uint32_t n_out = (uint32_t)hs.n_kept;
+    res->n_rows = n_out; res->n_bases = hs.n_bases; res->names_len = hs.names_len; res->max_len = hs.max_len; res->max_name = hs.max_name;
+    res->dropped_mask = hs.d_mask; res->dropped_short = hs.d_short; res->dropped_mate = hs.d_mate; res->dropped_bin = hs.d_bin; res->n_bins_used = hs.n_used;
+    if (size_query) { ctx->timer.collect(); return RFQ_OK; }
+    if (a->d_bin_off && a->bin_cap < T64 + 1) {
+        memset(res, 0, sizeof *res);
+        return rfq_fail(ctx, RFQ_E_NOSPACE, "output buffers too small: need %llu bin offsets (bin_cap < T + 1 = n_bins + rest + 1)", (unsigned long long)(T64 + 1));
+    }
+    if (rows_asked && (rc = rows_room(ctx, a, n_out, hs.names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
+    if (n_out == 0) {
+        if (a->d_bin_off) HIPCHK(ctx, hipMemsetAsync(a->d_bin_off, 0, (size_t)(T + 1) * 8, S));
+        return rows_none(ctx, a->d_name_off);
+    }
+    const uint32_t units_out = n_out / nr;
+    const uint16_t* skey = nullptr; const uint32_t* sidx = nullptr;
+    ctx->timer.begin("group:rank", S);
+    if ((rc = group_rank(ctx, kk, (uint32_t)units, units_out, T, &skey, &sidx)) != RFQ_OK) return rc;
+    ctx->timer.end(S);
+    RowsJudged j; j.n_out = n_out; j.names_len = hs.names_len;
+    if (named) HIPCHK(ctx, table(ctx->b[B_P], ((size_t)n_out + 2) * 8, j.noff));          // (the name sizes in output order, scanned into rows_write's offsets)
+    return rows_write(ctx, in, a, j, GROUP_STAGES,
+        [&](const uint32_t*, const uint64_t* nsz, SelRow* tab, uint64_t* ooff) -> int {
+            hipLaunchKernelGGL(k_group_tables, dim3((units_out + 255u) / 256u), dim3(256), 0, S, si, sidx, units_out, tab, (uint64_t*)nsz, a->d_lens);
+            KCHK(ctx, "k_group_tables");
+            if (named) {
+                scan_exclusive<uint64_t>(S, nsz, ooff, n_out, ctx->b[B_SCANTMP].as<uint64_t>(), 1);
+                KCHK(ctx, "scan_exclusive");
+                if (a->d_name_off) HIPCHK(ctx, hipMemcpyAsync(a->d_name_off, ooff, ((size_t)n_out + 1) * 8, hipMemcpyDeviceToDevice, S));
+            }
+            if (a->d_bin_off) {
+                hipLaunchKernelGGL(k_group_bin_off, dim3((T + 256u) / 256u), dim3(256), 0, S, skey, units_out, T, nr, a->d_bin_off);
+                KCHK(ctx, "k_group_bin_off");
+            }
+            return RFQ_OK;
+        },
+        [&](RowsOut& r, const SelRow* tab) -> int {
+            r.vec_in = rows_vec(in->row_len, a->d_bases ? in->d_bases : nullptr, a->d_quals ? in->d_quals : nullptr);      // (of the buffers that are read)
+            hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)r.n_out + r.per - 1) / r.per)), dim3(256), 0, S, r, tab);
             return launched(ctx, "k_sel_rows");
         });
 }

@@ -86,6 +86,11 @@ and leaves the sample per pair, the keep byte and the start select_rows takes, a
     dm = demux_rows(codec, t, i7, i5, sheet=[(0, 0), (1, 1), ...], pairs=True, skip1=1)                  # dm["counts"], dm["summary"]["why_combo"]: index hopping
     per_sample = split_rows(codec, t, dm["sample"], len(sheet), start=dm["start"], pairs=True)           # the unassigned rows last, whole
 
+or, in ONE pass over the rows (rfq_group_rows: a stable sort of the kept units by bin; the bins are views of one result):
+
+    g = group_rows(codec, t, dm["sample"], len(sheet), start=dm["start"], pairs=True)                    # g["bin_off"]: the first row of every bin
+    per_sample = group_parts(g)                                                                          # one read-back; None for an empty bin
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -160,9 +165,10 @@ def fastq_to_tensors(codec, fq1: torch.Tensor, fq2: torch.Tensor = None, paired=
     return out
 
 
-def _compact(codec, t, call, kw_of, row_len, pad):
-    """What select_rows and merge_pairs share: `call` (RfqCodec.select_rows / merge_rows) as a size query, then once more into five new tensors of exactly the
-    reported sizes, both ordered with torch's current stream.  kw_of(n, dev) checks the caller's own inputs and returns the arguments they become.  -> the last
+def _compact(codec, t, call, kw_of, row_len, pad, more_of=None):
+    """What select_rows, merge_pairs and group_rows share: `call` (RfqCodec.select_rows / merge_rows / group_rows) as a size query, then once more into five new
+    tensors of exactly the reported sizes, both ordered with torch's current stream.  kw_of(n, dev) checks the caller's own inputs and returns the arguments they
+    become; more_of(q, dev) makes the call's further outputs from the size query's result and returns the arguments of the writing call they become.  -> the last
     result struct, the rows dict ("bases", "quals", "lens" and, when `t` has them, "names" + "name_off")."""
     bases, quals, lens = t["bases"], t["quals"], t["lens"]
     named = t.get("name_off") is not None
@@ -180,10 +186,11 @@ def _compact(codec, t, call, kw_of, row_len, pad):
         ol = torch.empty((m,), dtype=torch.int32, device=dev)
         blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if named else None
         off = torch.zeros((m + 1,), dtype=name_off.dtype, device=dev) if named else None
+        more = more_of(q, dev) if more_of is not None else {}
         if m:
             q = call(*rows, row_len=L, pad_base=pad, pad_qual=pad, out_bases=ob.data_ptr(), bases_cap=m * L, out_quals=oq.data_ptr(), quals_cap=m * L,
                      out_lens=ol.data_ptr(), lens_cap=m, out_names=blob.data_ptr() if (named and nl) else None, names_cap=nl if named else 0,
-                     out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **kw)
+                     out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **more, **kw)
     finally:
         codec.set_stream(None)
     out = {"bases": ob, "quals": oq, "lens": ol}
@@ -208,6 +215,78 @@ def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_l
         return dict(pairs=pairs, min_len=min_len, **sel)
     q, out = _compact(codec, t, codec.select_rows, kw_of, row_len, pad)
     out["dropped"] = {"mask": int(q.dropped_mask), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}
+    return out
+
+
+def group_rows(codec, t, bin, n_bins, keep=None, start=None, length=None, pairs=False, rest=True, min_len=1, row_len=None, pad=255):
+    """select_rows with the kept rows GROUPED by `bin` in ONE pass (rfq_group_rows): bin [U] int32, one entry per unit - a row, with pairs the rows 2k / 2k + 1;
+    demux_rows' "sample" as it lies -, 0 .. n_bins - 1; a unit with bin < 0 goes to one more bin, the last (rest=True), or is dropped (rest=False); a bin >= n_bins
+    is refused.  keep / start / length / pairs / min_len / row_len / pad: select_rows'.  -> select_rows' dict with the rows sorted by (bin, input row) - a stable
+    sort, pairs stay adjacent -, plus "bin_off": [T + 1] int64 on the device, T = n_bins + rest, the first output row of every bin and the row count last, and
+    "dropped": {"mask", "bin", "short", "mate"}.  The rows of bin b are rows [bin_off[b], bin_off[b + 1]) - what select_rows gives for the mask keep & (bin == b),
+    byte for byte; group_parts cuts them out.  A size query and one call, both ordered with torch's current stream; the context goes back to its own stream
+    afterwards."""
+    T = int(n_bins) + (1 if rest else 0)
+    box = {}
+
+    def kw_of(n, dev):
+        sel = {}
+        for key, v, dts in (("d_keep", keep, (torch.bool, torch.uint8)), ("d_start", start, (torch.int32,)), ("d_len", length, (torch.int32,))):
+            if v is not None:
+                assert v.dtype in dts and v.is_contiguous() and v.numel() == n and v.device == dev, "keep: [n] bool / uint8, start / length: [n] int32, on the rows' device"
+                sel[key] = v.data_ptr()
+        assert not pairs or n % 2 == 0, "rows in pairs"
+        U = n // 2 if pairs else n
+        assert bin.dtype == torch.int32 and bin.is_contiguous() and bin.numel() == U and bin.device == dev, "bin: [U] int32 on the rows' device"
+        return dict(pairs=pairs, min_len=min_len, d_bin=bin.data_ptr() if U else None, n_bins=n_bins, rest=rest, **sel)
+
+    def more_of(q, dev):
+        box["bin_off"] = torch.zeros((T + 1,), dtype=torch.int64, device=dev)          # (no rows: every bin starts at 0, and nothing is called)
+        return dict(out_bin_off=box["bin_off"].data_ptr(), bin_cap=T + 1)
+    q, out = _compact(codec, t, codec.group_rows, kw_of, row_len, pad, more_of)
+    out["bin_off"] = box["bin_off"]
+    out["dropped"] = {"mask": int(q.dropped_mask), "bin": int(q.dropped_bin), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}
+    return out
+
+
+def group_parts(g):
+    """The bins of a group_rows result as a list of T entries, None for an empty bin, otherwise a dict of VIEWS of the result's tensors: "bases" / "quals" / "lens" -
+    the bin's rows, which are contiguous -, and, where the rows have names, "names" - the bin's slice of the blob - and "name_off" - its offsets less the first (a
+    slice of ONE new tensor that holds every bin's rows + 1 rebased offsets, made by a handful of torch calls whatever the number of bins).  rows_to_fastq and
+    encode_tensors take an entry as it stands.  ONE read-back: bin_off, with the name offsets at those rows."""
+    bin_off = g["bin_off"]
+    named = g.get("name_off") is not None
+    dev = bin_off.device
+    noff = None
+    if named:
+        noff = g["name_off"] if g["name_off"].dtype == torch.int64 else g["name_off"].view(torch.int64)
+    cut = (torch.stack([bin_off, noff[bin_off]]) if named else bin_off.unsqueeze(0)).cpu().tolist()
+    rows = cut[0]
+    used = [b for b in range(len(rows) - 1) if rows[b] != rows[b + 1]]
+    at = {}                                                                   # bin -> where its rows + 1 offsets start in `flat`
+    if named and used:
+        counts = [rows[b + 1] - rows[b] + 1 for b in used]
+        total = 0
+        for b, c in zip(used, counts):
+            at[b] = total; total += c
+        meta = torch.tensor([counts, [rows[b] - at[b] for b in used], [cut[1][b] for b in used]], dtype=torch.int64).to(dev)
+        src = torch.arange(total, device=dev) + torch.repeat_interleave(meta[1], meta[0], output_size=total)
+        flat = noff[src] - torch.repeat_interleave(meta[2], meta[0], output_size=total)
+    T = len(rows) - 1
+    out = [None] * T
+    if not used:
+        return out
+
+    def pieces(x, ends):                                                      # (one call cuts every view: a Python slice per bin and tensor costs more than the GPU's part of the call)
+        return torch.tensor_split(x, ends) if ends else (x,)
+    views = {k: pieces(g[k], rows[1:T]) for k in ("bases", "quals", "lens")}
+    if named:
+        views["names"] = pieces(g["names"], cut[1][1:T])
+        offs = dict(zip(used, pieces(flat, [at[b] for b in used[1:]])))
+    for b in used:
+        out[b] = {k: v[b] for k, v in views.items()}
+        if named:
+            out[b]["name_off"] = offs[b]
     return out
 
 
@@ -526,7 +605,8 @@ def demux_rows(codec, t, barcodes1, barcodes2=None, sheet=None, pairs=False, cod
     2 ambiguous, 4 the read ends in front of the window's end, 8 both matched but the pair is not in the sheet, 128 masked by `keep`), "best": [n] int32 (the row's
     nearest barcode, -1 where nothing was compared), "dist": [n] uint8 (its distance, 255 where best is -1), "keep": [n] uint8 and "start": [n] int32 - what
     select_rows and split_rows take: 1 and the first base behind barcode and linker for the rows of an assigned unit, 0 and 0 otherwise -, "counts": [n_samples + 1]
-    int64 (the candidate units per sample, last the unassigned), "summary": dict of the batch's counts}.  A unit is a row, with pairs the rows 2k / 2k + 1 (U units).
+    int64 (the candidate units per sample, last the unassigned), "summary": dict of the batch's counts}.  A unit is a row, with pairs the rows 2k / 2k + 1 (U units);
+    "sample" is what group_rows takes as bin and split_rows as sample.
     barcodes1 / barcodes2: a list of str / bytes of ONE length per set (1 .. 32 bases, at most 4096, A C G T), read at [off, off + len) of R1 / R2; barcodes2 and
     sheet need pairs.  sheet: a list of (i, j), sample s the pair listed s-th; None: every combination, sample i * n2 + j.  A row matches with d1 <= max_mm and
     d2 - d1 >= min_delta, d1 / d2 the Hamming distances of the best and the second-best barcode (an N never agrees; min_delta=0 lets the lowest index win a tie).
@@ -565,7 +645,7 @@ def split_rows(codec, t, sample, n_samples, start=None, length=None, pairs=False
     row_len, pad.  select_rows' min_len = 1 holds here too: a unit one of whose rows has nothing left behind its start (barcode, prefix and linker took the whole read,
     or an unassigned mate is empty) is dropped from its bin with both rows, so a bin may hold fewer units than demux_rows' "counts" says - the result's "dropped" counts them;
     min_len=0 keeps them, as rows of length 0 that rows_to_fastq and encode_tensors refuse.  A select_rows pass reads a mask byte and a few words per row and moves only the rows it keeps, so a pass per sample is cheap beside moving the rows
-    once (DESIGN.md has the measured time).  Grouping the rows by sample in ONE pass is not offered."""
+    once (DESIGN.md has the measured time).  group_rows + group_parts give the same bins in ONE pass over the rows."""
     dev = t["bases"].device
     n = int(t["bases"].shape[0])
     U = n // 2 if pairs else n

@@ -1,5 +1,5 @@
 // asan_common.h - what the stand-alone sanitizer programs of the rows family share (tools/select_asan_main.cpp, judge_asan_main.cpp, adapter_asan_main.cpp,
-// merge_asan_main.cpp, dedup_asan_main.cpp, profile_asan_main.cpp, screen_asan_main.cpp, kmers_asan_main.cpp, demux_asan_main.cpp): the generator, a device buffer that ends with its data, the failure line, the rows of a call.  Each program is
+// merge_asan_main.cpp, dedup_asan_main.cpp, profile_asan_main.cpp, screen_asan_main.cpp, kmers_asan_main.cpp, demux_asan_main.cpp, group_asan_main.cpp): the generator, a device buffer that ends with its data, the failure line, the rows of a call.  Each program is
 // one translation unit.
 #pragma once
 #include "../include/rfq_hip.h"
