@@ -618,7 +618,59 @@ def run_threads(jobs, timeout_s=120.0):
 # the encoder's and decoder's own result buffers): include/rfq_hip.h says "result pointers stay valid until the next call on the same context" - the next call
 # invalidates them, so each is read BEFORE the next kind's call is issued, inside its own step.
 CALL_KINDS = ("encode", "decode", "scan", "first_diff", "decode_rows", "decode_names", "text_rows", "select_rows", "judge_rows", "adapter_rows", "merge_rows",
-              "rows_to_text", "encode_rows", "dedup_rows")
+              "rows_to_text", "encode_rows", "dedup_rows", "profile_rows", "screen_rows", "kmers_rows", "demux_rows", "group_rows")
+
+# The entry points of include/rfq_hip.h a kind's step calls (beside the memory helpers every step uses).  tests/test_call_kinds.py holds this list against the
+# library's exports: an entry point that is in no step and not in NOT_A_CALL_KIND fails there by name, so the next one cannot stay out of the circuits unnoticed.
+KIND_ENTRY_POINTS = {
+    "encode": ("rfq_encode_batch",), "decode": ("rfq_decode_batch",), "scan": ("rfq_scan_batch",), "first_diff": ("rfq_compare_bytes",),
+    "decode_rows": ("rfq_decode_rows",), "decode_names": ("rfq_decode_names",), "text_rows": ("rfq_text_rows",), "select_rows": ("rfq_select_rows",),
+    "judge_rows": ("rfq_judge_rows",), "adapter_rows": ("rfq_adapter_rows",), "merge_rows": ("rfq_merge_rows",), "rows_to_text": ("rfq_rows_to_text",),
+    "encode_rows": ("rfq_encode_rows",), "dedup_rows": ("rfq_dedup_rows",), "profile_rows": ("rfq_profile_rows",),
+    "screen_rows": ("rfq_screen_build", "rfq_screen_rows"),
+    "kmers_rows": ("rfq_kmers_init", "rfq_kmers_rows", "rfq_kmers_read", "rfq_screen_rows"),      # (the read's index is screened with: that is what it is for)
+    "demux_rows": ("rfq_demux_rows",), "group_rows": ("rfq_group_rows",),
+}
+NOT_A_CALL_KIND = (
+    ("rfq_create", "makes the context every step runs on"), ("rfq_destroy", "ends it"), ("rfq_last_error", "read by every refusing step: the message"),
+    ("rfq_set_stream", "which stream the calls run on: tests/test_*_api.py"),
+    ("rfq_set_header", "the file in progress: check_two_batches"), ("rfq_get_header", "check_two_batches, check_header_survives_refusal"),
+    ("rfq_clear_header", "in front of every encode step"),
+    ("rfq_last_timings", "read behind steps: the stage markers"), ("rfq_version", "a constant string"),
+    ("rfq_set_option", "a switch, not a call on data: test_switches_stay_with_their_context"), ("rfq_get_option", "reads a switch"),
+    ("rfq_option_name", "lists the switches"),
+    ("rfq_dev_malloc", "memory helper: every step's buffers"), ("rfq_dev_free", "memory helper"), ("rfq_copy_h2d", "memory helper: every step's inputs"),
+    ("rfq_copy_d2h", "memory helper: every step's results"), ("rfq_copy_d2d", "memory helper"), ("rfq_copy_peer", "memory helper between two contexts"),
+    ("rfq_copy_h2d_async", "memory helper: the host queue's uploads"), ("rfq_copy_done", "asks after such an upload"), ("rfq_copy_sync", "waits for them"),
+    ("rfq_host_alloc", "pinned host memory"), ("rfq_host_free", "pinned host memory"), ("rfq_host_register", "pins the caller's"),
+    ("rfq_host_unregister", "unpins it"),
+    ("rfq_selftest_wave", "a self-test of the wave primitives: keeps nothing on the context"),
+)
+# what a fresh context's codec.timings() must show of each of these kinds (the stage names of rfq_encode.hip), collected over the calls of its step: first_results
+CALL_STAGES = {"profile_rows": ("profile:rows",), "screen_rows": ("screen:build", "screen:rows"), "kmers_rows": ("kmers:init", "kmers:rows", "kmers:read"),
+               "demux_rows": ("demux:rows",), "group_rows": ("group:judge", "group:rank", "group:tables", "group:rows", "group:names")}
+
+
+def _items(d):
+    """a dict as something that compares with =="""
+    return tuple(sorted(d.items()))
+
+
+def _slots_of(values):
+    """the non-empty slots of a screen index of these canonical values, in ascending order (include/rfq_hip.h, rfq_screen_build: "a slot is 0 (empty) or bit 63 | value")"""
+    return np.array(sorted(v | 1 << 63 for v in values), np.uint64).tobytes()
+
+
+def _index_set(body):
+    """What include/rfq_hip.h defines of a screen index's bytes: the 64-byte header, and the SET of the slots behind it - "WHICH slot a value lands in may depend on the
+    order of arrival: the index BYTES are private and may differ from run to run".  So an index comes back as (header, non-empty slots in ascending order)."""
+    slots = np.frombuffer(body[64:], np.uint64)
+    return body[:64], np.sort(slots[slots != 0]).tobytes()
+
+
+def _note(codec, marks):
+    if marks is not None:
+        marks.update(n for n, _ in codec.timings())
 
 
 class Calls:
@@ -626,14 +678,19 @@ class Calls:
     def __init__(self):
         import _adapter as A
         import _dedup as D
+        import _demux as X
+        import _group as G
         import _judge as J
+        import _kmers as K
         import _merge as M
         import _names as N
+        import _profile as P
         import _rows as W
         import _rows_enc as R
+        import _screen as Sc
         import _select as S
         import _text_rows as T
-        self.mod = dict(A=A, D=D, J=J, M=M, N=N, W=W, R=R, S=S, T=T)
+        self.mod = dict(A=A, D=D, J=J, M=M, N=N, W=W, R=R, S=S, T=T, P=P, Sc=Sc, K=K, X=X, G=G)
         self.fq1, self.fq2 = O.gen(O.NOVA_PE150, 70, seed=21)
         self.paired, self.cb = O.PE_TWO_FILES, 10000
         self.want = O.encode_file(self.fq1, self.fq2, self.paired, self.cb)
@@ -661,6 +718,7 @@ class Calls:
         self.m_want = M.expected(*self.m_rows, False)
         self.d_rows = D.planted(100, True, 53, sizes=(20, 5, 2) + (1,) * 40)
         self.d_want = D.expected(*self.d_rows, pairs=True, best=True, hist_len=8)
+        self._make_profile(P); self._make_screen(Sc); self._make_kmers(K, Sc); self._make_demux(X); self._make_group(G)
         # --- what the refusing kinds send (REFUSING_CALL_KINDS): each a fixture above with the ONE mutation its own module's refusal tests make
         import _hostile
         self.code_rows = R.rows_of(self.fq1, self.fq2, self.paired, extra="x16", codes=True)
@@ -684,6 +742,97 @@ class Calls:
             raise AssertionError("the oracle splits an SE image")
         except O.OracleError as e:
             self.split_said = str(e)
+
+    # --- the fixtures of the five kinds behind dedup: each the smallest that still takes the call's default kernel with more than one workgroup (or wave) at work
+    def _make_profile(self, P):
+        """129 pairs at row_len 150 under a keep / start / length triple: the LDS kernel, 16 units a workgroup's step"""
+        B, Q, lens = P.random_rows(258, 150, 71, codes=False)
+        start, length = P.random_windows(lens, 72)
+        keep = (np.random.default_rng(73).random(258) < 0.8).astype(np.uint8)
+        self.p_rows = (B, Q, lens, keep, start, length); self.p_kw = dict(pairs=True, cycles=150, qbins=64, len_bins=151)
+        self.p_want = P.expected(B, Q, lens, False, True, keep, start, length, 150, 64, 151)
+        assert min(self.p_want["summary"]["counted"]) > 50 and self.p_want["summary"]["max_len"] > 100
+        assert P.BAD["window_past_the_read"] == ("length", "l+1")             # (_profile.check_device_refusal: length = lens - start + 1, here in the last row)
+        bad = length.copy(); bad[-1] = lens[-1] - start[-1] + 1
+        self.p_bad = (B, Q, lens, keep, start, bad)
+
+    def _make_screen(self, Sc):
+        """two references, k = 21; 65 pairs at row_len 150, every other row with a stretch of a reference (one in four of those reverse-complemented)"""
+        rng = np.random.default_rng(74); k = 21
+        self.s_refs = [Sc.rand_seq(rng, 300), Sc.rand_seq(rng, 260)]; self.s_k = k
+        seqs = []
+        for i in range(130):
+            l = int(rng.integers(60, 151)); s = bytearray(Sc.rand_seq(rng, l))
+            if i % 2 == 0:
+                ref = self.s_refs[(i // 2) % 2]; w = int(rng.integers(k, 50)); at = int(rng.integers(0, len(ref) - w + 1))
+                piece = ref[at:at + w] if i % 8 else Sc.revcomp(ref[at:at + w])
+                p = int(rng.integers(0, l - w + 1)); s[p:p + w] = piece
+            seqs.append(bytes(s))
+        self.s_rows = Sc.rows_of(seqs, 150, "ascii", seed=75); self.s_kw = dict(pairs=True, min_hits=2, min_pct=10)
+        self.s_set = Sc.ref_set(self.s_refs, k)[0]
+        self.s_want = Sc.expected(*self.s_rows, self.s_set, k, False, **self.s_kw)
+        s = self.s_want["summary"]
+        assert 10 < s["n_matched"] < 65 and s["n_kept"] == 65 - s["n_matched"] and int((self.s_want["hits"] == 1).sum()) > 0, s
+        self.s_slots = _slots_of(self.s_set)
+
+    def _make_kmers(self, K, Sc):
+        """k = 17; 130 rows at row_len 150 in two calls of 64 and 66: three in four are stretches of one sequence of 1500 bases (either strand), so that values
+        come back within a call and in the second call, the others are of their own; an N in every tenth"""
+        rng = np.random.default_rng(76); k = 17
+        genome = Sc.rand_seq(rng, 1500); seqs = []
+        for i in range(130):
+            l = int(rng.integers(40, 151))
+            if i % 4 == 3:
+                s = Sc.rand_seq(rng, l)
+            else:
+                at = int(rng.integers(0, 1500 - l + 1)); s = genome[at:at + l] if i % 3 else Sc.revcomp(genome[at:at + l])
+            s = bytearray(s)
+            if i % 10 == 0:
+                s[l // 2] = ord("N")
+            seqs.append(bytes(s))
+        B, lens = Sc.rows_of(seqs, 150, "ascii", seed=77)
+        self.k_k = k; self.k_rows = ((B[:64], lens[:64]), (B[64:], lens[64:]))
+        (c1, km1, s1), (c2, km2, s2) = (K.model(b, l, k, False) for b, l in self.k_rows)
+        self.k_cnt = c1 + c2
+        self.k_want = [(km1, dict(s1, n_new=len(c1), n_kmers=len(c1), total=sum(c1.values()), lost=0)),
+                       (km2, dict(s2, n_new=len(set(c2) - set(c1)), n_kmers=len(self.k_cnt), total=sum(self.k_cnt.values()), lost=0))]
+        sel = {v for v, _ in K.selected(self.k_cnt, 2)}
+        # (more values than the smallest table has slots: kmers_full; values the second call adds to and values it brings; values that stay below min_count)
+        assert len(self.k_cnt) > 2048 and set(c1) & set(c2) and set(c2) - set(c1) and 200 < len(sel) < len(self.k_cnt) - 200, (len(self.k_cnt), len(sel))
+        self.k_sel_slots = _slots_of(sel)
+        self.k_screen = Sc.expected(*self.k_rows[1], sel, k, False)          # (the read's index, screened with: the second call's rows)
+        assert 0 < self.k_screen["summary"]["n_matched"] < 66
+
+    def _make_demux(self, X):
+        """two sets of 8 and 6 barcodes of 8 bases, a sheet of some of the 48 combinations; 66 pairs at row_len 64: _demux.pair_rows' units - every combination
+        exact, and every reason alone -, the ambiguous read _demux.check_pairs plants, and pairs of random bases"""
+        rng = np.random.default_rng(78); L = 64; off = (X.COMPOSE["off1"], X.COMPOSE["off2"])
+        set1 = X.distinct_barcodes(rng, 7, 8, min_dist=4); set2 = X.distinct_barcodes(rng, 6, 8, min_dist=4)
+        amb = X.mutate(set1[0], 2); set1 = set1 + [X.mutate(amb, 5)]          # (set1[7] is 2 from set1[0]: `amb` is 1 from both)
+        every = [(i, j) for i in range(8) for j in range(6)]
+        sheet = [(0, 0)] + [every[k] for k in rng.permutation(48)[:20] if every[k] != (0, 0)]
+        seqs, lens = X.pair_rows(rng, set1, set2, off, L)
+        seqs += [(X.rand_seq(rng, off[0]) + amb + X.rand_seq(rng, 20))[:L], (set2[0] + X.rand_seq(rng, 9))[:L]]; lens += [len(s) for s in seqs[-2:]]
+        while len(seqs) < 132:
+            seqs.append(X.rand_seq(rng, int(rng.integers(0, L + 1)))); lens.append(len(seqs[-1]))
+        self.x_rows = X.rows_of(seqs, L, lens=lens)
+        self.x_cfg = X.Cfg(set1, set2, sheet, pairs=True, **X.COMPOSE)
+        self.x_want = X.expected(*self.x_rows, self.x_cfg, False)
+        s = self.x_want["summary"]
+        assert all(s[f] >= 1 for f in ("why_none", "why_ambig", "why_short", "why_combo")) and 0 < s["n_exact"] < s["n_assigned"] and s["n_units"] == 66, s
+
+    def _make_group(self, G):
+        """GR_TILE + 1 units at row_len 16, with names: two tiles of the sort; 300 bins and the rest bin: both digit passes"""
+        U = G.GR_TILE + 1; rng = np.random.default_rng(79)
+        B, Q, lens, names = G.case_rows(U, 16, 79)
+        bins = rng.integers(-1, 300, U).astype(np.int32)
+        keep = (rng.random(U) < 0.9).astype(np.uint8); start = np.minimum(rng.integers(0, 4, U), lens - 1).astype(np.int32)
+        length = (rng.random(U) * (lens - start + 1)).astype(np.int32)
+        self.g_rows = (B, Q, lens, names, bins); self.g_bins = 300; self.g_kw = dict(rest=True, keep=keep, start=start, length=length)
+        e = G.expected(*self.g_rows, 300, **self.g_kw)
+        assert e["used"] > 256 and int(e["bin_off"][300]) < len(e["idx"]) and e["mask"] > 0 and e["short"] > 0 and len(e["idx"]) > 1024, (e["used"], e["mask"], e["short"], len(e["idx"]))
+        self.g_bad_unit = 1000
+        self.g_bad = bins.copy(); self.g_bad[self.g_bad_unit] = 300           # (_group.check_device_refusal: a bin equal to n_bins)
 
     # each returns every output's bytes, as something that compares with ==
     def encode(self, c):
@@ -775,6 +924,88 @@ class Calls:
         D.compare(out, summ, self.d_want, "calls circuit:")
         return tuple(sorted(raw.items())), tuple(sorted(summ.items()))
 
+    # (marks: a set that takes the stage names codec.timings() shows behind every call of the step - first_results)
+    def profile_rows(self, c, marks=None, rows=None):
+        P = self.mod["P"]; dev = P.dev_rows(c, *(rows or self.p_rows))
+        try:
+            out, summ, raw = P.run(c, dev, False, **self.p_kw)
+            _note(c, marks)
+        finally:
+            dev.free()
+        P.compare(out, summ, self.p_want, "calls circuit:")
+        return _items(raw), _items(summ)
+
+    def screen_rows(self, c, marks=None, lens=None):
+        """rfq_screen_build into an index of the step's own, then rfq_screen_rows with it; the index comes back as _index_set gives it and is the model's set"""
+        Sc = self.mod["Sc"]; idx = Sc.Index(c, self.s_refs, self.s_k)         # (compares the build's result with the model's counts)
+        try:
+            _note(c, marks)
+            index = _index_set(idx.g.body())
+            assert index[1] == self.s_slots, "the index holds %d values, the model's set %d, or others" % (len(index[1]) // 8, len(self.s_set))
+            dev = Sc.dev_rows(c, self.s_rows[0], self.s_rows[1] if lens is None else lens)
+            try:
+                out, summ, raw = Sc.run(c, dev, idx, **self.s_kw)
+                _note(c, marks)
+            finally:
+                dev.free()
+        finally:
+            idx.free()
+        Sc.compare(out, summ, self.s_want, "calls circuit:")
+        return index, _items(raw), _items(summ)
+
+    def kmers_rows(self, c, marks=None, slots=None):
+        """rfq_kmers_init on a table of the step's own, two rfq_kmers_rows into it, rfq_kmers_read: the pairs, the spectrum and the screen index, which
+        rfq_screen_rows is then given.  The table's bytes and the order of the pairs are private (include/rfq_hip.h): the pairs come back sorted, the index as
+        _index_set gives it.  slots: what kmers_full changes"""
+        K, Sc = self.mod["K"], self.mod["Sc"]
+        t = K.Table(c, self.k_k, K.pow2(2 * len(self.k_cnt)) if slots is None else slots); gi = None
+        try:
+            _note(c, marks)
+            counted = []
+            for (B, ln), (kmers, want) in zip(self.k_rows, self.k_want):
+                dev = Sc.dev_rows(c, B, ln)
+                try:
+                    got, summ, raw = t.count(dev)
+                    _note(c, marks)
+                finally:
+                    dev.free()
+                assert np.array_equal(got, kmers), "calls circuit: kmers differ, first in row %d" % int(np.nonzero(got != kmers)[0][0])
+                assert summ == want, ("calls circuit:", {f: (summ[f], want[f]) for f in K.ROWS_FIELDS if summ[f] != want[f]})
+                counted.append((raw, _items(summ)))
+            checked = t.check(hist_len=16, min_count=2, cnt=self.k_cnt, what="calls circuit")      # (the pairs, the spectrum, the header: the model's)
+            _note(c, marks)
+            got = t.read(min_count=2, index=True); gi = got["index"]
+            assert got["pairs"] == checked["pairs"] and got["summary"] == checked["summary"], "the read with an index selects otherwise"
+            index = _index_set(gi.body())
+            assert index[1] == self.k_sel_slots, "the read's index holds %d values, the model selects %d, or others" % (len(index[1]) // 8, len(self.k_sel_slots) // 8)
+            dev = Sc.dev_rows(c, *self.k_rows[1])
+            try:
+                out, summ, raw = Sc.run(c, dev, None, index=(gi.ptr, gi.n))
+            finally:
+                dev.free()
+            Sc.compare(out, summ, self.k_screen, "calls circuit, the read's index:")
+            return tuple(counted), tuple(checked["pairs"]), checked["hist"].tobytes(), _items(checked["summary"]), index, _items(raw), _items(summ)
+        finally:
+            t.free()
+            if gi is not None:
+                gi.free()
+
+    def demux_rows(self, c, marks=None, lens=None):
+        X = self.mod["X"]; dev = X.dev_rows(c, self.x_rows[0], self.x_rows[1] if lens is None else lens)
+        try:
+            out, summ, raw = X.run(c, dev, self.x_cfg, False, X.ALL)
+            _note(c, marks)
+        finally:
+            dev.free()
+        X.compare(out, summ, self.x_want, "calls circuit:")
+        return _items(raw), _items(summ)
+
+    def group_rows(self, c, marks=None):
+        G = self.mod["G"]
+        e, r, got = G.call(c, *self.g_rows, self.g_bins, per_bin=False, **self.g_kw)       # (a size query and the writing call, both against _group.expected)
+        _note(c, marks)
+        return G.fields_of(r), _items(got)
+
     # --- the refusing kinds: each raises AssertionError unless the call is refused with the code, and the fragment of the message, its module's own tests expect
     @staticmethod
     def _refused(codes, fragment, f, exact=False):
@@ -822,6 +1053,37 @@ class Calls:
         D = self.mod["D"]; B, Q, lens = self.d_rows; lens, needle = self._too_long(lens, B.shape[1])
         return self._on_rows(c, D.dev_rows(c, B, Q, lens), lambda d: self._refused((-3,), needle, lambda: D.run(c, d, pairs=True, best=True, hist_len=8)))
 
+    def bad_profile_rows(self, c):
+        """a window past the read in the last row: the call's own exit (PF_ERR_WIN), beside the family's bad length"""
+        needle = "ends behind its read: start < 0, len < 0 or start + len > lens[i] (first such row: %d)" % (len(self.p_bad[2]) - 1)
+        return self._refused((-3,), needle, lambda: self.profile_rows(c, rows=self.p_bad))
+
+    def bad_screen_rows(self, c):
+        lens, needle = self._too_long(self.s_rows[1], self.s_rows[0].shape[1])
+        return self._refused((-3,), needle, lambda: self.screen_rows(c, lens=lens))      # (the build in front of it is a good one)
+
+    def bad_kmers_rows(self, c):
+        K, Sc = self.mod["K"], self.mod["Sc"]; B, lens = self.k_rows[0]; lens, needle = self._too_long(lens, B.shape[1])
+        t = K.Table(c, self.k_k, K.pow2(2 * len(self.k_cnt)))
+        try:
+            return self._on_rows(c, Sc.dev_rows(c, B, lens), lambda d: self._refused((-3,), needle, lambda: t.count(d)))
+        finally:
+            t.free()
+
+    def kmers_full(self, c):
+        """the good rows into a table of the smallest size, which has fewer slots than they have values: refused behind the kernels, the table is discarded"""
+        return self._refused((RFQ_E_NOSPACE,), "the table is too full", lambda: self.kmers_rows(c, slots=1024))
+
+    def bad_demux_rows(self, c):
+        lens, needle = self._too_long(self.x_rows[1], self.x_rows[0].shape[1])
+        return self._refused((-3,), needle, lambda: self.demux_rows(c, lens=lens))
+
+    def bad_group_rows(self, c):
+        G = self.mod["G"]; B, Q, lens, names, _ = self.g_rows; kw = self.g_kw
+        dev = G.dev_group(c, B, Q, lens, names, self.g_bad, kw["keep"], kw["start"], kw["length"])
+        return self._on_rows(c, dev, lambda d: self._refused((-3,), "first such unit: %d)" % self.g_bad_unit,
+                                                             lambda: c.group_rows(*d.args(), **G.kw_of(d, self.g_bins, True, False, 1))))
+
     def bad_rows_to_text(self, c):
         dev = self.mod["W"].DevRows(c, *self.code_rows)
         return self._on_rows(c, dev, lambda d: self._refused((-5,), None, lambda: c.rows_to_text(*d.args(), paired=self.paired, codes=True)))
@@ -851,7 +1113,14 @@ class Calls:
 
 
 REFUSING_CALL_KINDS = ("bad_select_rows", "bad_judge_rows", "bad_adapter_rows", "bad_merge_rows", "bad_dedup_rows", "bad_rows_to_text", "bad_encode_rows",
-                       "bad_text_rows", "bad_decode_rows", "bad_decode_names", "bad_encode", "bad_decode")
+                       "bad_text_rows", "bad_decode_rows", "bad_decode_names", "bad_encode", "bad_decode", "bad_profile_rows", "bad_screen_rows", "bad_kmers_rows",
+                       "kmers_full", "bad_demux_rows", "bad_group_rows")
+# the good kind each refusing kind is a mutation of; and the kinds without one, with the reason (tests/test_call_kinds.py: every kind is in one of the two)
+REFUSING_KIND_OF = dict({k: k[4:] for k in REFUSING_CALL_KINDS if k.startswith("bad_")}, kmers_full="kmers_rows")
+NO_REFUSING_KIND = (
+    ("scan", "the encoder's front (index and cut) and nothing behind it: its one exit on the device, enc_cut, is qual_short_late's in the refusal circuits over the inputs"),
+    ("first_diff", "compares two byte ranges: no verdict block, nothing the device can refuse"),
+)
 
 
 def calls_refusal_circuit():
@@ -878,7 +1147,12 @@ def first_results(make_codec):
     for kind in CALL_KINDS:
         c = make_codec()
         try:
-            out[kind] = getattr(calls(), kind)(c)
+            if kind in CALL_STAGES:                                          # (the step reaches the stages it is there for)
+                marks = set()
+                out[kind] = getattr(calls(), kind)(c, marks=marks)
+                assert set(CALL_STAGES[kind]) <= marks, (kind, CALL_STAGES[kind], sorted(marks))
+            else:
+                out[kind] = getattr(calls(), kind)(c)
         finally:
             c.close()
     return out
@@ -907,7 +1181,15 @@ def walk_calls(codec, first, seq, start=0, stop=None, prev=None, kinds=CALL_KIND
 # any-length kernels, the largest scratch), then a SMALL one (40 rows at a stride of 150, every one a row of the large batch) on the same context - the small one's
 # bytes and summary are a fresh context's, and the large batch again gives its own first result.  Both sizes are compared with the module's host reference inside
 # every call.  One row in 25 of the large batch is 1100 bases long, the others 100 .. 150: the host references are Python loops over the bases.
-NOTHING_LEFT_CALLS = ("decode_rows", "decode_names", "text_rows", "select_rows", "judge_rows", "adapter_rows", "merge_rows", "rows_to_text", "encode_rows")
+NOTHING_LEFT_CALLS = ("decode_rows", "decode_names", "text_rows", "select_rows", "judge_rows", "adapter_rows", "merge_rows", "rows_to_text", "encode_rows",
+                      "dedup_rows", "profile_rows", "screen_rows", "kmers_rows", "demux_rows", "group_rows")
+# the kinds that are not among them, with the reason (tests/test_call_kinds.py: every kind is in one of the two; every rows kind is above)
+NO_NOTHING_LEFT = (
+    ("encode", "the circuits over the inputs run three_records behind se150_big: buffers far larger than the batch"),
+    ("decode", "the same circuits, decoding"),
+    ("scan", "the encoder's front: the same buffers, the same circuits"),
+    ("first_diff", "keeps one word of scratch whatever the size"),
+)
 BIG_ROWS, BIG_LEN, SMALL_ROWS, SMALL_LEN = 5000, 1100, 40, 150
 
 
@@ -919,7 +1201,7 @@ def _embed(short, long_, L):
 
 
 class Batch:
-    """the inputs of the nine calls at one size, and their host references; small=True: rows that all occur in Batch(False)"""
+    """the inputs of the fifteen calls at one size, and their host references; small=True: rows that all occur in Batch(False)"""
     def __init__(self, small, mod):
         import _rows_enc as R
         A, J = mod["A"], mod["J"]
@@ -989,6 +1271,174 @@ class Batch:
     @functools.cached_property
     def m_want(self):
         return self.mod["M"].expected(*self.m_rows, False)
+
+    # --- the six kinds behind encode_rows: the batch's own rows (5000 at a stride of 1100, 40 at 150), and per-call parameters that differ in the direction that
+    # leaves something behind - the large call has the longer barcodes, the more bins, the larger k and table, the tables beyond the LDS
+    @functools.cached_property
+    def d_rows(self):
+        """the rows with planted classes: six rows in ten take the bytes and the length of one of a few others (rows 0 and 1 among them: 1100 and 150 bases in
+        the large batch), every row with scores of its own"""
+        B, Q, lens, _ = self.rows; n = len(lens); rng = np.random.default_rng(66)
+        pool = np.concatenate([[0, 1], rng.choice(np.arange(2, n), max(3, n // 100), replace=False)])
+        src = np.arange(n); planted = rng.random(n) < 0.6
+        src[planted] = pool[rng.integers(0, len(pool), int(planted.sum()))]
+        return np.ascontiguousarray(B[src]), rng.integers(0, 42, Q.shape).astype(np.uint8), lens[src]
+
+    @functools.cached_property
+    def d_want(self):
+        e = self.mod["D"].expected(*self.d_rows, best=True, hist_len=8)
+        assert e["summary"]["max_class"] >= 5 and e["summary"]["n_dups"] > len(self.d_rows[2]) // 3
+        return e
+
+    @functools.cached_property
+    def p_kw(self):
+        return dict(pairs=False, cycles=7, qbins=3, len_bins=2) if self.small else dict(pairs=True, cycles=BIG_LEN, qbins=64, len_bins=BIG_LEN + 1)
+
+    @functools.cached_property
+    def p_want(self):
+        B, Q, lens, _ = self.rows; kw = self.p_kw
+        return self.mod["P"].expected(B, Q, lens, False, kw["pairs"], self.sel["keep"], self.sel["start"], self.sel["length"], kw["cycles"], kw["qbins"], kw["len_bins"])
+
+    def _seq(self, i):
+        return self.rows[0][i, :int(self.rows[2][i])].tobytes()
+
+    @functools.cached_property
+    def s_refs(self):
+        """(references, k): the large batch k = 31 and forty of its rows whole (the first, of 1100 bases, among them); the small one k = 15 and two stretches
+        of 120 bases of its rows - 240 bases: an index of the smallest size, 1024 slots"""
+        n = len(self.rows[2])
+        return ([self._seq(0)[15:135], self._seq(n // 2)[:120]], 15) if self.small else ([self._seq(i) for i in range(0, n, n // 40)], 31)
+
+    @functools.cached_property
+    def s_kw(self):
+        return dict(pairs=not self.small, min_hits=2, min_pct=10)
+
+    @functools.cached_property
+    def s_want(self):
+        Sc = self.mod["Sc"]; refs, k = self.s_refs
+        self.s_set = Sc.ref_set(refs, k)[0]
+        e = Sc.expected(self.rows[0], self.rows[2], self.s_set, k, False, **self.s_kw)
+        assert 0 < e["summary"]["n_matched"] < e["summary"]["n_candidates"]
+        return e
+
+    @functools.cached_property
+    def k_want(self):
+        """(k, slots, cand, the model's Counter, kmers, summary): the large batch k = 31 in a table of twice its values; the small one k = 15 and its first three
+        rows, which is what the smallest table (1024 slots, for 512 values) takes"""
+        K = self.mod["K"]; B, _, lens, _ = self.rows
+        k = 15 if self.small else 31
+        cand = (np.arange(len(lens)) < 3).astype(np.uint8) if self.small else None
+        cnt, kmers, s = K.model(B, lens, k, False, cand)
+        slots = K.pow2(2 * len(cnt))
+        assert (slots == 1024 and 256 < len(cnt) <= 512) if self.small else slots >= 1 << 18, (slots, len(cnt))
+        return k, slots, cand, cnt, kmers, dict(s, n_new=len(cnt), n_kmers=len(cnt), total=sum(cnt.values()), lost=0)
+
+    @functools.cached_property
+    def x_case(self):
+        """(B, lens, Cfg): the large batch as pairs against two sets of 512 barcodes of 32 bases, every combination a sample (262144 count cells: beyond the LDS
+        table); the small one as rows against one set of 3 barcodes of 8.  The barcodes are planted into a copy of the rows - exact, with one and with three
+        mismatches, from a pool of a few hundred windows, so that the model's loop over the barcodes runs once per window -; one row in 50 keeps its own bases"""
+        X = self.mod["X"]; B, _, lens, _ = self.rows; B = B.copy(); n = len(lens); rng = np.random.default_rng(67)
+        if self.small:
+            sets = [X.distinct_barcodes(rng, 3, 8, min_dist=3)]; cfg = X.Cfg(sets[0], off1=3, skip1=2)
+        else:
+            sets = [[X.rand_seq(rng, 32) for _ in range(512)] for _ in range(2)]      # (random 32-mers: about 24 bases apart)
+            assert all(len(set(x)) == 512 for x in sets)
+            cfg = X.Cfg(sets[0], sets[1], pairs=True, off1=3, off2=0, skip1=2, skip2=1, max_mm=1, min_delta=1)
+        for m, bcs in enumerate(sets):
+            pool = []
+            for j in range(0, len(bcs), max(1, len(bcs) // 64)):
+                b = bcs[j]; pool += [b, X.mutate(b, j % len(b)), X.mutate(X.mutate(X.mutate(b, 0), 3), 5), X.mutate(b, 1, ord("N"))]
+            pool = np.array([np.frombuffer(p, np.uint8) for p in pool])
+            rows = np.arange(m, n, len(sets)); rows = rows[rows % 50 >= 2]
+            off = cfg.off[m]
+            B[rows, off:off + pool.shape[1]] = pool[rng.integers(0, len(pool), len(rows))]
+        return B, lens, cfg
+
+    @functools.cached_property
+    def x_want(self):
+        B, lens, cfg = self.x_case
+        e = self.mod["X"].expected(B, lens, cfg, False); s = e["summary"]
+        assert s["n_assigned"] > s["n_units"] // 4 and s["why_none"] > 0 and s["n_exact"] < s["n_assigned"], s
+        return e
+
+    @functools.cached_property
+    def g_case(self):
+        """(bins, n_bins, rest): the large batch over 4097 bins, all of them in reach, and the rest bin; the small one over 3 bins, and units of bin -1 fall"""
+        n = len(self.rows[2]); rng = np.random.default_rng(68)
+        if self.small:
+            return (np.arange(n) % 4 - 1).astype(np.int32), 3, False
+        bins = rng.integers(-1, 4097, n).astype(np.int32); bins[:3] = (4096, 0, -1)
+        return bins, 4097, True
+
+    def dedup_rows(self, c):
+        D = self.mod["D"]; dev = D.dev_rows(c, *self.d_rows)
+        try:
+            out, summ, raw = D.run(c, dev, best=True, hist_len=8)
+        finally:
+            dev.free()
+        D.compare(out, summ, self.d_want, "nothing left:")
+        return _items(raw), _items(summ)
+
+    def profile_rows(self, c):
+        P = self.mod["P"]; B, Q, lens, _ = self.rows
+        dev = P.dev_rows(c, B, Q, lens, self.sel["keep"], self.sel["start"], self.sel["length"])
+        try:
+            out, summ, raw = P.run(c, dev, False, **self.p_kw)
+        finally:
+            dev.free()
+        P.compare(out, summ, self.p_want, "nothing left:")
+        return _items(raw), _items(summ)
+
+    def screen_rows(self, c):
+        Sc = self.mod["Sc"]; want = self.s_want; refs, k = self.s_refs
+        idx = Sc.Index(c, refs, k)
+        try:
+            assert (idx.bytes == 64 + 8 * 1024) == self.small
+            index = _index_set(idx.g.body())
+            assert index[1] == _slots_of(self.s_set), "nothing left: the index is not the model's set"
+            dev = Sc.dev_rows(c, self.rows[0], self.rows[2])
+            try:
+                out, summ, raw = Sc.run(c, dev, idx, **self.s_kw)
+            finally:
+                dev.free()
+        finally:
+            idx.free()
+        Sc.compare(out, summ, want, "nothing left:")
+        return index, _items(raw), _items(summ)
+
+    def kmers_rows(self, c):
+        K, Sc = self.mod["K"], self.mod["Sc"]; k, slots, cand, cnt, kmers, want = self.k_want
+        t = K.Table(c, k, slots)
+        try:
+            dev = Sc.dev_rows(c, self.rows[0], self.rows[2], cand)
+            try:
+                got, summ, raw = t.count(dev)
+            finally:
+                dev.free()
+            assert np.array_equal(got, kmers), "nothing left: kmers differ, first in row %d" % int(np.nonzero(got != kmers)[0][0])
+            assert summ == want, ("nothing left:", {f: (summ[f], want[f]) for f in K.ROWS_FIELDS if summ[f] != want[f]})
+            read = t.check(hist_len=16, cnt=cnt, what="nothing left")
+            return raw, _items(summ), tuple(read["pairs"]), read["hist"].tobytes(), _items(read["summary"])
+        finally:
+            t.free()
+
+    def demux_rows(self, c):
+        X = self.mod["X"]; B, lens, cfg = self.x_case; want = self.x_want
+        dev = X.dev_rows(c, B, lens)
+        try:
+            out, summ, raw = X.run(c, dev, cfg, False, X.ALL)
+        finally:
+            dev.free()
+        X.compare(out, summ, want, "nothing left:")
+        return _items(raw), _items(summ)
+
+    def group_rows(self, c):
+        G = self.mod["G"]; B, Q, lens, names = self.rows; bins, n_bins, rest = self.g_case
+        e, r, got = G.call(c, B, Q, lens, names, bins, n_bins, rest=rest, keep=self.sel["keep"], start=self.sel["start"], length=self.sel["length"],
+                           min_len=self.sel["min_len"], per_bin=False)
+        assert (r.n_bins_used > 1000 and r.dropped_bin == 0) if rest else (r.n_bins_used == 3 and r.dropped_bin > 0), (r.n_bins_used, r.dropped_bin)
+        return G.fields_of(r), _items(got)
 
     def decode_rows(self, c):
         n, ml, B, Q, lens = self.rows_want

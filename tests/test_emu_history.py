@@ -1,17 +1,19 @@
 """CPU (the SIMT interpreter build, tests/emu): what a context carries from call to call.  Every other test makes a result once, on a context whose earlier calls
 are whatever the collection order gave; here ONE context lives through a sequence in which every input follows every other one exactly once (tests/_history.py:
 an Eulerian circuit over a dozen texts, each there for one piece of rfq_ctx state, each proven to reach that state by its stage markers on a fresh context or, where no stage shows it, by the oracle's image), and
-every image and text is the oracle's.  The same over the fourteen KINDS of call.  Then the refusals: every refusing input (and refusing kind of call) behind and in
+every image and text is the oracle's.  The same over the nineteen KINDS of call.  Then the refusals: every refusing input (and refusing kind of call) behind and in
 front of every good one and every other refusing one, each refusal the oracle's; and a small batch behind a large one for every rows call.  The interpreter runs the
 host code the product runs - the bookkeeping between calls is host code - but no two workgroups at once: races are tests/test_gpu_history.py's.
 
-A circuit costs about 0.2 s per call here, so each is cut into PARTS slices that share one context through a module fixture and run in order."""
+A circuit costs about 0.2 s per call here, so each is cut into PARTS slices (the two circuits over the kinds of call, which have grown with the kinds, into
+CALLS_PARTS) that share one context through a module fixture and run in order."""
 import pytest
 
 import _engine as E
 import _history as H
 
 PARTS = 4
+CALLS_PARTS = 8                                 # (362 and 1009 calls: no slice longer than the longest of the four that 197 and 481 calls were cut into)
 NAMES = [i.name for i in H.inputs()]
 
 
@@ -56,8 +58,8 @@ def lives(make):
     return life
 
 
-def _slice(n, part):
-    return n * part // PARTS, n * (part + 1) // PARTS
+def _slice(n, part, parts=PARTS):
+    return n * part // parts, n * (part + 1) // parts
 
 
 @pytest.mark.parametrize("k", [1, 2, 5, 12, 13])
@@ -178,23 +180,24 @@ def first(make):
     return H.first_results(make)
 
 
-@pytest.mark.parametrize("part", range(PARTS))
+@pytest.mark.parametrize("part", range(CALLS_PARTS))
 def test_every_kind_of_call_behind_every_other(lives, first, part):
     seq = H.euler(len(H.CALL_KINDS)); life = lives("calls")
-    assert len(H.CALL_KINDS) == 14 and len(seq) == 197
-    a, b = _slice(len(seq), part)
+    assert len(H.CALL_KINDS) == 19 and len(seq) == 362
+    a, b = _slice(len(seq), part, CALLS_PARTS)
     life[1] = H.walk_calls(life[0], first, seq, a, b, prev=life[1])
 
 
-@pytest.mark.parametrize("part", range(PARTS))
+@pytest.mark.parametrize("part", range(CALLS_PARTS))
 def test_every_refusing_kind_of_call_behind_and_in_front_of_every_kind(lives, first, part):
     kinds, seq = H.calls_refusal_circuit(); life = lives("refusing calls")
     g, r = len(H.CALL_KINDS), len(H.REFUSING_CALL_KINDS)
-    assert (g, r) == (14, 12) and len(kinds) == 26 and len(seq) == 2 * g * r + r * r + 1
-    a, b = _slice(len(seq), part)
+    assert (g, r) == (19, 18) and len(kinds) == 37 and len(seq) == 2 * g * r + r * r + 1 == 1009
+    a, b = _slice(len(seq), part, CALLS_PARTS)
     life[1] = H.walk_calls(life[0], first, seq, a, b, prev=life[1], kinds=kinds)
 
 
 @pytest.mark.parametrize("kind", H.NOTHING_LEFT_CALLS)
 def test_nothing_is_left_of_a_larger_call(lives, make, kind):
+    assert len(H.NOTHING_LEFT_CALLS) == 15
     H.check_nothing_left(lives("nothing left")[0], make, kind)

@@ -8,7 +8,8 @@ B. Repeats.  Inputs with many more workgroups than the device has compute units,
    move the communication between workgroups (the look-back of k_line_index, the plane words at tile edges of k_gather2, the segment counters, the chunk walk's
    atomicMin, the list chain).  Every result is compared ON the device (rfq_compare_bytes) with the oracle's, uploaded once.
 C. Contexts side by side.  include/rfq_hip.h: "distinct contexts may be used concurrently" - two and three contexts on device 0, a host thread each, walk A's
-   sequence from different offsets; per-context switches stay per context; two contexts run B's largest input at the same time (the host queue's configuration).
+   sequences (the inputs', and the one over the kinds of call) from different offsets; per-context switches stay per context; two contexts run B's largest
+   input at the same time (the host queue's configuration).
 
 B and C can SHOW a race - a mismatch names repeat, offset, chunk, section and stages - and can never rule one out: sixteen equal results are sixteen equal results.
 R is a condition of the test, not a measurement of anything.  No loop here runs until something differs or goes on after a difference."""
@@ -89,7 +90,7 @@ def test_mixed_lengths_end_with_the_file(fresh):
 
 def test_every_kind_of_call_behind_every_other(fresh):
     seq = H.euler(len(H.CALL_KINDS))
-    assert len(H.CALL_KINDS) == 14 and len(seq) == 197
+    assert len(H.CALL_KINDS) == 19 and len(seq) == 362
     H.walk_calls(fresh(), H.first_results(fresh), seq)
 
 
@@ -143,6 +144,7 @@ def test_the_header_made_survives_a_refusal_at_the_last_exit(fresh):
 
 @pytest.mark.parametrize("kind", H.NOTHING_LEFT_CALLS)
 def test_nothing_is_left_of_a_larger_call(fresh, kind):
+    assert len(H.NOTHING_LEFT_CALLS) == 15
     H.check_nothing_left(fresh(), fresh, kind)
 
 
@@ -178,7 +180,7 @@ def test_every_refusing_kind_of_call_behind_and_in_front_of_every_kind():
     assert line, tail
     s = json.loads(line[-1][8:])
     assert not s["failed"], s["failed"]
-    assert (s["g"], s["r"], s["steps"]) == (14, 12, 2 * 14 * 12 + 12 * 12 + 1), s
+    assert (s["g"], s["r"], s["steps"]) == (19, 18, 2 * 19 * 18 + 18 * 18 + 1) and s["steps"] == 1009, s
 
 
 # ---------------------------------------------------------------- B: the same result every time
@@ -309,6 +311,27 @@ def test_contexts_side_by_side_walk_the_circuit(fresh, n_threads):
         mine = _rotated(seq, i * len(seq) // n_threads)
         assert len(mine) == len(seq) and set(zip(mine, mine[1:])) == set(zip(seq, seq[1:]))
         return lambda: H.walk(codecs[i], mine, kinds[i])
+    H.run_threads([job(i) for i in range(n_threads)])
+
+
+@pytest.fixture(scope="module")
+def first(make):
+    """what every kind of call gives first on a fresh context, made once for the walks side by side"""
+    return H.first_results(make)
+
+
+@pytest.mark.parametrize("n_threads", [2, 3])
+def test_contexts_side_by_side_walk_the_calls_circuit(fresh, first, n_threads):
+    """the kinds of call - the rows family with its device-wide tables (dedup's claims, the k-mer table's claims and 64-bit adds, the profile's adds) among
+    them - on two and three contexts at the same time, each from another place of the circuit, all against one set of first results.  No refusing kinds: a
+    fault in a thread could not be contained.  One walk per context"""
+    seq = H.euler(len(H.CALL_KINDS))
+    codecs = [fresh() for _ in range(n_threads)]
+
+    def job(i):
+        mine = _rotated(seq, i * len(seq) // n_threads)
+        assert len(mine) == len(seq) and set(zip(mine, mine[1:])) == set(zip(seq, seq[1:]))
+        return lambda: H.walk_calls(codecs[i], first, mine)
     H.run_threads([job(i) for i in range(n_threads)])
 
 
