@@ -1,7 +1,8 @@
 // enc/rows_dedup.h - rows -> a keep byte per row that leaves ONE unit (a row, or a pair of rows) of every class of units with identical keys, the representative
 // and the size of every class, a class-size histogram and one summary (rfq_dedup_rows): the step between rfq_judge_rows and rfq_select_rows that relates rows to
 // each other.  It decides and moves no bytes.
-// Part of rfq_encode_kernels.h (included from there, last, behind rows_lanes.h whose 16-byte pieces, group reductions and unit walk it uses; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, behind rows_lanes.h whose 16-byte pieces, group reductions, unit walk and candidate test it uses, and behind
+// rows_kmer_lanes.h for its slot read slot_peek; not a stand-alone header).
 #pragma once
 // A key is (k, bytes [0, k)) of a row, k = min(length, key_len); a pair's key is R1's followed by R2's (include/rfq_hip.h has the rules).  Three kernels:
 //   k_dedup_key<16> / <64>   a unit of rows of up to 256 / 1024 bytes is held by a group of 16 lanes (a DPP row) / by a wave, a lane loads ONE 16-byte group of the
@@ -36,10 +37,6 @@ typedef RowsSums<DD_NSUM> DedupStat;
 
 // the key window of a row of l bytes
 __device__ __forceinline__ uint32_t dd_kwin(const DedupIn& in, uint32_t l) { return in.key_len && in.key_len < l ? in.key_len : l; }
-__device__ __forceinline__ bool dd_cand(const DedupIn& in, uint64_t u) {
-    if (!in.cand) return true;
-    return in.pairs ? (in.cand[2ull * u] != 0u && in.cand[2ull * u + 1ull] != 0u) : in.cand[u] != 0u;
-}
 // ---- the fingerprint: the sum over a key's 16-byte groups of mix(group bytes, group index) - a sum, so that the lanes' parts combine with row_sum / wave_sum in
 // any order -, then the length folded in; groups that hold no key byte add nothing, so the value is a function of the key alone.
 __device__ __forceinline__ unsigned long long dd_avalanche(unsigned long long x) {
@@ -73,7 +70,7 @@ template <int LPR> __global__ void __launch_bounds__(256) k_dedup_key(DedupIn in
     for (uint32_t it = 0; it < DD_ITER; it++) {
         const uint64_t u = ug.unit(it, DD_ITER);
         if (ug.past(u, in.n_units)) break;
-        const bool live = u < in.n_units, cand = live && dd_cand(in, u);
+        const bool live = u < in.n_units, cand = live && rows_cand(in, u);
         unsigned long long fp = 0ull, lsum = 0ull; uint32_t score = 0u;
         for (uint32_t i = 0; i < nr; i++) {
             const uint64_t g = rows_unit_row(in.pairs, u, i);
@@ -96,7 +93,7 @@ template <int LPR> __global__ void __launch_bounds__(256) k_dedup_key(DedupIn in
 // per row.
 __global__ void __launch_bounds__(64) k_dedup_key_long(DedupIn in, DedupStat* __restrict__ st) {
     const uint64_t u = blockIdx.x; const uint32_t x0 = 16u * threadIdx.x, nr = in.pairs ? 2u : 1u;
-    const bool cand = dd_cand(in, u);
+    const bool cand = rows_cand(in, u);
     unsigned long long acc[2] = { 0ull, 0ull };
     unsigned long long fp = 0ull, lsum = 0ull; uint32_t score = 0u;
     for (uint32_t i = 0; i < nr; i++) {
@@ -120,15 +117,8 @@ __global__ void __launch_bounds__(64) k_dedup_key_long(DedupIn in, DedupStat* __
     rows_sums_out<1>(acc, st->c);
 }
 
-// ---- the table.  A slot is tag32 << 32 | (unit + 1), 0 = empty.  It is read through the compare-and-swap's return value or through a relaxed agent-scope atomic
-// load and never through a plain load: another compute unit's claim is visible in the L2, not in this one's vector L1.  A slot never changes once it is claimed.
-__device__ __forceinline__ unsigned long long dd_peek(const unsigned long long* p) {
-#ifdef RFQ_SIMT_EMULATION
-    return __atomic_load_n(p, __ATOMIC_RELAXED);
-#else
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
+// ---- the table.  A slot is tag32 << 32 | (unit + 1), 0 = empty.  It is read through the compare-and-swap's return value or through slot_peek and never through a
+// plain load.  A slot never changes once it is claimed.
 // the keys of units u and v are equal: lengths first, then the bytes 16 at a time (the rows are read-only input of the call: nothing needs ordering)
 __device__ __forceinline__ bool dd_same(const DedupIn& in, uint64_t u, uint64_t v) {
     const uint32_t nr = in.pairs ? 2u : 1u;
@@ -147,6 +137,7 @@ __device__ __forceinline__ bool dd_same(const DedupIn& in, uint64_t u, uint64_t 
 }
 // grid ceil(n_units / 256) x 256 threads, a lane per unit.  The walk ends: the table has at least twice as many slots as there are units, and every unit claims at
 // most one.  Whoever claimed a class's slot, every member arrives at it: members probe the same chain from the same start, and a slot, once claimed, stays.
+// (Not sc_claim: a slot here is a tag and its claimant, equality is decided on the rows' bytes, and the walk has no bound.)
 __global__ void __launch_bounds__(256) k_dedup_claim(DedupIn in) {
     const uint64_t u = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (u >= in.n_units) return;
@@ -159,7 +150,7 @@ __global__ void __launch_bounds__(256) k_dedup_claim(DedupIn in) {
     uint64_t s = (uint64_t)(fp * 0x9E3779B97F4A7C15ull >> 20) & mask;
     if (in.collide) s = fp & 15ull;
     for (;;) {
-        unsigned long long cur = dd_peek(&in.tab[s]);
+        unsigned long long cur = slot_peek(&in.tab[s]);
         if (cur == 0ull) cur = atomicCAS(&in.tab[s], 0ull, mine);
         if (cur == 0ull) break;                                             // (claimed: the slot is my class's, and I am its first member)
         if ((cur >> 32) == tag && dd_same(in, u, (uint64_t)(uint32_t)cur - 1ull)) break;

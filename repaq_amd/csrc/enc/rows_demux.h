@@ -1,8 +1,9 @@
 // enc/rows_demux.h - rows against one or two sets of barcodes -> a sample per unit, the reason where there is none, the best barcode and its distance per row, the
 // keep byte and the start rfq_select_rows takes, a count per sample and one summary (rfq_demux_rows): the step that asks WHOSE a read is, in front of the ones that
 // trim, judge, deduplicate and screen.  It decides and moves no bytes.
-// Part of rfq_encode_kernels.h (included from there, last, behind rows_lanes.h whose 16-byte loads, unit walk, length check and sums it uses, behind rows_adapter.h
-// whose base classes - ar_bits, ar_cls - are the rule's, and behind rows_screen.h whose sc_lane turns 16 bytes into 2-bit classes; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, behind rows_lanes.h whose 16-byte loads, unit walk, candidate test, length check and sums it uses, behind
+// rows_adapter.h whose base class ar_cls is the rule's, and behind rows_kmer_lanes.h whose sc_lane turns 16 bytes into 2-bit classes and whose sc_win takes the
+// window out of them; not a stand-alone header).
 #pragma once
 // Everything is integer arithmetic on the base bytes (include/rfq_hip.h has the rules).  A barcode of up to 32 bases is 2 bits a base, base j in bits 2j and 2j + 1:
 // one 32-bit word up to 16 bases, two beyond (the host packs them).  The distance of a window to a barcode is the number of positions that do not agree - the
@@ -55,10 +56,6 @@ __device__ __forceinline__ DmRow dm_verdict(const DemuxIn& in, uint32_t best, ui
     DmRow r; r.best = (int32_t)best; r.d1 = d1;
     r.why = d1 > in.max_mm ? DM_NONE : (d2 - d1 < in.min_delta ? DM_AMBIG : 0u);
     return r;
-}
-__device__ __forceinline__ bool dm_cand(const DemuxIn& in, uint64_t u) {
-    if (!in.cand) return true;
-    return in.pairs ? (in.cand[2ull * u] != 0u && in.cand[2ull * u + 1ull] != 0u) : in.cand[u] != 0u;
 }
 
 // ---- a unit's verdict
@@ -171,7 +168,7 @@ template <int W> __global__ void __launch_bounds__(256) k_demux_rows(DemuxIn in,
         const uint64_t u = ug.unit(it, in.steps);
         if (ug.past(u, in.n_units)) break;
         if (u >= in.n_units) continue;
-        const bool cand = dm_cand(in, u);
+        const bool cand = rows_cand(in, u);
         uint32_t l[2] = { 0u, 0u }; DmRow r[2] = { dm_no_row(0u), dm_no_row(0u) };
 #pragma unroll
         for (uint32_t i = 0; i < 2u; i++) {                                  // (a constant bound: l and r stay in registers)
@@ -213,7 +210,7 @@ __global__ void __launch_bounds__(256) k_demux_rows_general(DemuxIn in, DemuxSta
     const uint32_t nr = in.pairs ? 2u : 1u;
     unsigned long long acc[DM_NSUM] = {};
     if (u < in.n_units) {
-        const bool cand = dm_cand(in, u);
+        const bool cand = rows_cand(in, u);
         uint32_t l[2] = { 0u, 0u }; DmRow r[2] = { dm_no_row(0u), dm_no_row(0u) };
 #pragma unroll
         for (uint32_t i = 0; i < 2u; i++) {                                  // (a constant bound: l and r stay in registers)

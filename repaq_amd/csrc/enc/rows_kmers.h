@@ -1,12 +1,12 @@
 // enc/rows_kmers.h - rows -> a table of the canonical k-mers they hold with a count beside each value, in a caller-owned buffer that adds up across calls
 // (rfq_kmers_init, rfq_kmers_rows), and such a table -> its spectrum, its (value, count) list and a screen index of the selected values (rfq_kmers_read): the k-mer
 // section of a QC report, the k-mer spectrum, screening by abundance.
-// Part of rfq_encode_kernels.h (included from there, last, behind rows_screen.h whose 16 positions of a lane - sc_lane, sc_win, sc_rc32, grp_next -, hash and slot
-// format it uses as they stand, behind rows_dedup.h whose slot read dd_peek and claim loop are the table's, and behind rows_lanes.h; not a stand-alone header).
+// Part of rfq_encode_kernels.h (included from there, behind rows_lanes.h and behind rows_kmer_lanes.h whose k-mers of a row - sc_kmers_row, sc_kmers_row_long - and
+// set - the slot format, the screen index's header, sc_start, sc_claim - it uses as they stand; not a stand-alone header).
 #pragma once
 // The k-mer rules are rfq_screen_rows' (include/rfq_hip.h).  The table is a 64-byte header, S slots of 64 bits (0 = empty, else bit 63 | canonical value: the
-// screen index's slot and linear probing, its hash sc_start applied to the value mixed - km_start) and S counts of 64 bits, count[s] beside slot[s].  A slot is claimed as rows_dedup.h claims one - peek, atomicCAS on
-// empty, compare -, and count[s] is added to only once slot[s] is known to hold the value; no kernel reads a count it adds to.
+// screen index's slot and linear probing, its hash sc_start applied to the value mixed - km_start) and S counts of 64 bits, count[s] beside slot[s].  A slot is
+// claimed with sc_claim, and count[s] is added to only once slot[s] is known to hold the value; no kernel reads a count it adds to.
 //   k_kmers_rows<16> / <64>    the screen's common path (a row of up to 256 / 1024 bytes held by 16 lanes / by a wave, a lane's 16 positions from three words).
 //                              LDS = true: the workgroup first combines in a table of KM_LDS_SLOTS (value, count) pairs in LDS - claimed with an LDS compare-and-
 //                              swap, added to with LDS atomics; a k-mer that finds no LDS slot within KM_LDS_PROBES probes goes straight to device memory - and
@@ -16,7 +16,7 @@
 //   k_kmers_hdr                one thread: the call's sums into the header (n_kmers, total, the INCOMPLETE flag when a k-mer was lost).
 //   k_kmers_count              a lane per slot: entries, sum of counts, the selected ones and their sum, the largest count.
 //   k_kmers_write              a lane per slot: the spectrum (bins in LDS where hist_len fits, flushed once), the list (a cursor reserved once per wave) and
-//                              the screen index of the selected values (k_screen_build's claim loop: entries are re-inserted, never copied slot by slot).
+//                              the screen index of the selected values (k_screen_build's claim: entries are re-inserted, never copied slot by slot).
 // A probe walk takes at most min(S, KM_WALK) steps (S under the collide flag), every slot number is masked to S: a table that was written over cannot hang a call or
 // take it outside its S slots and S counts.  A k-mer whose walk ends without an empty slot or its own value is LOST and counted as such: the host refuses the call.
 // All sums are integers and leave a workgroup through rows_sums_out.  A count is 64 bits wide and every add to one is a 64-bit atomicAdd (counts past 2^32 are not
@@ -68,21 +68,20 @@ typedef RowsSums<KM_RSUM> KmersReadStat;
 __device__ __forceinline__ unsigned long long km_mul(unsigned long long v) { return v * 0xFF51AFD7ED558CCDull; }
 __device__ __forceinline__ uint64_t km_start(unsigned long long v, uint64_t mask, uint32_t collide) { const unsigned long long m = km_mul(v); return sc_start(m ^ (m >> 32), mask, collide); }
 __device__ __forceinline__ void km_add_dev(const KmersIn& in, unsigned long long v, unsigned long long c, unsigned long long (&acc)[KM_NSUM]) {
-    const uint64_t mask = in.S - 1ull; const unsigned long long key = v | (1ull << 63);
-    uint64_t s = km_start(v, mask, in.collide);
-    for (uint32_t n = 0; n < in.walk; n++) {
-        unsigned long long cur = dd_peek(&in.tab[s]);
-        if (cur == 0ull) { cur = atomicCAS(&in.tab[s], 0ull, key); if (cur == 0ull) { acc[3] += 1ull; cur = key; } }      // (claimed: a value the table did not hold)
-        if (cur == key) { atomicAdd(&in.cnt[s], c); acc[2] += c; return; }  // (64 bits: a hot value's count passes 2^32 in a large file)
-        s = (s + 1ull) & mask;
-    }
-    acc[4] += c;
+    const uint64_t mask = in.S - 1ull;
+    const ScSlot at = sc_claim(in.tab, mask, km_start(v, mask, in.collide), sc_key(v), in.walk);
+    const bool held = at.s != SC_NO_SLOT;
+    if (held) atomicAdd(&in.cnt[at.s], c);                                   // (64 bits: a hot value's count passes 2^32 in a large file)
+    // (every sum under its own constant index, no branch between them: the compiler folds `acc[2] += c` and `acc[4] += c` on two paths into one add at a computed
+    // index, and sums indexed like that live in scratch)
+    acc[2] += held ? c : 0ull; acc[3] += at.claimed ? 1ull : 0ull; acc[4] += held ? 0ull : c;
 }
 __device__ __forceinline__ uint32_t km_lds_start(unsigned long long v) { return (uint32_t)(km_mul(v) >> 40) & (KM_LDS_SLOTS - 1u); }       // (bits 40 and up: every base but the first few of k > 25)
-// one occurrence: into the workgroup's LDS table where a slot is free or holds the value within KM_LDS_PROBES probes, else into device memory
+// one occurrence: into the workgroup's LDS table where a slot is free or holds the value within KM_LDS_PROBES probes, else into device memory.  (The LDS walk is
+// not sc_claim: 32-bit slot numbers, a volatile LDS read where that one takes an agent-scope load, and the count is added inside the walk.)
 template <bool LDS> __device__ __forceinline__ void km_add(const KmersIn& in, unsigned long long* lk, uint32_t* lc, unsigned long long v, unsigned long long (&acc)[KM_NSUM]) {
     if constexpr (LDS) {
-        const unsigned long long key = v | (1ull << 63);
+        const unsigned long long key = sc_key(v);
         uint32_t s = km_lds_start(v);
         for (uint32_t n = 0; n < KM_LDS_PROBES; n++) {
             unsigned long long cur = ((volatile unsigned long long*)lk)[s];
@@ -93,26 +92,11 @@ template <bool LDS> __device__ __forceinline__ void km_add(const KmersIn& in, un
     }
     km_add_dev(in, v, 1ull, acc);
 }
-// The k-mers that begin in lane a's 16 positions, b and c the next 32 (sc_count16's forming): every valid one is added; returns their number
-template <bool LDS> __device__ __forceinline__ uint32_t km_count16(const KmersIn& in, unsigned long long* lk, uint32_t* lc, const ScLane& a, const ScLane& b, const ScLane& c,
-                                                                   unsigned long long (&acc)[KM_NSUM]) {
-    if (!a.v) return 0u;
-    const uint32_t k = in.k; uint32_t kmers = 0u;
-    const unsigned long long V = (unsigned long long)a.v | ((unsigned long long)b.v << 16) | ((unsigned long long)c.v << 32), mk = (1ull << k) - 1ull;
-    const uint32_t r0 = sc_rc32(c.w), r1 = sc_rc32(b.w), r2 = sc_rc32(a.w);
-    for (uint32_t j = 0; j < 16u; j++) {
-        if (((V >> j) & mk) != mk) continue;
-        const unsigned long long f = sc_win(a.w, b.w, c.w, 2u * j, k), rc = sc_win(r0, r1, r2, 2u * (48u - j - k), k);
-        kmers++;
-        km_add<LDS>(in, lk, lc, f < rc ? f : rc, acc);
-    }
-    return kmers;
-}
 __device__ __forceinline__ bool km_counted(const KmersIn& in, uint64_t g) { return !in.cand || in.cand[g] != 0u; }
 
 // grid ceil(n_rows / (256 / LPR * steps)) x 256 threads.  A group of the workgroup (UnitGroup: LPR lanes) takes a row per step, in.steps steps.  ALL rows' lengths
-// are checked, counted or not; only a counted row's bytes are loaded.  What depends on the row only masks: the lane moves and the reductions are called by every
-// lane of the wave.
+// are checked, counted or not; only a counted row's bytes are loaded.  What depends on the row only masks: the lane moves (inside sc_kmers_row) and the reductions
+// are called by every lane of the wave.  Every valid k-mer is added where it is formed (sc_kmers_row<1>: the add's walks are not copied 16 times).
 template <int LPR, bool LDS> __global__ void __launch_bounds__(256) k_kmers_rows(KmersIn in, KmersStat* __restrict__ st) {
     const UnitGroup<LPR> ug{};
     // (a static block on the GPU and under the interpreter, whose buffer for dynamic LDS holds 64 KB)
@@ -128,13 +112,7 @@ template <int LPR, bool LDS> __global__ void __launch_bounds__(256) k_kmers_rows
         if (ug.past(g, in.n_rows)) break;
         const bool live = g < in.n_rows, counted = live && km_counted(in, g);
         const uint32_t l = live ? rows_len_checked(in, g, st, ug.gl == 0u) : 0u;
-        uint32_t b[4] = { 0u, 0u, 0u, 0u };
-        const bool mine = counted && ug.x0 < l;
-        if (mine) rows_ld16(in.b, in.vec_in, in.total, g * in.row_len, ug.x0, l, b);
-        const ScLane a = sc_lane(in.ascii, b, mine ? rows_span(ug.x0, 0u, l) : 0u);
-        ScLane n1, n2;
-        n1.w = grp_next<LPR>(a.w, 0u); n1.v = grp_next<LPR>(a.v, 0u); n2.w = grp_next<LPR>(n1.w, 0u); n2.v = grp_next<LPR>(n1.v, 0u);
-        const uint32_t nk = grp_sum<LPR>(km_count16<LDS>(in, km_key, km_cnt, a, n1, n2, acc));
+        const uint32_t nk = grp_sum<LPR>(sc_kmers_row<1>(in, ug, g, l, counted, [&](unsigned long long v) __attribute__((always_inline)) { km_add<LDS>(in, km_key, km_cnt, v, acc); }));
         if (ug.gl == 0u && live) {
             if (in.kmers) in.kmers[g] = nk;                                  // (0 for a row that is not counted: none of its bytes was loaded)
             if (counted) { acc[0] += 1ull; acc[1] += l; }
@@ -150,29 +128,13 @@ template <int LPR, bool LDS> __global__ void __launch_bounds__(256) k_kmers_rows
     rows_sums_out<4>(acc, st->c);
 }
 
-// grid n_rows x 64 threads: a wave per row (k_screen_rows_long's walk: tiles of 1024 positions, a tile's k-mers formed one step later, when lanes 62 and 63 can
-// take the next tile's first two words)
+// grid n_rows x 64 threads: a wave per row, sc_kmers_row_long's walk; every k-mer goes straight to device memory
 __global__ void __launch_bounds__(64) k_kmers_rows_long(KmersIn in, KmersStat* __restrict__ st) {
-    const uint64_t g = blockIdx.x; const uint32_t x0 = 16u * threadIdx.x;
+    const uint64_t g = blockIdx.x;
     const bool counted = km_counted(in, g);
     unsigned long long acc[KM_NSUM] = {};
     const uint32_t l = rows_len_checked(in, g, st, threadIdx.x == 0u);
-    const uint64_t rowbase = g * in.row_len;
-    uint32_t nk = 0u;
-    ScLane prev; prev.w = prev.v = 0u;
-    if (counted) for (uint64_t t0 = 0; t0 < (uint64_t)l + 1024u; t0 += 1024u) {
-        ScLane cur; cur.w = cur.v = 0u;
-        const uint64_t p0 = t0 + x0;
-        if (p0 < l) {
-            uint32_t b[4];
-            rows_ld16(in.b, in.vec_in, in.total, rowbase, (uint32_t)p0, l, b);
-            cur = sc_lane(in.ascii, b, rows_span((uint32_t)p0, 0u, l));
-        }
-        const uint32_t w0 = wave_read(cur.w, 0u), v0 = wave_read(cur.v, 0u), w1 = wave_read(cur.w, 1u), v1 = wave_read(cur.v, 1u);
-        const ScLane n1 = sc_next64(prev, w0, v0), n2 = sc_next64(n1, w1, v1);
-        nk += km_count16<false>(in, nullptr, nullptr, prev, n1, n2, acc);
-        prev = cur;
-    }
+    const uint32_t nk = sc_kmers_row_long<1>(in, g, l, counted, [&](unsigned long long v) __attribute__((always_inline)) { km_add_dev(in, v, 1ull, acc); });
     const uint32_t t = wave_sum<uint32_t>(nk);
     if (threadIdx.x == 0u) {
         if (in.kmers) in.kmers[g] = t;
@@ -247,15 +209,8 @@ __global__ void __launch_bounds__(256) k_kmers_write(KmersReadIn in, KmersReadSt
             }
         }
         if (in.itab && sel) {
-            const unsigned long long v = key & ~(1ull << 63), ikey = v | (1ull << 63); const uint64_t mask = in.iS - 1ull;
-            uint64_t p = sc_start(v, mask, in.icollide);
-            for (uint64_t n = 0; n < in.iS; n++) {
-                unsigned long long cur = dd_peek(&in.itab[p]);
-                if (cur == 0ull) cur = atomicCAS(&in.itab[p], 0ull, ikey);
-                if (cur == 0ull) { claimed[0] = claimed[0] + 1ull; break; }
-                if (cur == ikey) break;
-                p = (p + 1ull) & mask;
-            }
+            const unsigned long long v = key & ~(1ull << 63); const uint64_t mask = in.iS - 1ull;
+            if (sc_claim(in.itab, mask, sc_start(v, mask, in.icollide), sc_key(v), in.iS).claimed) claimed[0] += 1ull;
         }
     }
     if (hist_lds) {

@@ -1,6 +1,8 @@
 // enc/rows_lanes.h - what the kernels of the rows family share: the reductions over a group of lanes, a lane's 16 bytes of a row as SWAR masks, and the walk, length
-// check and sums of the calls that DECIDE (rfq_judge_rows, rfq_adapter_rows, rfq_dedup_rows: a verdict per unit - a row, or a pair of rows -, no row moved).
-// Part of rfq_encode_kernels.h (included from there, in front of the rows_*.h that use it; not a stand-alone header).
+// check, candidate test and sums of the calls that DECIDE (rfq_judge_rows, rfq_adapter_rows, rfq_dedup_rows, rfq_profile_rows, rfq_screen_rows, rfq_kmers_rows,
+// rfq_demux_rows: a verdict or a count per unit - a row, or a pair of rows -, no row moved).
+// Part of rfq_encode_kernels.h (included from there, in front of the rows_*.h that use it; not a stand-alone header).  What only the calls that read bases 2 bits
+// at a time share - a lane's classes, the k-mers of a row, the set of slots - is rows_kmer_lanes.h's.
 #pragma once
 #define ROWS_ERR_LEN 1u               // a length that is negative or greater than row_len (RFQ_E_ARG)
 // what the host reads back of a deciding call: zeroed per call, bad_row = ~0, N sums of the call's own
@@ -115,6 +117,11 @@ template <int NW, int N> __device__ __forceinline__ void rows_sums_out(unsigned 
 
 // ---- the walk of a common-path kernel: 256 threads in groups of LPR lanes, a group takes a unit (a row, or the pair of rows 2u and 2u + 1) per step
 __device__ __forceinline__ uint64_t rows_unit_row(uint32_t pairs, uint64_t u, uint32_t i) { return pairs ? 2ull * u + i : u; }
+// unit u is a candidate, of a call's *In block (cand: a byte per ROW, null = every unit; pairs): all of its rows are
+template <class In> __device__ __forceinline__ bool rows_cand(const In& in, uint64_t u) {
+    if (!in.cand) return true;
+    return in.pairs ? (in.cand[2ull * u] != 0u && in.cand[2ull * u + 1ull] != 0u) : in.cand[u] != 0u;
+}
 // A thread's place: group `grp` of the workgroup's R, lane `gl` of the group, which holds the row's bytes from x0 on.  A wave holds GW groups.
 template <int LPR> struct UnitGroup {
     static constexpr uint32_t R = 256u / LPR, GW = 64u / LPR;

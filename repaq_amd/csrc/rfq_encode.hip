@@ -1023,6 +1023,19 @@ template <size_t NO, size_t NI> static int rows_apart(rfq_ctx* ctx, const Span (
         if (sel_overlap(o.p, o.n, i.p, i.n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the input %s%s", o.what, i.what, tail);
     return RFQ_OK;
 }
+// nor may two outputs of a call that writes several tables lie on each other
+template <size_t NO> static int rows_outs_apart(rfq_ctx* ctx, const Span (&outs)[NO]) {
+    for (size_t i = 0; i < NO; i++) for (size_t k = i + 1; k < NO; k++)
+        if (sel_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the output %s", outs[i].what, outs[k].what);
+    return RFQ_OK;
+}
+// A workgroup pays for its set-up - a table in LDS it fills or flushes - once, so the grid is capped at `wg_cap` workgroups (at least one) and the steps each takes
+// follow from that: `units` units, `per_step` a step and workgroup, the steps clamped to lo .. hi.  The grid is rows_steps_grid of them: beyond hi it grows instead.
+static uint64_t rows_steps_for(uint64_t units, uint64_t per_step, uint64_t wg_cap, uint64_t lo, uint64_t hi) {
+    const uint64_t per_round = per_step * std::max<uint64_t>(wg_cap, 1u);
+    return std::min(std::max((units + per_round - 1u) / per_round, lo), hi);
+}
+static uint32_t rows_steps_grid(uint64_t units, uint64_t per_step, uint64_t steps) { return (uint32_t)((units + per_step * steps - 1u) / (per_step * steps)); }
 // ---- the plan of a compacting call (rfq_select_rows over rows, rfq_merge_rows over pairs): judge, two scans, ONE read-back; the caller refuses or goes on; tables,
 // row writer, names writer.  A caller supplies its unit count, its stage names and three launches - the judge, the tables kernel, the row writer - and keeps its own
 // argument checks (in its own order: the first refusal met is the one reported), its verdict on the Stat and its result fields.
@@ -1861,9 +1874,7 @@ extern "C" int rfq_profile_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_p
     {
         Span ins[8]; rows_src_spans(in, false, ins);
         ins[5] = { a->d_keep, n, "d_keep" }; ins[6] = { a->d_start, n * 4ull, "d_start" }; ins[7] = { a->d_len, n * 4ull, "d_len" };
-        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
-        for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) for (size_t k = i + 1; k < sizeof outs / sizeof outs[0]; k++)
-            if (sel_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the output %s", outs[i].what, outs[k].what);
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK || (rc = rows_outs_apart(ctx, outs)) != RFQ_OK) return rc;
     }
     res->n_rows = n;
     hipStream_t S = ctx->stream;
@@ -1893,13 +1904,12 @@ extern "C" int rfq_profile_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_p
     ProfileStat* dst = nullptr; ProfileStat hs;
     if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
     if (lds) {
-        const uint32_t R = in->row_len <= 256u ? 16u : 4u, gcap = std::max(1u, PF_WG_PER_CU * ctx->n_cu / (uint32_t)M);       // rows a step, workgroups of a mate
+        const uint32_t R = in->row_len <= 256u ? 16u : 4u;                    // rows a step
         const uint64_t units = n / M;
-        const uint64_t steps = std::min<uint64_t>(std::max<uint64_t>((units + (uint64_t)R * gcap - 1u) / ((uint64_t)R * gcap), 1u), PF_ROWS_MAX / R);
-        const uint64_t gm = (units + R * steps - 1u) / (R * steps);
+        const uint64_t steps = rows_steps_for(units, R, PF_WG_PER_CU * ctx->n_cu / (uint32_t)M, 1u, PF_ROWS_MAX / R);       // (the cap: workgroups of a mate)
         pi.steps = (uint32_t)steps; pi.lds_words = (uint32_t)words;
         const auto k = in->row_len <= 256u ? k_profile_rows<16> : k_profile_rows<64>;
-        hipLaunchKernelGGL(k, dim3((uint32_t)(gm * M)), dim3(256), (size_t)words * 4u, S, pi, dst);
+        hipLaunchKernelGGL(k, dim3(rows_steps_grid(units, R, steps) * (uint32_t)M), dim3(256), (size_t)words * 4u, S, pi, dst);
     } else hipLaunchKernelGGL(k_profile_rows_long, dim3((uint32_t)n), dim3(64), 0, S, pi, dst);
     KCHK(ctx, "k_profile_rows");
     ctx->timer.end(S);
@@ -2009,11 +2019,11 @@ extern "C" int rfq_screen_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_sc
     if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
     if (lds) {
         // a workgroup pays for its copy of the slots once: at most two workgroups per compute unit (one where the slots take more than 64 KiB), the steps follow
-        const uint32_t R = (uint32_t)SC_LDS_NT / (in->row_len <= 256u ? 16u : 64u), gcap = std::max(1u, ctx->n_cu * (hd.S * 8u <= 65536u ? 2u : 1u));
-        const uint64_t steps = std::max<uint64_t>((units + (uint64_t)R * gcap - 1u) / ((uint64_t)R * gcap), 1u);
+        const uint32_t R = (uint32_t)SC_LDS_NT / (in->row_len <= 256u ? 16u : 64u);
+        const uint64_t steps = rows_steps_for(units, R, ctx->n_cu * (hd.S * 8u <= 65536u ? 2u : 1u), 1u, UINT64_MAX);
         si.steps = (uint32_t)steps;
         const auto k = in->row_len <= 256u ? k_screen_rows<16, SC_LDS_NT, true> : k_screen_rows<64, SC_LDS_NT, true>;
-        hipLaunchKernelGGL(k, dim3((uint32_t)((units + R * steps - 1u) / (R * steps))), dim3(SC_LDS_NT), (size_t)hd.S * 8u, S, si, dst);
+        hipLaunchKernelGGL(k, dim3(rows_steps_grid(units, R, steps)), dim3(SC_LDS_NT), (size_t)hd.S * 8u, S, si, dst);
     } else {
         si.steps = SC_ITER;
         rows_launch_by_len(S, general, in->row_len, units, SC_ITER, k_screen_rows<16, 256, false>, k_screen_rows<64, 256, false>, k_screen_rows_long, si, dst);
@@ -2109,8 +2119,7 @@ extern "C" int rfq_kmers_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_kme
     ki.tab = (unsigned long long*)((uint8_t*)a->d_table + sizeof(KmersHdr)); ki.cnt = ki.tab + hd.S; ki.S = hd.S; ki.kmers = a->d_kmers;
     const bool general = ctx->opt.kmers == RfqOpts::KMERS_GENERAL, direct = ctx->opt.kmers == RfqOpts::KMERS_DIRECT;
     // a workgroup pays for the flush of its LDS table once: KM_WG_PER_CU workgroups per compute unit, the steps follow (at least KM_ITER, the family's walk; RFQ_KMERS=direct keeps the same grid)
-    const uint32_t R = in->row_len <= 256u ? 16u : 4u; const uint64_t gcap = std::max<uint64_t>(1, (uint64_t)KM_WG_PER_CU * ctx->n_cu);
-    ki.steps = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + R * gcap - 1u) / (R * gcap), KM_ITER), KM_STEPS_MAX);
+    ki.steps = (uint32_t)rows_steps_for(n, in->row_len <= 256u ? 16u : 4u, (uint64_t)KM_WG_PER_CU * ctx->n_cu, KM_ITER, KM_STEPS_MAX);
     ctx->timer.begin("kmers:rows", S);
     KmersStat* dst = nullptr; KmersStat hs;
     if ((rc = rows_stat_fresh(ctx, S, &dst)) != RFQ_OK) return rc;
@@ -2142,9 +2151,7 @@ extern "C" int rfq_kmers_read(rfq_ctx* ctx, const rfq_kmers_read_args* a, rfq_km
         const Span outs[] = { { a->d_hist, a->hist_len * 8ull, "d_hist" }, { a->d_values, (unsigned long long)a->list_cap * 8ull, "d_values" }, { a->d_counts, (unsigned long long)a->list_cap * 8ull, "d_counts" },
                               { a->d_index, a->index_cap, "d_index" } };
         const Span ins[] = { { a->d_table, a->table_bytes, "d_table" } };
-        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
-        for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) for (size_t k = i + 1; k < sizeof outs / sizeof outs[0]; k++)
-            if (sel_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the output %s", outs[i].what, outs[k].what);
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK || (rc = rows_outs_apart(ctx, outs)) != RFQ_OK) return rc;
     }
     hipStream_t S = ctx->stream;
     if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
@@ -2274,9 +2281,7 @@ extern "C" int rfq_demux_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_dem
         ins[5] = { a->d_in, n, "d_in" };
         const Span outs[] = { { a->d_sample, units * 4ull, "d_sample" }, { a->d_why, units, "d_why" }, { a->d_best, n * 4ull, "d_best" }, { a->d_dist, n, "d_dist" }, { a->d_keep, n, "d_keep" },
                               { a->d_start, n * 4ull, "d_start" }, { a->d_counts, ((unsigned long long)n_samples + 1ull) * 8ull, "d_counts" } };
-        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK) return rc;
-        for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) for (size_t k = i + 1; k < sizeof outs / sizeof outs[0]; k++)
-            if (sel_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return rfq_fail(ctx, RFQ_E_ARG, "the output %s overlaps the output %s", outs[i].what, outs[k].what);
+        if ((rc = rows_apart(ctx, outs, ins, "")) != RFQ_OK || (rc = rows_outs_apart(ctx, outs)) != RFQ_OK) return rc;
     }
     res->n_units = units; res->n_samples = n_samples;
     hipStream_t S = ctx->stream;
@@ -2301,10 +2306,10 @@ extern "C" int rfq_demux_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_dem
     else {
         // a workgroup pays for its copy of the sets and the flush of its counts once: DM_WG_PER_CU workgroups per compute unit, the steps follow
         di.lds_counts = a->d_counts && n_samples + 1u <= DM_LDS_COUNTS ? 1u : 0u;
-        const uint64_t gcap = std::max<uint64_t>(1, (uint64_t)DM_WG_PER_CU * ctx->n_cu), steps = std::max<uint64_t>((units + 256u * gcap - 1u) / (256u * gcap), 1u);
+        const uint64_t steps = rows_steps_for(units, 256u, (uint64_t)DM_WG_PER_CU * ctx->n_cu, 1u, UINT64_MAX);
         di.steps = (uint32_t)steps;
         const auto k = W == 1u ? k_demux_rows<1> : k_demux_rows<2>;
-        hipLaunchKernelGGL(k, dim3((uint32_t)((units + 256u * steps - 1u) / (256u * steps))), dim3(256), ((size_t)(nb[0] + nb[1]) * W + (di.lds_counts ? n_samples + 1u : 0u)) * 4u + 8u, S, di, dst);
+        hipLaunchKernelGGL(k, dim3(rows_steps_grid(units, 256u, steps)), dim3(256), ((size_t)(nb[0] + nb[1]) * W + (di.lds_counts ? n_samples + 1u : 0u)) * 4u + 8u, S, di, dst);
     }
     KCHK(ctx, "k_demux_rows");
     ctx->timer.end(S);

@@ -23,12 +23,13 @@
 #include "enc/assemble.h"                     // chunk layout (incl. the mSize bug) and image assembly
 #include "enc/rows_text.h"                    // rows -> FASTQ text in front of the encoder (rfq_rows_to_text, rfq_encode_rows)
 #include "enc/text_rows.h"                    // FASTQ text -> rows, lengths and names from the line index (rfq_text_rows)
-#include "enc/rows_lanes.h"                   // what the rows kernels below share: group reductions, 16-byte pieces, the deciding calls' walk, length check and sums
+#include "enc/rows_lanes.h"                   // what the rows kernels below share: group reductions, 16-byte pieces, the deciding calls' walk, length check, candidate test and sums
 #include "enc/rows_select.h"                  // rows -> the kept rows, trimmed, with their names (rfq_select_rows)
 #include "enc/rows_group.h"                   // rows -> the kept rows grouped by a bin per unit in one pass, trimmed, with their names and the first row of every bin (rfq_group_rows)
 #include "enc/rows_judge.h"                   // rows -> keep, window, reason and metrics per row + a QC summary (rfq_judge_rows)
 #include "enc/rows_adapter.h"                 // rows -> the length adapter removal leaves, insert sizes of the pairs + a summary (rfq_adapter_rows)
 #include "enc/rows_merge.h"                   // pairs -> one read per overlapping pair, the consensus of both mates, with R1's names (rfq_merge_rows)
+#include "enc/rows_kmer_lanes.h"              // what the kernels below that read bases 2 bits at a time share: a lane's 16 positions, the k-mers of a row, the set of slots and its one claim (behind rows_adapter.h for ar_bits / ar_cls)
 #include "enc/rows_dedup.h"                   // rows -> a keep byte that leaves one unit of every class of identical units, class sizes + a summary (rfq_dedup_rows)
 #include "enc/rows_profile.h"                 // rows under a keep / start / length triple -> per-cycle base content, position x score, length / mean-quality / GC tables (rfq_profile_rows)
 #include "enc/rows_screen.h"                  // references -> an index of canonical k-mers; rows against it -> k-mers, hits and a keep byte per row + a summary (rfq_screen_build, rfq_screen_rows)
