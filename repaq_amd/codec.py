@@ -46,6 +46,19 @@ class RfqCodec:
         if rc != A.RFQ_OK:
             raise RfqError(rc, self._L.rfq_last_error(self._h).decode("latin-1"))
 
+    def _call(self, fn, Result, *structs, more=()):
+        """THE call step: the entry point `fn` on this context with the argument structs by reference, `more` as it stands and a new Result behind them; a status
+        other than RFQ_OK raises RfqError with the context's message -> the result struct"""
+        r = Result()
+        self._check(getattr(self._L, fn)(self._h, *map(C.byref, structs), *more, C.byref(r)))
+        return r
+
+    @staticmethod
+    def _raw(a, raw):
+        """raw: fields of an argument struct set as given (the tests' refusals)"""
+        for k, v in (raw or {}).items():
+            setattr(a, k, v)
+
     def version(self):
         return self._L.rfq_version().decode()
 
@@ -110,16 +123,13 @@ class RfqCodec:
                file_off1=0, file_off2=0, nolb_from1=U64_MAX, nolb_from2=U64_MAX, d_out=None, out_cap=0, flush_all=False):
         a = A.EncodeArgs(d_fq1, n1, d_fq2, n2, paired, chunk_bases, 1 if final else 0, 1 if emit_header else 0,
                          file_off1, file_off2, nolb_from1, nolb_from2, d_out, out_cap, 1 if flush_all else 0, 0)
-        r = A.EncodeResult()
-        self._check(self._L.rfq_encode_batch(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_encode_batch", A.EncodeResult, a)
 
     # --- the plan pass of a chunk-parallel encode: where every chunk ends in the input stream(s)
     def scan(self, d_fq1, n1, d_fq2=None, n2=0, paired=SE, chunk_bases=1_000_000, final=True, file_off1=0, file_off2=0, carry_bases=0):
         """rfq_scan_batch: the plan pass.  carry_bases: bases the chunk that is open at the start of this text took from the text in front of it."""
         a = A.EncodeArgs(d_fq1, n1, d_fq2, n2, paired, chunk_bases, 1 if final else 0, 0, file_off1, file_off2, U64_MAX, U64_MAX, None, 0, 0, carry_bases)
-        r = A.ScanResult()
-        self._check(self._L.rfq_scan_batch(self._h, C.byref(a), C.byref(r)))
+        r = self._call("rfq_scan_batch", A.ScanResult, a)
         ends1 = [r.h_end1[i] for i in range(r.n_chunks)]
         ends2 = [r.h_end2[i] for i in range(r.n_chunks)] if (paired == PE_TWO_FILES and r.n_chunks) else []
         return r, ends1, ends2
@@ -131,9 +141,7 @@ class RfqCodec:
         chunk_off, n_chunks = _chunk_index(chunk_off, n_chunks)
         a = A.DecodeArgs(d_rfq, n, 1 if has_header else 0, 1 if split_pe else 0, 1 if final else 0, 1 if bug_compat else 0, d_out1, cap1, d_out2, cap2,
                          chunk_off, n_chunks, 0)
-        r = A.DecodeResult()
-        self._check(self._L.rfq_decode_batch(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_decode_batch", A.DecodeResult, a)
 
     # --- the reads of an image as fixed-stride rows (rfq_decode_rows)
     def decode_rows(self, d_rfq, n, row_len=0, codes=False, qual_offset=33, pad_base=255, pad_qual=255, d_bases=None, bases_cap=0, d_quals=None, quals_cap=0,
@@ -145,9 +153,7 @@ class RfqCodec:
         a = A.DecodeRowsArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off,
                              n_chunks, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII, qual_offset, pad_base, pad_qual, 0,
                              d_bases, bases_cap, d_quals, quals_cap, d_lens, lens_cap)
-        r = A.DecodeRowsResult()
-        self._check(self._L.rfq_decode_rows(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_decode_rows", A.DecodeRowsResult, a)
 
     def decode_rows_bytes(self, rfq: bytes, row_len=None, codes=False, qual_offset=33, pad_base=255, pad_qual=255, bases=True, quals=True, lens=True, **kw):
         """host bytes in, numpy arrays out: (n_rows, max_len, bases [n, L] uint8, quals [n, L] uint8, lens [n] int32) - None for an output not asked
@@ -184,9 +190,7 @@ class RfqCodec:
         chunk_off, n_chunks = _chunk_index(chunk_off, n_chunks)
         a = A.DecodeNamesArgs(d_rfq, n, 1 if has_header else 0, 1 if final else 0, chunk_off,
                               n_chunks, 1 if size_only else 0, d_names, names_cap, d_name_off, off_cap)
-        r = A.DecodeNamesResult()
-        self._check(self._L.rfq_decode_names(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_decode_names", A.DecodeNamesResult, a)
 
     def decode_names_bytes(self, rfq: bytes, **kw):
         """host bytes in, the list of name lines (bytes, '@' included) out"""
@@ -203,17 +207,17 @@ class RfqCodec:
 
     # --- the way back: fixed-stride rows -> FASTQ text (rfq_rows_to_text) -> image (rfq_encode_rows)
     @staticmethod
-    def _rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset):
-        return A.RowsIn(n_rows, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII, qual_offset, (C.c_uint8 * 3)(), d_bases, d_quals, d_lens, d_names, names_len, d_name_off)
+    def _rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset, base_mode=None):
+        """base_mode: the C constant as it stands instead of `codes`, for callers that keep the C constants (and the tests of the refusal)"""
+        mode = base_mode if base_mode is not None else (A.ROWS_CODE if codes else A.ROWS_ASCII)
+        return A.RowsIn(n_rows, row_len, mode, qual_offset, (C.c_uint8 * 3)(), d_bases, d_quals, d_lens, d_names, names_len, d_name_off)
 
     def rows_to_text(self, n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, paired=SE, codes=False, qual_offset=33,
                      d_out1=None, cap1=0, d_out2=None, cap2=0, size_only=False):
         """rfq_rows_to_text: rows in the layout of decode_rows (device pointers; d_lens int32, d_name_off n_rows + 1 uint64 offsets into the name lines
         d_names) -> the FASTQ text(s).  No output buffer = context-owned texts, valid until the next call.  Returns RowsTextResult."""
         a = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset)
-        r = A.RowsTextResult()
-        self._check(self._L.rfq_rows_to_text(self._h, C.byref(a), paired, d_out1, cap1, d_out2, cap2, 1 if size_only else 0, C.byref(r)))
-        return r
+        return self._call("rfq_rows_to_text", A.RowsTextResult, a, more=(paired, d_out1, cap1, d_out2, cap2, 1 if size_only else 0))
 
     def encode_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, paired=SE, codes=False, qual_offset=33,
                     chunk_bases=1_000_000, final=True, emit_header=True, file_off1=0, file_off2=0, nolb_from1=U64_MAX, nolb_from2=U64_MAX,
@@ -223,9 +227,7 @@ class RfqCodec:
         a = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, qual_offset)
         e = A.EncodeArgs(d_fq1, 0, None, 0, paired, chunk_bases, 1 if final else 0, 1 if emit_header else 0,
                          file_off1, file_off2, nolb_from1, nolb_from2, d_out, out_cap, 1 if flush_all else 0, 0)
-        r = A.EncodeResult()
-        self._check(self._L.rfq_encode_rows(self._h, C.byref(a), C.byref(e), C.byref(r)))
-        return r
+        return self._call("rfq_encode_rows", A.EncodeResult, a, e)
 
     def _put_rows(self, bases, quals, lens, names):
         """numpy rows + a list of name lines -> device buffers: (pointers to free, positional arguments of rows_to_text / encode_rows)"""
@@ -275,9 +277,7 @@ class RfqCodec:
         (n_rows, n_bases, names_len, max_len, max_name, consumed1, consumed2, input_ended)."""
         a = A.TextRowsArgs(d_fq1, n1, d_fq2, n2, paired, 1 if final else 0, file_off1, file_off2, row_len, A.ROWS_CODE if codes else A.ROWS_ASCII,
                            qual_offset, pad_base, pad_qual, 0, d_bases, bases_cap, d_quals, quals_cap, d_lens, lens_cap, d_names, names_cap, d_name_off, off_cap)
-        r = A.TextRowsResult()
-        self._check(self._L.rfq_text_rows(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_text_rows", A.TextRowsResult, a)
 
     def text_rows_bytes(self, fq1: bytes, fq2: bytes = b"", paired=SE, row_len=None, codes=False, qual_offset=33, pad_base=255, pad_qual=255, final=True, **kw):
         """host bytes in, numpy arrays out: (result of the call, bases [n, L] uint8, quals [n, L] uint8, lens [n] int32, the list of name lines).
@@ -318,9 +318,7 @@ class RfqCodec:
         rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, False, 0)
         a = A.SelectRowsArgs(d_keep, d_start, d_len, 1 if pairs else 0, min_len, row_len, pad_base, pad_qual, (C.c_uint8 * 2)(),
                              out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap, out_name_off, off_cap)
-        r = A.SelectRowsResult()
-        self._check(self._L.rfq_select_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_select_rows", A.SelectRowsResult, rows, a)
 
     # --- select_rows with the kept rows grouped by a bin per unit, in one pass (rfq_group_rows)
     def group_rows(self, n_rows, row_len_in, d_bases, d_quals, d_lens, d_names=None, names_len=0, d_name_off=None, d_bin=None, n_bins=1, rest=True, d_keep=None,
@@ -334,11 +332,8 @@ class RfqCodec:
         rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, False, 0)
         a = A.GroupRowsArgs(d_keep, d_start, d_len, 1 if pairs else 0, min_len, d_bin, n_bins, 1 if rest else 0, out_bin_off, bin_cap, row_len, pad_base, pad_qual,
                             (C.c_uint8 * 2)(), out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap, out_name_off, off_cap)
-        for k, v in (raw or {}).items():
-            setattr(a, k, v)
-        r = A.GroupRowsResult()
-        self._check(self._L.rfq_group_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        self._raw(a, raw)
+        return self._call("rfq_group_rows", A.GroupRowsResult, rows, a)
 
     # --- the step that decides: rows -> keep, window, reason and metrics per row (rfq_judge_rows)
     def judge_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, codes=False, trim_front=0, trim_tail=0, poly_g=0, cut_front=False, cut_right=False,
@@ -349,15 +344,11 @@ class RfqCodec:
         (< 0: off), min_mean_q, qual_q + max_lowq_pct, min_complexity_pct.  d_keep / d_why: n_rows bytes, d_start / d_len: n_rows int32 - what select_rows
         takes -, d_metrics: n_rows x 4 uint32 (qsum, n_cnt, lowq, trans); an output that is None is not produced.  Returns JudgeRowsResult (n_rows, n_kept,
         why_short, why_n, why_meanq, why_lowq, why_complex, bases / qsum / q20 / q30 _in and _out)."""
-        rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, codes, 0)
-        if base_mode is not None:
-            rows.base_mode = base_mode                                       # (as it stands, for callers that keep the C constants)
+        rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, codes, 0, base_mode)
         flags = cut_flags if cut_flags is not None else (A.CUT_FRONT if cut_front else 0) | (A.CUT_RIGHT if cut_right else 0) | (A.CUT_TAIL if cut_tail else 0)
         a = A.JudgeRowsArgs(trim_front, trim_tail, poly_g, flags, cut_window, cut_mean_q, max_len, min_len, max_n, min_mean_q, qual_q, max_lowq_pct,
                             min_complexity_pct, 0, d_keep, d_start, d_len, d_why, d_metrics)
-        r = A.JudgeRowsResult()
-        self._check(self._L.rfq_judge_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_judge_rows", A.JudgeRowsResult, rows, a)
 
     # --- adapter removal, in front of the judge: rows -> the length that is left, the detector, insert sizes (rfq_adapter_rows)
     def adapter_rows(self, n_rows, row_len, d_bases, d_lens, codes=False, pairs=False, min_overlap=0, max_diff=0, max_diff_pct=0, adapter1=None, adapter2=None,
@@ -367,15 +358,11 @@ class RfqCodec:
         with adapter_min and adapter_mm_per.  d_len: n_rows int32 - what select_rows takes as d_len and a later judge_rows as d_lens -, d_how: n_rows bytes
         (CUT_BY_OVERLAP | CUT_BY_ADAPTER), d_insert / d_diff: n_rows / 2 int32, d_insert_hist: hist_len uint64; an output that is None is not produced.
         Returns AdapterRowsResult (n_rows, n_pairs, pairs_found, rows_cut, rows_cut_overlap, rows_cut_adapter, bases_in, bases_out)."""
-        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
-        if base_mode is not None:
-            rows.base_mode = base_mode
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0, base_mode)
         a1 = bytes(adapter1) if adapter1 is not None else None; a2 = bytes(adapter2) if adapter2 is not None else None
         a = A.AdapterRowsArgs(1 if pairs else 0, min_overlap, max_diff, max_diff_pct, a1, len(a1) if a1 else 0, a2, len(a2) if a2 else 0, adapter_min, adapter_mm_per,
                               hist_len, d_len, d_how, d_insert, d_diff, d_insert_hist)
-        r = A.AdapterRowsResult()
-        self._check(self._L.rfq_adapter_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_adapter_rows", A.AdapterRowsResult, rows, a)
 
     # --- behind the adapter step: every pair with an insert size -> one row, the consensus of both mates (rfq_merge_rows)
     def merge_rows(self, n_rows, row_len_in, d_bases, d_quals, d_lens, d_names=None, names_len=0, d_name_off=None, d_insert=None, codes=False, row_len=0,
@@ -386,14 +373,10 @@ class RfqCodec:
         front, the reverse complement of R2 from the back, the consensus of include/rfq_hip.h where both cover a position, under R1's name.  out_*: the merged rows at
         stride row_len (up to 2 * row_len_in - 1), their lengths, name lines and n_out + 1 uint64 offsets; no output pointer at all = a size query, an output that
         is None is not produced.  Returns MergeRowsResult (n_rows, n_bases, names_len, max_len, max_name, n_pairs, overlap_bases)."""
-        rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, 0)
-        if base_mode is not None:
-            rows.base_mode = base_mode
+        rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, 0, base_mode)
         a = A.MergeRowsArgs(d_insert, row_len, pad_base, pad_qual, (C.c_uint8 * 2)(), out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap,
                             out_name_off, off_cap)
-        r = A.MergeRowsResult()
-        self._check(self._L.rfq_merge_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_merge_rows", A.MergeRowsResult, rows, a)
 
     # --- between the judge and select_rows: one unit of every class of identical units is kept (rfq_dedup_rows)
     def dedup_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, pairs=False, key_len=0, best_qual=False, mode=None, hist_len=0, d_in=None, d_keep=None,
@@ -408,9 +391,7 @@ class RfqCodec:
         rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, False, 0)
         a = A.DedupRowsArgs(1 if pairs else 0, mode if mode is not None else (A.DEDUP_BEST_QUAL if best_qual else A.DEDUP_FIRST), key_len, hist_len, d_in, d_keep,
                             d_dup_of, d_count, d_hist)
-        r = A.DedupRowsResult()
-        self._check(self._L.rfq_dedup_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_dedup_rows", A.DedupRowsResult, rows, a)
 
     # --- the report beside the steps that decide: rows under select_rows' triple -> the tables of a QC report (rfq_profile_rows)
     def profile_rows(self, n_rows, row_len, d_bases, d_quals, d_lens, codes=False, pairs=False, d_keep=None, d_start=None, d_len=None, cycles=0, qbins=0, len_bins=0,
@@ -420,13 +401,9 @@ class RfqCodec:
         i & 1) the tables, uint64 each: d_base_cnt / d_base_qsum [M][cycles][5] (positions / score sum per cycle and class A C G T other), d_qual_hist
         [M][cycles][qbins], d_len_hist [M][len_bins], d_meanq_hist [M][qbins], d_gc_hist [M][101]; the last row / bin of each collects what lies beyond; a table
         that is None is not produced.  Returns ProfileRowsResult (n_rows, max_len and, per mate, counted, bases, qsum, q20, q30, gc, other)."""
-        rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, codes, 0)
-        if base_mode is not None:
-            rows.base_mode = base_mode
+        rows = self._rows_in(n_rows, row_len, d_bases, d_quals, d_lens, None, 0, None, codes, 0, base_mode)
         a = A.ProfileRowsArgs(1 if pairs else 0, cycles, qbins, len_bins, d_keep, d_start, d_len, d_base_cnt, d_base_qsum, d_qual_hist, d_len_hist, d_meanq_hist, d_gc_hist)
-        r = A.ProfileRowsResult()
-        self._check(self._L.rfq_profile_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_profile_rows", A.ProfileRowsResult, rows, a)
 
     # --- what a read is: reference sequences -> an index of canonical k-mers, rows against it -> k-mers, hits and a keep byte (rfq_screen_build, rfq_screen_rows)
     def screen_build(self, d_refs, refs_len, d_ref_off, n_refs, k=25, d_index=None, index_cap=0, size_only=False):
@@ -435,9 +412,7 @@ class RfqCodec:
         d_index (16-byte aligned, index_cap bytes).  size_only: nothing is written, the result says how large the buffer has to be.  Returns ScreenBuildResult
         (n_refs, ref_bases, n_positions, n_kmers, slots, index_bytes)."""
         a = A.ScreenBuildArgs(k, 1 if size_only else 0, d_refs, refs_len, d_ref_off, n_refs, d_index, index_cap)
-        r = A.ScreenBuildResult()
-        self._check(self._L.rfq_screen_build(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_screen_build", A.ScreenBuildResult, a)
 
     def screen_rows(self, n_rows, row_len, d_bases, d_lens, d_index, index_bytes, codes=False, pairs=False, min_hits=1, min_pct=0, keep_matched=False, mode=None,
                     d_in=None, d_kmers=None, d_hits=None, d_keep=None, base_mode=None):
@@ -447,14 +422,10 @@ class RfqCodec:
         matches with H >= max(min_hits, 1) and 100 * H >= min_pct * K over its rows; it is kept when it does not match (keep_matched: when it does).  mode: the C
         constant as it stands, for the tests of the refusal.  Returns ScreenRowsResult (n_units, n_candidates, n_matched, n_kept, kmers, hits, bases_in,
         bases_kept)."""
-        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
-        if base_mode is not None:
-            rows.base_mode = base_mode
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0, base_mode)
         a = A.ScreenRowsArgs(1 if pairs else 0, mode if mode is not None else (A.SCREEN_KEEP_MATCHED if keep_matched else A.SCREEN_DROP_MATCHED), min_hits, min_pct,
                              d_index, index_bytes, d_in, d_kmers, d_hits, d_keep)
-        r = A.ScreenRowsResult()
-        self._check(self._L.rfq_screen_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_screen_rows", A.ScreenRowsResult, rows, a)
 
     # --- which k-mers the reads hold, and how often: a caller-owned table that adds up across calls, and its reader (rfq_kmers_init, rfq_kmers_rows, rfq_kmers_read)
     def kmers_init(self, k=25, slots=0, d_table=None, table_cap=0, size_only=False):
@@ -462,22 +433,16 @@ class RfqCodec:
         S = the power of two >= max(1024, slots) slots, 64 + 16 * S bytes; ask for slots >= 2 x the distinct values expected.  size_only: nothing is written, the
         result says how large the buffer has to be.  Returns KmersInitResult (slots, table_bytes)."""
         a = A.KmersInitArgs(k, 1 if size_only else 0, slots, d_table, table_cap)
-        r = A.KmersInitResult()
-        self._check(self._L.rfq_kmers_init(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_kmers_init", A.KmersInitResult, a)
 
     def kmers_rows(self, n_rows, row_len, d_bases, d_lens, d_table, table_bytes, codes=False, d_in=None, d_kmers=None, base_mode=None):
         """rfq_kmers_rows: adds 1 to the count of the canonical value of every valid k-mer of every counted row (qualities and names are not looked at) in a table of
         kmers_init; calls on one table add up.  d_in: n_rows bytes, non-zero = the row is counted (judge_rows' d_keep; None: all).  d_kmers: n_rows uint32 - the
         row's valid k-mers, what screen_rows' d_kmers holds - or None.  A table that is too full refuses the call (RFQ_E_NOSPACE) and stays refused until it is
         formatted again.  Returns KmersRowsResult (n_rows, n_counted, bases_in, added, n_new, n_kmers, total, lost)."""
-        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
-        if base_mode is not None:
-            rows.base_mode = base_mode
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0, base_mode)
         a = A.KmersRowsArgs(d_table, table_bytes, d_in, d_kmers)
-        r = A.KmersRowsResult()
-        self._check(self._L.rfq_kmers_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_kmers_rows", A.KmersRowsResult, rows, a)
 
     def kmers_read(self, d_table, table_bytes, min_count=1, max_count=0, size_only=False, hist_len=0, d_hist=None, d_values=None, d_counts=None, list_cap=0,
                    d_index=None, index_cap=0):
@@ -487,9 +452,7 @@ class RfqCodec:
         selected values, which screen_rows takes; an output that is None is not produced.  size_only: nothing is written.  Returns KmersReadResult (k, slots,
         n_kmers, total, max_count, n_selected, selected_total, index_slots, index_bytes)."""
         a = A.KmersReadArgs(d_table, table_bytes, min_count, max_count, 1 if size_only else 0, hist_len, d_hist, d_values, d_counts, list_cap, d_index, index_cap)
-        r = A.KmersReadResult()
-        self._check(self._L.rfq_kmers_read(self._h, C.byref(a), C.byref(r)))
-        return r
+        return self._call("rfq_kmers_read", A.KmersReadResult, a)
 
     # --- whose read is this: rows against one or two sets of barcodes (rfq_demux_rows)
     @staticmethod
@@ -515,9 +478,7 @@ class RfqCodec:
         [n_rows] int32, d_dist [n_rows] uint8, d_keep [n_rows] uint8 and d_start [n_rows] int32 - what select_rows takes -, d_counts [n_samples + 1] uint64; an
         output that is None is not produced.  raw: a dict of DemuxRowsArgs fields set as they stand, for the tests of the refusals.  Returns DemuxRowsResult
         (n_units, n_candidates, n_assigned, n_samples, n_exact, why_none, why_ambig, why_short, why_combo, bases_in, bases_out)."""
-        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0)
-        if base_mode is not None:
-            rows.base_mode = base_mode
+        rows = self._rows_in(n_rows, row_len, d_bases, None, d_lens, None, 0, None, codes, 0, base_mode)
         n1, len1, b1 = self._barcode_set(barcodes1)
         n2, len2, b2 = self._barcode_set(barcodes2)
         flat = None
@@ -525,11 +486,8 @@ class RfqCodec:
             flat = (C.c_int32 * max(2 * len(sheet), 1))(*[int(x) for p in sheet for x in p])
         a = A.DemuxRowsArgs(1 if pairs else 0, n1, len1, off1, skip1, b1, n2, len2, off2, skip2, b2, flat, len(sheet) if sheet is not None else 0, max_mm, min_delta,
                             d_in, d_sample, d_why, d_best, d_dist, d_keep, d_start, d_counts)
-        for k, v in (raw or {}).items():
-            setattr(a, k, v)
-        r = A.DemuxRowsResult()
-        self._check(self._L.rfq_demux_rows(self._h, C.byref(rows), C.byref(a), C.byref(r)))
-        return r
+        self._raw(a, raw)
+        return self._call("rfq_demux_rows", A.DemuxRowsResult, rows, a)
 
     # --- --compare on the device: first offset at which two device texts differ (n when identical)
     def first_diff(self, d_a, d_b, n) -> int:

@@ -96,11 +96,87 @@ A torch mask still works (t["bases"][keep] and so on), but the name blob then ha
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
 
 This is the only module of the package that imports torch."""
+import collections
+import contextlib
 import ctypes as C
 
 import torch
 
 from ._capi import SE, PE_TWO_FILES
+
+U8, I32, MASK, OFFS = (torch.uint8,), (torch.int32,), (torch.bool, torch.uint8), (torch.int64, torch.uint64)
+
+
+@contextlib.contextmanager
+def _on_stream(codec, dev):
+    """the context on torch's current stream of `dev` for the block, and back on its own stream afterwards, however the block ends"""
+    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    try:
+        yield
+    finally:
+        codec.set_stream(None)
+
+
+# the first eight fields are, in this order, the rows as every RfqCodec method takes them; a part that is absent, not looked at or empty is None
+_Rows = collections.namedtuple("_Rows", "n L bases quals lens names names_len name_off dev U off_dtype")
+
+
+def _rows_of(t, quals=False, names=False, pairs=False):
+    """THE check of a rows dict, before any call: "bases" [n, L >= 1] uint8, contiguous, on a GPU; the other parts contiguous, of the dtype and the count that go
+    with it, on the same device.  quals / names: True - required; None - taken when `t` has it ("name_off" decides for the names); False - not looked at.
+    pairs: n must be even, and U = n / 2 units (else U = n).  -> _Rows."""
+    bases = t["bases"]
+    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8, contiguous, on the GPU"
+    n, L = int(bases.shape[0]), int(bases.shape[1])
+    dev = bases.device
+    assert not pairs or n % 2 == 0, "rows in pairs"
+    p_q = p_n = p_o = off_dtype = None
+    nl = 0
+    if quals or (quals is None and t.get("quals") is not None):
+        q = t["quals"]
+        assert q.dtype == torch.uint8 and q.is_contiguous() and q.shape == bases.shape and q.device == dev, "quals: [n, L] uint8, contiguous, on the rows' device"
+        p_q = q.data_ptr()
+    if names or (names is None and t.get("name_off") is not None):
+        blob, off = t["names"], t["name_off"]
+        nl, off_dtype = blob.numel(), off.dtype
+        p_n = _per(blob, None, dev, U8, "names: a uint8 blob (pack_names)")
+        p_o = _per(off, n + 1, dev, OFFS, "name_off: [n + 1] int64")
+    return _Rows(n, L, bases.data_ptr(), p_q, _per(t["lens"], n, dev, I32, "lens: [n] int32"), p_n, nl, p_o, dev, n // 2 if pairs else n, off_dtype)
+
+
+def _per(x, count, dev, dtypes, what, optional=False):
+    """THE check of a tensor with one entry per row or unit (or, count=None, of any size): dtype, contiguity, count and device -> its pointer; None for an
+    optional tensor that is None and for an empty one (an empty tensor has no pointer to hand over)"""
+    if x is None and optional:
+        return None
+    assert x is not None and x.dtype in dtypes and x.is_contiguous() and (count is None or x.numel() == count) and x.device == dev, what + ", contiguous, on the rows' device"
+    return x.data_ptr() if x.numel() else None
+
+
+def _triple(keep, start, length, n, dev):
+    """select_rows' triple, checked, as the d_keep / d_start / d_len of a call (None: every row / 0 / to the end of the read)"""
+    return dict(d_keep=_mask(keep, n, dev), d_start=_per(start, n, dev, I32, "start: [n] int32", True), d_len=_per(length, n, dev, I32, "length: [n] int32", True))
+
+
+def _mask(keep, n, dev):
+    return _per(keep, n, dev, MASK, "keep: [n] bool / uint8", True)
+
+
+def _summary(r, fields):
+    return {f: int(getattr(r, f)) for f in fields}
+
+
+def _rows_out(prefix, m, L, nl, named, off_dtype, dev):
+    """Five new tensors for m rows at stride L (and, named, nl name bytes with m + 1 offsets of off_dtype) -> the rows dict, the pointers and caps as the keyword
+    arguments of the writing call (`prefix`: "d_" or "out_")"""
+    out = {"bases": torch.empty((m, L), dtype=torch.uint8, device=dev), "quals": torch.empty((m, L), dtype=torch.uint8, device=dev),
+           "lens": torch.empty((m,), dtype=torch.int32, device=dev)}
+    kw = {prefix + "bases": out["bases"].data_ptr(), "bases_cap": m * L, prefix + "quals": out["quals"].data_ptr(), "quals_cap": m * L,
+          prefix + "lens": out["lens"].data_ptr(), "lens_cap": m}
+    if named:
+        out["names"] = torch.empty((nl,), dtype=torch.uint8, device=dev); out["name_off"] = torch.zeros((m + 1,), dtype=off_dtype, device=dev)
+        kw.update({prefix + "names": out["names"].data_ptr() if nl else None, "names_cap": nl, prefix + "name_off": out["name_off"].data_ptr(), "off_cap": m + 1})
+    return out, kw
 
 
 def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offset=33, pad=255, names=False):
@@ -110,21 +186,13 @@ def decode_tensors(codec, rfq: torch.Tensor, row_len=None, codes=True, qual_offs
     A size query and the decode, both ordered with torch's current stream; the context goes back to its own stream afterwards."""
     assert rfq.dtype == torch.uint8 and rfq.is_cuda and rfq.is_contiguous(), "rfq must be a contiguous uint8 tensor on the GPU"
     n = rfq.numel()
-    codec.set_stream(torch.cuda.current_stream(rfq.device).cuda_stream)
-    try:
+    with _on_stream(codec, rfq.device):
         q = codec.decode_rows(rfq.data_ptr(), n)
         L = max(int(q.max_len), 1) if row_len is None else int(row_len)
         rows = int(q.n_rows)
-        bases = torch.empty((rows, L), dtype=torch.uint8, device=rfq.device)
-        quals = torch.empty((rows, L), dtype=torch.uint8, device=rfq.device)
-        lens = torch.empty((rows,), dtype=torch.int32, device=rfq.device)
+        out, kw = _rows_out("d_", rows, L, 0, False, None, rfq.device)
         if rows:
-            codec.decode_rows(rfq.data_ptr(), n, row_len=L, codes=codes, qual_offset=qual_offset, pad_base=pad, pad_qual=pad,
-                              d_bases=bases.data_ptr(), bases_cap=rows * L, d_quals=quals.data_ptr(), quals_cap=rows * L,
-                              d_lens=lens.data_ptr(), lens_cap=rows)
-    finally:
-        codec.set_stream(None)
-    out = {"bases": bases, "quals": quals, "lens": lens}
+            codec.decode_rows(rfq.data_ptr(), n, row_len=L, codes=codes, qual_offset=qual_offset, pad_base=pad, pad_qual=pad, **kw)
     if names:
         out["names"], out["name_off"] = decode_names(codec, rfq)
     return out
@@ -142,26 +210,14 @@ def fastq_to_tensors(codec, fq1: torch.Tensor, fq2: torch.Tensor = None, paired=
         assert t is not None and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous(), "fq1 / fq2 must be contiguous uint8 tensors on the GPU"
     dev = fq1.device
     src = dict(d_fq2=fq2.data_ptr() if two else None, n2=fq2.numel() if two else 0, paired=paired, final=final)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
+    with _on_stream(codec, dev):
         q = codec.text_rows(fq1.data_ptr(), fq1.numel(), **src)
         L = max(int(q.max_len), 1) if row_len is None else int(row_len)
-        rows, nl = int(q.n_rows), int(q.names_len)
-        bases = torch.empty((rows, L), dtype=torch.uint8, device=dev)
-        quals = torch.empty((rows, L), dtype=torch.uint8, device=dev)
-        lens = torch.empty((rows,), dtype=torch.int32, device=dev)
-        blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if names else None
-        off = torch.zeros((rows + 1,), dtype=torch.int64, device=dev) if names else None
+        rows = int(q.n_rows)
+        out, kw = _rows_out("d_", rows, L, int(q.names_len), names, torch.int64, dev)
         if rows:
-            codec.text_rows(fq1.data_ptr(), fq1.numel(), row_len=L, codes=codes, qual_offset=qual_offset, pad_base=pad, pad_qual=pad,
-                            d_bases=bases.data_ptr(), bases_cap=rows * L, d_quals=quals.data_ptr(), quals_cap=rows * L, d_lens=lens.data_ptr(), lens_cap=rows,
-                            d_names=blob.data_ptr() if (names and nl) else None, names_cap=nl if names else 0,
-                            d_name_off=off.data_ptr() if names else None, off_cap=rows + 1 if names else 0, **src)
-    finally:
-        codec.set_stream(None)
-    out = {"bases": bases, "quals": quals, "lens": lens, "consumed": (int(q.consumed1), int(q.consumed2))}
-    if names:
-        out["names"], out["name_off"] = blob, off
+            codec.text_rows(fq1.data_ptr(), fq1.numel(), row_len=L, codes=codes, qual_offset=qual_offset, pad_base=pad, pad_qual=pad, **kw, **src)
+    out["consumed"] = (int(q.consumed1), int(q.consumed2))
     return out
 
 
@@ -170,32 +226,16 @@ def _compact(codec, t, call, kw_of, row_len, pad, more_of=None):
     tensors of exactly the reported sizes, both ordered with torch's current stream.  kw_of(n, dev) checks the caller's own inputs and returns the arguments they
     become; more_of(q, dev) makes the call's further outputs from the size query's result and returns the arguments of the writing call they become.  -> the last
     result struct, the rows dict ("bases", "quals", "lens" and, when `t` has them, "names" + "name_off")."""
-    bases, quals, lens = t["bases"], t["quals"], t["lens"]
-    named = t.get("name_off") is not None
-    names, name_off = (t["names"], t["name_off"]) if named else (bases.new_empty((0,)), torch.zeros((int(bases.shape[0]) + 1,), dtype=torch.int64, device=bases.device))
-    n, L_in, p_b, p_q, p_l, p_n, nl_in, p_o = _rows_args(bases, quals, lens, names, name_off)
-    dev = bases.device
-    kw = kw_of(n, dev)
-    rows = (n, L_in, p_b, p_q, p_l, p_n if named else None, nl_in if named else 0, p_o if named else None)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        q = call(*rows, **kw)
+    R = _rows_of(t, quals=True, names=None)
+    kw = kw_of(R.n, R.dev)
+    with _on_stream(codec, R.dev):
+        q = call(*R[:8], **kw)
         L = max(int(q.max_len), 1) if row_len is None else int(row_len)
-        m, nl = int(q.n_rows), int(q.names_len)
-        ob = torch.empty((m, L), dtype=torch.uint8, device=dev); oq = torch.empty((m, L), dtype=torch.uint8, device=dev)
-        ol = torch.empty((m,), dtype=torch.int32, device=dev)
-        blob = torch.empty((nl,), dtype=torch.uint8, device=dev) if named else None
-        off = torch.zeros((m + 1,), dtype=name_off.dtype, device=dev) if named else None
-        more = more_of(q, dev) if more_of is not None else {}
+        m = int(q.n_rows)
+        out, okw = _rows_out("out_", m, L, int(q.names_len), R.name_off is not None, R.off_dtype, R.dev)
+        more = more_of(q, R.dev) if more_of is not None else {}
         if m:
-            q = call(*rows, row_len=L, pad_base=pad, pad_qual=pad, out_bases=ob.data_ptr(), bases_cap=m * L, out_quals=oq.data_ptr(), quals_cap=m * L,
-                     out_lens=ol.data_ptr(), lens_cap=m, out_names=blob.data_ptr() if (named and nl) else None, names_cap=nl if named else 0,
-                     out_name_off=off.data_ptr() if named else None, off_cap=m + 1 if named else 0, **more, **kw)
-    finally:
-        codec.set_stream(None)
-    out = {"bases": ob, "quals": oq, "lens": ol}
-    if named:
-        out["names"], out["name_off"] = blob, off
+            q = call(*R[:8], row_len=L, pad_base=pad, pad_qual=pad, **okw, **more, **kw)
     return q, out
 
 
@@ -207,12 +247,7 @@ def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_l
     bytes are the rows' own, names are kept whole.  A size query and one call, both ordered with torch's current stream; the context goes back to its own
     stream afterwards."""
     def kw_of(n, dev):
-        sel = {}
-        for key, v, dts in (("d_keep", keep, (torch.bool, torch.uint8)), ("d_start", start, (torch.int32,)), ("d_len", length, (torch.int32,))):
-            if v is not None:
-                assert v.dtype in dts and v.is_contiguous() and v.numel() == n and v.device == dev, "keep: [n] bool / uint8, start / length: [n] int32, on the rows' device"
-                sel[key] = v.data_ptr()
-        return dict(pairs=pairs, min_len=min_len, **sel)
+        return dict(pairs=pairs, min_len=min_len, **_triple(keep, start, length, n, dev))
     q, out = _compact(codec, t, codec.select_rows, kw_of, row_len, pad)
     out["dropped"] = {"mask": int(q.dropped_mask), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}
     return out
@@ -230,15 +265,9 @@ def group_rows(codec, t, bin, n_bins, keep=None, start=None, length=None, pairs=
     box = {}
 
     def kw_of(n, dev):
-        sel = {}
-        for key, v, dts in (("d_keep", keep, (torch.bool, torch.uint8)), ("d_start", start, (torch.int32,)), ("d_len", length, (torch.int32,))):
-            if v is not None:
-                assert v.dtype in dts and v.is_contiguous() and v.numel() == n and v.device == dev, "keep: [n] bool / uint8, start / length: [n] int32, on the rows' device"
-                sel[key] = v.data_ptr()
+        sel = _triple(keep, start, length, n, dev)
         assert not pairs or n % 2 == 0, "rows in pairs"
-        U = n // 2 if pairs else n
-        assert bin.dtype == torch.int32 and bin.is_contiguous() and bin.numel() == U and bin.device == dev, "bin: [U] int32 on the rows' device"
-        return dict(pairs=pairs, min_len=min_len, d_bin=bin.data_ptr() if U else None, n_bins=n_bins, rest=rest, **sel)
+        return dict(pairs=pairs, min_len=min_len, d_bin=_per(bin, n // 2 if pairs else n, dev, I32, "bin: [U] int32"), n_bins=n_bins, rest=rest, **sel)
 
     def more_of(q, dev):
         box["bin_off"] = torch.zeros((T + 1,), dtype=torch.int64, device=dev)          # (no rows: every bin starts at 0, and nothing is called)
@@ -301,19 +330,15 @@ def judge_rows(codec, t, codes=True, metrics=False, **criteria):
     row fails for), "summary": dict of the batch's counts} and, with metrics=True, "metrics": [n, 4] int32 (qsum, n_cnt, lowq, trans of the window).  keep, start
     and length are what select_rows takes.  "quals" must hold the scores (qual_offset taken off, as decode_tensors and fastq_to_tensors leave them).  One call,
     ordered with torch's current stream; the context goes back to its own stream afterwards."""
-    bases, quals, lens = t["bases"], t["quals"], t["lens"]
-    n, L, p_b, p_q, p_l = _rows_args(bases, quals, lens, bases.new_empty((0,)), torch.zeros((int(bases.shape[0]) + 1,), dtype=torch.int64, device=bases.device))[:5]
-    dev = bases.device
+    R = _rows_of(t, quals=True)
+    n, dev = R.n, R.dev
     keep = torch.empty((n,), dtype=torch.uint8, device=dev); why = torch.empty((n,), dtype=torch.uint8, device=dev)
     start = torch.empty((n,), dtype=torch.int32, device=dev); length = torch.empty((n,), dtype=torch.int32, device=dev)
     met = torch.empty((n, 4), dtype=torch.int32, device=dev) if metrics else None
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        r = codec.judge_rows(n, L, p_b, p_q, p_l, codes=codes, d_keep=keep.data_ptr(), d_start=start.data_ptr(), d_len=length.data_ptr(), d_why=why.data_ptr(),
+    with _on_stream(codec, dev):
+        r = codec.judge_rows(*R[:5], codes=codes, d_keep=keep.data_ptr(), d_start=start.data_ptr(), d_len=length.data_ptr(), d_why=why.data_ptr(),
                              d_metrics=met.data_ptr() if metrics else None, **criteria)
-    finally:
-        codec.set_stream(None)
-    out = {"keep": keep, "start": start, "length": length, "why": why, "summary": {f: int(getattr(r, f)) for f in SUMMARY_FIELDS}}
+    out = {"keep": keep, "start": start, "length": length, "why": why, "summary": _summary(r, SUMMARY_FIELDS)}
     if metrics:
         out["metrics"] = met
     return out
@@ -331,12 +356,9 @@ def trim_adapters(codec, t, pairs=False, codes=True, adapter1=None, adapter2=Non
     (one mismatch per that many compared bases; 0: exact).  hist_len > 0 (pairs): "insert_hist", [hist_len] int64, the last bin holds every longer insert.
     "length" is select_rows' length (start 0) and, as "lens", what a later judge_rows takes.  One call, ordered with torch's current stream; the context goes
     back to its own stream afterwards."""
-    bases, lens = t["bases"], t["lens"]
-    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
-    n, L = int(bases.shape[0]), int(bases.shape[1])
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == bases.device, "lens: [n] int32 on the rows' device"
+    R = _rows_of(t)
     assert not hist_len or pairs, "the insert-size histogram is for pairs"
-    dev = bases.device
+    n, dev = R.n, R.dev
     length = torch.empty((n,), dtype=torch.int32, device=dev); how = torch.empty((n,), dtype=torch.uint8, device=dev)
     insert = torch.empty((n // 2,), dtype=torch.int32, device=dev) if pairs else None
     diff = torch.empty((n // 2,), dtype=torch.int32, device=dev) if pairs else None
@@ -344,14 +366,11 @@ def trim_adapters(codec, t, pairs=False, codes=True, adapter1=None, adapter2=Non
     crit = dict(min_overlap=min_overlap, max_diff=max_diff, max_diff_pct=max_diff_pct) if pairs else {}
     if adapter1 is not None or adapter2 is not None:
         crit.update(adapter_min=adapter_min, adapter_mm_per=adapter_mm_per)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        r = codec.adapter_rows(n, L, bases.data_ptr(), lens.data_ptr(), codes=codes, pairs=pairs, adapter1=adapter1, adapter2=adapter2, hist_len=hist_len,
+    with _on_stream(codec, dev):
+        r = codec.adapter_rows(n, R.L, R.bases, R.lens, codes=codes, pairs=pairs, adapter1=adapter1, adapter2=adapter2, hist_len=hist_len,
                                d_len=length.data_ptr(), d_how=how.data_ptr(), d_insert=insert.data_ptr() if pairs else None, d_diff=diff.data_ptr() if pairs else None,
                                d_insert_hist=hist.data_ptr() if hist_len else None, **crit)
-    finally:
-        codec.set_stream(None)
-    out = {"length": length, "how": how, "summary": {f: int(getattr(r, f)) for f in ADAPTER_FIELDS}}
+    out = {"length": length, "how": how, "summary": _summary(r, ADAPTER_FIELDS)}
     if pairs:
         out["insert"], out["diff"] = insert, diff
     if hist_len:
@@ -371,11 +390,10 @@ def merge_pairs(codec, t, insert, row_len=None, pad=255, unmerged=True, codes=Tr
     narrow the choice with torch.where(cond, insert, -1).  Rows are padded with `pad` to row_len (None: the longest merged read).  "quals" must hold the scores.
     A size query and one call, both ordered with torch's current stream; the context goes back to its own stream afterwards."""
     def kw_of(n, dev):
-        assert n % 2 == 0 and insert.dtype == torch.int32 and insert.is_contiguous() and insert.numel() == n // 2 and insert.device == dev, \
-            "rows in pairs, insert: [n / 2] int32 on the rows' device"
-        return dict(d_insert=insert.data_ptr(), codes=codes)
+        assert n % 2 == 0, "rows in pairs"
+        return dict(d_insert=_per(insert, n // 2, dev, I32, "insert: [n / 2] int32"), codes=codes)
     q, merged = _compact(codec, t, codec.merge_rows, kw_of, row_len, pad)
-    out = {"merged": merged, "summary": {f: int(getattr(q, f)) for f in MERGE_FIELDS}}
+    out = {"merged": merged, "summary": _summary(q, MERGE_FIELDS)}
     if unmerged:
         out["unmerged"] = select_rows(codec, t, keep=(insert < 0).repeat_interleave(2), pairs=True)
     return out
@@ -392,29 +410,16 @@ def dedup_rows(codec, t, pairs=False, key_len=0, best_qual=False, keep=None, his
     The kept member is the lowest index, with best_qual the one with the highest score sum over its key (ties: the lowest index).  keep: [n] bool / uint8 - only
     units all of whose rows are non-zero there are looked at (judge_rows' "keep"); the others get keep 0, dup_of -1.  hist_len > 0: "hist", [hist_len] int64, bin
     c - 1 = classes of size c, the last bin every larger class.  One call, ordered with torch's current stream; the context goes back to its own stream afterwards."""
-    bases, lens = t["bases"], t["lens"]
-    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
-    n, L = int(bases.shape[0]), int(bases.shape[1])
-    dev = bases.device
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
-    assert not pairs or n % 2 == 0, "rows in pairs"
-    quals = t["quals"] if best_qual else None
-    if best_qual:
-        assert quals.dtype == torch.uint8 and quals.is_contiguous() and quals.shape == bases.shape and quals.device == dev, "quals: [n, L] uint8 on the rows' device"
-    if keep is not None:
-        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
-    U = n // 2 if pairs else n
+    R = _rows_of(t, quals=bool(best_qual), pairs=pairs)
+    n, U, dev = R.n, R.U, R.dev
+    d_in = _mask(keep, n, dev)
     out_keep = torch.empty((n,), dtype=torch.uint8, device=dev); dup_of = torch.empty((U,), dtype=torch.int32, device=dev)
     count = torch.empty((U,), dtype=torch.int32, device=dev)
     hist = torch.empty((hist_len,), dtype=torch.int64, device=dev) if hist_len else None
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        r = codec.dedup_rows(n, L, bases.data_ptr(), quals.data_ptr() if best_qual else None, lens.data_ptr(), pairs=pairs, key_len=key_len, best_qual=best_qual,
-                             hist_len=hist_len, d_in=keep.data_ptr() if keep is not None else None, d_keep=out_keep.data_ptr(), d_dup_of=dup_of.data_ptr(),
-                             d_count=count.data_ptr(), d_hist=hist.data_ptr() if hist_len else None)
-    finally:
-        codec.set_stream(None)
-    out = {"keep": out_keep, "dup_of": dup_of, "count": count, "summary": {f: int(getattr(r, f)) for f in DEDUP_FIELDS}}
+    with _on_stream(codec, dev):
+        r = codec.dedup_rows(*R[:5], pairs=pairs, key_len=key_len, best_qual=best_qual, hist_len=hist_len, d_in=d_in, d_keep=out_keep.data_ptr(),
+                             d_dup_of=dup_of.data_ptr(), d_count=count.data_ptr(), d_hist=hist.data_ptr() if hist_len else None)
+    out = {"keep": out_keep, "dup_of": dup_of, "count": count, "summary": _summary(r, DEDUP_FIELDS)}
     if hist_len:
         out["hist"] = hist
     return out
@@ -432,29 +437,16 @@ def profile_rows(codec, t, pairs=False, codes=True, keep=None, start=None, lengt
     the last row / bin of each collects what lies beyond.  cycles / len_bins default to the rows' stride (+ 1 for the lengths); tables: the ones wanted.  "summary":
     n_rows, max_len (the longest counted window) and, per mate, lists of counted, bases, qsum, q20, q30, gc, other.  No row is moved.  One call, ordered with torch's
     current stream; the context goes back to its own stream afterwards."""
-    bases, quals, lens = t["bases"], t["quals"], t["lens"]
-    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
-    n, L = int(bases.shape[0]), int(bases.shape[1])
-    dev = bases.device
-    assert quals.dtype == torch.uint8 and quals.is_contiguous() and quals.shape == bases.shape and quals.device == dev, "quals: [n, L] uint8 on the rows' device"
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
-    assert not pairs or n % 2 == 0, "rows in pairs"
-    if keep is not None:
-        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
-    for name, w in (("start", start), ("length", length)):
-        assert w is None or (w.dtype == torch.int32 and w.is_contiguous() and w.numel() == n and w.device == dev), name + ": [n] int32 on the rows' device"
+    R = _rows_of(t, quals=True, pairs=pairs)
+    L, dev = R.L, R.dev
+    sel = _triple(keep, start, length, R.n, dev)
     assert set(tables) <= set(PROFILE_TABLES), "tables: of " + ", ".join(PROFILE_TABLES)
     cycles = L if cycles is None else cycles; len_bins = L + 1 if len_bins is None else len_bins
     M = 2 if pairs else 1
     shapes = dict(base_cnt=(M, cycles, 5), base_qsum=(M, cycles, 5), qual_hist=(M, cycles, qbins), len_hist=(M, len_bins), meanq_hist=(M, qbins), gc_hist=(M, 101))
     out = {k: torch.empty(shapes[k], dtype=torch.int64, device=dev) for k in PROFILE_TABLES if k in tables}
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        r = codec.profile_rows(n, L, bases.data_ptr(), quals.data_ptr(), lens.data_ptr(), codes=codes, pairs=pairs, d_keep=keep.data_ptr() if keep is not None else None,
-                               d_start=start.data_ptr() if start is not None else None, d_len=length.data_ptr() if length is not None else None, cycles=cycles,
-                               qbins=qbins, len_bins=len_bins, **{"d_" + k: v.data_ptr() for k, v in out.items()})
-    finally:
-        codec.set_stream(None)
+    with _on_stream(codec, dev):
+        r = codec.profile_rows(*R[:5], codes=codes, pairs=pairs, cycles=cycles, qbins=qbins, len_bins=len_bins, **sel, **{"d_" + k: v.data_ptr() for k, v in out.items()})
     out["summary"] = dict({f: [int(getattr(r, f)[m]) for m in range(M)] for f in PROFILE_FIELDS}, n_rows=int(r.n_rows), max_len=int(r.max_len))
     return out
 
@@ -479,14 +471,11 @@ def screen_index(codec, refs, k=25):
     # (references of no bytes at all are still references: the call wants a pointer for them, and an empty tensor has none)
     at = blob if blob.numel() else torch.zeros((1,), dtype=torch.uint8, device=blob.device)
     src = (at.data_ptr(), blob.numel(), off.data_ptr(), n_refs)
-    codec.set_stream(torch.cuda.current_stream(blob.device).cuda_stream)
-    try:
+    with _on_stream(codec, blob.device):
         q = codec.screen_build(*src, k=k, size_only=True)
         index = torch.empty((int(q.index_bytes),), dtype=torch.uint8, device=blob.device)
         r = codec.screen_build(*src, k=k, d_index=index.data_ptr(), index_cap=index.numel())
-    finally:
-        codec.set_stream(None)
-    return {"index": index, "k": k, "n_kmers": int(r.n_kmers), "slots": int(r.slots), "summary": {f: int(getattr(r, f)) for f in SCREEN_BUILD_FIELDS}}
+    return {"index": index, "k": k, "n_kmers": int(r.n_kmers), "slots": int(r.slots), "summary": _summary(r, SCREEN_BUILD_FIELDS)}
 
 
 def screen_rows(codec, t, index, pairs=False, codes=True, keep=None, min_hits=1, min_pct=0, keep_matched=False):
@@ -497,26 +486,17 @@ def screen_rows(codec, t, index, pairs=False, codes=True, keep=None, min_hits=1,
     with keep_matched it is the one that stays - a bait.  keep: [n] bool / uint8 - only units all of whose rows are non-zero there are looked at (judge_rows'
     "keep"); the others get 0 / 0 / 0.  "lens" may be what trim_adapters or judge_rows left.  One call, ordered with torch's current stream; the context goes back
     to its own stream afterwards."""
-    bases, lens = t["bases"], t["lens"]
     index = index["index"] if isinstance(index, dict) else index
-    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
-    n, L = int(bases.shape[0]), int(bases.shape[1])
-    dev = bases.device
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
-    assert index.dtype == torch.uint8 and index.is_contiguous() and index.device == dev, "index: screen_index's uint8 tensor on the rows' device"
-    assert not pairs or n % 2 == 0, "rows in pairs"
-    if keep is not None:
-        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
+    R = _rows_of(t, pairs=pairs)
+    n, dev = R.n, R.dev
+    p_ix = _per(index, None, dev, U8, "index: screen_index's uint8 tensor")
+    d_in = _mask(keep, n, dev)
     out_keep = torch.empty((n,), dtype=torch.uint8, device=dev)
     hits = torch.empty((n,), dtype=torch.int32, device=dev); kmers = torch.empty((n,), dtype=torch.int32, device=dev)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        r = codec.screen_rows(n, L, bases.data_ptr(), lens.data_ptr(), index.data_ptr(), index.numel(), codes=codes, pairs=pairs, min_hits=min_hits, min_pct=min_pct,
-                              keep_matched=keep_matched, d_in=keep.data_ptr() if keep is not None else None, d_kmers=kmers.data_ptr(), d_hits=hits.data_ptr(),
-                              d_keep=out_keep.data_ptr())
-    finally:
-        codec.set_stream(None)
-    return {"keep": out_keep, "hits": hits, "kmers": kmers, "summary": {f: int(getattr(r, f)) for f in SCREEN_FIELDS}}
+    with _on_stream(codec, dev):
+        r = codec.screen_rows(n, R.L, R.bases, R.lens, p_ix, index.numel(), codes=codes, pairs=pairs, min_hits=min_hits, min_pct=min_pct, keep_matched=keep_matched,
+                              d_in=d_in, d_kmers=kmers.data_ptr(), d_hits=hits.data_ptr(), d_keep=out_keep.data_ptr())
+    return {"keep": out_keep, "hits": hits, "kmers": kmers, "summary": _summary(r, SCREEN_FIELDS)}
 
 
 KMERS_ROWS_FIELDS = ("n_rows", "n_counted", "bases_in", "added", "n_new", "n_kmers", "total", "lost")
@@ -530,13 +510,10 @@ def kmer_table(codec, k=25, slots=1 << 20):
     made again.  The table outlives the calls: count the batches of a file into one.  A size query and one call, both ordered with torch's current stream; the
     context goes back to its own stream afterwards."""
     dev = torch.device("cuda", codec.device)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
+    with _on_stream(codec, dev):
         q = codec.kmers_init(k=k, slots=slots, size_only=True)
         table = torch.empty((int(q.table_bytes),), dtype=torch.uint8, device=dev)
         r = codec.kmers_init(k=k, slots=slots, d_table=table.data_ptr(), table_cap=table.numel())
-    finally:
-        codec.set_stream(None)
     return {"table": table, "k": k, "slots": int(r.slots)}
 
 
@@ -547,23 +524,15 @@ def count_kmers(codec, t, table, codes=True, keep=None):
     total after the call}.  keep: [n] bool / uint8 - only rows that are non-zero there are counted (judge_rows' "keep"; rows, not pairs).  "lens" may be what
     trim_adapters or judge_rows left.  Calls on one table add up, in any order; ONE call at a time on a table.  One call, ordered with torch's current stream; the
     context goes back to its own stream afterwards."""
-    bases, lens = t["bases"], t["lens"]
     table = table["table"] if isinstance(table, dict) else table
-    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
-    n, L = int(bases.shape[0]), int(bases.shape[1])
-    dev = bases.device
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
-    assert table.dtype == torch.uint8 and table.is_contiguous() and table.device == dev, "table: kmer_table's uint8 tensor on the rows' device"
-    if keep is not None:
-        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
+    R = _rows_of(t)
+    n, dev = R.n, R.dev
+    p_tab = _per(table, None, dev, U8, "table: kmer_table's uint8 tensor")
+    d_in = _mask(keep, n, dev)
     kmers = torch.empty((n,), dtype=torch.int32, device=dev)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        r = codec.kmers_rows(n, L, bases.data_ptr(), lens.data_ptr(), table.data_ptr(), table.numel(), codes=codes, d_in=keep.data_ptr() if keep is not None else None,
-                             d_kmers=kmers.data_ptr())
-    finally:
-        codec.set_stream(None)
-    return {"kmers": kmers, "summary": {f: int(getattr(r, f)) for f in KMERS_ROWS_FIELDS}}
+    with _on_stream(codec, dev):
+        r = codec.kmers_rows(n, R.L, R.bases, R.lens, p_tab, table.numel(), codes=codes, d_in=d_in, d_kmers=kmers.data_ptr())
+    return {"kmers": kmers, "summary": _summary(r, KMERS_ROWS_FIELDS)}
 
 
 def kmer_counts(codec, table, min_count=1, max_count=0, hist_len=0, index=False):
@@ -577,8 +546,7 @@ def kmer_counts(codec, table, min_count=1, max_count=0, hist_len=0, index=False)
     assert table.dtype == torch.uint8 and table.is_cuda and table.is_contiguous(), "table: kmer_table's uint8 tensor on the GPU"
     dev = table.device
     tb = (table.data_ptr(), table.numel())
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
+    with _on_stream(codec, dev):
         q = codec.kmers_read(*tb, min_count=min_count, max_count=max_count, size_only=True)
         m = int(q.n_selected)
         values = torch.empty((m,), dtype=torch.int64, device=dev); counts = torch.empty((m,), dtype=torch.int64, device=dev)
@@ -588,12 +556,10 @@ def kmer_counts(codec, table, min_count=1, max_count=0, hist_len=0, index=False)
         r = codec.kmers_read(*tb, min_count=min_count, max_count=max_count, hist_len=hist_len, d_hist=hist.data_ptr() if hist_len else None,
                              d_values=values.data_ptr() if m else None, d_counts=counts.data_ptr() if m else None, list_cap=m,
                              d_index=ix.data_ptr() if index else None, index_cap=ix.numel() if index else 0)
-    finally:
-        codec.set_stream(None)
     values, order = torch.sort(values)
     counts = counts[order]
     out_index = {"index": ix, "k": int(r.k), "n_kmers": m, "slots": int(r.index_slots)} if index else None
-    return {"values": values, "counts": counts, "hist": hist, "index": out_index, "summary": {f: int(getattr(r, f)) for f in KMERS_READ_FIELDS}}
+    return {"values": values, "counts": counts, "hist": hist, "index": out_index, "summary": _summary(r, KMERS_READ_FIELDS)}
 
 
 DEMUX_FIELDS = ("n_units", "n_candidates", "n_assigned", "n_samples", "n_exact", "why_none", "why_ambig", "why_short", "why_combo", "bases_in", "bases_out")
@@ -613,28 +579,19 @@ def demux_rows(codec, t, barcodes1, barcodes2=None, sheet=None, pairs=False, cod
     skip1 / skip2: linker bases cut with the barcode.  keep: [n] bool / uint8 - only units all of whose rows are non-zero there are looked at.  Barcodes of
     several lengths in one set, indels, barcodes at other places than a fixed offset from the read's start, N as a wildcard, barcodes in the name line and UMIs are
     not offered.  One call, ordered with torch's current stream; the context goes back to its own stream afterwards."""
-    bases, lens = t["bases"], t["lens"]
-    assert bases.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.is_contiguous() and bases.shape[1] >= 1, "bases: [n, L] uint8 on the GPU"
-    n, L = int(bases.shape[0]), int(bases.shape[1])
-    dev = bases.device
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n and lens.device == dev, "lens: [n] int32 on the rows' device"
-    assert not pairs or n % 2 == 0, "rows in pairs"
-    if keep is not None:
-        assert keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous() and keep.numel() == n and keep.device == dev, "keep: [n] bool / uint8 on the rows' device"
-    U = n // 2 if pairs else n
+    R = _rows_of(t, pairs=pairs)
+    n, U, dev = R.n, R.U, R.dev
+    d_in = _mask(keep, n, dev)
     n_samples = len(barcodes1) if barcodes2 is None else (len(sheet) if sheet is not None else len(barcodes1) * len(barcodes2))
     sample = torch.empty((U,), dtype=torch.int32, device=dev); why = torch.empty((U,), dtype=torch.uint8, device=dev)
     best = torch.empty((n,), dtype=torch.int32, device=dev); dist = torch.empty((n,), dtype=torch.uint8, device=dev)
     out_keep = torch.empty((n,), dtype=torch.uint8, device=dev); start = torch.empty((n,), dtype=torch.int32, device=dev)
     counts = torch.empty((n_samples + 1,), dtype=torch.int64, device=dev)
-    codec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    try:
-        r = codec.demux_rows(n, L, bases.data_ptr(), lens.data_ptr(), barcodes1, barcodes2, sheet, codes=codes, pairs=pairs, off1=off1, off2=off2, skip1=skip1, skip2=skip2,
-                             max_mm=max_mm, min_delta=min_delta, d_in=keep.data_ptr() if keep is not None else None, d_sample=sample.data_ptr(), d_why=why.data_ptr(),
+    with _on_stream(codec, dev):
+        r = codec.demux_rows(n, R.L, R.bases, R.lens, barcodes1, barcodes2, sheet, codes=codes, pairs=pairs, off1=off1, off2=off2, skip1=skip1, skip2=skip2,
+                             max_mm=max_mm, min_delta=min_delta, d_in=d_in, d_sample=sample.data_ptr(), d_why=why.data_ptr(),
                              d_best=best.data_ptr(), d_dist=dist.data_ptr(), d_keep=out_keep.data_ptr(), d_start=start.data_ptr(), d_counts=counts.data_ptr())
-    finally:
-        codec.set_stream(None)
-    return {"sample": sample, "why": why, "best": best, "dist": dist, "keep": out_keep, "start": start, "counts": counts, "summary": {f: int(getattr(r, f)) for f in DEMUX_FIELDS}}
+    return {"sample": sample, "why": why, "best": best, "dist": dist, "keep": out_keep, "start": start, "counts": counts, "summary": _summary(r, DEMUX_FIELDS)}
 
 
 def split_rows(codec, t, sample, n_samples, start=None, length=None, pairs=False, unassigned=True, **select_kw):
@@ -646,10 +603,9 @@ def split_rows(codec, t, sample, n_samples, start=None, length=None, pairs=False
     or an unassigned mate is empty) is dropped from its bin with both rows, so a bin may hold fewer units than demux_rows' "counts" says - the result's "dropped" counts them;
     min_len=0 keeps them, as rows of length 0 that rows_to_fastq and encode_tensors refuse.  A select_rows pass reads a mask byte and a few words per row and moves only the rows it keeps, so a pass per sample is cheap beside moving the rows
     once (DESIGN.md has the measured time).  group_rows + group_parts give the same bins in ONE pass over the rows."""
-    dev = t["bases"].device
-    n = int(t["bases"].shape[0])
-    U = n // 2 if pairs else n
-    assert sample.dtype == torch.int32 and sample.numel() == U and sample.device == dev, "sample: [U] int32 on the rows' device"
+    R = _rows_of(t, pairs=pairs)
+    n, dev = R.n, R.dev
+    _per(sample, R.U, dev, I32, "sample: [U] int32")
     bins = torch.where(sample >= 0, sample, torch.full_like(sample, n_samples)).to(torch.int64)
     have = torch.bincount(bins, minlength=n_samples + 1).cpu().tolist()
     unit_of = torch.arange(n, device=dev) // 2 if pairs else None
@@ -679,14 +635,11 @@ def decode_names(codec, rfq: torch.Tensor):
     sections and the coordinate streams are read, none of the bases or qualities).  The text of the strand lines is not carried.  One call with
     context-owned results, copied into tensors of the caller's; ordered with torch's current stream."""
     assert rfq.dtype == torch.uint8 and rfq.is_cuda and rfq.is_contiguous(), "rfq must be a contiguous uint8 tensor on the GPU"
-    codec.set_stream(torch.cuda.current_stream(rfq.device).cuda_stream)
-    try:
+    with _on_stream(codec, rfq.device):
         r = codec.decode_names(rfq.data_ptr(), rfq.numel())
         blob = _own_copy(codec, r.d_names, int(r.names_len), rfq.device)
         off = _own_copy(codec, r.d_name_off, 8 * (int(r.n_rows) + 1), rfq.device).view(torch.int64)
-        return blob, off
-    finally:
-        codec.set_stream(None)
+    return blob, off
 
 
 def pack_names(names, device):
@@ -699,18 +652,6 @@ def pack_names(names, device):
         off[1:] = np.cumsum(np.fromiter((len(x) for x in names), dtype=np.int64, count=n))
     blob = np.frombuffer(b"".join(names), dtype=np.uint8)
     return torch.from_numpy(blob.copy()).to(device), torch.from_numpy(off).to(device)
-
-
-def _rows_args(bases, quals, lens, names, name_off):
-    assert bases.dtype == torch.uint8 and quals.dtype == torch.uint8 and bases.is_cuda and bases.dim() == 2 and bases.shape == quals.shape, \
-        "bases / quals: [n, L] uint8 tensors on the GPU"
-    assert bases.is_contiguous() and quals.is_contiguous() and bases.shape[1] >= 1
-    n, L = int(bases.shape[0]), int(bases.shape[1])
-    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == n, "lens: [n] int32"
-    assert names.dtype == torch.uint8 and names.is_contiguous(), "names: a uint8 blob (pack_names)"
-    assert name_off.dtype in (torch.int64, torch.uint64) and name_off.is_contiguous() and name_off.numel() == n + 1, "name_off: [n + 1] int64"
-    assert all(t.device == bases.device for t in (quals, lens, names, name_off)), "all tensors on one device"
-    return (n, L, bases.data_ptr(), quals.data_ptr(), lens.data_ptr(), names.data_ptr() if names.numel() else None, names.numel(), name_off.data_ptr())
 
 
 def _own_copy(codec, d_ptr, n, device):
@@ -726,30 +667,24 @@ def encode_tensors(codec, bases, quals, lens, names, name_off, paired=SE, chunk_
     """Rows in the layout of decode_tensors (+ the names: pack_names) -> the .rfq image as a uint8 tensor, by rfq_encode_rows: the text is made
     and encoded on the GPU.  A PE file: rows 2k / 2k + 1 are R1 / R2 of pair k.  Several batches make one file: the first with flush_all=True,
     final=False, the last with emit_header=False.  Ordered with torch's current stream; the context goes back to its own stream afterwards."""
-    rows = _rows_args(bases, quals, lens, names, name_off)
-    codec.set_stream(torch.cuda.current_stream(bases.device).cuda_stream)
-    try:
-        r = codec.encode_rows(*rows, paired=paired, codes=codes, qual_offset=qual_offset, chunk_bases=chunk_bases, final=final, emit_header=emit_header,
+    R = _rows_of(dict(bases=bases, quals=quals, lens=lens, names=names, name_off=name_off), quals=True, names=True)
+    with _on_stream(codec, R.dev):
+        r = codec.encode_rows(*R[:8], paired=paired, codes=codes, qual_offset=qual_offset, chunk_bases=chunk_bases, final=final, emit_header=emit_header,
                               flush_all=flush_all)
-        return _own_copy(codec, r.d_rfq, int(r.rfq_len), bases.device)
-    finally:
-        codec.set_stream(None)
+        return _own_copy(codec, r.d_rfq, int(r.rfq_len), R.dev)
 
 
 def rows_to_fastq(codec, bases, quals, lens, names, name_off, paired=SE, codes=True, qual_offset=33):
     """The same rows -> the FASTQ text as a uint8 tensor (rfq_rows_to_text, written straight into the tensor); a pair of tensors with PE_TWO_FILES
     (rows 2k -> the first, rows 2k + 1 -> the second).  Ordered with torch's current stream."""
-    rows = _rows_args(bases, quals, lens, names, name_off)
-    codec.set_stream(torch.cuda.current_stream(bases.device).cuda_stream)
-    try:
-        q = codec.rows_to_text(*rows, paired=paired, codes=codes, qual_offset=qual_offset, size_only=True)
+    R = _rows_of(dict(bases=bases, quals=quals, lens=lens, names=names, name_off=name_off), quals=True, names=True)
+    with _on_stream(codec, R.dev):
+        q = codec.rows_to_text(*R[:8], paired=paired, codes=codes, qual_offset=qual_offset, size_only=True)
         n1, n2 = int(q.n1), int(q.n2)
         # (16 bytes more than the text: torch's allocations are 16-byte aligned, and the slack keeps a later rfq_encode_batch on the tensor inside it)
-        t1 = torch.empty((n1 + 16,), dtype=torch.uint8, device=bases.device)
-        t2 = torch.empty((n2 + 16,), dtype=torch.uint8, device=bases.device) if paired == PE_TWO_FILES else None
-        if rows[0]:
-            codec.rows_to_text(*rows, paired=paired, codes=codes, qual_offset=qual_offset, d_out1=t1.data_ptr(), cap1=n1 + 16,
+        t1 = torch.empty((n1 + 16,), dtype=torch.uint8, device=R.dev)
+        t2 = torch.empty((n2 + 16,), dtype=torch.uint8, device=R.dev) if paired == PE_TWO_FILES else None
+        if R.n:
+            codec.rows_to_text(*R[:8], paired=paired, codes=codes, qual_offset=qual_offset, d_out1=t1.data_ptr(), cap1=n1 + 16,
                                d_out2=t2.data_ptr() if t2 is not None else None, cap2=n2 + 16 if t2 is not None else 0)
-        return (t1[:n1], t2[:n2]) if paired == PE_TWO_FILES else t1[:n1]
-    finally:
-        codec.set_stream(None)
+    return (t1[:n1], t2[:n2]) if paired == PE_TWO_FILES else t1[:n1]
