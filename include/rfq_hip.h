@@ -320,7 +320,37 @@ RFQ_API int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* args, rfq_text
  * judged, kept or not.  After any refusal the context stays usable.
  * The row buffers may have any alignment, in and out: with row_len % 16 == 0 and 16-byte alignment they are loaded / stored in whole 16-byte groups, otherwise at
  * their own alignment - never a byte outside [d_x, d_x + n * row_len) of either side.  n_rows * row_len and the blob may exceed 4 GiB (n_rows < 2^32 - 16).
- * Synchronous on the context's stream, like rfq_text_rows; stage times through rfq_last_timings (select:judge, select:tables, select:rows, select:names). */
+ * Synchronous on the context's stream, like rfq_text_rows; stage times through rfq_last_timings (select:judge, select:tables, select:rows, select:names).
+ *
+ * A TAG of the read's own bases in the kept names (args->tag, a HOST struct; NULL: names are kept whole, everything above) - UMI extraction in the manner of fastp's
+ * --umi and umi_tools extract: the bases are cut off through d_start, the tag carries them in the name.
+ * part(i) is the d_tag_len[i] bytes of base row i from d_tag_start[i], as text: with rows->base_mode == RFQ_ROWS_CODE the codes 0 .. 4 become A C G T N, with
+ * RFQ_ROWS_ASCII the bytes stand as they lie (lower case and N survive).  base_mode is looked at only when tag is given.  The part may lie anywhere in the read:
+ * d_start / d_len are independent of it.  The unit's tag T: pairs = 0 - T(i) = part(i); pairs = 1 - both rows of pair u get T(u) = part(2u), then `join` if both parts
+ * have bytes, then part(2u + 1) (a kept pair's mate is kept too, so both rows are rows of this call).  The text inserted is X = sep, then prefix and join if
+ * prefix_len > 0, then T: 81 bytes at most.  If T is empty nothing is inserted at all and the name is the input name.  Where: RFQ_TAG_AT_SPACE - in front of the
+ * first 0x20 byte of the name (no other byte counts as a space), a name without one: at its end; RFQ_TAG_AT_END - at its end; a name of 0 bytes takes X at offset 0.
+ * names_len, max_name and name_off count the tags; the size query, RFQ_E_NOSPACE and "an output that is NULL is not produced" are unchanged.
+ * RFQ_E_ARG, judged on the host: tag with rows without names; d_tag_start or d_tag_len NULL (with n_rows > 0, like rows->d_bases below) or not 4-byte aligned; prefix_len > RFQ_TAG_PREFIX_MAX, h_prefix NULL
+ * with prefix_len > 0; sep, join or a prefix byte outside 0x21..0x7E; at other than the two; a bad base_mode; rows->d_bases NULL; a tag array that overlaps an output.
+ * Judged on the device before anything is written, ALL rows, kept or not, the message names the first such row: RFQ_E_ARG - tag_start < 0, tag_len < 0, tag_len >
+ * RFQ_TAG_PART_MAX, tag_start + tag_len > lens[i] (formed in 64 bits); RFQ_E_DATA - a part byte that is a code above 4 / an ASCII byte outside 0x21..0x7E.
+ * RFQ_E_ARG, behind the judge: a KEPT name of 4 GiB or more (the plan holds a name's length and the place in 32 bits); the plain call takes such a name.
+ * Stage times: select:tagplan (where X goes, X rendered once per output row into scratch of the context's) in front of select:names.  RFQ_TAG=general takes the
+ * other formulation: a thread per output name, byte by byte, no plan.
+ * NOT offered: UMIs read out of the name line (fastp's index1 / index2 / per_index), tags in rfq_group_rows / rfq_merge_rows, UMI quality filters, parts of more than
+ * RFQ_TAG_PART_MAX bases, UMI-aware near-duplicate removal (an inline UMI is part of rfq_dedup_rows' key when dedup runs before this step). */
+#define RFQ_TAG_PART_MAX   32             /* bases one row gives                                                        */
+#define RFQ_TAG_PREFIX_MAX 14
+#define RFQ_TAG_AT_SPACE   0              /* in front of the first 0x20 byte of the name; a name without one: at its end (fastp) */
+#define RFQ_TAG_AT_END     1
+typedef struct {
+    const int32_t* d_tag_start;           /* [n_rows] first base of row i's part                                        */
+    const int32_t* d_tag_len;             /* [n_rows] its bases, 0 .. RFQ_TAG_PART_MAX; 0: row i gives no part          */
+    const uint8_t* h_prefix;              /* HOST bytes or NULL                                                         */
+    uint32_t prefix_len;                  /* 0 .. RFQ_TAG_PREFIX_MAX                                                    */
+    uint8_t  sep, join, at, reserved;
+} rfq_name_tag;
 typedef struct {
     const uint8_t* d_keep;                /* [n_rows] bytes, non-zero = keep (a torch.bool tensor as it lies); NULL = every row */
     const int32_t* d_start;               /* [n_rows] first base kept of row i; NULL = 0                                */
@@ -334,6 +364,7 @@ typedef struct {
     int32_t* d_lens;  size_t lens_cap;    /* [n_out] (entries) or NULL                                                  */
     uint8_t* d_names; size_t names_cap;   /* blob, any alignment, or NULL                                               */
     uint64_t* d_name_off; size_t off_cap; /* [n_out + 1] (entries), 8-byte aligned, or NULL                             */
+    const rfq_name_tag* tag;              /* HOST struct, or NULL: names are kept whole (today's call)                  */
 } rfq_select_rows_args;
 typedef struct {
     uint64_t n_rows, n_bases, names_len;  /* of the OUTPUT                                                              */
@@ -854,7 +885,8 @@ RFQ_API int rfq_kmers_read(rfq_ctx* ctx, const rfq_kmers_read_args* args, rfq_km
  * compares byte by byte against the barcodes' ASCII bytes in device memory - with the same bytes in every output.  Synchronous on the context's stream, one read-back;
  * stage time through rfq_last_timings (demux:rows).
  * NOT offered: barcodes of different lengths within one set, indels, a barcode searched at several offsets or at the 3' end, N as a wildcard in a barcode; barcodes
- * read out of the name line, UMI extraction.  Grouping the rows by sample in one pass is rfq_group_rows' (d_bin = d_sample). */
+ * read out of the name line.  UMI extraction is rfq_select_rows' tag (rfq_name_tag: the bases behind the barcode go into the kept names; d_start here says where
+ * they begin).  Grouping the rows by sample in one pass is rfq_group_rows' (d_bin = d_sample). */
 #define RFQ_DEMUX_NONE   1                /* d1 > max_mm                                                                */
 #define RFQ_DEMUX_AMBIG  2                /* d2 - d1 < min_delta                                                        */
 #define RFQ_DEMUX_SHORT  4                /* lens[i] < off + len: no window                                             */
@@ -916,7 +948,7 @@ RFQ_API int rfq_host_unregister(rfq_ctx* ctx, void* h_ptr);
 RFQ_API int rfq_compare_bytes(rfq_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint64_t* first_diff);
 
 /* Test / diagnostic switches of one context: name = the RFQ_* environment variable of the same meaning (RFQ_GATHER=old, RFQ_QUAL=bytes|masks, RFQ_CODER=list|mask, RFQ_INDEX=2pass,
- * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general, RFQ_SCREEN=general|collide, RFQ_KMERS=general|collide|direct, RFQ_DEMUX=general; see RfqOpts in
+ * RFQ_IDX_TILES, RFQ_STREAMS=1, RFQ_SLICE_BYTES, RFQ_SLICE_BASES, RFQ_WALK=exact, RFQ_GW_SHIFT, RFQ_MATERIALISE=1, RFQ_TRACE, RFQ_G2_PAD, RFQ_SP_PAD, RFQ_JUDGE=general, RFQ_ADAPTER=general, RFQ_MERGE=general, RFQ_DEDUP=collide, RFQ_PROFILE=general, RFQ_SCREEN=general|collide, RFQ_KMERS=general|collide|direct, RFQ_DEMUX=general, RFQ_TAG=general; see RfqOpts in
  * repaq_amd/csrc/rfq_ctx.h), value NULL or "" = default.  Every switch selects another formulation of the same, bit-identical result - they exist so that
  * the tests can pin each one (tests/test_gpu_formulations.py forces every one of them on the GPU).  Unknown names and values that are not of the switch's
  * form or range are RFQ_E_ARG.  The environment is read once, by rfq_create; the batch calls never call getenv. */

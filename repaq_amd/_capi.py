@@ -103,12 +103,20 @@ class TextRowsResult(C.Structure):
                 ("consumed1", C.c_size_t), ("consumed2", C.c_size_t), ("input_ended", C.c_int32), ("reserved", C.c_int32)]
 
 
+TAG_PART_MAX, TAG_PREFIX_MAX, TAG_AT_SPACE, TAG_AT_END = 32, 14, 0, 1
+
+
+class NameTag(C.Structure):
+    _fields_ = [("d_tag_start", C.c_void_p), ("d_tag_len", C.c_void_p), ("h_prefix", C.c_char_p), ("prefix_len", C.c_uint32),
+                ("sep", C.c_uint8), ("join", C.c_uint8), ("at", C.c_uint8), ("reserved", C.c_uint8)]
+
+
 class SelectRowsArgs(C.Structure):
     _fields_ = [("d_keep", C.c_void_p), ("d_start", C.c_void_p), ("d_len", C.c_void_p), ("pairs", C.c_int32), ("min_len", C.c_uint32), ("row_len", C.c_uint32),
                 ("pad_base", C.c_uint8), ("pad_qual", C.c_uint8), ("reserved", C.c_uint8 * 2),
                 ("d_bases", C.c_void_p), ("bases_cap", C.c_size_t), ("d_quals", C.c_void_p), ("quals_cap", C.c_size_t),
                 ("d_lens", C.c_void_p), ("lens_cap", C.c_size_t), ("d_names", C.c_void_p), ("names_cap", C.c_size_t),
-                ("d_name_off", C.c_void_p), ("off_cap", C.c_size_t)]
+                ("d_name_off", C.c_void_p), ("off_cap", C.c_size_t), ("tag", C.POINTER(NameTag))]
 
 
 class SelectRowsResult(C.Structure):

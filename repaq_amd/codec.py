@@ -309,15 +309,24 @@ class RfqCodec:
     # --- the step in the middle: rows -> the kept rows, trimmed, with their names (rfq_select_rows)
     def select_rows(self, n_rows, row_len_in, d_bases, d_quals, d_lens, d_names=None, names_len=0, d_name_off=None, d_keep=None, d_start=None, d_len=None,
                     pairs=False, min_len=1, row_len=0, pad_base=255, pad_qual=255, out_bases=None, bases_cap=0, out_quals=None, quals_cap=0,
-                    out_lens=None, lens_cap=0, out_names=None, names_cap=0, out_name_off=None, off_cap=0):
+                    out_lens=None, lens_cap=0, out_names=None, names_cap=0, out_name_off=None, off_cap=0, codes=False, base_mode=None, tag=None):
         """rfq_select_rows: the first eight arguments are the rows as rows_to_text / encode_rows take them (d_name_off None: rows without names); d_keep
         n_rows mask bytes (non-zero = keep; None: every row), d_start / d_len n_rows int32 windows (None: 0 / to the end of the read), pairs: rows
         2k / 2k + 1 stand or fall together, min_len: a shorter window drops the row.  out_*: the kept rows at stride row_len, their lengths, name lines
         and n_out + 1 uint64 offsets; no output pointer at all = a size query, an output that is None is not produced.  The bytes are the rows' own.
+        tag (None: names are kept whole): a tag of the read's own bases written into the kept names (rfq_name_tag) - a dict of d_tag_start / d_tag_len (n_rows
+        int32 each: the part of row i), prefix (bytes, b""), sep (b":"), join (b"_"), at (TAG_AT_SPACE | TAG_AT_END), raw (fields of the struct set as given: the
+        tests' refusals); codes / base_mode say what the base rows hold and are looked at only with a tag.
         Returns SelectRowsResult (n_rows, n_bases, names_len, max_len, max_name, n_in, dropped_mask, dropped_short, dropped_mate)."""
-        rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, False, 0)
+        rows = self._rows_in(n_rows, row_len_in, d_bases, d_quals, d_lens, d_names, names_len, d_name_off, codes, 0, base_mode)
         a = A.SelectRowsArgs(d_keep, d_start, d_len, 1 if pairs else 0, min_len, row_len, pad_base, pad_qual, (C.c_uint8 * 2)(),
-                             out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap, out_name_off, off_cap)
+                             out_bases, bases_cap, out_quals, quals_cap, out_lens, lens_cap, out_names, names_cap, out_name_off, off_cap, None)
+        if tag is not None:
+            prefix = bytes(tag.get("prefix", b""))
+            t = A.NameTag(tag.get("d_tag_start"), tag.get("d_tag_len"), prefix if prefix else None, len(prefix), bytes(tag.get("sep", b":"))[0], bytes(tag.get("join", b"_"))[0],
+                          tag.get("at", A.TAG_AT_SPACE), 0)
+            self._raw(t, tag.get("raw"))
+            a.tag = C.pointer(t)
         return self._call("rfq_select_rows", A.SelectRowsResult, rows, a)
 
     # --- select_rows with the kept rows grouped by a bin per unit, in one pass (rfq_group_rows)

@@ -47,6 +47,9 @@ __device__ __forceinline__ uint32_t sel_window(const SelIn& in, uint32_t i, uint
 // - the rule of its own by which row g falls, asked of every row the mask lets through, in front of `short` (and what is wrong with the row's input to it);
 // rule.bad(st, g) - where an offending row is left; rule.row(g, kept, nl) - the verdict of row g and the bytes of its name; rule.finish(st, dr) - what the rule itself
 // sums up (dr: the thread's rows that fell by it), called by every thread behind the common reduction.
+// A rule whose kept names GROW (enc/rows_tag.h: a tag is written into them) says so here and has rule.grow(g, e, re): the bytes row g's name gains if it is kept
+// (e: what is wrong with the row's length or window, re: what is wrong with the rule's own input).  The other rules do not have the member and keep their code.
+template <class Rule> struct sel_rule_grows { static constexpr bool value = false; };
 template <class Stat, class Rule> __device__ __forceinline__ void sel_judge(const SelIn& in, Stat* __restrict__ st, Rule& rule) {
     __shared__ uint32_t s_dm[4], s_ds[4], s_dt[4];
     uint32_t ml = 0, mn = 0, err = 0, dm = 0, ds = 0, dt = 0, dr = 0; unsigned long long nb = 0;
@@ -61,6 +64,7 @@ template <class Stat, class Rule> __device__ __forceinline__ void sel_judge(cons
             if (b < a || (g + 1u == in.n_rows && b > in.names_len)) e |= SL_ERR_NOFF; else nl = b - a;
         }
         uint32_t re = 0; const bool falls = rule.drops(g, re);
+        if constexpr (sel_rule_grows<Rule>::value) nl += rule.grow(g, e, re);
         if (why != 1u && falls) why = 4u;                                    // (counted behind the mask and in front of `short`)
         if (why == 0 && in.pairs) { uint32_t ms, mw, me; if (sel_window(in, g ^ 1u, ms, mw, me) != 0) why = 3u; }      // (n_rows is even: the host saw to it)
         if (e) { err |= e; atomicMin(&st->bad_row, (unsigned long long)g); }

@@ -123,7 +123,12 @@ __global__ void __launch_bounds__(256) k_text_rows(Text T, TextRowsOut o, TextRo
 // them through; a line of text always has one): equal offsets are searched to the LAST of them, the name that holds the byte, and a tile in which more names start
 // than the LDS table holds searches off[] itself.  A group inside one name is one 16-byte load at the source's own alignment and one aligned store; a group that
 // holds a boundary is put together byte by byte in registers; the blob's first and last group, where they are not whole, are stored byte by byte.
-template <class Src> __device__ __forceinline__ void name_blob_write(const Src& src, const uint64_t* __restrict__ off, uint32_t n, uint8_t* __restrict__ blob, uint64_t names_len) {
+// The writer in two parts, so that a source whose names are not one run of bytes (enc/rows_tag.h: head, tag, tail) follows the same blob: name_blob_find - which
+// group is this thread's, which name holds its first byte -, then the fetch of the group's bytes.
+// A thread's group: blob bytes [qa, qe), stored at nb + A (nb: the 16-byte boundary at or below the blob); g: the name that holds byte qa
+struct NameGroup { uint8_t* nb; uint64_t A, qa, qe; uint32_t g; };
+// Every thread of the workgroup calls it (two barriers); false: the thread's group lies behind the blob.
+__device__ __forceinline__ bool name_blob_find(const uint64_t* __restrict__ off, uint32_t n, uint8_t* __restrict__ blob, uint64_t names_len, NameGroup& G) {
     __shared__ uint32_t s_rel[TN_RECS + 1]; __shared__ uint32_t s_r0, s_hi;
     const uint32_t shift = (uint32_t)((uintptr_t)blob & 15u); uint8_t* const nb = blob - shift;
     const uint64_t A0 = (uint64_t)blockIdx.x * TN_TILE;                      // (position from nb)
@@ -150,7 +155,7 @@ template <class Src> __device__ __forceinline__ void name_blob_write(const Src& 
     }
     __syncthreads();
     const uint64_t A = A0 + 16ull * threadIdx.x;
-    if (A >= names_len + shift) return;
+    if (A >= names_len + shift) return false;
     const uint64_t qa = A > shift ? A - shift : 0ull, qe = (A + 16u - shift < names_len) ? A + 16u - shift : names_len;   // this group's blob bytes [qa, qe)
     uint32_t g;
     if (in_lds) {
@@ -163,6 +168,19 @@ template <class Src> __device__ __forceinline__ void name_blob_write(const Src& 
         while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] <= qa) lo = mid; else hi = mid; }
         g = lo;
     }
+    G.nb = nb; G.A = A; G.qa = qa; G.qe = qe; G.g = g;
+    return true;
+}
+// a group put together in registers (h0: bytes 0 .. 7, h1: 8 .. 15): one aligned store where it is whole, else - the blob's first or last group - byte by byte
+__device__ __forceinline__ void name_group_store(const NameGroup& G, uint8_t* __restrict__ blob, unsigned long long h0, unsigned long long h1) {
+    const uint32_t nby = (uint32_t)(G.qe - G.qa);
+    if (G.qe - G.qa == 16u) *(uint4*)(G.nb + G.A) = make_uint4((uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32));
+    else for (uint32_t i = 0; i < nby; i++) blob[G.qa + i] = (uint8_t)(i < 8u ? h0 >> (8u * i) : h1 >> (8u * (i - 8u)));
+}
+template <class Src> __device__ __forceinline__ void name_blob_write(const Src& src, const uint64_t* __restrict__ off, uint32_t n, uint8_t* __restrict__ blob, uint64_t names_len) {
+    NameGroup G;
+    if (!name_blob_find(off, n, blob, names_len, G)) return;
+    uint8_t* const nb = G.nb; const uint64_t A = G.A, qa = G.qa, qe = G.qe; uint32_t g = G.g;
     uint64_t beg = off[g], end = off[g + 1];
     const bool whole = qe - qa == 16u;
     if (whole && qe <= end) {
@@ -178,8 +196,7 @@ template <class Src> __device__ __forceinline__ void name_blob_write(const Src& 
         const unsigned long long c = p[q - beg];
         if (i < 8u) h0 |= c << (8u * i); else h1 |= c << (8u * (i - 8u));
     }
-    if (whole) *(uint4*)(nb + A) = make_uint4((uint32_t)h0, (uint32_t)(h0 >> 32), (uint32_t)h1, (uint32_t)(h1 >> 32));
-    else for (uint32_t i = 0; i < nby; i++) blob[qa + i] = (uint8_t)(i < 8u ? h0 >> (8u * i) : h1 >> (8u * (i - 8u)));
+    name_group_store(G, blob, h0, h1);
 }
 
 // ---- names: the first line of every row, back to back (name_blob_write over the rows' name lines)

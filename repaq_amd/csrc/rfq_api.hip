@@ -54,11 +54,12 @@ extern "C" int rfq_set_option(rfq_ctx* c, const char* name, const char* value) {
     else if (n == "RFQ_SCREEN") { if (set && v != "general" && v != "collide") return rfq_fail(c, RFQ_E_ARG, "RFQ_SCREEN is general, collide or empty"); c->opt.screen = v == "general" ? RfqOpts::SCREEN_GENERAL : (v == "collide" ? RfqOpts::SCREEN_COLLIDE : RfqOpts::SCREEN_DEFAULT); }
     else if (n == "RFQ_KMERS") { if (set && v != "general" && v != "collide" && v != "direct") return rfq_fail(c, RFQ_E_ARG, "RFQ_KMERS is general, collide, direct or empty"); c->opt.kmers = v == "general" ? RfqOpts::KMERS_GENERAL : (v == "collide" ? RfqOpts::KMERS_COLLIDE : (v == "direct" ? RfqOpts::KMERS_DIRECT : RfqOpts::KMERS_DEFAULT)); }
     else if (n == "RFQ_DEMUX") { if (set && v != "general") return rfq_fail(c, RFQ_E_ARG, "RFQ_DEMUX is general or empty"); c->opt.demux_general = v == "general"; }
+    else if (n == "RFQ_TAG") { if (set && v != "general") return rfq_fail(c, RFQ_E_ARG, "RFQ_TAG is general or empty"); c->opt.tag_general = v == "general"; }
     else return rfq_fail(c, RFQ_E_ARG, "unknown option %s", name);
 #undef RFQ_OPT_NUM
     return RFQ_OK;
 }
-static const char* const RFQ_OPTION_NAMES[] = { "RFQ_GATHER", "RFQ_QUAL", "RFQ_CODER", "RFQ_INDEX", "RFQ_IDX_TILES", "RFQ_STREAMS", "RFQ_SLICE_BYTES", "RFQ_SLICE_BASES", "RFQ_WALK", "RFQ_GW_SHIFT", "RFQ_MATERIALISE", "RFQ_TRACE", "RFQ_G2_PAD", "RFQ_SP_PAD", "RFQ_POS_SEG", "RFQ_SPEC", "RFQ_MIRROR", "RFQ_JUDGE", "RFQ_ADAPTER", "RFQ_MERGE", "RFQ_DEDUP", "RFQ_PROFILE", "RFQ_SCREEN", "RFQ_KMERS", "RFQ_DEMUX" };
+static const char* const RFQ_OPTION_NAMES[] = { "RFQ_GATHER", "RFQ_QUAL", "RFQ_CODER", "RFQ_INDEX", "RFQ_IDX_TILES", "RFQ_STREAMS", "RFQ_SLICE_BYTES", "RFQ_SLICE_BASES", "RFQ_WALK", "RFQ_GW_SHIFT", "RFQ_MATERIALISE", "RFQ_TRACE", "RFQ_G2_PAD", "RFQ_SP_PAD", "RFQ_POS_SEG", "RFQ_SPEC", "RFQ_MIRROR", "RFQ_JUDGE", "RFQ_ADAPTER", "RFQ_MERGE", "RFQ_DEDUP", "RFQ_PROFILE", "RFQ_SCREEN", "RFQ_KMERS", "RFQ_DEMUX", "RFQ_TAG" };
 extern "C" const char* rfq_option_name(int i) { return (i >= 0 && i < (int)(sizeof RFQ_OPTION_NAMES / sizeof RFQ_OPTION_NAMES[0])) ? RFQ_OPTION_NAMES[i] : nullptr; }
 // the switch's current value in the form rfq_set_option takes ("" = its default): what a caller saves before it changes a switch for a while
 extern "C" int rfq_get_option(const rfq_ctx* c, const char* name, char* out, size_t cap) {
@@ -89,6 +90,7 @@ extern "C" int rfq_get_option(const rfq_ctx* c, const char* name, char* out, siz
     else if (n == "RFQ_SCREEN") v = o.screen == RfqOpts::SCREEN_GENERAL ? "general" : (o.screen == RfqOpts::SCREEN_COLLIDE ? "collide" : "");
     else if (n == "RFQ_KMERS") v = o.kmers == RfqOpts::KMERS_GENERAL ? "general" : (o.kmers == RfqOpts::KMERS_COLLIDE ? "collide" : (o.kmers == RfqOpts::KMERS_DIRECT ? "direct" : ""));
     else if (n == "RFQ_DEMUX") v = o.demux_general ? "general" : "";
+    else if (n == "RFQ_TAG") v = o.tag_general ? "general" : "";
     else return RFQ_E_ARG;
     if (v.size() + 1 > cap) return RFQ_E_NOSPACE;
     memcpy(out, v.c_str(), v.size() + 1);
@@ -126,6 +128,7 @@ extern "C" void rfq_destroy(rfq_ctx* c) {
     for (auto& b : c->rows_txt) b.release();
     c->rows_stat.release(); c->names_blob.release(); c->names_off.release();
     c->dedup_fp.release(); c->dedup_score.release(); c->dedup_slot.release(); c->dedup_tab.release(); c->dedup_best.release(); c->dedup_cnt.release(); c->demux_sets.release();
+    c->tag_x.release();
     c->group_kk.release(); c->group_used.release(); c->group_hist.release(); for (auto& b : c->group_key) b.release(); for (auto& b : c->group_idx) b.release();
     c->timer.destroy();
     if (c->copy) { (void)hipStreamDestroy(c->copy); for (auto& e : c->copy_ev) if (e) (void)hipEventDestroy(e); }

@@ -108,6 +108,7 @@ struct RfqOpts {
     // RFQ_KMERS=general|collide|direct  general, rfq_kmers_rows: the any-length kernel (a wave per row) for every row length, adds straight to device memory; direct: the common kernels without the workgroup's LDS table (default: rows of up to 1024 bytes held whole, a workgroup combines in LDS and flushes once); collide, rfq_kmers_init: four bits of the hash for the start slot, recorded in the table - long probe chains, at most 65536 slots (default: a 64-bit multiplicative hash)
     enum Kmers { KMERS_DEFAULT, KMERS_GENERAL, KMERS_COLLIDE, KMERS_DIRECT } kmers = KMERS_DEFAULT;
     bool demux_general = false;       // RFQ_DEMUX=general  rfq_demux_rows: a lane per unit compares byte by byte against the barcodes' ASCII bytes in device memory, counts by global atomics (default: the window as 2-bit classes against the packed sets in LDS, counts in an LDS table)
+    bool tag_general = false;         // RFQ_TAG=general    rfq_select_rows with a tag: a thread per output name writes it byte by byte, straight from the names and the base rows (default: a plan per output row in scratch, then the blob in 16-byte groups from head, tag and tail)
     bool no_mirror = false;           // RFQ_MIRROR=0       encode, two files: index R2 as well, even where R1's line table could serve both (default: one index, verified by the gather)
 };
 struct rfq_ctx {
@@ -192,6 +193,7 @@ struct rfq_ctx {
     DBuf demux_sets; std::vector<uint8_t> demux_host;
     // rfq_group_rows: the judge's word per unit, the bit per bin that holds a row, the two (key, unit) arrays of the sort and its digit table (sized per call, they only grow)
     DBuf group_kk, group_used, group_key[2], group_idx[2], group_hist;
+    DBuf tag_x;                            // rfq_select_rows with a tag: a record per output row - the text inserted into its name and where (sized per call, it only grows)
     std::vector<uint64_t> chunk_off;
     std::vector<uint64_t> scan_end[2];     // rfq_scan_batch: end offset of every chunk in each input stream
     StageTimer timer;

@@ -1087,8 +1087,22 @@ template <class Stat, class Judge> static int rows_judge(rfq_ctx* ctx, uint64_t 
     return RFQ_OK;
 }
 // tables(pos, noff, tab, ooff) launches the tables kernel (a rows_tables), rows(o, tab) completes o - vec_in and what else is its own - and launches the row writer;
-// k_sel_names follows the same table.  Ends the call: synchronised, the stage times collected.
-template <class A, class Tables, class Rows> static int rows_write(rfq_ctx* ctx, const rfq_rows_in* in, const A* a, const RowsJudged& j, const RowsStages& st, Tables tables, Rows rows) {
+// names(tab, ooff) writes the name blob along the same table and times its own stages - k_sel_names (rows_names_whole) unless the caller has another (rfq_select_rows
+// with a tag).  Ends the call: synchronised, the stage times collected.
+template <class A> static int rows_names_whole(rfq_ctx* ctx, const rfq_rows_in* in, const A* a, const RowsJudged& j, const char* stage, const SelRow* tab, const uint64_t* ooff) {
+    hipStream_t S = ctx->stream; int rc;
+    ctx->timer.begin(stage, S);
+    if (a->d_names && j.names_len) {
+        uint32_t blocks = 0;
+        if ((rc = name_blob_blocks(ctx, a->d_names, j.names_len, &blocks)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_sel_names, dim3(blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, tab, ooff, j.n_out, a->d_names, j.names_len);
+        KCHK(ctx, "k_sel_names");
+    }
+    ctx->timer.end(S);
+    return RFQ_OK;
+}
+template <class A, class Tables, class Rows, class Names> static int rows_write(rfq_ctx* ctx, const rfq_rows_in* in, const A* a, const RowsJudged& j, const RowsStages& st, Tables tables, Rows rows,
+        Names names) {
     hipStream_t S = ctx->stream; DBuf* B = ctx->b; int rc;
     const uint32_t n_out = j.n_out;
     ctx->timer.begin(st.tables, S);
@@ -1107,17 +1121,13 @@ template <class A, class Tables, class Rows> static int rows_write(rfq_ctx* ctx,
         if ((rc = rows(o, (const SelRow*)tab)) != RFQ_OK) return rc;
     }
     ctx->timer.end(S);
-    ctx->timer.begin(st.names, S);
-    if (a->d_names && j.names_len) {
-        uint32_t blocks = 0;
-        if ((rc = name_blob_blocks(ctx, a->d_names, j.names_len, &blocks)) != RFQ_OK) return rc;
-        hipLaunchKernelGGL(k_sel_names, dim3(blocks), dim3(TN_TPB), 0, S, in->d_names, in->d_name_off, (const SelRow*)tab, (const uint64_t*)ooff, n_out, a->d_names, j.names_len);
-        KCHK(ctx, "k_sel_names");
-    }
-    ctx->timer.end(S);
+    if ((rc = names((const SelRow*)tab, (const uint64_t*)ooff)) != RFQ_OK) return rc;
     HIPCHK(ctx, hipStreamSynchronize(S));
     ctx->timer.collect();
     return RFQ_OK;
+}
+template <class A, class Tables, class Rows> static int rows_write(rfq_ctx* ctx, const rfq_rows_in* in, const A* a, const RowsJudged& j, const RowsStages& st, Tables tables, Rows rows) {
+    return rows_write(ctx, in, a, j, st, tables, rows, [&](const SelRow* tab, const uint64_t* ooff) -> int { return rows_names_whole(ctx, in, a, j, st.names, tab, ooff); });
 }
 // ---- the argument rules the rows calls word alike.  Each is called where its call tests it: the first refusal met is the one reported.
 static int rows_pairs_arg(rfq_ctx* ctx, int32_t pairs, uint64_t n) {
@@ -1399,6 +1409,51 @@ extern "C" int rfq_text_rows(rfq_ctx* ctx, const rfq_text_rows_args* a, rfq_text
 // struct) - and ONE read-back: the verdict block and the two totals.  The host refuses or goes on; k_sel_tables makes the per-output-row tables (and the caller's
 // lens / name_off), k_sel_rows and k_sel_names follow them.
 static const RowsStages SELECT_STAGES = { "select:judge", "select:tables", "select:rows", "select:names" };
+// ---- rfq_select_rows with a tag (rfq_name_tag; enc/rows_tag.h).  What the host judges of it:
+#define TAG_X_MAX (1ull + RFQ_TAG_PREFIX_MAX + 1ull + 2ull * RFQ_TAG_PART_MAX + 1ull)        // sep, prefix, join, two parts and the join between them: 81
+static int select_tag_arg(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_name_tag* t, bool named) {
+    auto graph = [](uint8_t c) { return c >= 0x21u && c <= 0x7Eu; };
+    int rc;
+    if (!named) return rfq_fail(ctx, RFQ_E_ARG, "rows without names (d_name_off == NULL) take no tag");
+    if (in->n_rows && (!t->d_tag_start || !t->d_tag_len)) return rfq_fail(ctx, RFQ_E_ARG, "tag: null d_tag_start / d_tag_len");
+    if (((uintptr_t)t->d_tag_start | (uintptr_t)t->d_tag_len) & 3u) return rfq_fail(ctx, RFQ_E_ARG, "tag: d_tag_start and d_tag_len must be 4-byte aligned");
+    if (t->prefix_len > RFQ_TAG_PREFIX_MAX) return rfq_fail(ctx, RFQ_E_ARG, "tag: prefix_len is at most %d (got %u)", RFQ_TAG_PREFIX_MAX, t->prefix_len);
+    if (t->prefix_len && !t->h_prefix) return rfq_fail(ctx, RFQ_E_ARG, "tag: null h_prefix with prefix_len = %u", t->prefix_len);
+    if (!graph(t->sep) || !graph(t->join)) return rfq_fail(ctx, RFQ_E_ARG, "tag: sep and join must be bytes in 0x21..0x7E (got 0x%02x, 0x%02x)", t->sep, t->join);
+    for (uint32_t i = 0; i < t->prefix_len; i++)
+        if (!graph(t->h_prefix[i])) return rfq_fail(ctx, RFQ_E_ARG, "tag: the prefix holds a byte outside 0x21..0x7E (0x%02x at %u)", t->h_prefix[i], i);
+    if (t->at != RFQ_TAG_AT_SPACE && t->at != RFQ_TAG_AT_END) return rfq_fail(ctx, RFQ_E_ARG, "tag: at must be RFQ_TAG_AT_SPACE or RFQ_TAG_AT_END (got %u)", t->at);
+    if ((rc = rows_base_mode_arg(ctx, in)) != RFQ_OK) return rc;
+    if (in->n_rows && !in->d_bases) return rfq_fail(ctx, RFQ_E_ARG, "tag: null rows->d_bases");
+    return RFQ_OK;
+}
+// The names step of such a call: the plan (select:tagplan) and the writer that follows it, or - RFQ_TAG=general - the byte-wise writer alone (select:names either way)
+static int select_names_tag(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_select_rows_args* a, const RowsJudged& j, const TagIn& ti, const SelRow* tab, const uint64_t* ooff) {
+    hipStream_t S = ctx->stream; int rc;
+    const bool wanted = a->d_names && j.names_len, general = ctx->opt.tag_general;
+    TagNames nm; memset(&nm, 0, sizeof nm);
+    nm.names = in->d_names; nm.in_off = in->d_name_off; nm.names_len = in->names_len; nm.tab = tab; nm.n_out = j.n_out;
+    uint8_t* xs = nullptr;
+    if (wanted && !general) {
+        ctx->timer.begin("select:tagplan", S);
+        HIPCHK(ctx, table(ctx->tag_x, (size_t)j.n_out * TAG_STRIDE, xs));
+        hipLaunchKernelGGL(k_tag_plan, dim3((uint32_t)(((uint64_t)j.n_out + TP_ROWS - 1u) / TP_ROWS)), dim3(256), 0, S, ti, nm, xs);
+        KCHK(ctx, "k_tag_plan");
+        ctx->timer.end(S);
+    }
+    ctx->timer.begin(SELECT_STAGES.names, S);
+    if (wanted && general) {
+        hipLaunchKernelGGL(k_sel_names_tag_general, dim3((uint32_t)(((uint64_t)j.n_out + 255u) / 256u)), dim3(256), 0, S, ti, nm, ooff, a->d_names);
+        KCHK(ctx, "k_sel_names_tag_general");
+    } else if (wanted) {
+        uint32_t blocks = 0;
+        if ((rc = name_blob_blocks(ctx, a->d_names, j.names_len, &blocks)) != RFQ_OK) return rc;
+        hipLaunchKernelGGL(k_sel_names_tag, dim3(blocks), dim3(TN_TPB), 0, S, nm, (const uint8_t*)xs, ooff, a->d_names, j.names_len);
+        KCHK(ctx, "k_sel_names_tag");
+    }
+    ctx->timer.end(S);
+    return RFQ_OK;
+}
 extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_select_rows_args* a, rfq_select_rows_result* res) {
     if (!ctx || !in || !a || !res) return RFQ_E_ARG;
     memset(res, 0, sizeof *res);
@@ -1413,10 +1468,13 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     if (n && (!in->d_lens || (a->d_bases && !in->d_bases) || (a->d_quals && !in->d_quals) || (a->d_names && in->names_len && !in->d_names)))
         return rfq_fail(ctx, RFQ_E_ARG, "null row / name pointer");
     if ((rc = rows_dst_aligned(ctx, in, a, (uintptr_t)a->d_start | (uintptr_t)a->d_len, "d_lens, d_start and d_len")) != RFQ_OK) return rc;
-    {   // the bytes a call can write (its cap, and never more than n_rows rows of row_len) against the bytes it reads
-        Span ins[8]; rows_src_spans(in, named, ins);
+    const rfq_name_tag* const tg = a->tag;
+    if (tg && (rc = select_tag_arg(ctx, in, tg, named)) != RFQ_OK) return rc;
+    {   // the bytes a call can write (its cap, and never more than n_rows rows of row_len) against the bytes it reads; with a tag the names grow by up to TAG_X_MAX each
+        Span ins[10]; rows_src_spans(in, named, ins);
         ins[5] = { a->d_keep, n, "d_keep" }; ins[6] = { a->d_start, n * 4ull, "d_start" }; ins[7] = { a->d_len, n * 4ull, "d_len" };
-        Span outs[5]; rows_dst_spans(a, n, in->names_len, outs);
+        ins[8] = { tg ? tg->d_tag_start : nullptr, n * 4ull, "tag->d_tag_start" }; ins[9] = { tg ? tg->d_tag_len : nullptr, n * 4ull, "tag->d_tag_len" };
+        Span outs[5]; rows_dst_spans(a, n, (uint64_t)in->names_len + (tg ? n * TAG_X_MAX : 0ull), outs);
         if ((rc = rows_apart(ctx, outs, ins, ": selection in place is not offered")) != RFQ_OK) return rc;
     }
     if ((rc = rows_begin(ctx)) != RFQ_OK) return rc;
@@ -1424,9 +1482,17 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     SelIn si; memset(&si, 0, sizeof si);
     si.lens = in->d_lens; si.name_off = in->d_name_off; si.keep = a->d_keep; si.start = a->d_start; si.len = a->d_len;
     si.names_len = in->names_len; si.n_rows = (uint32_t)n; si.row_len = in->row_len; si.pairs = a->pairs ? 1u : 0u; si.min_len = a->min_len;
+    TagIn ti; memset(&ti, 0, sizeof ti);
+    if (tg) {
+        ti.tstart = tg->d_tag_start; ti.tlen = tg->d_tag_len; ti.lens = in->d_lens; ti.bases = in->d_bases; ti.total = n * in->row_len; ti.row_len = in->row_len;
+        ti.codes = in->base_mode == RFQ_ROWS_CODE ? 1u : 0u; ti.pairs = si.pairs; ti.prefix_len = tg->prefix_len; ti.sep = tg->sep; ti.join = tg->join; ti.at = tg->at;
+        if (tg->prefix_len) memcpy(ti.prefix, tg->h_prefix, tg->prefix_len);
+    }
     SelStat hs; RowsJudged j;
     rc = rows_judge(ctx, n, named, SELECT_STAGES.judge, [&](uint32_t* flag, uint64_t* nsz, SelStat* dst) -> int {
-        hipLaunchKernelGGL(k_sel_judge, dim3((uint32_t)((n + SJ_ROWS - 1u) / SJ_ROWS)), dim3(256), 0, ctx->stream, si, flag, nsz, dst);
+        const dim3 grid((uint32_t)((n + SJ_ROWS - 1u) / SJ_ROWS));
+        if (tg) { hipLaunchKernelGGL(k_sel_judge_tag, grid, dim3(256), 0, ctx->stream, si, ti, flag, nsz, dst); return launched(ctx, "k_sel_judge_tag"); }
+        hipLaunchKernelGGL(k_sel_judge, grid, dim3(256), 0, ctx->stream, si, flag, nsz, dst);
         return launched(ctx, "k_sel_judge");
     }, &hs, &j);
     if (rc != RFQ_OK) return rc;
@@ -1434,21 +1500,25 @@ extern "C" int rfq_select_rows(rfq_ctx* ctx, const rfq_rows_in* in, const rfq_se
     if (hs.err & SL_ERR_LEN) return rows_len_refusal(ctx, in->row_len, br);
     if (hs.err & SL_ERR_WIN) return rfq_fail(ctx, RFQ_E_ARG, "a window starts below 0, has a negative length or ends behind its read (first such row: %llu)", br);
     if (hs.err & SL_ERR_NOFF) return rfq_fail(ctx, RFQ_E_ARG, "the name offsets decrease or end past names_len = %zu (first such row: %llu)", in->names_len, br);
+    if (hs.err & SL_ERR_TAG) return rfq_fail(ctx, RFQ_E_ARG, "a tag part starts below 0, has a negative length, more than %d bases or ends behind its read (first such row: %llu)", RFQ_TAG_PART_MAX, br);
+    if (hs.err & SL_ERR_TAGB) return rfq_fail(ctx, RFQ_E_DATA, "a tag part holds %s (first such row: %llu)", ti.codes ? "a base code above 4" : "a byte outside 0x21..0x7E", br);
+    if (tg && hs.max_name == 0xFFFFFFFFu) return rfq_fail(ctx, RFQ_E_ARG, "a name of 4 GiB or more takes no tag");
     res->n_rows = j.n_out; res->n_bases = hs.n_bases; res->names_len = j.names_len; res->max_len = hs.max_len; res->max_name = hs.max_name;
     res->dropped_mask = hs.d_mask; res->dropped_short = hs.d_short; res->dropped_mate = hs.d_mate;
     if (rows_size_query(a)) { ctx->timer.collect(); return RFQ_OK; }
     if ((rc = rows_room(ctx, a, j.n_out, j.names_len, hs.max_len)) != RFQ_OK) { memset(res, 0, sizeof *res); return rc; }
     if (j.n_out == 0) return rows_none(ctx, a->d_name_off);
-    return rows_write(ctx, in, a, j, SELECT_STAGES,
-        [&](const uint32_t* pos, const uint64_t* noff, SelRow* tab, uint64_t* ooff) -> int {
-            hipLaunchKernelGGL(k_sel_tables, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, si, pos, noff, tab, ooff, a->d_lens, a->d_name_off);
-            return launched(ctx, "k_sel_tables");
-        },
-        [&](RowsOut& r, const SelRow* tab) -> int {
-            r.vec_in = rows_vec(in->row_len, a->d_bases ? in->d_bases : nullptr, a->d_quals ? in->d_quals : nullptr);      // (of the buffers that are read)
-            hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)r.n_out + r.per - 1) / r.per)), dim3(256), 0, ctx->stream, r, tab);
-            return launched(ctx, "k_sel_rows");
-        });
+    auto tables = [&](const uint32_t* pos, const uint64_t* noff, SelRow* tab, uint64_t* ooff) -> int {
+        hipLaunchKernelGGL(k_sel_tables, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, si, pos, noff, tab, ooff, a->d_lens, a->d_name_off);
+        return launched(ctx, "k_sel_tables");
+    };
+    auto rows = [&](RowsOut& r, const SelRow* tab) -> int {
+        r.vec_in = rows_vec(in->row_len, a->d_bases ? in->d_bases : nullptr, a->d_quals ? in->d_quals : nullptr);      // (of the buffers that are read)
+        hipLaunchKernelGGL(k_sel_rows, dim3((uint32_t)(((uint64_t)r.n_out + r.per - 1) / r.per)), dim3(256), 0, ctx->stream, r, tab);
+        return launched(ctx, "k_sel_rows");
+    };
+    if (!tg) return rows_write(ctx, in, a, j, SELECT_STAGES, tables, rows);
+    return rows_write(ctx, in, a, j, SELECT_STAGES, tables, rows, [&](const SelRow* tab, const uint64_t* ooff) -> int { return select_names_tag(ctx, in, a, j, ti, tab, ooff); });
 }
 // ---------------------------------------------------------------- rows -> the kept rows grouped by a bin per unit, in one pass: rfq_group_rows of include/rfq_hip.h
 // rfq_select_rows with another ordering step (enc/rows_group.h).  The judging pass is select's under one more rule (k_group_judge) and leaves a word per unit and

@@ -25,6 +25,7 @@
 #include "enc/text_rows.h"                    // FASTQ text -> rows, lengths and names from the line index (rfq_text_rows)
 #include "enc/rows_lanes.h"                   // what the rows kernels below share: group reductions, 16-byte pieces, the deciding calls' walk, length check, candidate test and sums
 #include "enc/rows_select.h"                  // rows -> the kept rows, trimmed, with their names (rfq_select_rows)
+#include "enc/rows_tag.h"                     // a tag of the read's own bases written into the kept names of rfq_select_rows: the judge's rule, the plan, the two names writers (rfq_name_tag)
 #include "enc/rows_group.h"                   // rows -> the kept rows grouped by a bin per unit in one pass, trimmed, with their names and the first row of every bin (rfq_group_rows)
 #include "enc/rows_judge.h"                   // rows -> keep, window, reason and metrics per row + a QC summary (rfq_judge_rows)
 #include "enc/rows_adapter.h"                 // rows -> the length adapter removal leaves, insert sizes of the pairs + a summary (rfq_adapter_rows)

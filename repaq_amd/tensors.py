@@ -91,6 +91,10 @@ or, in ONE pass over the rows (rfq_group_rows: a stable sort of the kept units b
     g = group_rows(codec, t, dm["sample"], len(sheet), start=dm["start"], pairs=True)                    # g["bin_off"]: the first row of every bin
     per_sample = group_parts(g)                                                                          # one read-back; None for an empty bin
 
+inline UMIs: the molecular barcode leaves the read and goes into its name while select_rows writes the name blob (rfq_name_tag) - fastp's --umi:
+
+    s = extract_umi(codec, t, "per_read", 8, umi_skip=2, prefix="UMI", pairs=True)                       # names "@...:UMI_ACGTACGT_TTGCAAGG 1:N:0:ACGT"; start=dm["start"]: behind a barcode
+
 A torch mask still works (t["bases"][keep] and so on), but the name blob then has to be re-packed by hand and nothing is trimmed.
 
 The text of the strand lines is not carried: rows always write "+", so the round trip is byte-exact for files whose strand lines are "+".
@@ -239,15 +243,32 @@ def _compact(codec, t, call, kw_of, row_len, pad, more_of=None):
     return q, out
 
 
-def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_len=1, row_len=None, pad=255):
+def _tag_kw(tag, codes, n, dev):
+    """select_rows' tag dict, checked, as the `tag` / `codes` of RfqCodec.select_rows"""
+    from . import _capi as A
+    unknown = set(tag) - {"start", "length", "sep", "prefix", "join", "at"}
+    assert not unknown, "tag: unknown keys %s" % sorted(unknown)
+    at = {"space": A.TAG_AT_SPACE, "end": A.TAG_AT_END}.get(tag.get("at", "space"))
+    assert at is not None, 'tag: at is "space" or "end"'
+    sep, join = str(tag.get("sep", ":")).encode(), str(tag.get("join", "_")).encode()
+    assert len(sep) == 1 and len(join) == 1, "tag: sep and join are one byte each"
+    assert n == 0 or (tag["start"].numel() == n and tag["length"].numel() == n), "tag: start and length are [n] int32"
+    return dict(codes=codes, tag=dict(d_tag_start=_per(tag["start"], n, dev, I32, "tag start: [n] int32"), d_tag_len=_per(tag["length"], n, dev, I32, "tag length: [n] int32"),
+                                      prefix=str(tag.get("prefix", "")).encode(), sep=sep, join=join, at=at))
+
+
+def select_rows(codec, t, keep=None, start=None, length=None, pairs=False, min_len=1, row_len=None, pad=255, tag=None, codes=True):
     """The rows of decode_tensors / fastq_to_tensors (`t`: "bases", "quals", "lens", optionally "names" + "name_off") -> a new dict with the same keys for the
     rows that are KEPT, each TRIMMED to bases [start, start + length) (rfq_select_rows), plus "dropped": {"mask", "short", "mate"}.  keep: [n] bool or uint8,
     non-zero = keep (None: every row); start / length: [n] int32 (None: 0 / to the end of the read); pairs: rows 2k / 2k + 1 stand or fall together; a row
     whose window is shorter than min_len is dropped (and with pairs its mate); rows are padded with `pad` to row_len (None: the longest kept window).  The
-    bytes are the rows' own, names are kept whole.  A size query and one call, both ordered with torch's current stream; the context goes back to its own
-    stream afterwards."""
+    bytes are the rows' own, names are kept whole - unless tag is given: {"start", "length": [n] int32 - the bases [start, start + length) of row i, at most 32,
+    are its part of the tag, wherever they lie in the read -, optional "sep" (":"), "prefix" (""), "join" ("_"), "at" ("space" | "end")}: the kept names take
+    sep, prefix + join, the part (with pairs both rows of a pair take R1's part, join, R2's part) in front of their first space, or at their end (rfq_name_tag);
+    a unit whose parts are empty keeps its names.  codes: what the base rows were made with (looked at only with a tag).  A size query and one call, both ordered
+    with torch's current stream; the context goes back to its own stream afterwards."""
     def kw_of(n, dev):
-        return dict(pairs=pairs, min_len=min_len, **_triple(keep, start, length, n, dev))
+        return dict(pairs=pairs, min_len=min_len, **_triple(keep, start, length, n, dev), **(_tag_kw(tag, codes, n, dev) if tag is not None else {}))
     q, out = _compact(codec, t, codec.select_rows, kw_of, row_len, pad)
     out["dropped"] = {"mask": int(q.dropped_mask), "short": int(q.dropped_short), "mate": int(q.dropped_mate)}
     return out
@@ -688,3 +709,7 @@ def rows_to_fastq(codec, bases, quals, lens, names, name_off, paired=SE, codes=T
             codec.rows_to_text(*R[:8], paired=paired, codes=codes, qual_offset=qual_offset, d_out1=t1.data_ptr(), cap1=n1 + 16,
                                d_out2=t2.data_ptr() if t2 is not None else None, cap2=n2 + 16 if t2 is not None else 0)
     return (t1[:n1], t2[:n2]) if paired == PE_TWO_FILES else t1[:n1]
+
+
+# extract_umi lives in repaq_amd/umi.py (it makes no call of its own: two arrays with torch ops, then select_rows) and is offered here beside select_rows
+from .umi import extract_umi  # noqa: E402,F401
